@@ -13,7 +13,11 @@ one all-gather per layer exchanges activations (glnn_amd/dist.py).  The student 
 distillation step of the products student MLP3w8 (100-2048-2048-47, B=4096, KL soft-label pass) under the
 same protocol and is reported in the "student" object.
 
-Extra objects on the JSON line (rank 0, N = 1): "roofline" for the dominant kernel (the aggregation), from
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed forwards, the outputs of the last one when
+--dump-outputs DIR is given (DIR/<name>.npy, a seeded sample of the rows), and the line.  Everything else -- the self-check of the timed
+output, the student leg and every extra object below -- runs only with --full (off by default).
+
+Extra objects on the JSON line (--full; rank 0, N = 1): "roofline" for the dominant kernel (the aggregation), from
 per-launch HIP events recorded inside the timed region on the launch stream; "roofline_reordered": the same kernels on
 the same graph with its nodes renumbered by descending in-degree (SURVEY 8d allows a locality-ordered figure beside the
 random-order one; `value` stays the random-order number); and "cpu_baseline" (SURVEY 8d / BASELINE.md section 3): the
@@ -48,6 +52,11 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed teacher forwards (default 100: a >= 3 s timed region at ~33 ms each; "
                     "--workload xl: 10 rank-forwards of ~170 ms; --emulate: 3 per emulated rank)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: the self-check of the timed output, "
+                    "the student leg, the roofline / reordered / clustered / chunked objects, the small students, teacher training, the CPU "
+                    "baseline and (N = 1, products at scale 1.0) the arxiv and xl legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed forwards, write what the last one computed to "
+                    "DIR/<name>.npy (float32 / float64; a fixed seeded sample of the rows)")
     ap.add_argument("--exchange", default="allgather", choices=["allgather", "halo"],
                     help="N > 1: per-layer all-gather of every rank's rows (default) or halo exchange of only the referenced remote rows")
     ap.add_argument("--locality", type=float, default=0.0,
@@ -106,6 +115,8 @@ def main():
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 3 if args.emulate else (10 if args.workload == "xl" else 100)
+    if args.dump_outputs and (args.emulate or args.workload == "xl"):
+        raise SystemExit("--dump-outputs: only the products / arxiv teacher forward writes its outputs")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)          # `python bench.py --gpus N` by itself: spawn the N ranks (one per GPU) and relay their line

@@ -1,4 +1,4 @@
-"""The products / arxiv workloads of bench.py: teacher forward (1 GPU or row-sharded over N ranks) + student distillation steps, and the
+"""The products / arxiv workloads of bench.py: teacher forward (1 GPU or row-sharded over N ranks) + (--full) student distillation steps, and the
 extra objects of the N = 1 line."""
 import os
 import time
@@ -61,6 +61,20 @@ def emit_failure(args, rank, world, lad, why):
     return None
 
 
+DUMP_ROWS = 131072      # rows of the sampled output: 131072 x 47 fp32 = 24.6 MB (the whole products output is 460 MB)
+
+
+def dump_outputs(path, out, row0):
+    """--dump-outputs: what the last timed forward returned -- the teacher's output rows (first C.SAGE_DIMS[-1] columns, fp32) at a
+    fixed seeded sample of rows, and those rows' global ids (float64, exact) -- as <path>/teacher_out.npy and teacher_out_rows.npy."""
+    n, c = out.shape[0], C.SAGE_DIMS[-1]
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+    sample = out[torch.from_numpy(rows).to(out.device), :c].float().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "teacher_out.npy"), np.ascontiguousarray(sample, dtype=np.float32))
+    np.save(os.path.join(path, "teacher_out_rows.npy"), (rows + row0).astype(np.float64))
+
+
 def run_products(args, rank, world, dev, barrier):
     import torch.distributed as dist
     from glnn_amd import data, ops
@@ -69,6 +83,8 @@ def run_products(args, rank, world, dev, barrier):
     from glnn_amd.models import Model
     from glnn_amd.student import StudentEngine
     C.use_workload(args.workload)
+    full = args.full        # plain run: only what the headline figure needs (bench.py docstring)
+    verify_on = full and not args.no_verify
 
     # ---- synthetic ogbn-products-shaped inputs, generated in HBM (seed 0, identical on every rank) --------
     torch.manual_seed(0)
@@ -109,7 +125,7 @@ def run_products(args, rank, world, dev, barrier):
         for spec in filter(None, os.environ.get("GLNN_BENCH_INJECT", "").split(",")):      # tests: "async:1000000,probe:1"
             kind, cnt = spec.split(":")
             gdist.INJECT_FAIL[kind] = int(cnt)
-        if not args.no_verify:      # the unsharded forward of this rank's rows, before the full graph is dropped: the sharded result
+        if verify_on:               # the unsharded forward of this rank's rows, before the full graph is dropped: the sharded result
             with torch.no_grad():   # (whatever the transport did) must reproduce it
                 ref_own = teacher.inference(FullNeighborLoader(g, 4096), feats)[shards.lo:shards.hi].clone()
         shard_graph = g.row_range(shards.lo, shards.hi)
@@ -216,10 +232,11 @@ def run_products(args, rank, world, dev, barrier):
         # A sub-millisecond forward (the arxiv-shaped graph: three launches, 0.85 ms) is timed WITHOUT the per-launch events and the events
         # are taken over a second pass of the same K forwards: two timing events per launch inside the timed region cost it 0.25-0.4 ms per
         # forward (profiles/r05_arxiv_event_overhead.txt: 1.10-1.26 ms with them, 0.84 without).  The products forward (33 ms) keeps them
-        # inside the timed region, as the contract asks.
+        # inside the timed region, as the contract asks.  The events feed the roofline object only: at N = 1 a plain run (no --full)
+        # records none.
         events_apart = world == 1 and C.GRAPH != "ogbn-products"
         barrier()
-        if not events_apart:
+        if not events_apart and (full or world > 1):
             ops.set_timing(timing)      # per-launch HIP events on every rank (N > 1: kernel time vs wall time = the exposed exchange)
         gdist.EXCHANGE_STATS.update(collectives=0, floats_received=0)
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -244,10 +261,11 @@ def run_products(args, rank, world, dev, barrier):
                 regs.append(time.perf_counter() - t0)
             regions_ms = [1e3 * r_ / args.steps for r_ in regs]
             t_teacher = sorted(regs)[1]
-            ops.set_timing(timing)
-            for _ in range(args.steps):
-                teacher_forward()
-            barrier()
+            if full:
+                ops.set_timing(timing)
+                for _ in range(args.steps):
+                    teacher_forward()
+                barrier()
         ops.set_timing(None)
         return dict(timing=timing, ev0=ev0, ev1=ev1, t_teacher=t_teacher, regions_ms=regions_ms)
 
@@ -275,11 +293,13 @@ def run_products(args, rank, world, dev, barrier):
                 "exchange_exposed_ms": own_ms - sum(kms.values()), "kernels": kms}
         rank_diag = [None] * world
         dist.all_gather_object(rank_diag, mine)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_timed, shards.lo if world > 1 else 0)
     verify = None
-    if not args.no_verify:
+    if verify_on:
         verify = verify_single(g, feats, teacher, out_timed, ops) if world == 1 else verify_sharded(out_timed, ref_own, dev, dist)
     chunked = None
-    if world == 1 and not args.no_chunked_leg:
+    if world == 1 and full and not args.no_chunked_leg:
         chunked = chunked_leg(g, feats, teacher, FullNeighborLoader, ops, out_timed)
     del out_timed, ref_own
     placement = None
@@ -293,85 +313,87 @@ def run_products(args, rank, world, dev, barrier):
         t_teacher = float(tt.item())
     edges_per_s = edges_per_forward * args.steps / t_teacher
 
-    # ---- student: fused distillation steps (soft-label pass: KL against teacher log-probs) ----------------
-    sd = C.STUDENT
-    student = Model(dict(model_name=sd["name"], num_layers=3, feat_dim=sd["dims"][0], hidden_dim=sd["dims"][1],
-                         label_dim=sd["dims"][-1], dropout_ratio=sd["dropout"], norm_type="batch", device=dev))
-    student.train()
-    opt = torch.optim.Adam(student.parameters(), lr=sd["lr"], weight_decay=sd["wd"])
-    eng = StudentEngine(student, opt, sd["batch"])
-    out_t = ops.as_feat(out_t)
-    k_student = args.steps * args.student_steps_per_step
-    w_student = max(args.warmup, 3)
-    gen = torch.Generator(device="cpu")
-    gen.manual_seed(1234 + rank)
-    nb = max(1, n // sd["batch"])
-    perm = torch.randperm(n, generator=gen)[: nb * sd["batch"]].view(nb, -1).to(dev)     # train_and_eval.py:65-71
+    s_rung = None
+    if full:
+        # ---- student: fused distillation steps (soft-label pass: KL against teacher log-probs) ------------
+        sd = C.STUDENT
+        student = Model(dict(model_name=sd["name"], num_layers=3, feat_dim=sd["dims"][0], hidden_dim=sd["dims"][1],
+                             label_dim=sd["dims"][-1], dropout_ratio=sd["dropout"], norm_type="batch", device=dev))
+        student.train()
+        opt = torch.optim.Adam(student.parameters(), lr=sd["lr"], weight_decay=sd["wd"])
+        eng = StudentEngine(student, opt, sd["batch"])
+        out_t = ops.as_feat(out_t)
+        k_student = args.steps * args.student_steps_per_step
+        w_student = max(args.warmup, 3)
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(1234 + rank)
+        nb = max(1, n // sd["batch"])
+        perm = torch.randperm(n, generator=gen)[: nb * sd["batch"]].view(nb, -1).to(dev)     # train_and_eval.py:65-71
 
-    def student_overlapped():
-        eng.overlap = OverlappedGradSync(eng, world, average=True)      # big weight gradients are all-reduced from inside the backward (grad_ready hook)
+        def student_overlapped():
+            eng.overlap = OverlappedGradSync(eng, world, average=True)      # big weight gradients are all-reduced from inside the backward (grad_ready hook)
 
-    def student_after_backward():
-        if getattr(eng, "overlap", None) is not None:
-            eng.overlap.detach()
-            eng.overlap = None
-        eng.grad_sync = make_grad_sync(eng.flat_grads, world, average=True)
+        def student_after_backward():
+            if getattr(eng, "overlap", None) is not None:
+                eng.overlap.detach()
+                eng.overlap = None
+            eng.grad_sync = make_grad_sync(eng.flat_grads, world, average=True)
 
-    def timed_student():
-        for i in range(w_student):
-            eng.step(feats, perm[i % nb], ops.LOSS_KL, out_t, 1.0)
-        barrier()
-        t0 = time.perf_counter()
-        for i in range(k_student):
-            eng.step(feats, perm[(w_student + i) % nb], ops.LOSS_KL, out_t, 1.0)
-        barrier()
-        return time.perf_counter() - t0
+        def timed_student():
+            for i in range(w_student):
+                eng.step(feats, perm[i % nb], ops.LOSS_KL, out_t, 1.0)
+            barrier()
+            t0 = time.perf_counter()
+            for i in range(k_student):
+                eng.step(feats, perm[(w_student + i) % nb], ops.LOSS_KL, out_t, 1.0)
+            barrier()
+            return time.perf_counter() - t0
 
-    if world == 1:
-        s_rungs = [("1 GPU", None)]
-    elif args.student_global_bn:     # one N*B-row batch split over ranks, global BN statistics, summed gradients
-        s_rungs = [("batch split, global BatchNorm statistics", lambda: eng.enable_batch_split(world, rank))]
-    elif args.no_grad_overlap:       # data parallel: every rank runs its own B-row batches, gradients averaged over ranks
-        s_rungs = [("one all-reduce after the backward", student_after_backward)]
-    else:
-        s_rungs = [("all-reduce from inside the backward", student_overlapped), ("one all-reduce after the backward", student_after_backward)]
-    t_student, s_rung = None, None
-    for s_rung, setup in s_rungs:
-        if setup is not None:
-            ok, _ = lad.attempt(f"student set-up [{s_rung}]", setup)
-            if not ok:
-                continue
-        ok, t_student = lad.attempt(f"student timed region [{s_rung}]", timed_student)
-        if ok:
-            break
-    if t_student is None:            # no gradient exchange works: the student figure is null, the line still stands
-        t_student = float("nan")
-    if world > 1 and t_student == t_student:
-        tt = torch.tensor([t_student], device=dev, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        t_student = float(tt.item())
-    student_steps_per_s = world * k_student / t_student      # B-row batches processed per second, whole job
-    student_local_ms = None
-    if world > 1 and not args.student_global_bn and t_student == t_student:
-        # diagnostic, outside the timed region: the same step WITHOUT the gradient exchange (a second engine on a copy of the model: one
-        # C call per step, Adam fused) -- the difference to the timed step is what data parallelism costs per step (exposed all-reduce
-        # + the two-call form of the step), max over ranks
-        s2 = Model(dict(model_name=sd["name"], num_layers=3, feat_dim=sd["dims"][0], hidden_dim=sd["dims"][1], label_dim=sd["dims"][-1],
-                        dropout_ratio=sd["dropout"], norm_type="batch", device=dev))
-        s2.train()
-        e2 = StudentEngine(s2, torch.optim.Adam(s2.parameters(), lr=sd["lr"], weight_decay=sd["wd"]), sd["batch"])
-        k2 = min(k_student, 200)
-        for i in range(3):
-            e2.step(feats, perm[i % nb], ops.LOSS_KL, out_t, 1.0)
-        barrier()
-        t0 = time.perf_counter()
-        for i in range(k2):
-            e2.step(feats, perm[i % nb], ops.LOSS_KL, out_t, 1.0)
-        torch.cuda.synchronize()
-        tt = torch.tensor([(time.perf_counter() - t0) / k2], device=dev, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        student_local_ms = 1e3 * float(tt.item())
-        del s2, e2
+        if world == 1:
+            s_rungs = [("1 GPU", None)]
+        elif args.student_global_bn:     # one N*B-row batch split over ranks, global BN statistics, summed gradients
+            s_rungs = [("batch split, global BatchNorm statistics", lambda: eng.enable_batch_split(world, rank))]
+        elif args.no_grad_overlap:       # data parallel: every rank runs its own B-row batches, gradients averaged over ranks
+            s_rungs = [("one all-reduce after the backward", student_after_backward)]
+        else:
+            s_rungs = [("all-reduce from inside the backward", student_overlapped), ("one all-reduce after the backward", student_after_backward)]
+        t_student, s_rung = None, None
+        for s_rung, setup in s_rungs:
+            if setup is not None:
+                ok, _ = lad.attempt(f"student set-up [{s_rung}]", setup)
+                if not ok:
+                    continue
+            ok, t_student = lad.attempt(f"student timed region [{s_rung}]", timed_student)
+            if ok:
+                break
+        if t_student is None:            # no gradient exchange works: the student figure is null, the line still stands
+            t_student = float("nan")
+        if world > 1 and t_student == t_student:
+            tt = torch.tensor([t_student], device=dev, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            t_student = float(tt.item())
+        student_steps_per_s = world * k_student / t_student      # B-row batches processed per second, whole job
+        student_local_ms = None
+        if world > 1 and not args.student_global_bn and t_student == t_student:
+            # diagnostic, outside the timed region: the same step WITHOUT the gradient exchange (a second engine on a copy of the model: one
+            # C call per step, Adam fused) -- the difference to the timed step is what data parallelism costs per step (exposed all-reduce
+            # + the two-call form of the step), max over ranks
+            s2 = Model(dict(model_name=sd["name"], num_layers=3, feat_dim=sd["dims"][0], hidden_dim=sd["dims"][1], label_dim=sd["dims"][-1],
+                            dropout_ratio=sd["dropout"], norm_type="batch", device=dev))
+            s2.train()
+            e2 = StudentEngine(s2, torch.optim.Adam(s2.parameters(), lr=sd["lr"], weight_decay=sd["wd"]), sd["batch"])
+            k2 = min(k_student, 200)
+            for i in range(3):
+                e2.step(feats, perm[i % nb], ops.LOSS_KL, out_t, 1.0)
+            barrier()
+            t0 = time.perf_counter()
+            for i in range(k2):
+                e2.step(feats, perm[i % nb], ops.LOSS_KL, out_t, 1.0)
+            torch.cuda.synchronize()
+            tt = torch.tensor([(time.perf_counter() - t0) / k2], device=dev, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            student_local_ms = 1e3 * float(tt.item())
+            del s2, e2
 
     if rank != 0:
         if world > 1:
@@ -421,31 +443,32 @@ def run_products(args, rank, world, dev, barrier):
                      + ", 47-wide projection of layer 3 (chunked, overlapped with layer 2); layer 2 needs none")
                     if args.exchange == "allgather" else
                     "halo all-to-all of the narrow side of each layer boundary, only the remote rows this rank's edges reference"},
-        "student": {"metric": f"student distill steps/s ({sd['name']} {'-'.join(map(str, sd['dims']))}, B={sd['batch']} per rank, dropout "
-                              f"{sd['dropout']}, BN, KL soft-label step incl. gather, fwd, loss, bwd, Adam)",
-                    "value": student_steps_per_s, "unit": "steps/s", "steps": k_student, "warmup": w_student,
-                    "ms_per_step": 1e3 * t_student / k_student, "global_batch": world * sd["batch"],
-                    "batchnorm": "global batch statistics (exchange hook)" if (world > 1 and args.student_global_bn)
-                                 else "per-rank batch statistics",
-                    "scaling": "weak",
-                    "gradient_exchange": None if world == 1 else ("one all-reduce after the backward" if "after" in (s_rung or "") and not args.student_global_bn
-                                                                  else "weight gradients >= 1 MB all-reduced from inside the backward (grad_ready hook), the rest after it"),
-                    "local_step_ms": student_local_ms,
-                    "dp_overhead_ms": None if student_local_ms is None else 1e3 * t_student / k_student - student_local_ms,
-                    "gflop_per_step": 3 * 2 * sd["batch"] * sum(a * b for a, b in zip(sd["dims"][:-1], sd["dims"][1:])) / 1e9},
     }
-    result["student"]["tflops"] = result["student"]["gflop_per_step"] * k_student / t_student / 1e3      # per GPU
-    result["student"]["frac_of_fp32_mfma_peak"] = result["student"]["tflops"] / 157.3      # v_mfma_f32_32x32x2_f32 dense peak
-    if t_student != t_student:      # every gradient-exchange rung failed: null figures, the errors are under exchange.ladder
-        for k_ in ("value", "ms_per_step", "tflops", "frac_of_fp32_mfma_peak"):
-            result["student"][k_] = None
+    if full:
+        result["student"] = {"metric": f"student distill steps/s ({sd['name']} {'-'.join(map(str, sd['dims']))}, B={sd['batch']} per rank, dropout "
+                                       f"{sd['dropout']}, BN, KL soft-label step incl. gather, fwd, loss, bwd, Adam)",
+                             "value": student_steps_per_s, "unit": "steps/s", "steps": k_student, "warmup": w_student,
+                             "ms_per_step": 1e3 * t_student / k_student, "global_batch": world * sd["batch"],
+                             "batchnorm": "global batch statistics (exchange hook)" if (world > 1 and args.student_global_bn)
+                                          else "per-rank batch statistics",
+                             "scaling": "weak",
+                             "gradient_exchange": None if world == 1 else ("one all-reduce after the backward" if "after" in (s_rung or "") and not args.student_global_bn
+                                                                           else "weight gradients >= 1 MB all-reduced from inside the backward (grad_ready hook), the rest after it"),
+                             "local_step_ms": student_local_ms,
+                             "dp_overhead_ms": None if student_local_ms is None else 1e3 * t_student / k_student - student_local_ms,
+                             "gflop_per_step": 3 * 2 * sd["batch"] * sum(a * b for a, b in zip(sd["dims"][:-1], sd["dims"][1:])) / 1e9}
+        result["student"]["tflops"] = result["student"]["gflop_per_step"] * k_student / t_student / 1e3      # per GPU
+        result["student"]["frac_of_fp32_mfma_peak"] = result["student"]["tflops"] / 157.3      # v_mfma_f32_32x32x2_f32 dense peak
+        if t_student != t_student:      # every gradient-exchange rung failed: null figures, the errors are under exchange.ladder
+            for k_ in ("value", "ms_per_step", "tflops", "frac_of_fp32_mfma_peak"):
+                result["student"][k_] = None
 
     if chunked is not None:
         result["chunked"] = chunked
     # ---- roofline of the dominant kernel (N = 1): per-launch HIP events from the timed region -------------
-    if world == 1 and timing:
-        full = C.GRAPH == "ogbn-products" and args.scale == 1.0
-        result["roofline"] = roofline_object(timing, nnz, n, with_traffic=full)
+    if world == 1 and full and timing:
+        with_traffic = C.GRAPH == "ogbn-products" and args.scale == 1.0
+        result["roofline"] = roofline_object(timing, nnz, n, with_traffic=with_traffic)
         result["roofline"].update(hbm_estimate(result["roofline"], g))
         if args.reorder != "none":
             result["roofline_reordered"] = reordered_leg(args, g, feats, teacher, FullNeighborLoader, ops, data)
@@ -454,29 +477,29 @@ def run_products(args, rank, world, dev, barrier):
             result["roofline_clustered"] = clustered_leg(args, n, teacher, FullNeighborLoader, ops, data, dev)
 
     # ---- the B = 512 students of BASELINE configs[2] (latency-bound: steps/s, not an MFMA fraction) -- an extra object ----
-    if world == 1 and not args.no_small_students:
+    if world == 1 and full and not args.no_small_students:
         result["students_small"] = small_student_leg(dev, Model, StudentEngine, ops)
 
     # ---- sampled-block teacher TRAINING (SURVEY 8f rows 1+2; reference train_sage, train_and_eval.py:32-56) -- an extra object ----
-    if world == 1 and not args.no_train_leg:
+    if world == 1 and full and not args.no_train_leg:
         result["teacher_training"] = teacher_training_leg(g, feats, labels, dev, data)
 
     # ---- CPU baseline on the host cores (oracle = 'port'; bounded sample) ---------------------------------
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(sd, dev, min(C.CPU_SAMPLE_SCALE, args.scale), 1.0 if args.scale >= 1.0 else 0.1)
 
     # ---- BASELINE configs[1]+[2] and configs[4] on the same clock (N = 1, full-size products run): child processes of this one, after
     #      this process has released its device memory (the XL rank-forward keeps 228 GB resident).  A failed leg is reported, not fatal.
-    if world == 1 and C.GRAPH == "ogbn-products" and args.scale == 1.0 and args.locality == 0:
+    if world == 1 and full and C.GRAPH == "ogbn-products" and args.scale == 1.0 and args.locality == 0:
         del g, feats, labels, out_t, teacher, student, eng, opt, perm, loader, shards
         import gc
         gc.collect()
         torch.cuda.empty_cache()
         if not args.no_arxiv_leg:
             result["arxiv"] = child_leg("arxiv", ["--workload", "arxiv", "--steps", "200", "--warmup", "5", "--student-steps-per-step", "10", "--no-cpu-baseline",
-                                                   "--no-train-leg", "--no-small-students", "--reorder", "none"], 600)
+                                                   "--no-train-leg", "--no-small-students", "--reorder", "none", "--full"], 600)
         if not args.no_xl_leg:
-            result["xl"] = child_leg("xl", ["--workload", "xl", "--steps", "5", "--warmup", "1"], 900)
+            result["xl"] = child_leg("xl", ["--workload", "xl", "--steps", "5", "--warmup", "1", "--full"], 900)
 
     if ops.PLACEMENT_LOG:       # which allocations were tried for the gathered matrices, and the probe ms of each (set-up, outside every timed region)
         result["placement"] = list(ops.PLACEMENT_LOG)

@@ -97,3 +97,22 @@ def test_checked_backend_catches_a_wrong_launch_and_accepts_right_ones():
     c3 = bench.CheckedBackend(OffByALittle(), sample=n)
     c3.gemm(agg, w)
     assert not c3.ok and c3.report[0]["max_abs_diff_vs_fp64"] > 5e-4
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: a seeded row sample of the teacher output (first 47 columns of the padded rows, fp32) and the sampled
+    rows' global ids (float64), the same sample every time; at the products shape the files stay far below 64 MB."""
+    from benchlib.products import DUMP_ROWS, dump_outputs
+    n = 200000
+    out = torch.arange(n * 48, dtype=torch.float32).view(n, 48)
+    dump_outputs(str(tmp_path / "a"), out, 0)
+    dump_outputs(str(tmp_path / "b"), out, 5)
+    y, rows = np.load(tmp_path / "a" / "teacher_out.npy"), np.load(tmp_path / "a" / "teacher_out_rows.npy")
+    assert y.dtype == np.float32 and rows.dtype == np.float64 and y.shape == (DUMP_ROWS, 47) and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(y, out.numpy()[rows.astype(np.int64), :47])
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "teacher_out.npy"), y)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "teacher_out_rows.npy"), rows + 5)
+    assert DUMP_ROWS * (47 * 4 + 8) < 64 << 20
+    small = torch.ones(10, 48)
+    dump_outputs(str(tmp_path / "c"), small, 0)
+    assert np.load(tmp_path / "c" / "teacher_out.npy").shape == (10, 47)

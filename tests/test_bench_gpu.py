@@ -37,7 +37,7 @@ def _run(cmd, env=None):
 
 
 def test_bench_single_gpu_line():
-    out = _run([sys.executable, "bench.py", "--scale", "0.02", "--steps", "2", "--warmup", "1"])
+    out = _run([sys.executable, "bench.py", "--scale", "0.02", "--steps", "2", "--warmup", "1", "--full"])
     assert REQUIRED <= out.keys()
     assert out["n_gpus"] == 1 and out["steps"] == 2 and out["unit"] == "edges/s" and out["value"] > 0
     assert "workload" in out["config"] and out["dtype"] == "f32" and out["vs_baseline"] is None
@@ -70,7 +70,7 @@ def test_bench_single_gpu_line():
 def test_bench_two_ranks_driver_launch_line(extra):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                "--master-port", str(port), "bench.py", "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1"] + extra,
+                "--master-port", str(port), "bench.py", "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1", "--full"] + extra,
                env={"GLNN_SINGLE_DEVICE": "1", "GLNN_DIST_BACKEND": "gloo"})
     assert REQUIRED <= out.keys()
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["scaling"] == "strong"
@@ -118,7 +118,7 @@ def test_bench_two_ranks_survive_failing_collectives():
     and the line says which rungs ran and what failed above them."""
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                "--master-port", str(port), "bench.py", "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1"],
+                "--master-port", str(port), "bench.py", "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1", "--full"],
                env={"GLNN_SINGLE_DEVICE": "1", "GLNN_DIST_BACKEND": "gloo", "GLNN_BENCH_INJECT": "async:1000000,grad_overlap:1000000,probe:1"})
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["verified"] is True and out["verify"]["max_abs_diff_vs_unsharded"] <= 1e-4
     ex = out["exchange"]
@@ -137,7 +137,7 @@ def test_bench_two_ranks_fall_back_to_one_launch_per_chunk_when_the_signals_fail
     fails on a node (injected: every wait raises), the ladder's next rung runs the same autotuned forms with one launch per chunk."""
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                "--master-port", str(port), "bench.py", "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1"],
+                "--master-port", str(port), "bench.py", "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1", "--full"],
                env={"GLNN_SINGLE_DEVICE": "1", "GLNN_DIST_BACKEND": "gloo", "GLNN_BENCH_INJECT": "signal:1000000"})
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["verified"] is True
     lad = out["exchange"]["ladder"]
@@ -158,7 +158,7 @@ def test_bench_two_ranks_print_a_null_line_when_no_all_gather_works():
 def test_bench_self_launches_its_ranks(l1):
     """`python bench.py --gpus 2` with NO launcher: bench.py spawns the two ranks itself (it used to run one rank and
     print n_gpus 1); both layer-1 exchange variants; the sharded output verifies against the unsharded forward."""
-    out = _run([sys.executable, "bench.py", "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1", "--layer1-exchange", l1],
+    out = _run([sys.executable, "bench.py", "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1", "--layer1-exchange", l1, "--full"],
                env={"GLNN_SINGLE_DEVICE": "1", "GLNN_DIST_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["rccl_ranks"] == 2 and out["backend"] == "gloo"
     assert [d["rank"] for d in out["devices"]] == [0, 1]
@@ -175,7 +175,7 @@ def test_bench_halo_exchange_with_partitioner_two_ranks():
     overlapped exchange: the sharded output verifies against the unsharded forward on the relabelled graph, and the halo moves
     fewer bytes than an all-gather of the same rows would (n_pad * 148 floats per rank and forward)."""
     out = _run([sys.executable, "bench.py", "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1", "--exchange", "halo",
-                "--locality", "0.95", "--shuffle-ids", "--partition", "lp"], env={"GLNN_SINGLE_DEVICE": "1", "GLNN_DIST_BACKEND": "gloo"})
+                "--locality", "0.95", "--shuffle-ids", "--partition", "lp", "--full"], env={"GLNN_SINGLE_DEVICE": "1", "GLNN_DIST_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["verified"] is True and out["config"]["partition"] == "lp" and out["config"]["halo_overlap"] is True
     assert out["config"]["partition_seconds"] > 0
     full = 4e-9 * out["config"]["nodes"] * 148 / 2          # what one rank would receive from the other under the all-gather
@@ -235,3 +235,22 @@ def test_bench_xl_two_ranks_driver_launch_line():
     assert cfg["shards"] == 2 and cfg["nodes_total"] == 2 * cfg["rows_per_gpu"] and "EMULATED" not in cfg["parallelism"]
     assert out["per_forward"]["emulated_fill_ms"] is None and out["per_forward"]["collectives"] == 8
     assert abs(out["value"] - 2 * 3 * cfg["nnz_per_gpu"] * 2 / (out["ms_per_step"] * 2e-3)) < 1e-3 * out["value"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_identical_outputs(tmp_path):
+    """Without --full the line carries the headline figure only (no self-check, no student, no extra objects), --steps is the number
+    of timed forwards, and --dump-outputs writes the last timed forward's sampled rows: the same arrays from two runs with the same
+    arguments."""
+    outs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = _run([sys.executable, "bench.py", "--scale", "0.02", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert REQUIRED <= out.keys() and out["steps"] == 3 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+        assert abs(out["value"] - out["config"]["edges_aggregated_per_step"] / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+        assert out["verified"] is None and not {"student", "roofline", "cpu_baseline", "teacher_training", "students_small", "chunked"} & out.keys()
+        y, rows = np.load(d / "teacher_out.npy"), np.load(d / "teacher_out_rows.npy")
+        assert y.dtype == np.float32 and rows.dtype == np.float64 and y.shape == (rows.shape[0], 47) and np.isfinite(y).all()
+        assert rows.shape[0] == min(out["config"]["nodes"], 131072) and (np.diff(rows) > 0).all() and rows[-1] < out["config"]["nodes"]
+        outs.append((y, rows))
+    np.testing.assert_array_equal(outs[0][1], outs[1][1])
+    np.testing.assert_array_equal(outs[0][0], outs[1][0])
