@@ -74,6 +74,12 @@ SIGNATURES = {
     "glnn_block_build_ids": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
     "glnn_csr_transpose_workspace_bytes": [c_i64, c_i64],
     "glnn_csr_transpose": [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "glnn_appnp_prop_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_u32, c_int,
+                            c_vp, c_i64, c_vp],
+    "glnn_appnp_prop_bwd_f32": [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_f32, c_f32, c_u32, c_int, c_int,
+                                c_vp, c_i64, c_vp, c_i64, c_vp],
+    "glnn_csr_transpose_eids": [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "glnn_edge_drop_mask_u8": [c_i64, c_int, c_f32, c_u32, c_vp, c_vp],
     "glnn_gather_rows_f32": [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp],
     "glnn_scatter_rows_f32": [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp],
 }

@@ -181,3 +181,73 @@ def norm_act_drop(z, bn, p, relu=True):
     if bn is not None:
         return _NormActDropFn.apply(z, bn.weight, bn.bias, bn, float(p), seed, relu)
     return _NormActDropFn.apply(z, None, None, None, float(p), seed, relu)
+
+
+# ------------------------------------------------------------------------------------------ APPNP propagation (dgl APPNPConv)
+def appnp_fwd(g, h0, k, alpha, edge_drop=0.0, seed=0):
+    """h_K of K power iterations  h_t = (1 - alpha) D_in^-1/2 M_t A D_out^-1/2 h_{t-1} + alpha h0  (reference models.py:342, dgl
+    APPNPConv): K launches of glnn_appnp_prop_f32 ping-ponging two buffers; M_t = the edge-dropout mask of iteration t (edge_drop = 0: none)."""
+    h0 = ops.as_feat(h0)
+    n, d = h0.shape
+    if k == 0:
+        out = ops.feat_empty(n, d, h0.device)
+        out.copy_(h0)
+        return out
+    in_norm, out_norm = g.degree_norms()
+    nnz = g.num_edges()
+    bufs = [ops.feat_empty(n, d, h0.device) for _ in range(min(k, 2))]
+    x = h0
+    for t in range(1, k + 1):
+        x = ops.appnp_propagate(g.indptr, g.indices, x, nnz, t, in_norm, out_norm, h0, alpha, edge_drop, seed, x_scaled=t > 1,
+                                last=t == k, out=bufs[t % len(bufs)])
+    return x
+
+
+def appnp_bwd(g, dy, k, alpha, edge_drop=0.0, seed=0):
+    """dL/dh0 from dL/dh_K: the propagation is linear, so no iterate is saved --  acc = 0; for t = K..1: acc += alpha g_t,
+    g_{t-1} = (1 - alpha) P_t^T g_t;  dL/dh0 = g_0 + acc.  K launches of glnn_appnp_prop_bwd_f32 over the transposed graph with edge ids
+    (each launch evaluates the same edge mask as forward iteration t)."""
+    dy = ops.as_feat(dy)
+    n, d = dy.shape
+    if k == 0:
+        return dy
+    in_norm, out_norm = g.degree_norms()
+    tg, t_eids = g.transposed_eids()
+    nnz = g.num_edges()
+    acc = ops.feat_empty(n, d, dy.device) if k > 1 else None
+    bufs = [ops.feat_empty(n, d, dy.device) for _ in range(min(k, 2))]
+    x = dy
+    for t in range(k, 0, -1):
+        x = ops.appnp_propagate_bwd(tg.indptr, tg.indices, t_eids, x, nnz, t, t == k, in_norm, out_norm, alpha, edge_drop, seed, acc=acc,
+                                    out=bufs[t % len(bufs)])
+    return x
+
+
+class AppnpPropFn(torch.autograd.Function):
+    """APPNPConv(k, alpha, edge_drop) as a differentiable op on the HIP path; the backward replays the forward's edge masks from (seed, t)."""
+
+    @staticmethod
+    def forward(ctx, graph, h0, k, alpha, edge_drop, seed):
+        ctx.graph, ctx.k, ctx.alpha, ctx.edge_drop, ctx.seed = graph, k, alpha, edge_drop, seed
+        return appnp_fwd(graph, h0.detach(), k, alpha, edge_drop, seed)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None
+        dh0 = appnp_bwd(ctx.graph, dy.contiguous(), ctx.k, ctx.alpha, ctx.edge_drop, ctx.seed)
+        return None, dh0, None, None, None, None
+
+
+def appnp_propagate(graph, h0, k, alpha, edge_drop, training):
+    """APPNPConv forward of the reference's APPNP (models.py:342): edge dropout only in training; its counter-based seed is drawn like
+    norm_act_drop's (torch.initial_seed() and a call counter)."""
+    p = float(edge_drop) if training else 0.0
+    seed = 0
+    if p > 0:
+        _drop_counter[0] += 1
+        seed = (int(torch.initial_seed()) * 0x85EBCA77 + _drop_counter[0] * 0x9E3779B1 + 0x41505050) & 0xFFFFFFFF
+    if training and torch.is_grad_enabled() and h0.requires_grad:
+        return AppnpPropFn.apply(graph, h0, int(k), float(alpha), p, seed)
+    with torch.no_grad():
+        return appnp_fwd(graph, h0, int(k), float(alpha), p, seed)

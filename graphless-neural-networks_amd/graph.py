@@ -136,6 +136,17 @@ class CSRGraph:
             self._cache[key] = t
         return self._cache[key]
 
+    def transposed_eids(self):
+        """(transposed graph, t_eids): transposed(False)'s CSR built with the original edge id (CSR position) of every transposed entry
+        (glnn_csr_transpose_eids), cached -- what the APPNP backward gathers over, evaluating each edge's dropout mask by its id."""
+        if "tr_eids" not in self._cache:
+            from . import ops
+            t_indptr, t_indices, t_eids = ops.csr_transpose_eids(self.indptr, self.indices, self.n_dst, self.n_src, self.num_edges())
+            t = CSRGraph(t_indptr, t_indices, self.n_src, self.n_dst)
+            t._nnz = self.num_edges()
+            self._cache["tr_eids"] = (t, t_eids)
+        return self._cache["tr_eids"]
+
     def reverse(self):
         """dgl-style reversed graph (every edge u->v becomes v->u): the transposed CSR."""
         if self.indptr.is_cuda:

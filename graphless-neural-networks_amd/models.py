@@ -6,7 +6,8 @@ forward_fitnet / inference`, and state_dict key names (encoder.layers.{i}.weight
 .fc_neigh.weight|bias, encoder.norms.{i}.*).  What changed is where the arithmetic runs: every
 Linear / SAGEConv / GraphConv / BatchNorm(eval) / ReLU goes through libglnn_hip.so.
 
-GAT / APPNP (ablation-only teachers) are out of scope and raise."""
+APPNP (an ablation teacher, models.py:282-344) runs its MLP trunk on the same kernels and its K-step propagation on
+csrc/appnp.hip (docs/APPNP_SEMANTICS.md).  GAT (ablation-only) is out of scope and raises."""
 import contextlib
 
 import torch
@@ -14,7 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .autograd import linear_fn, norm_act_drop
+from .autograd import appnp_propagate, linear_fn, norm_act_drop
 from .nn import GraphConv, SAGEConv
 
 
@@ -432,6 +433,26 @@ class GCN(nn.Module):
         return h_list, h
 
 
+class APPNP(MLP):
+    """reference models.py:282-344: the MLP trunk (same layers, norms and state_dict keys) followed by dgl APPNPConv(k, alpha, edge_drop)
+    -- K power iterations of personalised-PageRank propagation with a fresh edge-dropout mask per iteration in training."""
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", edge_drop=0.5,
+                 alpha=0.1, k=10):
+        super().__init__(num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, norm_type)
+        self.activation = activation
+        self.k, self.alpha, self.edge_drop = int(k), float(alpha), float(edge_drop)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for layer in self.layers:          # (the reference re-initialises its Linears once more: the RNG stream is kept in step)
+            layer.reset_parameters()
+
+    def forward(self, g, feats):
+        h_list, h = super().forward(feats)
+        return h_list, appnp_propagate(g, h, self.k, self.alpha, self.edge_drop, self.training)
+
+
 class Model(nn.Module):
     """Wrapper of different models (reference models.py:347-429)."""
 
@@ -446,8 +467,10 @@ class Model(nn.Module):
             self.encoder = SAGE(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
         elif "GCN" in conf["model_name"]:
             self.encoder = GCN(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
-        elif "GAT" in conf["model_name"] or "APPNP" in conf["model_name"]:
-            raise NotImplementedError(f"{conf['model_name']}: ablation-only teacher (reference models.py:202-344), "
+        elif "APPNP" in conf["model_name"]:
+            self.encoder = APPNP(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
+        elif "GAT" in conf["model_name"]:
+            raise NotImplementedError(f"{conf['model_name']}: ablation-only teacher (reference models.py:202-279), "
                                       "outside the MI355X hot-path scope (SURVEY.md section 2 row 5)")
         else:
             raise ValueError(f"Unknown model_name {conf['model_name']}")

@@ -1006,3 +1006,84 @@ def scatter_rows(x, rows, out):
     rc = _lib.lib().glnn_scatter_rows_f32(_p(x), _ld(x), _p(rows), rows.numel(), d, _p(out), _ld(out), _stream())
     _lib.check(rc, "glnn_scatter_rows_f32")
     return out
+
+
+# --------------------------------------------------------------------------------------------- APPNP propagation
+def _appnp_check(indptr, indices, x, n, name):
+    _need_cuda(indptr, indices, x)
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32:
+        raise ValueError(f"{name}: indptr must be int64 and indices int32")
+    if x.shape[0] < n:
+        raise ValueError(f"{name}: x must hold the graph's {n} rows")
+
+
+def appnp_propagate(indptr, indices, x, nnz, t, dst_norm, src_norm, h0, alpha, edge_drop=0.0, seed=0, x_scaled=True, last=False, out=None):
+    """ONE forward iteration t (1-based) of APPNP propagation, glnn_appnp_prop_f32 (square graph, n = x.shape[0]):
+    h_t = (1 - alpha) D_in^-1/2 M_t A D_out^-1/2 h_{t-1} + alpha h0.  x is the previous iteration's stored output -- already scaled by
+    src_norm (x_scaled) -- or h0 itself at t = 1 (x_scaled=False: the kernel multiplies by src_norm per edge).  The stored output is
+    src_norm * h_t unless `last`."""
+    x = as_feat(x)
+    h0 = as_feat(h0)
+    n, d = h0.shape
+    _appnp_check(indptr, indices, x, n, "appnp_propagate")
+    _need_cuda(dst_norm, src_norm, h0, out)
+    if x.shape[1] != d:
+        raise ValueError("appnp_propagate: x and h0 must have the same width")
+    if out is None:
+        out = feat_empty(n, d, x.device)
+    _mat(out, "appnp_propagate out")
+    with _Timed("appnp_prop", d=d, n_dst=n, nnz=int(nnz), edge_drop=float(edge_drop)):
+        rc = _lib.lib().glnn_appnp_prop_f32(_p(indptr), _p(indices), n, int(nnz), _p(x), _ld(x), d,
+                                            None if x_scaled else _p(_vec(src_norm, n, "src_norm")), _p(_vec(dst_norm, n, "dst_norm")),
+                                            None if last else _p(_vec(src_norm, n, "src_norm")), _p(h0), _ld(h0), float(alpha),
+                                            float(edge_drop), int(seed) & 0xFFFFFFFF, int(t), _p(out), _ld(out), _stream())
+    _lib.check(rc, "glnn_appnp_prop_f32")
+    return out
+
+
+def appnp_propagate_bwd(t_indptr, t_indices, t_eids, x, nnz, t, first, dst_norm, src_norm, alpha, edge_drop=0.0, seed=0, acc=None,
+                        out=None):
+    """ONE backward iteration t (called for t = K .. 1) over the transposed graph with its edge ids (csr_transpose_eids),
+    glnn_appnp_prop_bwd_f32.  first (t = K): x = dL/dh_K unscaled and the running sum starts at alpha * x; otherwise x is the previous
+    call's output dst_norm * g_t and `acc` the running sum (updated in place).  Returns out: dst_norm * g_{t-1} for t > 1, dL/dh0 at t = 1."""
+    x = as_feat(x)
+    n, d = x.shape
+    _appnp_check(t_indptr, t_indices, x, n, "appnp_propagate_bwd")
+    _need_cuda(t_eids, dst_norm, src_norm, acc, out)
+    if out is None:
+        out = feat_empty(n, d, x.device)
+    _mat(out, "appnp_propagate_bwd out")
+    if acc is not None:
+        _mat(acc, "appnp_propagate_bwd acc")
+    with _Timed("appnp_prop_bwd", d=d, n_dst=n, nnz=int(nnz), edge_drop=float(edge_drop)):
+        rc = _lib.lib().glnn_appnp_prop_bwd_f32(_p(t_indptr), _p(t_indices), _p(t_eids), n, int(nnz), _p(x), _ld(x), d,
+                                                _p(_vec(dst_norm, n, "dst_norm")) if first else None, _p(_vec(src_norm, n, "src_norm")),
+                                                _p(_vec(dst_norm, n, "dst_norm")) if t > 1 else None, float(alpha), float(edge_drop),
+                                                int(seed) & 0xFFFFFFFF, int(t), 1 if first else 0, _p(acc), 0 if acc is None else _ld(acc),
+                                                _p(out), _ld(out), _stream())
+    _lib.check(rc, "glnn_appnp_prop_bwd_f32")
+    return out
+
+
+def csr_transpose_eids(indptr, indices, n_dst, n_src, nnz):
+    """glnn_csr_transpose_eids: (t_indptr [n_src+1], t_indices [nnz], t_eids [nnz]) -- csr_transpose plus the original edge id (CSR
+    position) of every transposed entry."""
+    _need_cuda(indptr, indices)
+    dev = indptr.device
+    nnz = int(nnz)
+    t_indptr = torch.empty(n_src + 1, dtype=torch.int64, device=dev)
+    t_indices, t_eids = _i32(nnz, dev), _i32(nnz, dev)
+    wsb = int(_lib.lib().glnn_csr_transpose_workspace_bytes(n_src, nnz))
+    ws = torch.empty((wsb + 7) // 8, dtype=torch.int64, device=dev)
+    rc = _lib.lib().glnn_csr_transpose_eids(_p(indptr), _p(indices) if nnz else None, n_dst, n_src, nnz, _p(t_indptr),
+                                            _p(t_indices) if nnz else None, _p(t_eids) if nnz else None, _p(ws), ws.numel() * 8, _stream())
+    _lib.check(rc, "glnn_csr_transpose_eids")
+    return t_indptr, t_indices, t_eids
+
+
+def edge_drop_mask(nnz, t, edge_drop, seed, device):
+    """glnn_edge_drop_mask_u8: uint8 [nnz], 1 = edge kept in iteration t (1-based) -- the mask the propagation kernels evaluate."""
+    mask = torch.empty(max(int(nnz), 1), dtype=torch.uint8, device=device)[:int(nnz)]
+    rc = _lib.lib().glnn_edge_drop_mask_u8(int(nnz), int(t), float(edge_drop), int(seed) & 0xFFFFFFFF, _p(mask) if nnz else None, _stream())
+    _lib.check(rc, "glnn_edge_drop_mask_u8")
+    return mask

@@ -35,7 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .autograd import graphconv_bwd, graphconv_fwd
+from .autograd import appnp_bwd, appnp_fwd, graphconv_bwd, graphconv_fwd
 from .student import _mix32
 
 
@@ -47,8 +47,8 @@ def check_supported(model, criterion, optimizer):
     """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE / GCN teacher."""
     enc = model.encoder
     name = model.model_name
-    if "MLP" in name or not ("SAGE" in name or "GCN" in name):
-        raise NotImplementedError(f"TeacherEngine: SAGE or GCN teachers only (got {name})")
+    if "MLP" in name or not ("SAGE" in name or "GCN" in name or "APPNP" in name):
+        raise NotImplementedError(f"TeacherEngine: SAGE, GCN or APPNP teachers only (got {name})")
     if not (isinstance(criterion, nn.NLLLoss) and criterion.reduction == "mean" and criterion.weight is None
             and criterion.ignore_index == -100):
         raise NotImplementedError("TeacherEngine: the criterion must be nn.NLLLoss() (reference train_teacher.py:237)")
@@ -58,6 +58,9 @@ def check_supported(model, criterion, optimizer):
     if "SAGE" in name:
         if enc.norm_type not in ("none", "batch") or not _is_relu(enc.activation):
             raise NotImplementedError("TeacherEngine: SAGE with norm_type none|batch and ReLU (the reference's configs)")
+    elif "APPNP" in name:
+        if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
+            raise NotImplementedError("TeacherEngine: APPNP with norm_type none|batch|layer and ReLU (models.py:282-344)")
     else:
         if enc.norm_type not in ("none", "batch", "layer"):      # train.conf.yaml: cora-style GCN none, pokec / penn94 GCN batch
             raise NotImplementedError("TeacherEngine: GCN with norm_type none|batch|layer")
@@ -90,7 +93,7 @@ class _Arena:
 class TeacherEngine:
     def __init__(self, model, optimizer):
         self.model, self.enc, self.opt = model, model.encoder, optimizer
-        self.kind = "sage" if "SAGE" in model.model_name else "gcn"
+        self.kind = "sage" if "SAGE" in model.model_name else ("appnp" if "APPNP" in model.model_name else "gcn")
         self.L = self.enc.num_layers
         self.bn = self.enc.norm_type == "batch"
         self.p = float(self.enc.dropout.p)
@@ -397,6 +400,78 @@ class TeacherEngine:
                 dz, _, _ = ops.bn_relu_bwd(da, y_prev, dz=da, dz_col_sum=self.grad(enc.layers[l - 1].bias))
             else:                          # dropout backward, then the ReLU inside conv l-1 (y > 0 <=> z > 0)
                 dz, _, _ = ops.bn_relu_bwd(da, y_prev, dz=da, drop_p=p, drop_seed=seed_prev, dz_col_sum=self.grad(enc.layers[l - 1].bias))
+
+
+    # ------------------------------------------------------------------------------------------ full-graph APPNP
+    def _edge_seed(self, step=None):
+        """The edge-dropout seed of step `step` (default: the current one): a stream of its own, apart from the hidden-layer dropout seeds
+        _seed(layer) (layer < 8)."""
+        step = self.step_count if step is None else step
+        return _mix32(self.base_seed ^ 0x41505050 ^ _mix32(step * 131 + 0x7F)) if self.enc.edge_drop > 0 else 0
+
+    @torch.no_grad()
+    def step_appnp(self, g, feats, labels, idx_train, lamb=1.0):
+        """The reference's full-graph `train` (train_and_eval.py:12-29) over APPNP (models.py:326-344): the MLP trunk (glnn_gemm_f32 +
+        norm / ReLU / dropout tails), K launches of glnn_appnp_prop_f32, NLL over idx_train, K launches of glnn_appnp_prop_bwd_f32 over
+        the transposed graph, the trunk backward, Adam."""
+        ops._need_cuda(feats, labels, idx_train, g.indptr)
+        self.step_count += 1
+        try:
+            self._step_appnp_body(g, feats, labels, idx_train, lamb)
+        except Exception:
+            self.step_count -= 1          # the step never happened (see step_sage)
+            raise
+        self._adam()
+
+    def _appnp_tail_fwd(self, l, z):
+        """norms[l] -> relu -> dropout of hidden layer l (models.py:334-338)."""
+        if self.enc.norm_type == "layer":
+            seed = self._seed(l)
+            ln = self.enc.norms[l]
+            a, mu, rs = ops.layernorm_fwd(z, ln.weight, ln.bias, eps=ln.eps, relu=True, drop_p=self.p, drop_seed=seed)
+            return a, (mu, rs), seed
+        return self._tail_fwd(l, z)
+
+    def _appnp_tail_bwd(self, l, dh, z, stats, seed, bias_grad):
+        if self.enc.norm_type == "layer":
+            ln = self.enc.norms[l]
+            _, dg, db = ops.layernorm_bwd(dh, z, ln.weight, ln.bias, stats[0], stats[1], relu=True, drop_p=self.p, drop_seed=seed, dz=dh,
+                                         dz_col_sum=bias_grad)
+            self.grad(ln.weight).copy_(dg)
+            self.grad(ln.bias).copy_(db)
+            return dh
+        return self._tail_bwd(l, dh, z, stats, seed, bias_grad)
+
+    def _step_appnp_body(self, g, feats, labels, idx_train, lamb):
+        enc, L = self.enc, self.L
+        n = g.num_dst_nodes()
+        a = ops.as_feat(feats)
+        acts, saved = [a], []
+        for l, layer in enumerate(enc.layers):
+            z = ops.gemm(a, layer.weight, ep_shift=layer.bias)
+            if l != L - 1:
+                a, stats, seed = self._appnp_tail_fwd(l, z)
+                saved.append((z, stats, seed))
+                acts.append(a)
+            else:
+                a = z
+        seed_e = self._edge_seed()
+        logits = appnp_fwd(g, a, enc.k, enc.alpha, enc.edge_drop, seed_e)
+        logits_tr = ops.gather_rows(logits, idx_train)                            # out[idx_train] (train_and_eval.py:22)
+        _, dl = ops.softmax_loss(logits_tr, ops.LOSS_NLL, float(lamb), labels=labels, label_rows=idx_train, loss_out=self.loss_out,
+                                 loss_accum=self.loss_accum, workspace=self.ws_loss)
+        dlog = ops.feat_empty(n, logits.shape[1], self.dev, zero=True)
+        ops.scatter_rows(dl, idx_train, dlog)
+        dz = appnp_bwd(g, dlog, enc.k, enc.alpha, enc.edge_drop, seed_e)         # d/d(trunk logits)
+        for l in range(L - 1, -1, -1):
+            layer = enc.layers[l]
+            ops.gemm_tn(dz, acts[l], out=self.grad(layer.weight), col_sum_a=self.grad(layer.bias))    # dW = dz^T a, db = sum dz
+            if l == 0:
+                break
+            da = ops.gemm(dz, layer.weight, w_is_kn=True)                        # dz W
+            z, stats, seed = saved[l - 1]
+            dz = self._appnp_tail_bwd(l - 1, da, z, stats, seed, None)
+        ops.note_param_write()
 
 
 def get_engine(model, optimizer):

@@ -651,6 +651,40 @@ GLNN_API int glnn_csr_transpose(const int64_t* indptr, const int32_t* indices, i
                                 int64_t nnz, int add_self, int64_t* t_indptr, int32_t* t_indices,
                                 void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * APPNP propagation (dgl APPNPConv(k, alpha, edge_drop) of the reference APPNP teacher, models.py:282-344): K launches of ONE power
+ * iteration each, forward and backward, ping-ponging two buffers.  docs/APPNP_SEMANTICS.md states the arithmetic.  Square graph of n nodes,
+ * indptr / indices the in-CSR (rows = destinations); dst_norm / src_norm = in_deg.clamp(1)^-1/2 / out_deg.clamp(1)^-1/2 (glnn_degrees_f32,
+ * GLNN_DEG_RSQRT_CLAMP1).  Edge mask of step t (1-based): keep edge e iff glnn_edge_drop_mask_u8(t, edge_drop, seed)[e], weight
+ * 1 / (1 - edge_drop); edge_drop = 0 disables it.  nnz = indptr[n] < 2^31.  Deterministic (no float atomics).
+ *
+ * Forward step t:  h_t[i] = (1 - alpha) dst_norm[i] sum_{kept e = (j -> i)} w * xs[j]  +  alpha h0[i],   xs[j] = x_norm[j] x[j] when
+ *   x_norm != NULL (t = 1: x = h0, x_norm = src_norm), else x[j] (x = the previous step's output, already scaled).
+ *   out[i] = src_norm_out[i] h_t[i] when src_norm_out != NULL (t < K: the next step's pre-scaled input), else h_t[i] (t = K). */
+GLNN_API int glnn_appnp_prop_f32(const int64_t* indptr, const int32_t* indices, int64_t n, int64_t nnz, const float* x,
+                                 int64_t ldx, int d, const float* x_norm, const float* dst_norm, const float* src_norm_out,
+                                 const float* h0, int64_t ldh0, float alpha, float edge_drop, uint32_t seed, int t, float* out,
+                                 int64_t ldo, void* stream);
+/* Backward step t (called for t = K .. 1) over the transposed CSR with the original edge ids (glnn_csr_transpose_eids):
+ *   g_{t-1}[j] = (1 - alpha) src_norm[j] sum_{kept e = (j -> i)} w * xs[i],  xs = x_norm * x when x_norm != NULL (first step, t = K:
+ *   x = g_K = dL/dh_K unscaled, x_norm = dst_norm), else x (the previous step's output q_t = dst_norm * g_t).
+ *   first != 0 (t = K): the running sum starts at alpha g_K[j] (read from x); otherwise it is read from acc.
+ *   t > 1: acc[j] += alpha g_{t-1}[j], out[j] = dst_norm_out[j] g_{t-1}[j];   t = 1: out[j] = g_0[j] + acc = dL/dh0 (acc not written).
+ *   acc may be NULL when K = 1 (first and t = 1). */
+GLNN_API int glnn_appnp_prop_bwd_f32(const int64_t* t_indptr, const int32_t* t_indices, const int32_t* t_eids, int64_t n,
+                                     int64_t nnz, const float* x, int64_t ldx, int d, const float* x_norm, const float* src_norm,
+                                     const float* dst_norm_out, float alpha, float edge_drop, uint32_t seed, int t, int first,
+                                     float* acc, int64_t ldacc, float* out, int64_t ldo, void* stream);
+/* glnn_csr_transpose (add_self = 0) plus t_eids [nnz]: the original edge id (CSR position) of every transposed entry; parallel edges keep
+ * ascending edge ids.  t_indptr / t_indices are exactly glnn_csr_transpose's.  Workspace as glnn_csr_transpose.
+ * GLNN_ERR_UNSUPPORTED for nnz >= 2^31. */
+GLNN_API int glnn_csr_transpose_eids(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src,
+                                     int64_t nnz, int64_t* t_indptr, int32_t* t_indices, int32_t* t_eids,
+                                     void* workspace, int64_t workspace_bytes, void* stream);
+/* The APPNP edge keep-mask the propagation kernels evaluate on the fly: mask[e] = 1 iff edge e is kept in step t (t >= 1) under
+ * (edge_drop, seed) -- the role glnn_dropout_mask_u8 plays for the feature dropout (parity tests feed it to the oracle). */
+GLNN_API int glnn_edge_drop_mask_u8(int64_t nnz, int t, float edge_drop, uint32_t seed, uint8_t* mask, void* stream);
+
 /* K7  row gather: out[i,:] = x[rows[i],:]  (feats[idx], reference train_and_eval.py:42,76,
  *     models.py:136) and scatter y[rows[i],:] = x[i,:] (models.py:145). */
 GLNN_API int glnn_gather_rows_f32(const float* x, int64_t ldx, const int64_t* rows, int64_t n_rows,
