@@ -59,6 +59,9 @@ SIGNATURES = {
     "glnn_sage_fwd_bwd_f32": [c_vp, c_vp],
     "glnn_sage_train_step_f32": [c_vp, c_vp, c_vp],
     "glnn_sage_step_ws_bn_floats": [c_i64, c_int],
+    "glnn_sage_fwd_bwd_ln_f32": [c_vp, c_vp, c_vp],
+    "glnn_sage_train_step_ln_f32": [c_vp, c_vp, c_vp, c_vp],
+    "glnn_sage_step_ws_ln_floats": [c_i64, c_int],
     "glnn_act_fwd_f32": [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_f32, c_u32, c_vp, c_i64, c_vp],
     "glnn_norm_drop_fwd_f32": [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_int, c_f32, c_u32, c_vp, c_i64, c_vp],
     "glnn_bn_bwd_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_f32, c_u32, c_vp, c_i64,
@@ -160,6 +163,16 @@ class SageStepDesc(ctypes.Structure):
                 ("ws_loss", c_vp), ("ws_loss_floats", c_i64), ("loss_out", c_vp), ("loss_accum", c_vp)]
 
 
+class SageLnLayer(ctypes.Structure):
+    """glnn_sage_ln_layer of include/glnn_hip.h (field for field)."""
+    _fields_ = [(n, c_vp) for n in ("gamma", "beta", "ggamma", "gbeta", "mean", "rstd")]
+
+
+class SageLnDesc(ctypes.Structure):
+    """glnn_sage_ln_desc of include/glnn_hip.h (field for field)."""
+    _fields_ = [("eps", c_f32), ("reserved", ctypes.c_int32), ("layer", SageLnLayer * SAGE_MAX_LAYERS)]
+
+
 _lib = None
 
 
@@ -189,13 +202,15 @@ def lib():
         h.glnn_csr_transpose_workspace_bytes.restype = c_i64
         h.glnn_layernorm_bwd_workspace_floats.restype = c_i64
         h.glnn_sage_step_ws_bn_floats.restype = c_i64
+        h.glnn_sage_step_ws_ln_floats.restype = c_i64
         h.glnn_last_error.argtypes = []
         h.glnn_last_error.restype = ctypes.c_char_p
         h.glnn_reload_options.argtypes = []
         h.glnn_reload_options.restype = None
         if h.glnn_abi_version() != ABI_VERSION:
             raise GlnnError(f"{LIB_PATH}: ABI version {h.glnn_abi_version()} != {ABI_VERSION} expected by this package; rebuild")
-        for which, mirror in ((0, MlpStepDesc), (1, SageStepDesc), (2, SageLayer), (3, AdamDesc), (4, HubPlanDesc), (5, ChunkSignalsDesc)):
+        for which, mirror in ((0, MlpStepDesc), (1, SageStepDesc), (2, SageLayer), (3, AdamDesc), (4, HubPlanDesc), (5, ChunkSignalsDesc),
+                              (6, SageLnDesc)):
             if h.glnn_struct_bytes(which) != ctypes.sizeof(mirror):
                 raise GlnnError(f"{LIB_PATH}: sizeof({mirror.__name__}) is {h.glnn_struct_bytes(which)} in the library, "
                                 f"{ctypes.sizeof(mirror)} in this binding")

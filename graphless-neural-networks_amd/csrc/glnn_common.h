@@ -45,6 +45,7 @@ struct Options {
   int bn0_in_gemm;          // GLNN_STUDENT_BN0_IN_GEMM=0: the first hidden layer's BatchNorm backward stays partial + apply launches behind a plain input-gradient GEMM
   int signal_fence;         // GLNN_SIGNAL_NO_FENCE=1: glnn_stream_wait_value32 without the empty kernel behind the wait (tests: the negative control)
   int cls_fused;            // GLNN_STUDENT_CLS_FUSED=0: the large-batch classifier stays a split-K GEMM launch + a loss launch (cls_block.hip off)
+  int sage_fuse_ln_bwd;     // GLNN_SAGE_FUSE_LN_BWD=0: the LayerNorm teacher's transposed aggregation writes dh and glnn_layernorm_bwd_f32 follows
 };
 const Options& opts();
 
@@ -212,7 +213,8 @@ int gemm_split_partials(const float* a, int64_t lda, const int64_t* a_rows, cons
                         int64_t workspace_floats, int* splits, void* stream);
 
 // spmm.hip: the SAGE-"gcn" aggregation over rows stored as pre-activations z, the hidden layer's tail applied in the gather
-struct SourceTail { const float* scale; const float* shift; float drop_p; uint32_t drop_seed; };      // scale / shift NULL: no affine (norm "none")
+// scale / shift NULL: no affine (norm "none"); mean / rstd (per SOURCE row, with scale = gamma, shift = beta): the tail is a LayerNorm
+struct SourceTail { const float* scale; const float* shift; float drop_p; uint32_t drop_seed; const float* mean = nullptr; const float* rstd = nullptr; };
 // nnz (optional): the block's edge count; a sparse block (<= 6 in-edges per row on average; plain SAGE aggregation) takes the short-row kernel (same bits)
 int spmm_csr_tail(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, const float* z, int64_t ldz, int d,
                   const SourceTail& tail, float* out, int64_t ldo, void* stream, int64_t nnz = -1);
@@ -237,6 +239,16 @@ int bn_bwd_parts_finish(const float* s1, const float* s2, int nparts, int h, int
 int bn_bwd_deferred_finish(float* ws, int64_t ws_floats, int nslots, int h, int64_t rows, const float* z, int64_t ldz, const float* gamma,
                            const float* mean, const float* rstd, float* dgamma, float* dbeta, float* dz_col_sum, struct BnApplyA* defer_apply,
                            void* stream);
+// spmm.hip: the transposed aggregation A^T dY (col-scaled SUM) whose epilogue is the WHOLE backward of the LayerNorm -> ReLU -> dropout tail
+// of the layer in front: out = dz (dh = the aggregate is never written), per-workgroup column partials of dgamma, dbeta and sum dz in `ws`
+// ([*nslots][3][d], ln_fold's layout).  GLNN_ERR_UNSUPPORTED = nothing launched (d > 256, unaligned rows, ws too small).
+struct LnTail { const float* z; int64_t ldz; const float* mean; const float* rstd; const float* gamma; const float* beta; float drop_p;
+                uint32_t drop_seed; };
+int spmm_csr_ln_dz(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, const float* x, int64_t ldx, int d,
+                   const float* col_scale, const LnTail& tail, float* out, int64_t ldo, float* ws, int64_t ws_floats, int* nslots, void* stream);
+int64_t spmm_csr_ln_dz_ws_floats(int64_t n_dst, int d);
+// layernorm.hip: out_k[c] = sum over the nparts partials ws[p][k][c] (k = dgamma, dbeta, dz_col_sum; NULL outputs skipped), fixed order
+int ln_fold(const float* ws, int nparts, int h, float* dgamma, float* dbeta, float* dz_col_sum, void* stream);
 int spmm_csr_nnz(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, int64_t nnz, const float* x, int64_t ldx, int d,
                  int mode, const float* col_scale, const float* x_self, int64_t ld_self, const int64_t* self_rows, float* out, int64_t ldo,
                  void* stream);

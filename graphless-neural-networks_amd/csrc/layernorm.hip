@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdArgs a) {
   const int nq = (a.h + 255) / 256;                 // float4 per lane
   const int hp = (a.h + 3) & ~3;
   const float* zr = a.z + r * a.ldz;
-  float* yr = a.y + r * a.ldy;
+  float* yr = a.y ? a.y + r * a.ldy : nullptr;
   float4 v[kMaxQuads];
   float s = 0.f;
   if (REGS) {
@@ -98,6 +98,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const LnFwdArgs a) {
     if (a.mean_out) a.mean_out[r] = mean;
     if (a.rstd_out) a.rstd_out[r] = rstd;
   }
+  if (!a.y) return;                                 // statistics only (the consumer applies the tail itself: glnn::spmm_csr_tail)
   if (REGS) {
 #pragma unroll
     for (int j = 0; j < kMaxQuads; ++j) {
@@ -273,10 +274,10 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const float* __restrict__ 
 extern "C" int glnn_layernorm_fwd_f32(const float* z, int64_t ldz, int64_t rows, int h, const float* gamma, const float* beta, float eps,
                                       int relu, float drop_p, uint32_t drop_seed, float* y, int64_t ldy, float* mean_out,
                                       float* rstd_out, void* stream) {
-  GLNN_REQUIRE(z && y, "glnn_layernorm_fwd_f32: null pointer");
+  GLNN_REQUIRE(z && (y || (mean_out && rstd_out)), "glnn_layernorm_fwd_f32: null pointer (y may be NULL only with mean_out and rstd_out)");
   GLNN_REQUIRE(rows >= 0 && h >= 1, "glnn_layernorm_fwd_f32: bad sizes");
   const int64_t hp = (h + 3) & ~3;
-  GLNN_REQUIRE(ldz >= hp && ldy >= hp && ldz % 4 == 0 && ldy % 4 == 0 && glnn::aligned16(z) && glnn::aligned16(y),
+  GLNN_REQUIRE(ldz >= hp && ldz % 4 == 0 && glnn::aligned16(z) && (!y || (ldy >= hp && ldy % 4 == 0 && glnn::aligned16(y))),
                "glnn_layernorm_fwd_f32: rows must be float4 rows (leading dimensions multiples of 4, >= round4(h), 16-byte aligned)");
   GLNN_REQUIRE(gamma || !beta, "glnn_layernorm_fwd_f32: beta without gamma");
   GLNN_REQUIRE(drop_p >= 0.f && drop_p < 1.f && eps > 0.f, "glnn_layernorm_fwd_f32: drop_p in [0,1), eps > 0");
@@ -325,4 +326,12 @@ extern "C" int glnn_layernorm_bwd_f32(const float* da, int64_t ldda, const float
   if (rc != GLNN_OK || !want_cols) return rc;
   hipLaunchKernelGGL(ln_fold_kernel, dim3((h + 63) / 64), dim3(256), 0, st, workspace, nchunks, h, dgamma, dbeta, dz_col_sum);
   return glnn::check_launch("glnn_layernorm_bwd_f32(fold)");
+}
+
+// the fold of glnn_layernorm_bwd_f32 over partials another kernel left in its layout (glnn::spmm_csr_ln_dz)
+int glnn::ln_fold(const float* ws, int nparts, int h, float* dgamma, float* dbeta, float* dz_col_sum, void* stream) {
+  GLNN_REQUIRE(ws && nparts >= 1 && h >= 1, "glnn::ln_fold: bad arguments");
+  hipLaunchKernelGGL(ln_fold_kernel, dim3((h + 63) / 64), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), ws, nparts, h, dgamma, dbeta,
+                     dz_col_sum);
+  return glnn::check_launch("glnn::ln_fold");
 }

@@ -16,10 +16,18 @@
 // last sums of gradient partials -- the split slabs of every weight gradient, the column-sum partials behind the last layer's bias gradient,
 // the loss kernel's per-workgroup losses -- are registered in *pf for it instead of being folded by launches of their own (six launches of
 // ~4.6 us each on the products configuration); every weight gradient then gets its own part of ws_tn (the slabs wait there for Adam).
-static int sage_fwd_bwd_impl(const glnn_sage_step_desc* d, void* stream, glnn::PendingFolds* pf) {
+// ln != NULL (glnn_sage_fwd_bwd_ln_f32): the hidden tails are LayerNorm -> ReLU -> dropout with the parameters and row statistics in *ln
+static int sage_fwd_bwd_impl(const glnn_sage_step_desc* d, void* stream, glnn::PendingFolds* pf, const glnn_sage_ln_desc* ln = nullptr) {
   GLNN_REQUIRE(d && d->x && d->labels && d->dlogits && d->loss_out, "glnn_sage_fwd_bwd_f32: null pointer");
   const int L = d->num_layers;
   GLNN_REQUIRE(L >= 1 && L <= GLNN_SAGE_MAX_LAYERS, "glnn_sage_fwd_bwd_f32: num_layers=%d outside [1,%d]", L, GLNN_SAGE_MAX_LAYERS);
+  if (ln) {
+    GLNN_REQUIRE(!d->batchnorm && ln->eps > 0.f, "glnn_sage_fwd_bwd_ln_f32: batchnorm must be 0 and eps > 0");
+    for (int l = 0; l < L - 1; ++l) {
+      const glnn_sage_ln_layer& q = ln->layer[l];
+      GLNN_REQUIRE(q.gamma && q.beta && q.ggamma && q.gbeta && q.mean && q.rstd, "glnn_sage_fwd_bwd_ln_f32: hidden layer %d: null pointer", l);
+    }
+  }
   const float p = d->dropout_p;
   for (int l = 0; l < L; ++l) {
     const glnn_sage_layer& y = d->layer[l];
@@ -51,7 +59,11 @@ static int sage_fwd_bwd_impl(const glnn_sage_step_desc* d, void* stream, glnn::P
     if (l > 0 && !d->layer[l - 1].h) {
       // the hidden layer in front left only z: its tail (BatchNorm affine, ReLU, dropout) is evaluated in this layer's gather
       const glnn_sage_layer& pv = d->layer[l - 1];
-      const glnn::SourceTail tail = {d->batchnorm ? pv.a_scale : nullptr, d->batchnorm ? pv.a_shift : nullptr, p, pv.drop_seed};
+      glnn::SourceTail tail = {d->batchnorm ? pv.a_scale : nullptr, d->batchnorm ? pv.a_shift : nullptr, p, pv.drop_seed};
+      if (ln) {                                              // LayerNorm: gamma / beta per column, the statistics per source row
+        const glnn_sage_ln_layer& q = ln->layer[l - 1];
+        tail = {q.gamma, q.beta, p, pv.drop_seed, q.mean, q.rstd};
+      }
       GLNN_TRY(glnn::spmm_csr_tail(y.indptr, y.indices, y.n_dst, n_src, pv.z, pv.ldz, d_in, tail, y.agg, y.ld_agg, stream, y.nnz));
     } else {
       GLNN_TRY(glnn::spmm_csr_nnz(y.indptr, y.indices, y.n_dst, n_src, y.nnz, src, ld_src, d_in, GLNN_AGG_SAGE_GCN, nullptr, src, ld_src,
@@ -65,6 +77,11 @@ static int sage_fwd_bwd_impl(const glnn_sage_step_desc* d, void* stream, glnn::P
       GLNN_TRY(glnn_gemm_f32(y.agg, y.ld_agg, nullptr, nullptr, nullptr, 0.f, 0u, y.n_dst, d_in, y.w, d_in, 0, d_out, nullptr, nullptr, y.b, 0,
                              y.z, y.ldz, d->ws_gemm, d->ws_gemm_floats, stream));
     if (l == L - 1) break;
+    if (ln) {          // the row statistics of z (h = tail(z) too when it is materialised)
+      const glnn_sage_ln_layer& q = ln->layer[l];
+      GLNN_TRY(glnn_layernorm_fwd_f32(y.z, y.ldz, y.n_dst, d_out, q.gamma, q.beta, ln->eps, 1, p, y.drop_seed, y.h, y.ldh, q.mean, q.rstd, stream));
+      continue;
+    }
     if (d->batchnorm)
       GLNN_TRY(glnn::bn_stats(y.z, y.ldz, y.n_dst, d_out, y.gamma, y.beta, d->bn_eps, d->bn_momentum, y.running_mean, y.running_var, y.nbt,
                               y.mean, y.rstd, y.a_scale, y.a_shift, d->ws_bn, d->ws_bn_floats, stream, nullptr, nullptr, nullptr, 0, nullptr,
@@ -125,6 +142,29 @@ static int sage_fwd_bwd_impl(const glnn_sage_step_desc* d, void* stream, glnn::P
                            d->dagg, d->ld_dagg, nullptr, 0, stream));
     GLNN_TRY(transposes(l, stream));
     const glnn_sage_layer& prev = d->layer[l - 1];         // its tail produced h_l: dz_{l-1} in place on dh
+    if (ln) {
+      // LayerNorm tail: the transposed aggregation's epilogue is its whole backward (dz stored, dh never written), the column partials of
+      // dgamma / dbeta / db_{l-1} folded behind it; otherwise (GLNN_SAGE_FUSE_LN_BWD=0, hidden width > 256) dh, then the LayerNorm backward
+      const glnn_sage_ln_layer& q = ln->layer[l - 1];
+      int rcl = GLNN_ERR_UNSUPPORTED;
+      if (glnn::opts().sage_fuse_ln_bwd) {
+        const glnn::LnTail tail = {prev.z, prev.ldz, q.mean, q.rstd, q.gamma, q.beta, p, prev.drop_seed};
+        int nslots = 0;
+        rcl = glnn::spmm_csr_ln_dz(y.t_indptr, y.t_indices, y.n_src, y.n_dst, d->dagg, d->ld_dagg, d_in, y.inv_deg, tail, d->dh, d->ld_dh, d->ws_bn,
+                                   d->ws_bn_floats, &nslots, stream);
+        if (rcl != GLNN_OK && rcl != GLNN_ERR_UNSUPPORTED) return rcl;
+        if (rcl == GLNN_OK) GLNN_TRY(glnn::ln_fold(d->ws_bn, nslots, d_in, q.ggamma, q.gbeta, prev.gb, stream));
+      }
+      if (rcl == GLNN_ERR_UNSUPPORTED) {
+        GLNN_TRY(glnn::spmm_csr_nnz(y.t_indptr, y.t_indices, y.n_src, y.n_dst, y.nnz + y.n_dst, d->dagg, d->ld_dagg, d_in, GLNN_AGG_SUM, y.inv_deg,
+                                    nullptr, 0, nullptr, d->dh, d->ld_dh, stream));
+        GLNN_TRY(glnn_layernorm_bwd_f32(d->dh, d->ld_dh, prev.z, prev.ldz, prev.n_dst, d_in, q.gamma, q.beta, q.mean, q.rstd, 1, p, prev.drop_seed,
+                                        d->dh, d->ld_dh, q.ggamma, q.gbeta, prev.gb, d->ws_bn, d->ws_bn_floats, stream));
+      }
+      dz = d->dh;
+      ld_dz = d->ld_dh;
+      continue;
+    }
     // layer 0's dz has one consumer (see above): its BatchNorm backward is deferred to dW_0's operand loads when that product's shape allows
     const bool defer = l == 1 && d->batchnorm && glnn::opts().sage_fuse_bn_apply && y.n_src == prev.n_dst &&
                        glnn::gemm_tn_takes_bn(d->dh, d->ld_dh, prev.n_dst, d_in, prev.agg, prev.ld_agg, d->dims[0], prev.z, prev.ldz, 8ll * d->dims[0] * d_in) && d->ws_tn &&      // (planned against the eight slabs that are guaranteed below)
@@ -176,6 +216,23 @@ extern "C" int glnn_sage_train_step_f32(const glnn_sage_step_desc* d, const glnn
   glnn::PendingFolds pf = {};
   const bool folds = glnn::opts().adam_folds && adam->num_tensors <= 32;
   GLNN_TRY(sage_fwd_bwd_impl(d, stream, folds ? &pf : nullptr));
+  return glnn::adam_step(adam->params, adam->grads, adam->exp_avg, adam->exp_avg_sq, adam->sizes, adam->num_tensors, adam->max_size, adam->lr,
+                         adam->beta1, adam->beta2, adam->eps, adam->weight_decay, adam->step, adam->grads_host, folds ? &pf : nullptr, stream);
+}
+
+// The LayerNorm form of the two calls above (norm_type "layer"): same launch sequence, LayerNorm tails (see include/glnn_hip.h)
+extern "C" int glnn_sage_fwd_bwd_ln_f32(const glnn_sage_step_desc* d, const glnn_sage_ln_desc* ln, void* stream) {
+  GLNN_REQUIRE(ln, "glnn_sage_fwd_bwd_ln_f32: null LayerNorm descriptor");
+  return sage_fwd_bwd_impl(d, stream, nullptr, ln);
+}
+
+extern "C" int glnn_sage_train_step_ln_f32(const glnn_sage_step_desc* d, const glnn_sage_ln_desc* ln, const glnn_adam_desc* adam, void* stream) {
+  GLNN_REQUIRE(ln, "glnn_sage_train_step_ln_f32: null LayerNorm descriptor");
+  GLNN_REQUIRE(adam && adam->params && adam->grads && adam->exp_avg && adam->exp_avg_sq && adam->sizes && adam->grads_host,
+               "glnn_sage_train_step_ln_f32: the Adam descriptor is incomplete");
+  glnn::PendingFolds pf = {};
+  const bool folds = glnn::opts().adam_folds && adam->num_tensors <= 32;
+  GLNN_TRY(sage_fwd_bwd_impl(d, stream, folds ? &pf : nullptr, ln));
   return glnn::adam_step(adam->params, adam->grads, adam->exp_avg, adam->exp_avg_sq, adam->sizes, adam->num_tensors, adam->max_size, adam->lr,
                          adam->beta1, adam->beta2, adam->eps, adam->weight_decay, adam->step, adam->grads_host, folds ? &pf : nullptr, stream);
 }

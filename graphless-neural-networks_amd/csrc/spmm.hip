@@ -134,30 +134,44 @@ struct SpmmArgs {
   int rows_per_block;           // rows a row-role workgroup pulls from its ticket (8 waves x 1..kRowsPerWave rows)
   // XF kernels only: every gathered row and every self row is  drop(relu(z * xf_scale + xf_shift))  of the stored row z -- the tail of the
   // hidden layer in front (BatchNorm affine, ReLU, counter-based dropout keyed by the SOURCE row id), evaluated in the gather instead of
-  // being written by a pass of its own (glnn_act_fwd_f32's arithmetic, element for element)
+  // being written by a pass of its own (glnn_act_fwd_f32's arithmetic, element for element).  xf_on == 2: the tail is a LayerNorm --
+  // drop(relu(((z - mean[u]) * rstd[u]) * gamma + beta)) with the SOURCE row's statistics (glnn_layernorm_fwd_f32's arithmetic)
   int xf_on; const float* xf_scale; const float* xf_shift; uint32_t xf_thr; uint32_t xf_seed; float xf_dscale;
+  const float* xf_mean; const float* xf_rstd;
   HubPlan hub;                  // n_hub == 0: hub rows are summed by the row's own workgroup (same order, same bits)
   ChunkMap cm;                  // n == 0: off (glnn_spmm_csr_chunks_f32: the chunks of a row range in ONE launch, a completion signal per chunk)
 };
 
-// per-lane constants of the source transform: the lane's four columns
-struct XfCols { float s[4], h[4]; uint32_t thr, seed; float dscale; int col; bool affine; };
+// per-lane constants of the source transform: the lane's four columns (XF == 2: gamma / beta, and the row-statistics arrays)
+struct XfCols { float s[4], h[4]; uint32_t thr, seed; float dscale; int col; bool affine; const float* mean; const float* rstd; };
 __device__ __forceinline__ XfCols load_xf_cols(const SpmmArgs& a, int col4) {
   XfCols x;
   x.thr = a.xf_thr; x.seed = a.xf_seed; x.dscale = a.xf_dscale; x.col = col4; x.affine = a.xf_scale != nullptr;
+  x.mean = a.xf_mean; x.rstd = a.xf_rstd;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const bool ok = x.affine && col4 + t < a.d;
-    x.s[t] = ok ? a.xf_scale[col4 + t] : 1.f;
+    x.s[t] = ok ? a.xf_scale[col4 + t] : (a.xf_on == 2 ? 0.f : 1.f);      // (LayerNorm: padding columns come out as 0)
     x.h[t] = ok ? a.xf_shift[col4 + t] : 0.f;
   }
   return x;
 }
+// XF == 1: drop(relu(z * s + h)) (BatchNorm affine / none);  XF == 2: drop(relu(((z - mean_u) * rstd_u) * s + h)) (LayerNorm)
+template <int XF>
 __device__ __forceinline__ float4 xf_apply(const XfCols& x, float4 v, uint32_t row) {
   float o[4] = {v.x, v.y, v.z, v.w};
+  float mu = 0.f, rs = 1.f;
+  if (XF == 2) { mu = x.mean[row]; rs = x.rstd[row]; }
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    float y = x.affine ? fmaf(o[t], x.s[t], x.h[t]) : o[t];
+    float y;
+    if (XF == 2) {
+      y = (o[t] - mu) * rs;
+      asm volatile("" : "+v"(y));      // xhat rounded as glnn_layernorm_fwd_f32 rounds it, then ONE fma with gamma / beta
+      y = fmaf(y, x.s[t], x.h[t]);
+    } else {
+      y = x.affine ? fmaf(o[t], x.s[t], x.h[t]) : o[t];
+    }
     y = fmaxf(y, 0.f);
     if (x.thr) y = glnn::drop_keep(x.seed, x.thr, row, (uint32_t)(x.col + t)) ? y * x.dscale : 0.f;
     asm volatile("" : "+v"(y));        // the ROUNDED tail value is what gets summed (act_fwd stored it): no fma of y * dscale into the row sum
@@ -227,7 +241,7 @@ __device__ __forceinline__ float4 fold_groups(float4 acc) {
   if (G >= 16) acc = add4(acc, shfl_xor4(acc, 4));
   return acc;
 }
-template <int LPR, int U, bool CS, bool XF = false>
+template <int LPR, int U, bool CS, int XF = 0>
 __device__ __forceinline__ float4 wave_gather_acc(const int32_t* __restrict__ indices, int64_t e0, int64_t e1,
                                                   int wave_id, int n_waves, const float* __restrict__ x,
                                                   int64_t ldx, int col4, bool col_ok,
@@ -262,7 +276,7 @@ __device__ __forceinline__ float4 wave_gather_acc(const int32_t* __restrict__ in
       if (XF) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          if (srcs[u] >= 0) v[u] = xf_apply(xf, v[u], (uint32_t)srcs[u]);      // (absent edges stay exact zeros)
+          if (srcs[u] >= 0) v[u] = xf_apply<XF>(xf, v[u], (uint32_t)srcs[u]);      // (absent edges stay exact zeros)
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) acc = CS ? fma4(s[u], v[u], acc) : add4(acc, v[u]);
@@ -270,7 +284,7 @@ __device__ __forceinline__ float4 wave_gather_acc(const int32_t* __restrict__ in
   }
   return acc;
 }
-template <int LPR, int U, bool CS, bool XF = false>
+template <int LPR, int U, bool CS, int XF = 0>
 __device__ __forceinline__ float4 wave_gather_sum(const int32_t* __restrict__ indices, int64_t e0, int64_t e1,
                                                   int wave_id, int n_waves, const float* __restrict__ x,
                                                   int64_t ldx, int col4, bool col_ok,
@@ -319,14 +333,14 @@ __device__ __forceinline__ void finish_row_s(const SpmmArgs& a, int64_t v, int64
   }
   st4_stream(a.out + (v + out_shift) * a.ldo + col4, make_float4(yy[0], yy[1], yy[2], yy[3]));
 }
-template <int MODE, bool XF = false>
+template <int MODE, int XF = 0>
 __device__ __forceinline__ void finish_row(const SpmmArgs& a, int64_t v, int64_t deg, float4 acc, int col4, const EpCols& ep,
                                            const XfCols& xf, int64_t out_shift = 0, int64_t self_shift = 0) {
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   if (MODE == GLNN_AGG_SAGE_GCN) {
     const int64_t sr = a.self_rows ? a.self_rows[v] : v + self_shift;
     s = ld4(a.x_self + sr * a.ld_self + col4);
-    if (XF) s = xf_apply(xf, s, (uint32_t)sr);
+    if (XF) s = xf_apply<XF>(xf, s, (uint32_t)sr);
   }
   finish_row_s<MODE>(a, v, deg, acc, s, col4, ep, out_shift);
 }
@@ -346,7 +360,7 @@ __device__ __forceinline__ int hub_find(const HubPlan& h, int64_t v) {
 // THIS WAVE's share T_w of a hub row's sum (valid in lanes < LPR): the partial sums P(s, w) of its 64-edge piece of every segment s, each
 // gathered into a fresh accumulator, added in ascending s -- read from the plan's slab when hub_gather_kernel left them there, gathered
 // here otherwise.  The caller folds the eight shares exactly as it folds the eight wave partials of any long row.  No barrier.
-template <int LPR, int U, bool CS, bool XF>
+template <int LPR, int U, bool CS, int XF>
 __device__ __forceinline__ float4 hub_wave_share(const HubPlan& h, const int32_t* __restrict__ indices, int64_t v, int64_t e0, int64_t e1,
                                                  const float* __restrict__ x, int64_t ldx, int col4, bool col_ok, const float* __restrict__ col_scale,
                                                  int wave, int lane, const XfCols& xf) {
@@ -367,7 +381,7 @@ __device__ __forceinline__ float4 hub_wave_share(const HubPlan& h, const int32_t
 }
 
 // one workgroup per segment of a hub row: its eight wave partials -> slab[8 segment + wave]
-template <int LPR, int U, bool CS, bool XF>
+template <int LPR, int U, bool CS, int XF>
 __global__ __launch_bounds__(kBlock) void hub_gather_kernel(const SpmmArgs a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -390,7 +404,7 @@ __global__ __launch_bounds__(kBlock) void hub_gather_kernel(const SpmmArgs a) {
 }
 
 // ---- long-row role: scan a strided share of the rows, whole workgroup per long row (deterministic LDS fold) ----
-template <int LPR, int U, int MODE, bool CS, bool XF = false>
+template <int LPR, int U, int MODE, bool CS, int XF = 0>
 __device__ __forceinline__ void long_rows_role(const SpmmArgs& a, int lane, int wave, int col4, bool col_ok, const EpCols& ep,
                                                const XfCols& xf) {
   __shared__ int64_t s_rows[kBlock];
@@ -435,7 +449,7 @@ __device__ __forceinline__ void long_rows_role(const SpmmArgs& a, int lane, int 
 // [rs, re)) workgroup b takes the sub-ranges b, b + n_long_blocks, .. of ceil((re - rs) / 512), dealt round-robin over the rows as above --
 // and when its share of a chunk is stored the workgroup arrives on the chunk's counter (every long-role workgroup arrives once per non-empty
 // chunk: expected = row workgroups of the chunk + n_long_blocks).
-template <int LPR, int U, int MODE, bool CS, bool XF>
+template <int LPR, int U, int MODE, bool CS, int XF>
 __device__ __forceinline__ void long_rows_role_chunks(const SpmmArgs& a, const ChunkMap& cm, int lane, int wave, int col4, bool col_ok,
                                                       const EpCols& ep, const XfCols& xf) {
   __shared__ int64_t s_rows[kBlock];
@@ -495,7 +509,7 @@ __device__ __forceinline__ void long_rows_role_chunks(const SpmmArgs& a, const C
   }
 }
 
-template <int LPR, int U, int MODE, bool CS, bool XF = false, bool CM = false>
+template <int LPR, int U, int MODE, bool CS, int XF = 0, bool CM = false>
 __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(const SpmmArgs a0) {
   // rows wider than 256 floats (raw cora / citeseer features): blockIdx.y = the 256-column tile of this workgroup -- one launch instead
   // of one per tile (14 for citeseer's 3703 features)
@@ -581,7 +595,7 @@ __device__ __forceinline__ int64_t readlane64(int64_t v, int l) {
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), l);
   return (int64_t)(((uint64_t)hi << 32) | lo);
 }
-template <int LPR, int U, int MODE, bool CS, bool XF = false>
+template <int LPR, int U, int MODE, bool CS, int XF = 0>
 __global__ __launch_bounds__(kBlock) void spmm_csr_short_kernel(const SpmmArgs a) {
   constexpr int G = 64 / LPR, RB = kShortRows, UB = kShortUnits;
   const int lane = threadIdx.x & 63;
@@ -657,7 +671,7 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_short_kernel(const SpmmArgs a
         const int64_t sr = readlane64(my_self, r < nr ? r : 0);
         if (live[r] && col_ok) {
           selfv[r] = ld4(a.x_self + sr * a.ld_self + col4);
-          if (XF) selfv[r] = xf_apply(xf, selfv[r], (uint32_t)sr);
+          if (XF) selfv[r] = xf_apply<XF>(xf, selfv[r], (uint32_t)sr);
         }
       }
     }
@@ -667,7 +681,7 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_short_kernel(const SpmmArgs a
 #pragma unroll
       for (int k = 0; k < UB; ++k) {
         if (XF) {
-          if (srcs[r][k] >= 0) v[r][k] = xf_apply(xf, v[r][k], (uint32_t)srcs[r][k]);
+          if (srcs[r][k] >= 0) v[r][k] = xf_apply<XF>(xf, v[r][k], (uint32_t)srcs[r][k]);
         }
         acc = CS ? fma4(sc[r][k], v[r][k], acc) : add4(acc, v[r][k]);
       }
@@ -877,6 +891,156 @@ __global__ __launch_bounds__(kBlock) void spmm_bn_dy_kernel(const SpmmArgs a, co
     for (int w = 1; w < kWavesPerBlock; ++w) { u = add4(u, s_part[w][lane]); w2 = add4(w2, s_part2[w][lane]); }
     st4(t.ws1 + (int64_t)blockIdx.x * t.h + col4, u);
     st4(t.ws2 + (int64_t)blockIdx.x * t.h + col4, w2);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// A^T dY WITH the whole LayerNorm backward behind it (glnn::spmm_csr_ln_dz): the transposed aggregation of a training step produces
+// dh = dL/dh of a hidden layer whose tail is LayerNorm -> ReLU -> dropout.  The LayerNorm's statistics are per ROW, and the wave that
+// finishes a row of dh holds all of it (LPR lanes x float4, d <= 256), so it finishes the backward right there:
+//     dy  = dh * keep/(1-p) * [xhat*gamma + beta > 0],   dxh = dy * gamma,   m1 = mean(dxh),   m2 = mean(dxh * xhat)   (wave reductions)
+//     dz  = rstd * (dxh - m1 - xhat * m2)                                        stored INSTEAD of dh
+// (glnn_layernorm_bwd_f32's expressions) and adds the row to per-lane column partials of dgamma = sum dy xhat, dbeta = sum dy and
+// sum dz (the bias gradient of the Linear in front).  Deterministic as spmm_bn_dy_kernel: rows dealt statically, a wave's rows in ascending
+// order, the long-row workgroups' rows sorted, the eight waves folded in fixed order into the workgroup's slot ws[blockIdx.x][3][h]; ln_fold
+// folds the slots.
+// ---------------------------------------------------------------------------------------------
+struct LnDzTail {
+  const float* z; int64_t ldz; const float* mean; const float* rstd; const float* gamma; const float* beta;
+  uint32_t dthr; uint32_t dseed; float dscale; float inv_h; float* ws; int h;
+};
+__device__ __forceinline__ float wave_sum64(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+// one finished row of dh (valid in the lanes with `mine`) -> dz.  Called by EVERY lane of the wave (the row reductions are shuffles): the
+// other lanes and the padding columns contribute zeros.
+template <bool DROP>
+__device__ __forceinline__ void finish_ln_row(const SpmmArgs& a, const LnDzTail& t, const float (&g)[4], const float (&b)[4], int64_t v, float4 acc,
+                                              float4 z4, int col4, bool mine, float (&pg)[4], float (&pb)[4], float (&pz)[4]) {
+  const float mu = t.mean[v], rs = t.rstd[v];
+  const float da[4] = {acc.x, acc.y, acc.z, acc.w}, zz[4] = {z4.x, z4.y, z4.z, z4.w};
+  float xh[4], dy[4], dxh[4];
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float x = 0.f, d = 0.f;
+    if (mine && col4 + k < t.h) {
+      x = (zz[k] - mu) * rs;
+      d = da[k];
+      if (DROP) d = glnn::drop_keep(t.dseed, t.dthr, (uint32_t)v, (uint32_t)(col4 + k)) ? d * t.dscale : 0.f;
+      if (!(fmaf(x, g[k], b[k]) > 0.f)) d = 0.f;
+    }
+    xh[k] = x;
+    dy[k] = d;
+    dxh[k] = d * g[k];
+    s1 += dxh[k];
+    s2 = fmaf(dxh[k], x, s2);
+  }
+  const float m1 = wave_sum64(s1) * t.inv_h, m2 = wave_sum64(s2) * t.inv_h;
+  if (!mine) return;
+  float o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    o[k] = col4 + k < t.h ? rs * (dxh[k] - m1 - xh[k] * m2) : 0.f;      // (padding columns are written as zero)
+    pg[k] = fmaf(dy[k], xh[k], pg[k]);
+    pb[k] += dy[k];
+    pz[k] += o[k];
+  }
+  st4_stream(a.out + v * a.ldo + col4, make_float4(o[0], o[1], o[2], o[3]));
+}
+
+template <int LPR, int U, bool DROP>
+__global__ __launch_bounds__(kBlock) void spmm_ln_dz_kernel(const SpmmArgs a, const LnDzTail t) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col4 = (lane % LPR) * 4;
+  const bool col_ok = col4 < a.d;
+  const bool mine = lane < LPR && col_ok;                 // the lanes that hold the finished row
+  float g[4], b[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const bool ok = col_ok && col4 + k < a.d;
+    g[k] = ok ? t.gamma[col4 + k] : 0.f;
+    b[k] = ok ? t.beta[col4 + k] : 0.f;
+  }
+  const XfCols xf = {};
+  float pg[4] = {0.f, 0.f, 0.f, 0.f}, pb[4] = {0.f, 0.f, 0.f, 0.f}, pz[4] = {0.f, 0.f, 0.f, 0.f};
+  __shared__ float4 s_part[kWavesPerBlock][64];
+  if ((int)blockIdx.x < a.n_long_blocks) {
+    // ---- long rows: spmm_bn_dy_kernel's scan, the found rows taken in ASCENDING order; wave 0 finishes them ----
+    __shared__ int64_t s_rows[kBlock], s_sorted[kBlock];
+    __shared__ int s_count;
+    const int64_t n_chunks = (a.n_dst + kBlock - 1) / kBlock;
+    for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += a.n_long_blocks) {
+      if (threadIdx.x == 0) s_count = 0;
+      __syncthreads();
+      const int64_t r = (int64_t)threadIdx.x * n_chunks + chunk;
+      if (r < a.n_dst && (a.indptr[r + 1] - a.indptr[r]) > kLongRow) s_rows[atomicAdd(&s_count, 1)] = r;
+      __syncthreads();
+      const int n_found = s_count;
+      if ((int)threadIdx.x < n_found) {
+        const int64_t me = s_rows[threadIdx.x];
+        int rank = 0;
+        for (int i = 0; i < n_found; ++i) rank += s_rows[i] < me ? 1 : 0;
+        s_sorted[rank] = me;
+      }
+      __syncthreads();
+      for (int i = 0; i < n_found; ++i) {
+        const int64_t v = s_sorted[i];
+        const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
+        float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (wave == 0 && mine) z4 = ld4(t.z + v * t.ldz + col4);
+        float4 acc;
+        if (e1 - e0 > kHubRow) acc = hub_wave_share<LPR, U, true, 0>(a.hub, a.indices, v, e0, e1, a.x, a.ldx, col4, col_ok, a.col_scale, wave, lane, xf);
+        else acc = wave_gather_sum<LPR, U, true, 0>(a.indices, e0, e1, wave, kWavesPerBlock, a.x, a.ldx, col4, col_ok, a.col_scale, lane, xf);
+        if (lane < LPR) s_part[wave][lane] = acc;
+        __syncthreads();
+        if (wave == 0) {
+          float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (lane < LPR) {
+            sum = s_part[0][lane];
+#pragma unroll
+            for (int w = 1; w < kWavesPerBlock; ++w) sum = add4(sum, s_part[w][lane]);
+          }
+          finish_ln_row<DROP>(a, t, g, b, v, sum, z4, col4, mine, pg, pb, pz);
+        }
+        __syncthreads();
+      }
+    }
+  } else {
+    // ---- row role, static: wave w takes the rows row_base + w + 8 i ----
+    const int64_t row_base = ((int64_t)blockIdx.x - a.n_long_blocks) * a.rows_per_block;
+#pragma unroll 1
+    for (int lr = wave; lr < a.rows_per_block; lr += kWavesPerBlock) {
+      const int64_t v = row_base + lr;
+      if (v >= a.n_dst) break;
+      const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
+      if (e1 - e0 > kLongRow) continue;
+      float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (mine) z4 = ld4(t.z + v * t.ldz + col4);                       // (in flight beside the gather)
+      const float4 acc = wave_gather_sum<LPR, U, true, 0>(a.indices, e0, e1, 0, 1, a.x, a.ldx, col4, col_ok, a.col_scale, lane, xf);
+      finish_ln_row<DROP>(a, t, g, b, v, acc, z4, col4, mine, pg, pb, pz);
+    }
+  }
+  // the workgroup's slot: the eight waves' partials folded in fixed order, one quantity after the other
+  float* slot = t.ws + (int64_t)blockIdx.x * 3 * t.h;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const float* p = q == 0 ? pg : (q == 1 ? pb : pz);
+    __syncthreads();
+    if (lane < LPR) s_part[wave][lane] = make_float4(p[0], p[1], p[2], p[3]);
+    __syncthreads();
+    if (wave == 0 && mine) {
+      float4 u = s_part[0][lane];
+#pragma unroll
+      for (int w = 1; w < kWavesPerBlock; ++w) u = add4(u, s_part[w][lane]);
+      const float uu[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (col4 + k < t.h) slot[q * t.h + col4 + k] = uu[k];
+    }
   }
 }
 
@@ -1152,7 +1316,8 @@ template <int LPR, int U>
 int launch_hub_gather(const SpmmArgs& a, int mode, int n_seg, hipStream_t st) {
   const bool cs = a.col_scale != nullptr;
   const dim3 g((unsigned)n_seg);
-  if (mode == GLNN_AGG_SAGE_GCN && a.xf_on) hipLaunchKernelGGL((hub_gather_kernel<LPR, U, false, true>), g, dim3(kBlock), 0, st, a);
+  if (mode == GLNN_AGG_SAGE_GCN && a.xf_on == 2) hipLaunchKernelGGL((hub_gather_kernel<LPR, U, false, 2>), g, dim3(kBlock), 0, st, a);
+  else if (mode == GLNN_AGG_SAGE_GCN && a.xf_on) hipLaunchKernelGGL((hub_gather_kernel<LPR, U, false, true>), g, dim3(kBlock), 0, st, a);
   else if (cs) hipLaunchKernelGGL((hub_gather_kernel<LPR, U, true, false>), g, dim3(kBlock), 0, st, a);
   else hipLaunchKernelGGL((hub_gather_kernel<LPR, U, false, false>), g, dim3(kBlock), 0, st, a);
   return glnn::check_launch("glnn_spmm_csr_f32(hub segments)");
@@ -1181,7 +1346,9 @@ int launch_lpr(const SpmmArgs& a, int mode, hipStream_t st, int grid, int col_ti
     hipLaunchKernelGGL((spmm_csr_kernel<LPR, U, GLNN_AGG_SAGE_GCN, false, false, true>), g, dim3(kBlock), 0, st, a);
     return glnn::check_launch("glnn_spmm_csr_chunks_f32");
   }
-  if (mode == GLNN_AGG_SAGE_GCN && a.xf_on) {
+  if (mode == GLNN_AGG_SAGE_GCN && a.xf_on == 2) {
+    hipLaunchKernelGGL((spmm_csr_kernel<LPR, U, GLNN_AGG_SAGE_GCN, false, 2>), g, dim3(kBlock), 0, st, a);
+  } else if (mode == GLNN_AGG_SAGE_GCN && a.xf_on) {
     hipLaunchKernelGGL((spmm_csr_kernel<LPR, U, GLNN_AGG_SAGE_GCN, false, true>), g, dim3(kBlock), 0, st, a);
   } else if (mode == GLNN_AGG_SAGE_GCN) {
     hipLaunchKernelGGL((spmm_csr_kernel<LPR, U, GLNN_AGG_SAGE_GCN, false>), g, dim3(kBlock), 0, st, a);
@@ -1286,6 +1453,7 @@ static int spmm_impl(const int64_t* indptr, const int32_t* indices, int64_t n_ds
   if (tail) {
     GLNN_REQUIRE(mode == GLNN_AGG_SAGE_GCN && d <= 256, "glnn::spmm_csr_tail: SAGE_GCN rows of <= 256 floats only");
     GLNN_REQUIRE((tail->scale == nullptr) == (tail->shift == nullptr) && tail->drop_p >= 0.f && tail->drop_p < 1.f, "glnn::spmm_csr_tail: bad tail");
+    GLNN_REQUIRE((tail->mean == nullptr) == (tail->rstd == nullptr) && (!tail->mean || tail->scale), "glnn::spmm_csr_tail: bad LayerNorm tail");
   }
   for (int c0 = 0; c0 < d; c0 += (wide ? d : 256)) {
     const int dt = wide ? 256 : ((d - c0) < 256 ? (d - c0) : 256);
@@ -1296,7 +1464,8 @@ static int spmm_impl(const int64_t* indptr, const int32_t* indices, int64_t n_ds
     a.x_self = x_self ? x_self + c0 : nullptr; a.ld_self = ld_self; a.self_rows = self_rows;
     a.ep_scale = ep_scale ? ep_scale + c0 : nullptr; a.ep_shift = ep_shift ? ep_shift + c0 : nullptr;
     a.relu = relu; a.out = out + c0; a.ldo = ldo;
-    a.xf_on = tail ? 1 : 0;
+    a.xf_on = tail ? (tail->mean ? 2 : 1) : 0;
+    a.xf_mean = tail ? tail->mean : nullptr; a.xf_rstd = tail ? tail->rstd : nullptr;
     a.xf_scale = tail ? tail->scale : nullptr; a.xf_shift = tail ? tail->shift : nullptr;
     a.xf_thr = tail ? glnn::drop_threshold(tail->drop_p) : 0u; a.xf_seed = tail ? tail->drop_seed : 0u;
     a.xf_dscale = tail ? 1.0f / (1.0f - tail->drop_p) : 1.f;
@@ -1450,6 +1619,50 @@ int glnn::spmm_csr_bn_dy(const int64_t* indptr, const int32_t* indices, int64_t 
   }
   *nslots = (int)slots;
   return glnn::check_launch("glnn::spmm_csr_bn_dy");
+}
+
+// out = dz of the LayerNorm -> ReLU -> dropout tail described by `tail`, behind the transposed aggregation (A x col_scale); per-workgroup
+// column partials of dgamma / dbeta / sum dz in ws ([*nslots][3][d]; glnn::ln_fold folds them).  See spmm_ln_dz_kernel.
+int64_t glnn::spmm_csr_ln_dz_ws_floats(int64_t n_dst, int d) { return n_dst < 1 || d < 1 ? 0 : 3 * bn_dy_grid(n_dst, nullptr, nullptr) * (int64_t)d; }
+
+int glnn::spmm_csr_ln_dz(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, const float* x, int64_t ldx, int d,
+                         const float* col_scale, const glnn::LnTail& tail, float* out, int64_t ldo, float* ws, int64_t ws_floats, int* nslots,
+                         void* stream) {
+  if (!indptr || !x || !out || !col_scale || !ws || !nslots || n_dst < 1 || n_src < 0 || n_src >= ((int64_t)1 << 31)) return GLNN_ERR_UNSUPPORTED;
+  const int dpad = (d + 3) & ~3;
+  if (d < 1 || d > 256 || (ldx & 3) || (ldo & 3) || (tail.ldz & 3) || ldx < dpad || ldo < dpad || tail.ldz < dpad) return GLNN_ERR_UNSUPPORTED;
+  if (!tail.z || !tail.mean || !tail.rstd || !tail.gamma || !tail.beta || tail.drop_p < 0.f || tail.drop_p >= 1.f) return GLNN_ERR_UNSUPPORTED;
+  if (!glnn::aligned16(x) || !glnn::aligned16(out) || !glnn::aligned16(tail.z)) return GLNN_ERR_UNSUPPORTED;
+  SpmmArgs a = {};
+  a.indptr = indptr; a.indices = indices; a.n_dst = n_dst; a.x = x; a.ldx = ldx; a.d = d; a.col_scale = col_scale; a.out = out; a.ldo = ldo;
+  const int64_t slots = bn_dy_grid(n_dst, &a.n_long_blocks, &a.rows_per_block);
+  if (slots >= ((int64_t)1 << 24) || 3 * slots * d > ws_floats) return GLNN_ERR_UNSUPPORTED;
+  LnDzTail t;
+  t.z = tail.z; t.ldz = tail.ldz; t.mean = tail.mean; t.rstd = tail.rstd; t.gamma = tail.gamma; t.beta = tail.beta;
+  t.dthr = glnn::drop_threshold(tail.drop_p); t.dseed = tail.drop_seed; t.dscale = 1.0f / (1.0f - tail.drop_p); t.inv_h = 1.0f / (float)d;
+  t.ws = ws; t.h = d;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 g((unsigned)slots);
+  const int dv = dpad / 4;
+  const bool drop = t.dthr != 0;
+#define GLNN_LN_DZ(LPR)                                                                                             \
+  do {                                                                                                              \
+    if (drop) hipLaunchKernelGGL((spmm_ln_dz_kernel<LPR, GLNN_SPMM_U, true>), g, dim3(kBlock), 0, st, a, t);        \
+    else hipLaunchKernelGGL((spmm_ln_dz_kernel<LPR, GLNN_SPMM_U, false>), g, dim3(kBlock), 0, st, a, t);            \
+  } while (0)
+  if (dv <= 8) GLNN_LN_DZ(8);
+  else if (dv <= 16) GLNN_LN_DZ(16);
+  else if (dv <= 32) GLNN_LN_DZ(32);
+  else GLNN_LN_DZ(64);
+#undef GLNN_LN_DZ
+  *nslots = (int)slots;
+  return glnn::check_launch("glnn::spmm_csr_ln_dz");
+}
+
+extern "C" int64_t glnn_sage_step_ws_ln_floats(int64_t n_dst, int hidden) {
+  if (n_dst < 1 || hidden < 1) return 0;
+  const int64_t fused = glnn::spmm_csr_ln_dz_ws_floats(n_dst, hidden), plain = glnn_layernorm_bwd_workspace_floats(n_dst, hidden);
+  return (fused > plain ? fused : plain) + 1024;
 }
 
 extern "C" int glnn_degrees_f32(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src,

@@ -56,8 +56,8 @@ def check_supported(model, criterion, optimizer):
     if type(optimizer) is not torch.optim.Adam or len(grp) != 1 or grp[0].get("amsgrad") or grp[0].get("maximize"):
         raise NotImplementedError("TeacherEngine: torch.optim.Adam, one param group, no amsgrad/maximize (train_teacher.py:234-236)")
     if "SAGE" in name:
-        if enc.norm_type not in ("none", "batch") or not _is_relu(enc.activation):
-            raise NotImplementedError("TeacherEngine: SAGE with norm_type none|batch and ReLU (the reference's configs)")
+        if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
+            raise NotImplementedError("TeacherEngine: SAGE with norm_type none|batch|layer and ReLU (the reference's configs)")
     elif "APPNP" in name:
         if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
             raise NotImplementedError("TeacherEngine: APPNP with norm_type none|batch|layer and ReLU (models.py:282-344)")
@@ -96,6 +96,7 @@ class TeacherEngine:
         self.kind = "sage" if "SAGE" in model.model_name else ("appnp" if "APPNP" in model.model_name else "gcn")
         self.L = self.enc.num_layers
         self.bn = self.enc.norm_type == "batch"
+        self.ln = self.enc.norm_type == "layer"
         self.p = float(self.enc.dropout.p)
         params = list(model.parameters())
         self.params = params
@@ -125,6 +126,7 @@ class TeacherEngine:
         self.loss_out = torch.zeros(1, **f32)
         self.loss_accum = torch.zeros(1, **f32)
         self._sage_desc = self._arena = self._arena_stream = None      # step_sage: persistent descriptor and scratch arena
+        self._sage_ln = None                                           # step_sage, norm_type "layer": the LayerNorm side descriptor
         self.ws_loss = torch.empty(1024, **f32)
         # step_sage: the hidden layers' h = dropout(relu(norm(z))) is NOT written -- the next layer's aggregation applies that tail to the z
         # rows it gathers (glnn::spmm_csr_tail; same arithmetic per element, so the step is bit-identical to the materialised form, one pass
@@ -189,6 +191,9 @@ class TeacherEngine:
                 bn = enc.norms[l]
                 sig += [ptr(bn.weight), ptr(bn.bias), ptr(self.grad(bn.weight)), ptr(self.grad(bn.bias)), ptr(bn.running_mean), ptr(bn.running_var),
                         ptr(bn.num_batches_tracked), bn.eps, bn.momentum]
+            elif l != len(enc.layers) - 1 and self.ln:
+                ln = enc.norms[l]
+                sig += [ptr(ln.weight), ptr(ln.bias), ptr(self.grad(ln.weight)), ptr(self.grad(ln.bias)), ln.eps]
         return sig + [ptr(self.ws_loss), ptr(self.loss_out), ptr(self.loss_accum)]
 
     def step_sage(self, blocks, feats, labels, output_nodes, lamb=1.0, input_nodes=None):
@@ -239,6 +244,15 @@ class TeacherEngine:
                     d.bn_eps, d.bn_momentum = bn.eps, bn.momentum
                     y.gamma, y.beta, y.ggamma, y.gbeta = ptr(bn.weight), ptr(bn.bias), ptr(self.grad(bn.weight)), ptr(self.grad(bn.bias))
                     y.running_mean, y.running_var, y.nbt = ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked)
+            self._sage_ln = None
+            if self.ln:          # nn.LayerNorm tails: parameters and gradients in the side descriptor (the row statistics are scratch)
+                lnd = self._sage_ln = _lib.SageLnDesc()
+                lnd.eps = enc.norms[0].eps
+                for l in range(L - 1):
+                    ln, q = enc.norms[l], lnd.layer[l]
+                    if ctypes.c_float(ln.eps).value != lnd.eps:
+                        raise NotImplementedError("TeacherEngine: the hidden LayerNorms of a SAGE teacher must share one eps")
+                    q.gamma, q.beta, q.ggamma, q.gbeta = ptr(ln.weight), ptr(ln.bias), ptr(self.grad(ln.weight)), ptr(self.grad(ln.bias))
             d.ws_loss, d.ws_loss_floats = ptr(self.ws_loss), self.ws_loss.numel()
             d.loss_out, d.loss_accum = ptr(self.loss_out), ptr(self.loss_accum)
             self._sage_static = self._sage_signature(enc)
@@ -267,6 +281,9 @@ class TeacherEngine:
                     max_rows, max_hidden = max(max_rows, n_dst), max(max_hidden, dims[l + 1])
                     if self.bn:
                         y.mean, y.rstd, y.a_scale, y.a_shift = (A.take(4 * dims[l + 1]) for _ in range(4))
+                    if self.ln:          # per-ROW statistics of z_l (written by the forward, read by the backward)
+                        q = self._sage_ln.layer[l]
+                        q.mean, q.rstd = A.take(4 * n_dst), A.take(4 * n_dst)
                 if l >= 1 and getattr(blk, "t_indptr", None) is not None:      # transposed by the loader (NodeDataLoader.global_first_block)
                     y.t_indptr, y.t_indices, y.inv_deg = ptr(blk.t_indptr), ptr(blk.t_indices), ptr(blk.inv_deg)
                     y.tr_ws, y.tr_ws_bytes = None, 0
@@ -285,6 +302,9 @@ class TeacherEngine:
             d.ws_bn_floats = (3 * nchunks + 2 + 3 * ((nchunks + 63) // 64)) * max_hidden + 1024
             if L > 1 and self.bn:     # room for the outermost layer's BatchNorm backward without passes of its own (round 5)
                 d.ws_bn_floats = max(d.ws_bn_floats, int(_lib.lib().glnn_sage_step_ws_bn_floats(blocks[0].num_dst_nodes(), dims[1])))
+            if self.ln:          # the LayerNorm backward's column partials (fused into the transposed aggregation, or its own launch)
+                for l in range(L - 1):
+                    d.ws_bn_floats = max(d.ws_bn_floats, int(_lib.lib().glnn_sage_step_ws_ln_floats(blocks[l].num_dst_nodes(), dims[l + 1])))
             # (x L: in the one-call step every layer's split slabs wait in ws_tn for the Adam launch to fold them -- csrc/sage_step.hip)
             d.ws_tn_floats = L * (64 * max(dims) + 256 * 128 * 128 + 2 * max(dims) * max(dims))
             # split-K slabs, sized as StudentEngine does; the GEMM only splits outputs of < 256 tiles, i.e. <= 512 slabs of 128 x 128
@@ -323,12 +343,17 @@ class TeacherEngine:
             g_ = self.opt.param_groups[0]
             ad = self.table.desc
             ad.lr, ad.beta1, ad.beta2, ad.eps, ad.weight_decay, ad.step = g_["lr"], g_["betas"][0], g_["betas"][1], g_["eps"], g_["weight_decay"], self.step_count
-            rc = _lib.lib().glnn_sage_train_step_f32(ctypes.byref(d), ctypes.byref(ad), ops._stream())
+            if self.ln:
+                rc = _lib.lib().glnn_sage_train_step_ln_f32(ctypes.byref(d), ctypes.byref(self._sage_ln), ctypes.byref(ad), ops._stream())
+            else:
+                rc = _lib.lib().glnn_sage_train_step_f32(ctypes.byref(d), ctypes.byref(ad), ops._stream())
+        elif self.ln:
+            rc = _lib.lib().glnn_sage_fwd_bwd_ln_f32(ctypes.byref(d), ctypes.byref(self._sage_ln), ops._stream())
         else:
             rc = _lib.lib().glnn_sage_fwd_bwd_f32(ctypes.byref(d), ops._stream())
         if rc != 0:
             self.step_count -= 1          # the step never happened: Adam's bias correction and the dropout seeds stay where they were
-        _lib.check(rc, "glnn_sage_train_step_f32" if one_call else "glnn_sage_fwd_bwd_f32")
+        _lib.check(rc, ("glnn_sage_train_step" if one_call else "glnn_sage_fwd_bwd") + ("_ln_f32" if self.ln else "_f32"))
         if not one_call:
             self._adam()
 

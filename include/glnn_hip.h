@@ -43,7 +43,7 @@ GLNN_API int glnn_abi_version(void);               /* bumped on any signature ch
 GLNN_API const char* glnn_last_error(void);        /* thread-local, never NULL */
 GLNN_API int glnn_device_info(int* cu_count, int* xcd_count, char* arch_buf, int arch_buf_len);
 /* sizeof of the descriptor structs below as THIS build sees them (0 = glnn_mlp_step_desc, 1 = glnn_sage_step_desc,
- * 2 = glnn_sage_layer, 3 = glnn_adam_desc; -1 otherwise): lets a binding in another language check its mirror of the layout at load time. */
+ * 2 = glnn_sage_layer, 3 = glnn_adam_desc, 4 = glnn_hub_plan, 5 = glnn_chunk_signals, 6 = glnn_sage_ln_desc; -1 otherwise): lets a binding in another language check its mirror of the layout at load time. */
 GLNN_API int64_t glnn_struct_bytes(int which);
 /* The library reads its GLNN_* environment switches (csrc/glnn_common.h, glnn::Options: choices between supported, equal-result
  * forms of a launch sequence, for tests and A/B timing) ONCE, at the first call.  This re-reads them; not for concurrent use. */
@@ -552,6 +552,26 @@ GLNN_API int glnn_sage_train_step_f32(const glnn_sage_step_desc* desc, const gln
  * max hidden + 1024 floats, chunks = ceil(max n_dst / 128): allocate the larger of the two. */
 GLNN_API int64_t glnn_sage_step_ws_bn_floats(int64_t n_dst_0, int hidden);
 
+/* The same step for SAGE teachers whose hidden layers end in nn.LayerNorm(hidden) -> ReLU -> dropout (reference models.py:87-97, 113-117,
+ * norm_type "layer"): desc->batchnorm must be 0, the desc's BatchNorm fields are unused; `ln` carries eps and, per hidden layer l, the
+ * LayerNorm's weight / bias (gamma, beta), their gradients and the row statistics of z_l (mean / rstd [n_dst_l] floats, written by the
+ * forward, read by the backward).  Forward per hidden layer: glnn_layernorm_fwd_f32 (h == NULL: the statistics alone, the next layer's
+ * gather applies the tail).  Backward: the transposed aggregation's epilogue is the whole LayerNorm backward (dz stored, dh never
+ * written; GLNN_SAGE_FUSE_LN_BWD=0 or a hidden width above 256: the aggregation writes dh, glnn_layernorm_bwd_f32 follows).
+ * ws_bn >= max over hidden layers of glnn_sage_step_ws_ln_floats(n_dst_l, dims[l+1]).  No float atomics: bit-reproducible. */
+typedef struct glnn_sage_ln_layer {
+  const float* gamma; const float* beta; float* ggamma; float* gbeta; float* mean; float* rstd;
+} glnn_sage_ln_layer;
+typedef struct glnn_sage_ln_desc {
+  float eps; int32_t reserved;
+  glnn_sage_ln_layer layer[GLNN_SAGE_MAX_LAYERS];     /* hidden layers 0 .. num_layers - 2 */
+} glnn_sage_ln_desc;
+GLNN_API int glnn_sage_fwd_bwd_ln_f32(const glnn_sage_step_desc* desc, const glnn_sage_ln_desc* ln, void* stream);
+/* ... and followed by the fused Adam launch (as glnn_sage_train_step_f32): bit-identical to glnn_sage_fwd_bwd_ln_f32 + glnn_adam_step_f32 */
+GLNN_API int glnn_sage_train_step_ln_f32(const glnn_sage_step_desc* desc, const glnn_sage_ln_desc* ln, const glnn_adam_desc* adam,
+                                         void* stream);
+GLNN_API int64_t glnn_sage_step_ws_ln_floats(int64_t n_dst, int hidden);
+
 /* y = dropout(relu(z * a_scale + a_shift)) materialised (a_scale/a_shift NULL: plain ReLU): the `norms[l](h)` ->
  * `activation` -> `dropout` tail of a TRAINING-mode SAGE layer (reference models.py:113-117), whose output the next
  * layer's aggregation gathers.  a_scale/a_shift come from glnn_bn_stats_f32; the backward is glnn_bn_relu_bwd_f32 with
@@ -576,7 +596,8 @@ GLNN_API int glnn_bn_bwd_f32(const float* da, int64_t ldda, const float* z, int6
 /* nn.LayerNorm(hidden) as a hidden-layer tail (reference models.py:28-31, 87-90, 174-186; train.conf.yaml uses norm_type
  * "layer" for the house_class MLP):
  *   forward   y = dropout(relu?(xhat * gamma + beta)),  xhat = (z - mean_row) * rstd_row,  rstd = 1/sqrt(biased var + eps);
- *             mean_out / rstd_out [rows] (optional) are what the backward needs; gamma/beta NULL = no affine.
+ *             mean_out / rstd_out [rows] (optional) are what the backward needs; gamma/beta NULL = no affine.  y may be NULL when
+ *             mean_out and rstd_out are given: the statistics alone (the SAGE LayerNorm step applies the tail in the next gather).
  *   backward  dy = da * keep/(1-p) * [relu ? xhat*gamma+beta > 0 : 1];  dgamma = sum_rows dy*xhat, dbeta = sum_rows dy;
  *             dz = rstd * (dy*gamma - mean_cols(dy*gamma) - xhat * mean_cols(dy*gamma*xhat));  dz_col_sum (optional) = sum_rows dz
  *             = the bias gradient of the Linear in front.  workspace >= glnn_layernorm_bwd_workspace_floats(rows, h) floats when
