@@ -22,6 +22,11 @@ SIGNATURES = {
     "glnn_pack_weight_f32": [c_vp, c_i64, c_int, c_int, c_vp, c_vp],
     "glnn_sage_fused_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_int, c_vp,
                             c_i64, c_vp, c_int, c_vp, c_i64, c_vp, c_vp],
+    "glnn_cast_f32_bf16": [c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_vp],
+    "glnn_spmm_csr_bf16": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
+                           c_int, c_vp, c_i64, c_int, c_vp],
+    "glnn_sage_fused_bf16": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_int, c_vp,
+                             c_i64, c_int, c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp],
     "glnn_hub_row_threshold": [],
     "glnn_hub_segment_edges": [],
     "glnn_spmm_csr_plan_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,

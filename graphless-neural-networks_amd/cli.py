@@ -64,7 +64,15 @@ def _parser(rows, description):
 
 
 def get_teacher_args(argv=None):
-    return _parser(_COMMON, "GLNN teacher (HIP hot path)").parse_args(argv)
+    p = _parser(_COMMON, "GLNN teacher (HIP hot path)")
+    # not a reference flag: the activation storage of the SAGE teacher's whole-graph evaluation forward (Model.inference(dtype=...)),
+    # bfloat16 = the gathered matrices stored as bf16, arithmetic and the saved log-probs fp32
+    p.add_argument("--inference_dtype", type=str, default="float32", choices=["float32", "bfloat16"],
+                   help="Activation storage of the SAGE teacher's evaluation forward (bfloat16: SAGE only)")
+    args = p.parse_args(argv)
+    if args.inference_dtype != "float32" and "SAGE" not in args.teacher:
+        p.error(f"--inference_dtype {args.inference_dtype} is implemented for the SAGE teacher only (got --teacher {args.teacher})")
+    return args
 
 
 def get_student_args(argv=None):

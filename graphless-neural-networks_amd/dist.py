@@ -372,6 +372,12 @@ def probe_link(world, rank, floats_per_rank, device, group=None, reps=3):
             "correct": float(t[1].item()) == 0.0, "reps": reps, "backend": dist.get_backend(group)}
 
 
+def _fp32_only(dtype, who):
+    if dtype != torch.float32:
+        raise NotImplementedError(f"{who}: the sharded teacher forward stores its activations in fp32 only (bf16 storage: "
+                                  "SAGE.inference(..., dtype=torch.bfloat16) on one device)")
+
+
 class ShardedTeacher:
     """SAGE layer-wise inference over a row-sharded graph.  `graph_shard` = full graph's rows [lo,hi)
     (glnn_amd.graph.CSRGraph.row_range), column indices global.
@@ -738,8 +744,10 @@ class ShardedTeacher:
                     out=out[off:off + nr], x_self=hw[sl], **self._kw(off, nr))
         return out
 
-    def forward(self, x_full):
-        """x_full: [>= n, F] replicated input features.  Returns this rank's rows of the logits [rows, C]."""
+    def forward(self, x_full, dtype=torch.float32):
+        """x_full: [>= n, F] replicated input features.  Returns this rank's rows of the logits [rows, C].  dtype: fp32 only (the bf16
+        activation storage of SAGE.inference is a whole-graph, single-device form)."""
+        _fp32_only(dtype, "ShardedTeacher")
         enc, sh, be, g = self.enc, self.sh, self.be, self.g
         x = be.as_feat(x_full)
         layout = "nat"          # row order of x: natural node ids ("nat"), rank-major slots ("own") or chunk-major ("cm")
@@ -1077,8 +1085,9 @@ class HaloShardedTeacher:
                     pending = (("y2", l), self._exchange_async(own, self._local(("y2", l), d_out, x.device), ("y", l)))
         return out
 
-    def forward(self, x_full):
-        """x_full: [>= n, F] replicated input features.  Returns this rank's rows of the logits [rows, C]."""
+    def forward(self, x_full, dtype=torch.float32):
+        """x_full: [>= n, F] replicated input features.  Returns this rank's rows of the logits [rows, C].  dtype: fp32 only."""
+        _fp32_only(dtype, "HaloShardedTeacher")
         if self.overlap:
             return self._forward_overlapped(x_full)
         enc, sh, be, g, pl = self.enc, self.sh, self.be, self.g, self.plan

@@ -288,14 +288,61 @@ class SAGE(nn.Module):
         self.__dict__["_placed_x"] = (weakref.ref(feats), sig, px)
         return px
 
-    def inference(self, dataloader, feats, whole_graph=True):
+    def _whole_graph_layer_bf16(self, l, g, x, projected):
+        """Layer l of the whole-graph sweep with bf16 activation storage: (y, projected for layer l+1 or None).  A matrix is stored as bf16
+        exactly when an aggregation gathers it -- the chained projection, a project-first layer's x @ W^T, and a hidden layer's output
+        when the next layer aggregates first; all sums, MFMA and epilogues are fp32 and the logits come out fp32."""
+        layer = self.layers[l]
+        ep_scale, ep_shift, relu = self._tail(l)
+        n = g.num_dst_nodes()
+        nxt = self.layers[l + 1] if l + 1 < self.num_layers else None
+        out_dtype = torch.bfloat16 if nxt is not None and nxt._in_feats <= nxt._out_feats else torch.float32
+        if projected is not None:
+            return ops.spmm(g.indptr, g.indices, projected, n, ops.AGG_SAGE_GCN, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu,
+                            out_dtype=out_dtype), None
+        if nxt is not None and layer.fused_eligible() and nxt._in_feats > nxt._out_feats and nxt._out_feats <= 256 \
+                and SAGE.CHAIN_NEXT_PROJECTION:
+            _, proj = ops.sage_fused(g.indptr, g.indices, x, n, layer.fc_neigh.weight, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu,
+                                     x_self=x[:n], w_next=nxt.fc_neigh.weight, want_out=False, tile_order=g.fused_tile_order(),
+                                     out_next_dtype=torch.bfloat16)
+            return None, proj
+        return layer.forward_bf16(g, x, x[:n], ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, out_dtype=out_dtype), None
+
+    def _inference_bf16(self, dataloader, feats, whole_graph):
+        g = getattr(dataloader, "graph", None)
+        if not whole_graph or g is None:
+            raise NotImplementedError("SAGE.inference(dtype=torch.bfloat16): the whole-graph sweep only (whole_graph=True over a loader with a "
+                                      "resident graph); the chunked and literal sweeps are fp32")
+        if self.norm_type == "layer":
+            raise NotImplementedError("SAGE.inference(dtype=torch.bfloat16): LayerNorm teachers are fp32 only (the per-row statistics pass "
+                                      "is not part of the bf16 storage path)")
+        with torch.no_grad():
+            first = self.layers[0]
+            if first._in_feats <= first._out_feats:         # layer 0 aggregates its input features: they are gathered, so bf16
+                x = ops.as_bf16_feat(feats) if feats.dtype == torch.bfloat16 else ops.to_bf16(feats)
+            else:                                           # layer 0 projects first: only its fp32 GEMM reads them
+                x = feats.float() if feats.dtype == torch.bfloat16 else feats
+            projected = None
+            for l in range(self.num_layers):
+                x, projected = self._whole_graph_layer_bf16(l, g, x, projected)
+            return x
+
+    def inference(self, dataloader, feats, whole_graph=True, dtype=torch.float32):
         """Layer-wise full-neighbour inference (reference models.py:121-148).
 
         `dataloader` is a glnn_amd.graph.FullNeighborLoader.  whole_graph=True aggregates every destination row
         of a layer in ONE launch over the resident CSR (each dst row is independent, so the result is identical
         to the chunked sweep); whole_graph=False walks the chunks exactly like the reference does
-        (gather input rows -> block conv -> fused BN/ReLU -> scatter)."""
+        (gather input rows -> block conv -> fused BN/ReLU -> scatter).
+
+        dtype=torch.bfloat16: the whole-graph sweep with bf16 activation STORAGE (_whole_graph_layer_bf16) -- the gathered matrices move
+        half the bytes; arithmetic stays fp32 and the returned logits are fp32.  `feats` may be fp32 (cast once per call) or bf16.  Its
+        buffers are plain allocations (no ops.placed_for_gather placement).  Not for whole_graph=False or LayerNorm teachers."""
         _need_hip(feats, "SAGE.inference")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"SAGE.inference: dtype must be torch.float32 or torch.bfloat16, not {dtype}")
+        if dtype == torch.bfloat16:
+            return self._inference_bf16(dataloader, feats, whole_graph)
         whole_graph = whole_graph and getattr(dataloader, "graph", None) is not None     # loaders that do not sweep arange(N)
         with torch.no_grad():
             x = ops.as_feat(feats)
@@ -491,7 +538,13 @@ class Model(nn.Module):
             return self.encoder(feats)
         return self.encoder(data, feats)
 
-    def inference(self, data, feats):
+    def inference(self, data, feats, dtype=torch.float32):
+        """dtype=torch.bfloat16: bf16 activation storage, the SAGE teacher's whole-graph forward only (SAGE.inference)."""
+        if dtype != torch.float32:
+            if "SAGE" not in self.model_name:
+                raise NotImplementedError(f"{self.model_name}.inference(dtype={dtype}): bf16 activation storage is implemented for the SAGE "
+                                          "teacher's whole-graph forward only")
+            return self.encoder.inference(data, feats, dtype=dtype)
         if "SAGE" in self.model_name:
             return self.encoder.inference(data, feats)
         return self.forward(data, feats)

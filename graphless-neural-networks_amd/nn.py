@@ -67,6 +67,28 @@ class SAGEConv(nn.Module):
         agg = ops.spmm(graph.indptr, graph.indices, h_src, n_dst, ops.AGG_SAGE_GCN)
         return ops.gemm(agg, w, ep_scale=ep_scale, ep_shift=shift, relu=relu, out=out)
 
+    def forward_bf16(self, graph, h_src, h_dst, ep_scale=None, ep_shift=None, relu=False, out_dtype=torch.float32):
+        """Eval-mode layer with bf16 activation STORAGE (SAGE.inference(..., dtype=torch.bfloat16)): the forms `forward` picks, where every
+        matrix an aggregation gathers is bf16 and all arithmetic is fp32.  h_src / h_dst: bf16 rows when the layer aggregates first, fp32
+        when it projects first (a GEMM is then their only reader).  out_dtype: torch.bfloat16 when the next layer gathers the result."""
+        n_dst = graph.num_dst_nodes()
+        w, b = self.fc_neigh.weight, self.fc_neigh.bias
+        fused_tail = ep_scale is not None or ep_shift is not None or relu
+        shift = ep_shift if fused_tail else b
+        if self._in_feats > self._out_feats:
+            # project first in fp32, store the projection as bf16, aggregate it
+            hw = ops.to_bf16(ops.gemm(ops.as_feat(h_src), w))
+            return ops.spmm(graph.indptr, graph.indices, hw, n_dst, ops.AGG_SAGE_GCN, ep_scale=ep_scale, ep_shift=shift, relu=relu,
+                            out_dtype=out_dtype)
+        if self._in_feats <= FUSED_SAGE_MAX_IN and self._out_feats <= 256:
+            order = graph.fused_tile_order() if n_dst == graph.n_dst else None
+            return ops.sage_fused(graph.indptr, graph.indices, h_src, n_dst, w, ep_scale=ep_scale, ep_shift=shift, relu=relu,
+                                  x_self=h_dst, tile_order=order, out_dtype=out_dtype)
+        # aggregate the bf16 rows into an fp32 matrix, then the fp32 GEMM
+        agg = ops.spmm(graph.indptr, graph.indices, h_src, n_dst, ops.AGG_SAGE_GCN, x_self=h_dst, out_dtype=torch.float32)
+        y = ops.gemm(agg, w, ep_scale=ep_scale, ep_shift=shift, relu=relu)
+        return ops.to_bf16(y) if out_dtype == torch.bfloat16 else y
+
 
 class GraphConv(nn.Module):
     def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True, activation=None,

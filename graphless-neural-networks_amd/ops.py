@@ -92,6 +92,76 @@ def feat_empty(n, d, device, zero=False):
     return buf[:, :d]
 
 
+DTYPE_F32, DTYPE_BF16 = 0, 1            # GLNN_DTYPE_* of include/glnn_hip.h
+
+
+def round8(d):
+    return (d + 7) // 8 * 8
+
+
+def bf16_empty(n, d, device, zero=False):
+    """[n, d] bf16 view of an [n, round8(d)] buffer: rows 16-byte aligned as the bf16 kernels need (a lane moves 8 bf16).  The counterpart
+    of feat_empty for the matrices the bf16 teacher forward gathers; a plain allocation (no ops.placed_for_gather placement)."""
+    buf = (torch.zeros if zero else torch.empty)((n, round8(d)), dtype=torch.bfloat16, device=device)
+    return buf[:, :d]
+
+
+def _bf16_mat(t, name):
+    if t.dtype != torch.bfloat16 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{name}: expected 2-D bfloat16 row-major tensor")
+    return t
+
+
+def as_bf16_feat(t):
+    """t itself if its layout suits the bf16 kernels (leading dimension a multiple of 8 elements, 16-byte aligned base), else a padded copy
+    (bf16_empty, padding zeroed)."""
+    _bf16_mat(t, "as_bf16_feat")
+    if _ld(t) % 8 == 0 and _ld(t) >= t.shape[1] and t.data_ptr() % 16 == 0:
+        return t
+    out = bf16_empty(t.shape[0], t.shape[1], t.device, zero=True)
+    out.copy_(t)
+    return out
+
+
+def to_bf16(x, out=None):
+    """glnn_cast_f32_bf16: x [n, d] fp32 -> bf16, round to nearest even (bit for bit x.to(torch.bfloat16); NaN stays NaN).  Returns a
+    bf16_empty view (or fills `out`, a bf16 [n, d] tensor whose leading dimension is a multiple of 8)."""
+    _need_cuda(x, out)
+    _mat(x, "to_bf16 x")
+    n, d = x.shape
+    if out is None:
+        out = bf16_empty(n, d, x.device)
+    elif tuple(out.shape) != (n, d) or _ld(_bf16_mat(out, "to_bf16 out")) % 8:
+        raise ValueError("to_bf16: out must be a bf16 [n, d] tensor with a leading dimension that is a multiple of 8")
+    if n == 0 or d == 0:
+        return out
+    rc = _lib.lib().glnn_cast_f32_bf16(_p(x), _ld(x), n, d, _p(out), _ld(out), _stream())
+    _lib.check(rc, "glnn_cast_f32_bf16")
+    return out
+
+
+def _out_like(out, out_dtype, default, n, d, device, name):
+    """The output of a bf16-input launch: `out` (whose dtype then decides), else a fresh matrix of out_dtype (default: `default`)."""
+    if out_dtype is not None and out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{name}: out_dtype must be torch.float32 or torch.bfloat16")
+    if out is None:
+        dt = default if out_dtype is None else out_dtype
+        return bf16_empty(n, d, device) if dt == torch.bfloat16 else feat_empty(n, d, device)
+    if out_dtype is not None and out.dtype != out_dtype:
+        raise ValueError(f"{name}: out is {out.dtype}, out_dtype {out_dtype}")
+    if out.dtype == torch.bfloat16:
+        _bf16_mat(out, name)
+    else:
+        _mat(out, name)
+    if out.shape[0] < n or out.shape[1] != d:
+        raise ValueError(f"{name}: out must hold {n} rows of {d} columns")
+    return out
+
+
+def _dtype_code(t):
+    return DTYPE_BF16 if t.dtype == torch.bfloat16 else DTYPE_F32
+
+
 _RANDPERM_LOCK = __import__("threading").Lock()
 
 
@@ -199,14 +269,20 @@ def hub_plan(indptr, n_dst):
 
 
 def spmm(indptr, indices, x, n_dst, mode, row_scale=None, col_scale=None, ep_scale=None, ep_shift=None,
-         relu=False, out=None, x_self=None, self_rows=None, hub=None, chunks=None):
+         relu=False, out=None, x_self=None, self_rows=None, hub=None, chunks=None, out_dtype=None):
     """K1/K2 glnn_spmm_csr_f32.  x: [n_src, d] feature tensor (see as_feat); returns [n_dst, d].
     chunks (ChunkSignals.launch(...), SAGE_GCN, d <= 256): ONE launch over the chunks of the row range -- `out` (and `x_self`, unless
     self_rows is given) are then WHOLE buffers addressed through the descriptor's per-chunk rows, and every chunk signals its completion.
     x_self (SAGE_GCN only): the destination rows' own features, default x[:n_dst] (a row shard passes its slice).
     self_rows (SAGE_GCN only, int64 [n_dst]): destination v's own row is x_self[self_rows[v]] (global-id blocks).
-    hub (optional HubPlan of (indptr, n_dst)): the hub rows' segments are gathered by one workgroup each first (same result bit for bit)."""
+    hub (optional HubPlan of (indptr, n_dst)): the hub rows' segments are gathered by one workgroup each first (same result bit for bit).
+    bf16 x (and x_self): glnn_spmm_csr_bf16, fp32 sums; the output is `out`'s dtype, else out_dtype (default bf16); no hub / chunks."""
     _need_cuda(indptr, indices, x, row_scale, col_scale, ep_scale, ep_shift, out, x_self, self_rows)
+    if x.dtype == torch.bfloat16:
+        return _spmm_bf16(indptr, indices, x, n_dst, mode, row_scale, col_scale, ep_scale, ep_shift, relu, out, x_self, self_rows, hub,
+                          chunks, out_dtype)
+    if out_dtype not in (None, torch.float32):
+        raise ValueError("spmm: fp32 rows give an fp32 output (a bf16 output needs bf16 rows: ops.to_bf16)")
     x = as_feat(x)
     if self_rows is not None and (self_rows.dtype != torch.int64 or not self_rows.is_contiguous() or self_rows.numel() < n_dst):
         raise ValueError("spmm: self_rows must be a contiguous int64 vector of n_dst row ids")
@@ -242,6 +318,33 @@ def _spmm_call(indptr, indices, n_dst, n_src, x, d, mode, row_scale, col_scale, 
     if plan is not None:
         return _lib.lib().glnn_spmm_csr_plan_f32(*args, plan, _stream())
     return _lib.lib().glnn_spmm_csr_f32(*args, _stream())
+
+
+def _spmm_bf16(indptr, indices, x, n_dst, mode, row_scale, col_scale, ep_scale, ep_shift, relu, out, x_self, self_rows, hub, chunks,
+               out_dtype):
+    if hub is not None or chunks is not None:
+        raise ValueError("spmm: bf16 rows take neither a hub plan nor chunks")
+    x = as_bf16_feat(x)
+    if self_rows is not None and (self_rows.dtype != torch.int64 or not self_rows.is_contiguous() or self_rows.numel() < n_dst):
+        raise ValueError("spmm: self_rows must be a contiguous int64 vector of n_dst row ids")
+    if x_self is None:
+        x_self = x
+    elif x_self.dtype != torch.bfloat16 or (self_rows is None and x_self.shape[0] < n_dst) or x_self.shape[1] != x.shape[1]:
+        raise ValueError("spmm: x_self must be bf16 like x and hold n_dst rows of the same width")
+    n_src, d = x.shape
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32:
+        raise ValueError("spmm: indptr must be int64 and indices int32")
+    out = _out_like(out, out_dtype, torch.bfloat16, n_dst, d, x.device, "spmm out")
+    x_self = as_bf16_feat(x_self)
+    with _Timed("spmm_bf16", d=d, n_dst=n_dst, mode=mode):
+        rc = _lib.lib().glnn_spmm_csr_bf16(
+            _p(indptr), _p(indices), n_dst, n_src, _p(x), _ld(x), d, mode,
+            _p(_vec(row_scale, n_dst, "row_scale")), _p(_vec(col_scale, n_src, "col_scale")),
+            _p(x_self) if mode == AGG_SAGE_GCN else None, _ld(x_self), _p(self_rows),
+            _p(_vec(ep_scale, d, "ep_scale")), _p(_vec(ep_shift, d, "ep_shift")), 1 if relu else 0,
+            _p(out), _ld(out), _dtype_code(out), _stream())
+    _lib.check(rc, "glnn_spmm_csr_bf16")
+    return out
 
 
 # Parameters and BatchNorm buffers are also written THROUGH RAW POINTERS by this library (the fused Adam launch, the statistics kernels, the
@@ -358,13 +461,20 @@ class ChunkSignals:
 
 
 def sage_fused(indptr, indices, x, n_dst, w, ep_scale=None, ep_shift=None, relu=False, out=None, x_self=None, w_packed=None,
-               w_next=None, out_next=None, want_out=True, tile_order=None, hub=None, chunks=None):
+               w_next=None, out_next=None, want_out=True, tile_order=None, hub=None, chunks=None, out_dtype=None, out_next_dtype=None):
     """K1F glnn_sage_fused_f32: epi(((A x + x_self)/(deg+1)) @ w.T) in one launch (d_in, d_out <= 256).
     w_next [d_out2, d_out]: also returns (.. , out @ w_next.T) -- the projection of the NEXT layer when it projects first;
     with want_out=False the hidden rows themselves are not written at all (returns (None, projected)).
     chunks (ChunkSignals.launch(...)): the launch covers the chunks of a row range -- x_self / out / out_next are then WHOLE buffers
-    addressed through the descriptor's per-chunk rows (they must be given), and every chunk signals its completion."""
+    addressed through the descriptor's per-chunk rows (they must be given), and every chunk signals its completion.
+    bf16 x (and x_self): glnn_sage_fused_bf16, the same fp32 MFMA on the fp32 aggregate; out / out_next are stored in their own dtype, else
+    in out_dtype / out_next_dtype (default bf16); no hub / chunks."""
     _need_cuda(indptr, indices, x, w, ep_scale, ep_shift, out, x_self, w_next, out_next)
+    if x.dtype == torch.bfloat16:
+        return _sage_fused_bf16(indptr, indices, x, n_dst, w, ep_scale, ep_shift, relu, out, x_self, w_packed, w_next, out_next, want_out,
+                                tile_order, hub, chunks, out_dtype, out_next_dtype)
+    if out_dtype not in (None, torch.float32) or out_next_dtype not in (None, torch.float32):
+        raise ValueError("sage_fused: fp32 rows give fp32 outputs (bf16 outputs need bf16 rows: ops.to_bf16)")
     if chunks is not None and (x_self is None or (out is None and want_out) or (w_next is not None and out_next is None)):
         raise ValueError("sage_fused(chunks=...): x_self and the output buffers must be given (they are addressed by the chunks' rows)")
     x = as_feat(x)
@@ -399,6 +509,43 @@ def sage_fused(indptr, indices, x, n_dst, w, ep_scale=None, ep_shift=None, relu=
         else:
             rc = _lib.lib().glnn_sage_fused_f32(*args, _stream())
     _lib.check(rc, "glnn_sage_fused_f32")
+    return out if w_next is None else (out, out_next)
+
+
+def _sage_fused_bf16(indptr, indices, x, n_dst, w, ep_scale, ep_shift, relu, out, x_self, w_packed, w_next, out_next, want_out, tile_order,
+                     hub, chunks, out_dtype, out_next_dtype):
+    if hub is not None or chunks is not None:
+        raise ValueError("sage_fused: bf16 rows take neither a hub plan nor chunks")
+    x = as_bf16_feat(x)
+    if x_self is not None and (x_self.dtype != torch.bfloat16 or x_self.shape[0] < n_dst or x_self.shape[1] != x.shape[1]):
+        raise ValueError("sage_fused: x_self must be bf16 like x and hold n_dst rows of the same width")
+    x_self = x if x_self is None else as_bf16_feat(x_self)
+    n_src, d_in = x.shape
+    d_out = w.shape[0]
+    if w.shape[1] != d_in:
+        raise ValueError("sage_fused: weight must be [d_out, d_in]")
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32:
+        raise ValueError("sage_fused: indptr must be int64 and indices int32")
+    if tile_order is not None and (tile_order.dtype != torch.int32 or not tile_order.is_contiguous() or tile_order.numel() != (n_dst + 31) // 32):
+        raise ValueError("sage_fused: tile_order must be a contiguous int32 permutation of the ceil(n_dst / 32) tile ids")
+    if w_packed is None:
+        w_packed = pack_weight(w)
+    if out is not None or want_out or w_next is None:
+        out = _out_like(out, out_dtype, torch.bfloat16, n_dst, d_out, x.device, "sage_fused out")
+    w2p, d_out2 = None, 0
+    if w_next is not None:
+        if w_next.shape[1] != d_out:
+            raise ValueError("sage_fused: w_next must be [d_out2, d_out]")
+        w2p, d_out2 = pack_weight(w_next), w_next.shape[0]
+        out_next = _out_like(out_next, out_next_dtype, torch.bfloat16, n_dst, d_out2, x.device, "sage_fused out_next")
+    with _Timed("sage_fused_bf16", d=d_in, n_dst=n_dst, d_out=d_out, d_chain=d_out2, d_written=(d_out if out is not None else 0) + d_out2):
+        rc = _lib.lib().glnn_sage_fused_bf16(
+            _p(indptr), _p(indices), n_dst, n_src, _p(x), _ld(x), d_in, _p(x_self), _ld(x_self),
+            _p(w_packed), d_out, _p(_vec(ep_scale, d_out, "ep_scale")), _p(_vec(ep_shift, d_out, "ep_shift")), 1 if relu else 0,
+            _p(out), _ld(out) if out is not None else 0, _dtype_code(out) if out is not None else DTYPE_F32,
+            _p(w2p), d_out2, _p(out_next), _ld(out_next) if out_next is not None else 0,
+            _dtype_code(out_next) if out_next is not None else DTYPE_F32, _p(tile_order), _stream())
+    _lib.check(rc, "glnn_sage_fused_bf16")
     return out if w_next is None else (out, out_next)
 
 

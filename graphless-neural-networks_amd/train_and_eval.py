@@ -98,11 +98,19 @@ def train_mini_batch(model, feats, labels, batch_size, criterion, optimizer, lam
     return eng.loss_accum.item() / num_batches      # the only host sync of the pass
 
 
-def evaluate(model, data, feats, labels, criterion, evaluator, idx_eval=None):
-    """reference train_and_eval.py:89-105"""
+INFERENCE_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16}
+
+
+def inference_dtype(conf):
+    """The activation storage of the teacher's evaluation forward (--inference_dtype, default float32)."""
+    return INFERENCE_DTYPES[conf.get("inference_dtype", "float32")]
+
+
+def evaluate(model, data, feats, labels, criterion, evaluator, idx_eval=None, dtype=torch.float32):
+    """reference train_and_eval.py:89-105.  dtype: Model.inference's activation storage (torch.bfloat16: SAGE teachers only)."""
     model.eval()
     with torch.no_grad():
-        logits = model.inference(data, feats)
+        logits = model.inference(data, feats, dtype=dtype) if dtype != torch.float32 else model.inference(data, feats)
         out = ops.log_softmax(logits)
         if idx_eval is None:
             loss = _apply_criterion(criterion, out, labels)
@@ -176,6 +184,7 @@ def run_transductive(conf, model, g, feats, labels, indices, criterion, evaluato
     set_seed(conf["seed"])
     device = conf["device"]
     batch_size = conf["batch_size"]
+    inf_dtype = inference_dtype(conf)          # --inference_dtype: the activation storage of the SAGE teacher's evaluation forward
     idx_train, idx_val, idx_test = indices
     feats, labels = feats.to(device), labels.to(device)
     idx_train, idx_val, idx_test = idx_train.to(device), idx_val.to(device), idx_test.to(device)
@@ -208,7 +217,7 @@ def run_transductive(conf, model, g, feats, labels, indices, criterion, evaluato
             _, l_va, s_va = evaluate_mini_batch(model, feats_val, labels_val, criterion, batch_size, evaluator)
             _, l_te, s_te = evaluate_mini_batch(model, feats_test, labels_test, criterion, batch_size, evaluator)
         else:
-            out, l_tr, s_tr = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_train)
+            out, l_tr, s_tr = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_train, dtype=inf_dtype)
             l_va, s_va = criterion(out[idx_val], labels[idx_val]).item(), evaluator(out[idx_val], labels[idx_val])
             l_te, s_te = criterion(out[idx_test], labels[idx_test]).item(), evaluator(out[idx_test], labels[idx_test])
         return [l_tr, l_va, l_te, s_tr, s_va, s_te], s_va, f"s_train: {s_tr:.4f} | s_val: {s_va:.4f} | s_test: {s_te:.4f}"
@@ -217,7 +226,7 @@ def run_transductive(conf, model, g, feats, labels, indices, criterion, evaluato
     if is_mlp:
         out, _, score_val = evaluate_mini_batch(model, feats, labels, criterion, batch_size, evaluator, idx_val)
     else:
-        out, _, score_val = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_val)
+        out, _, score_val = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_val, dtype=inf_dtype)
     score_test = evaluator(out[idx_test], labels[idx_test])
     logger.info(f"Best valid model at epoch: {best_epoch: 3d}, score_val: {score_val :.4f}, score_test: {score_test :.4f}")
     return out, score_val, score_test
@@ -263,6 +272,7 @@ def run_inductive(conf, model, g, feats, labels, indices, criterion, evaluator, 
     set_seed(conf["seed"])
     device = conf["device"]
     batch_size = conf["batch_size"]
+    inf_dtype = inference_dtype(conf)          # --inference_dtype: the activation storage of the SAGE teacher's evaluation forward
     obs_idx_train, obs_idx_val, obs_idx_test, idx_obs, idx_test_ind = [i.to(device) for i in indices]
     feats, labels = feats.to(device), labels.to(device)
     obs_feats, obs_labels = feats[idx_obs], labels[idx_obs]
@@ -299,10 +309,10 @@ def run_inductive(conf, model, g, feats, labels, indices, criterion, evaluator, 
             _, l_tt, s_tt = evaluate_mini_batch(model, feats_tt, labels_tt, criterion, batch_size, evaluator)
             _, l_ti, s_ti = evaluate_mini_batch(model, feats_ti, labels_ti, criterion, batch_size, evaluator)
         else:
-            obs_out, l_tr, s_tr = evaluate(model, obs_data_eval, obs_feats, obs_labels, criterion, evaluator, obs_idx_train)
+            obs_out, l_tr, s_tr = evaluate(model, obs_data_eval, obs_feats, obs_labels, criterion, evaluator, obs_idx_train, dtype=inf_dtype)
             l_va, s_va = criterion(obs_out[obs_idx_val], obs_labels[obs_idx_val]).item(), evaluator(obs_out[obs_idx_val], obs_labels[obs_idx_val])
             l_tt, s_tt = criterion(obs_out[obs_idx_test], obs_labels[obs_idx_test]).item(), evaluator(obs_out[obs_idx_test], obs_labels[obs_idx_test])
-            _, l_ti, s_ti = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_test_ind)
+            _, l_ti, s_ti = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_test_ind, dtype=inf_dtype)
         return ([l_tr, l_va, l_tt, l_ti, s_tr, s_va, s_tt, s_ti], s_va,
                 f"s_train: {s_tr:.4f} | s_val: {s_va:.4f} | s_tt: {s_tt:.4f} | s_ti: {s_ti:.4f}")
 
@@ -311,8 +321,8 @@ def run_inductive(conf, model, g, feats, labels, indices, criterion, evaluator, 
         obs_out, _, score_val = evaluate_mini_batch(model, obs_feats, obs_labels, criterion, batch_size, evaluator, obs_idx_val)
         out, _, score_test_ind = evaluate_mini_batch(model, feats, labels, criterion, batch_size, evaluator, idx_test_ind)
     else:
-        obs_out, _, score_val = evaluate(model, obs_data_eval, obs_feats, obs_labels, criterion, evaluator, obs_idx_val)
-        out, _, score_test_ind = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_test_ind)
+        obs_out, _, score_val = evaluate(model, obs_data_eval, obs_feats, obs_labels, criterion, evaluator, obs_idx_val, dtype=inf_dtype)
+        out, _, score_test_ind = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_test_ind, dtype=inf_dtype)
     score_test_tran = evaluator(obs_out[obs_idx_test], obs_labels[obs_idx_test])
     out[idx_obs] = obs_out
     logger.info(f"Best valid model at epoch: {best_epoch :3d}, score_val: {score_val :.4f}, score_test_tran: {score_test_tran :.4f}, score_test_ind: {score_test_ind :.4f}")

@@ -713,6 +713,42 @@ GLNN_API int glnn_gather_rows_f32(const float* x, int64_t ldx, const int64_t* ro
 GLNN_API int glnn_scatter_rows_f32(const float* x, int64_t ldx, const int64_t* rows, int64_t n_rows,
                                    int d, float* out, int64_t ldo, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * bf16 activation storage for the whole-graph SAGE teacher forward (csrc/sage_bf16.hip).  A matrix that an aggregation gathers may be
+ * STORED as bf16 (uint16_t bit patterns, torch.bfloat16); every sum, MFMA and epilogue stays fp32 and values are rounded to bf16 only
+ * when stored: round to nearest even, NaN -> 0x7FC0 (torch's Tensor.to(torch.bfloat16)).  bf16 matrices need a leading dimension that is a
+ * multiple of 8 elements and a 16-byte aligned base (a lane moves 8 bf16); columns [d, ld) are padding, written as 0 by these kernels.
+ * An fp32 output keeps the fp32 conventions above (ld a multiple of 4).  Results are deterministic (fixed-order folds, no float atomics)
+ * but not bit-equal to the fp32 entries run on the widened rows: a wave splits a row's edges over twice as many lane groups.
+ * ------------------------------------------------------------------------------------------ */
+#define GLNN_DTYPE_F32 0
+#define GLNN_DTYPE_BF16 1
+
+/* out[i, j] = bf16(x[i, j]) for j < d, 0 for the padding columns d <= j < d rounded up to 8 (columns beyond are not touched).
+ * ldx >= d (any), ldo a multiple of 8 and >= d. */
+GLNN_API int glnn_cast_f32_bf16(const float* x, int64_t ldx, int64_t n, int d, uint16_t* out, int64_t ldo,
+                                void* stream);
+
+/* glnn_spmm_csr_f32 over bf16 rows x / x_self (ldx, ld_self multiples of 8 and >= d rounded up to 8), both modes, the same epilogue;
+ * `out` holds fp32 (out_dtype GLNN_DTYPE_F32, ldo a multiple of 4) or bf16 (GLNN_DTYPE_BF16, ldo a multiple of 8).  Rows wider than
+ * 256 elements are processed in column tiles of 256 within one launch.  No hub plan / chunk variants. */
+GLNN_API int glnn_spmm_csr_bf16(const int64_t* indptr, const int32_t* indices, int64_t n_dst,
+                                int64_t n_src, const uint16_t* x, int64_t ldx, int d, int mode,
+                                const float* row_scale, const float* col_scale,
+                                const uint16_t* x_self, int64_t ld_self, const int64_t* self_rows,
+                                const float* ep_scale, const float* ep_shift, int relu, void* out,
+                                int64_t ldo, int out_dtype, void* stream);
+
+/* glnn_sage_fused_f32 over bf16 rows x / x_self: the fp32 aggregate of the 32-row tile in LDS feeds the same fp32 MFMA
+ * (v_mfma_f32_32x32x2_f32) passes; `out` and the chained `out2` are each stored fp32 or bf16 (out_dtype / out2_dtype, GLNN_DTYPE_*).
+ * The chained pass reads the fp32 hidden row, never its rounded copy. */
+GLNN_API int glnn_sage_fused_bf16(const int64_t* indptr, const int32_t* indices, int64_t n_dst,
+                                  int64_t n_src, const uint16_t* x, int64_t ldx, int d_in,
+                                  const uint16_t* x_self, int64_t ld_self, const float* w_packed,
+                                  int d_out, const float* ep_scale, const float* ep_shift, int relu,
+                                  void* out, int64_t ldo, int out_dtype, const float* w2_packed, int d_out2,
+                                  void* out2, int64_t ldo2, int out2_dtype, const int32_t* tile_order, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
