@@ -88,6 +88,13 @@ SIGNATURES = {
                                 c_vp, c_i64, c_vp, c_i64, c_vp],
     "glnn_csr_transpose_eids": [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "glnn_edge_drop_mask_u8": [c_i64, c_int, c_f32, c_u32, c_vp, c_vp],
+    "glnn_gat_scores_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "glnn_gat_attn_fwd_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_u32, c_int, c_vp, c_i64,
+                              c_vp, c_vp],
+    "glnn_gat_attn_bwd_workspace_floats": [c_i64, c_int, c_int],
+    "glnn_gat_attn_bwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                              c_vp, c_i64, c_vp, c_i64, c_f32, c_f32, c_u32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "glnn_gat_attn_mask_u8": [c_i64, c_int, c_f32, c_u32, c_vp, c_vp],
     "glnn_gather_rows_f32": [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp],
     "glnn_scatter_rows_f32": [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp],
 }
@@ -206,6 +213,7 @@ def lib():
         h.glnn_block_workspace_bytes.restype = c_i64
         h.glnn_csr_transpose_workspace_bytes.restype = c_i64
         h.glnn_layernorm_bwd_workspace_floats.restype = c_i64
+        h.glnn_gat_attn_bwd_workspace_floats.restype = c_i64
         h.glnn_sage_step_ws_bn_floats.restype = c_i64
         h.glnn_sage_step_ws_ln_floats.restype = c_i64
         h.glnn_last_error.argtypes = []

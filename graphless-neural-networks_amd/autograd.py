@@ -251,3 +251,73 @@ def appnp_propagate(graph, h0, k, alpha, edge_drop, training):
         return AppnpPropFn.apply(graph, h0, int(k), float(alpha), p, seed)
     with torch.no_grad():
         return appnp_fwd(graph, h0, int(k), float(alpha), p, seed)
+
+
+# ------------------------------------------------------------------------------------------ GAT layer (dgl 0.6.1 GATConv)
+def gat_layer_fwd(g, x, w, attn_l, attn_r, heads, out_feats, slope, relu, feat_p=0.0, feat_seed=0, attn_p=0.0, attn_seed=0, signed=True,
+                  want_lse=False):
+    """One GATConv forward (docs/GAT_SEMANTICS.md): projection with the feature dropout in the operand load, el / er from one read of z,
+    edge softmax + aggregation (+ ReLU).  Returns (y, (z, el, er, lse)); lse only when the backward will follow."""
+    z, z2 = ops.gat_project(x, w, feat_p, feat_seed, signed)
+    el, er = ops.gat_scores(z, attn_l, attn_r, heads, out_feats, z2=z2)
+    y, lse = ops.gat_attn_fwd(g.indptr, g.indices, g.num_edges(), z, el, er, heads, out_feats, slope, attn_p, attn_seed, relu=relu,
+                              want_lse=want_lse)
+    return y, (z, el, er, lse)
+
+
+def gat_layer_bwd(g, gy, y, saved, x, w, attn_l, attn_r, heads, out_feats, slope, feat_p=0.0, feat_seed=0, attn_p=0.0, attn_seed=0,
+                  signed=True, need_dx=True, dw=None, dattn_l=None, dattn_r=None):
+    """Backward of gat_layer_fwd.  gy = dL/dy ALREADY behind the activation mask (zero where a ReLU layer's y is 0).  Returns
+    (da = dz W -- the input gradient BEFORE the feature-dropout mask, or None; dW; dattn_l; dattn_r)."""
+    z, el, er, lse = saved
+    dz, dal, dar = ops.gat_attn_bwd(g, z, el, er, lse, attn_l, attn_r, gy, y, heads, out_feats, slope, attn_p, attn_seed,
+                                    dattn_l=dattn_l, dattn_r=dattn_r)
+    dw = ops.gat_project_wgrad(dz, x, feat_p, feat_seed, signed, out=dw)
+    da = ops.gemm(dz, w, w_is_kn=True) if need_dx else None
+    return da, dw, dal, dar
+
+
+class GatConvFn(torch.autograd.Function):
+    """GATConv as a differentiable op on the HIP path; the backward replays the forward's dropout masks from their seeds."""
+
+    @staticmethod
+    def forward(ctx, graph, x, w, attn_l, attn_r, heads, out_feats, slope, relu, feat_p, feat_seed, attn_p, attn_seed, signed):
+        x = ops.as_feat(x.detach())
+        y, saved = gat_layer_fwd(graph, x, w.detach(), attn_l.detach(), attn_r.detach(), heads, out_feats, slope, relu, feat_p, feat_seed,
+                                 attn_p, attn_seed, signed, want_lse=True)
+        ctx.graph, ctx.cfg = graph, (heads, out_feats, slope, relu, feat_p, feat_seed, attn_p, attn_seed, signed)
+        ctx.save_for_backward(x, w, attn_l, attn_r, y, *saved)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, attn_l, attn_r, y, z, el, er, lse = ctx.saved_tensors
+        heads, out_feats, slope, relu, feat_p, feat_seed, attn_p, attn_seed, signed = ctx.cfg
+        dy = ops.as_feat(dy.contiguous())
+        gy = ops.bn_relu_bwd(dy, y)[0] if relu else dy                     # dy * [y > 0]
+        da, dw, dal, dar = gat_layer_bwd(ctx.graph, gy, y, (z, el, er, lse), x, w.detach(), attn_l.detach(), attn_r.detach(), heads,
+                                         out_feats, slope, feat_p, feat_seed, attn_p, attn_seed, signed, need_dx=ctx.needs_input_grad[1])
+        if da is not None and feat_p > 0:
+            da = ops.act_fwd(da, drop_p=feat_p, drop_seed=feat_seed, relu=False)      # the feature-dropout mask and 1 / (1 - p)
+        return (None, da, dw, dal.view_as(attn_l), dar.view_as(attn_r)) + (None,) * 9
+
+
+def gat_conv_seeds(count):
+    """(feature-dropout seed, attention-dropout seed) of the count-th dropout draw of this process (tests replay the masks from them)."""
+    base = int(torch.initial_seed()) * 0x85EBCA77 + count * 0x9E3779B1
+    return (base + 0x47415446) & 0xFFFFFFFF, (base + 0x47415441) & 0xFFFFFFFF
+
+
+def gat_conv(graph, x, w, attn_l, attn_r, heads, out_feats, slope, relu, feat_drop, attn_drop, training, signed=True):
+    """GATConv forward: both dropouts only in training; their counter-based seeds are drawn like norm_act_drop's.  Differentiable in
+    training mode (appnp_propagate's rule); the eval forward keeps nothing for a backward."""
+    fp = float(feat_drop) if training else 0.0
+    ap = float(attn_drop) if training else 0.0
+    fs = as_ = 0
+    if fp > 0 or ap > 0:
+        _drop_counter[0] += 1
+        fs, as_ = gat_conv_seeds(_drop_counter[0])
+    if training and torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or attn_l.requires_grad or attn_r.requires_grad):
+        return GatConvFn.apply(graph, x, w, attn_l, attn_r, heads, out_feats, slope, relu, fp, fs, ap, as_, signed)
+    with torch.no_grad():
+        return gat_layer_fwd(graph, ops.as_feat(x), w, attn_l, attn_r, heads, out_feats, slope, relu, fp, fs, ap, as_, signed)[0]

@@ -378,6 +378,12 @@ def _fp32_only(dtype, who):
                                   "SAGE.inference(..., dtype=torch.bfloat16) on one device)")
 
 
+def _refuse_gat(encoder, who):
+    if type(encoder).__name__ == "GAT":
+        raise NotImplementedError(f"{who}: the GAT teacher is not sharded -- its edge softmax needs every in-edge of a row and the per-head "
+                                  "scores of the remote sources, an exchange the sharded forward does not have (whole-graph GAT only)")
+
+
 class ShardedTeacher:
     """SAGE layer-wise inference over a row-sharded graph.  `graph_shard` = full graph's rows [lo,hi)
     (glnn_amd.graph.CSRGraph.row_range), column indices global.
@@ -396,6 +402,7 @@ class ShardedTeacher:
         "mixed":  (round 6) a fraction `mixed_fraction` of every chunk's rows travels wide, the rest narrow -- the continuous form between
                   the two: `shards` is replaced by shards.mixed(mixed_fraction) (whole chunks of either kind).
         All are chunked and overlapped when shards.chunks > 1; results are identical."""
+        _refuse_gat(encoder, "ShardedTeacher")
         if widening_exchange not in ("narrow", "wide", "mixed"):
             raise ValueError("ShardedTeacher: widening_exchange must be 'narrow', 'wide' or 'mixed'")
         if widening_exchange == "mixed":
@@ -986,6 +993,7 @@ class HaloShardedTeacher:
         a widening layer projects its own rows while the halo rows of its aggregate travel, and an aggregation whose input is
         being exchanged runs in two passes over the split CSR of HaloPlan.split_csr (local-source edges + self first, then the
         remote-source edges once the halo has landed).  Same sums, local edges before remote ones (results equal to rounding)."""
+        _refuse_gat(encoder, "HaloShardedTeacher")
         self.enc, self.g, self.sh, self.be, self.group, self.overlap = encoder, graph_shard, shards, be, group, overlap
         if graph_shard.n_dst != shards.rows:
             raise ValueError(f"HaloShardedTeacher: the graph shard has {graph_shard.n_dst} rows, the shard range {shards.rows}")

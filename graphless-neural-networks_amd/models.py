@@ -7,7 +7,8 @@ forward_fitnet / inference`, and state_dict key names (encoder.layers.{i}.weight
 Linear / SAGEConv / GraphConv / BatchNorm(eval) / ReLU goes through libglnn_hip.so.
 
 APPNP (an ablation teacher, models.py:282-344) runs its MLP trunk on the same kernels and its K-step propagation on
-csrc/appnp.hip (docs/APPNP_SEMANTICS.md).  GAT (ablation-only) is out of scope and raises."""
+csrc/appnp.hip (docs/APPNP_SEMANTICS.md).  GAT (models.py:202-279) runs its edge-softmax attention on csrc/gat.hip
+(docs/GAT_SEMANTICS.md): every encoder the reference can name is on the HIP path."""
 import contextlib
 
 import torch
@@ -16,7 +17,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .autograd import appnp_propagate, linear_fn, norm_act_drop
-from .nn import GraphConv, SAGEConv
+from .nn import GATConv, GraphConv, SAGEConv
 
 
 def _bn_eval_fold(bn, bias):
@@ -500,8 +501,53 @@ class APPNP(MLP):
         return h_list, appnp_propagate(g, h, self.k, self.alpha, self.edge_drop, self.training)
 
 
+class GAT(nn.Module):
+    """reference models.py:202-279: num_layers GATConv layers, `num_heads` heads of hidden_dim // num_heads features on every hidden layer
+    (ReLU inside the conv, outputs flattened to [N, hidden_dim] and kept in h_list), one head of output_dim features on the last (its
+    mean over one head is a reshape).  No norm layers and no dropout outside the convs (feat_drop = dropout_ratio, attn_drop)."""
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, num_heads=8, attn_drop=0.3,
+                 negative_slope=0.2, residual=False):
+        super().__init__()
+        if num_layers <= 1:
+            raise NotImplementedError("GAT: num_layers must be > 1 (the reference asserts it, models.py:218)")
+        if residual:
+            raise NotImplementedError("GAT: residual=True is not implemented (the reference's Model never sets it)")
+        hidden_dim //= num_heads
+        self.num_layers = num_layers
+        self.num_heads = num_heads
+        self.activation = activation
+        self.layers = nn.ModuleList()
+        heads = [num_heads] * num_layers + [1]
+        self.layers.append(GATConv(input_dim, hidden_dim, heads[0], dropout_ratio, attn_drop, negative_slope, False, activation))
+        for l in range(1, num_layers - 1):
+            self.layers.append(GATConv(hidden_dim * heads[l - 1], hidden_dim, heads[l], dropout_ratio, attn_drop, negative_slope, residual,
+                                       activation))
+        self.layers.append(GATConv(hidden_dim * heads[-2], output_dim, heads[-1], dropout_ratio, attn_drop, negative_slope, residual, None))
+
+    def forward(self, g, feats):
+        _need_hip(feats, "GAT.forward")
+        if isinstance(g, (list, tuple)):
+            raise NotImplementedError("GAT: block (bipartite) inputs are not implemented: the reference's GAT runs on the whole graph")
+        h = feats
+        h_list = []
+        for l, layer in enumerate(self.layers):
+            h = layer(g, h, nonneg=True if l > 0 and self.layers[l - 1].relu() else None)   # a ReLU layer's output is >= 0
+            if l != self.num_layers - 1:
+                h = h.flatten(1)
+                h_list.append(h)
+            else:
+                h = h[:, 0]                    # mean(1) over the last layer's ONE head (heads[-1] = 1, models.py:225)
+        return h_list, h
+
+
 class Model(nn.Module):
-    """Wrapper of different models (reference models.py:347-429)."""
+    """Wrapper of different models (reference models.py:347-429).
+
+    GAT confs must name BOTH `num_heads` and `attn_dropout_ratio` (every GAT section of train.conf.yaml does): `num_heads` is honoured
+    -- the reference reads only `attn_dropout_ratio` and hard-wires 8 heads, which agrees wherever the reference is configured, since all
+    its sections say 8 -- and a conf without either key raises NotImplementedError naming it instead of taking an implicit default.
+    hidden_dim must be a positive multiple of num_heads (docs/GAT_SEMANTICS.md)."""
 
     def __init__(self, conf):
         super().__init__()
@@ -517,8 +563,15 @@ class Model(nn.Module):
         elif "APPNP" in conf["model_name"]:
             self.encoder = APPNP(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
         elif "GAT" in conf["model_name"]:
-            raise NotImplementedError(f"{conf['model_name']}: ablation-only teacher (reference models.py:202-279), "
-                                      "outside the MI355X hot-path scope (SURVEY.md section 2 row 5)")
+            missing = [k for k in ("num_heads", "attn_dropout_ratio") if k not in conf]
+            if missing:
+                raise NotImplementedError(f"{conf['model_name']}: the conf does not name {' or '.join(missing)}; GAT is built only from "
+                                          "confs that carry both num_heads and attn_dropout_ratio (no implicit 8 heads, "
+                                          "docs/GAT_SEMANTICS.md)")
+            heads = int(conf["num_heads"])
+            if heads < 1 or conf["hidden_dim"] < heads or conf["hidden_dim"] % heads:
+                raise ValueError(f"GAT: hidden_dim ({conf['hidden_dim']}) must be a positive multiple of num_heads ({heads})")
+            self.encoder = GAT(activation=F.relu, num_heads=heads, attn_drop=conf["attn_dropout_ratio"], **common).to(conf["device"])
         else:
             raise ValueError(f"Unknown model_name {conf['model_name']}")
 

@@ -1,7 +1,8 @@
-"""Drop-in modules for the two dgl layers the reference's hot path uses, computing on libglnn_hip.so.
+"""Drop-in modules for the dgl layers the reference's teachers use, computing on libglnn_hip.so.
 
   SAGEConv(in, out, "gcn")(block, (h, h_dst))   <- dgl.nn.SAGEConv, reference models.py:84-99,112,138
   GraphConv(in, out, activation=)(g, h)          <- dgl.nn.GraphConv, reference models.py:170-187,193
+  GATConv(in, out, heads, ...)(g, h)             <- dgl.nn.GATConv, reference models.py:228-267 (docs/GAT_SEMANTICS.md)
 
 Parameter names follow dgl 0.6.1 so that a reference `model.pth` loads: SAGEConv.fc_neigh.{weight,bias}
 (weight [out,in], xavier_uniform gain=relu; no fc_self for "gcn"), GraphConv.{weight [in,out] xavier_uniform,
@@ -11,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import GraphConvFn, SpmmFn, graphconv_fwd, linear_fn
+from .autograd import GraphConvFn, SpmmFn, gat_conv, graphconv_fwd, linear_fn
 
 
 FUSED_SAGE_MAX_IN = 256   # aggregate-first layers with d_in, d_out <= 256 take the single-launch K1F kernel.  Interleaved
@@ -119,3 +120,57 @@ class GraphConv(nn.Module):
         if torch.is_grad_enabled() and (feat.requires_grad or self.weight.requires_grad):
             return GraphConvFn.apply(graph, feat, self.weight, self.bias, relu)
         return graphconv_fwd(graph, ops.as_feat(feat), self.weight, self.bias, relu)[0]
+
+
+class GATConv(nn.Module):
+    """dgl 0.6.1 GATConv on a homogeneous graph (docs/GAT_SEMANTICS.md): fc [heads * out, in] without bias, attn_l / attn_r [1, heads, out],
+    no bias parameter, res_fc a None buffer (residual=False only).  forward returns [N, heads, out]."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2, residual=False, activation=None,
+                 allow_zero_in_degree=False):
+        super().__init__()
+        if isinstance(in_feats, (tuple, list)):
+            raise NotImplementedError("GATConv: bipartite (block) inputs are not implemented: the reference's GAT runs on the whole graph")
+        if residual:
+            raise NotImplementedError("GATConv: residual=True is not implemented (the reference's Model never sets it)")
+        if num_heads < 1 or num_heads > 64 or num_heads * out_feats > 256:
+            raise NotImplementedError("GATConv: the attention kernels take num_heads <= 64 and num_heads * out_feats <= 256")
+        self._in_feats, self._out_feats, self._num_heads = in_feats, out_feats, num_heads
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self.fc = nn.Linear(in_feats, out_feats * num_heads, bias=False)
+        self.attn_l = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.attn_r = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.negative_slope = float(negative_slope)
+        self.register_buffer("res_fc", None)
+        self.activation = activation
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        nn.init.xavier_normal_(self.fc.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn_l, gain=gain)
+        nn.init.xavier_normal_(self.attn_r, gain=gain)
+
+    def relu(self):
+        act = self.activation
+        relu = act is not None and getattr(act, "__name__", "") == "relu"
+        if act is not None and not relu:
+            raise NotImplementedError("GATConv: only activation=F.relu or None is used by the reference")
+        return relu
+
+    def forward(self, graph, feat, nonneg=None):
+        """nonneg: the caller knows feat >= 0 (a ReLU layer's output), so the feature dropout needs one product (ops.gat_project);
+        None: looked at here when the dropout is active."""
+        if isinstance(feat, tuple) or graph.num_dst_nodes() != graph.num_src_nodes() or feat.shape[0] != graph.num_dst_nodes():
+            raise NotImplementedError("GATConv: block (bipartite) inputs are not implemented: the reference's GAT runs on the whole graph")
+        if not self._allow_zero_in_degree and graph.has_zero_in_degree():
+            raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
+                               "(dgl GATConv semantics; add self-loops or set allow_zero_in_degree).")
+        if nonneg is None:
+            nonneg = not (self.training and self.feat_drop.p > 0) or ops.is_nonneg(feat)
+        y = gat_conv(graph, feat, self.fc.weight, self.attn_l, self.attn_r, self._num_heads, self._out_feats, self.negative_slope,
+                     self.relu(), self.feat_drop.p, self.attn_drop.p, self.training, signed=not nonneg)
+        return y.view(y.shape[0], self._num_heads, self._out_feats) if y.is_contiguous() else y.reshape(y.shape[0], self._num_heads,
+                                                                                                        self._out_feats)

@@ -1234,3 +1234,138 @@ def edge_drop_mask(nnz, t, edge_drop, seed, device):
     rc = _lib.lib().glnn_edge_drop_mask_u8(int(nnz), int(t), float(edge_drop), int(seed) & 0xFFFFFFFF, _p(mask) if nnz else None, _stream())
     _lib.check(rc, "glnn_edge_drop_mask_u8")
     return mask
+
+
+# --------------------------------------------------------------------------------------------- GAT attention (csrc/gat.hip)
+_UNIT = {}
+
+
+def _unit_affine(k, device, sign):
+    """(scale, shift) = (+-1, 0) vectors of length k: the identity tail that lets glnn_gemm_f32's operand transform apply a dropout mask."""
+    key = (str(device), sign)
+    if key not in _UNIT or _UNIT[key][0].numel() < k:
+        _UNIT[key] = (torch.full((max(k, 1024),), float(sign), dtype=torch.float32, device=device),
+                      torch.zeros(max(k, 1024), dtype=torch.float32, device=device))
+    return _UNIT[key]
+
+
+def gat_project(x, w, drop_p=0.0, drop_seed=0, signed=True):
+    """(z, z2) with feat_drop(x) @ w^T = z - z2 (z2 None: z alone), the dropout mask keep(row, col) of glnn_dropout_mask_u8 applied in the
+    GEMM's operand load: no dropped copy of x exists.  The operand transform is drop(max(x * scale + shift, 0)), so a non-negative x
+    (signed=False: a hidden layer's post-ReLU output, bag-of-words features) takes one product with scale 1, and a signed x two, with
+    scales +1 and -1 -- max(x, 0) - max(-x, 0) = x under the SAME mask.  gat_scores subtracts z2 while it reads z."""
+    x = as_feat(x)
+    if drop_p <= 0:
+        return gemm(x, w), None
+    k = x.shape[1]
+    one, zero = _unit_affine(k, x.device, 1)
+    z = gemm(x, w, a_scale=one, a_shift=zero, drop_p=drop_p, drop_seed=drop_seed)
+    if not signed:
+        return z, None
+    neg, _ = _unit_affine(k, x.device, -1)
+    return z, gemm(x, w, a_scale=neg, a_shift=zero, drop_p=drop_p, drop_seed=drop_seed)
+
+
+def gat_project_wgrad(dz, x, drop_p=0.0, drop_seed=0, signed=True, out=None):
+    """dW = dz^T feat_drop(x) with the mask in glnn_gemm_tn_f32's operand load (gat_project's counterpart)."""
+    x = as_feat(x)
+    if drop_p <= 0:
+        return gemm_tn(dz, x, out=out)
+    k = x.shape[1]
+    one, zero = _unit_affine(k, x.device, 1)
+    dw = gemm_tn(dz, x, b_scale=one, b_shift=zero, drop_p=drop_p, drop_seed=drop_seed, out=out)
+    if signed:
+        neg, _ = _unit_affine(k, x.device, -1)
+        dw.sub_(gemm_tn(dz, x, b_scale=neg, b_shift=zero, drop_p=drop_p, drop_seed=drop_seed))
+    return dw
+
+
+def gat_scores(z, attn_l, attn_r, heads, out_feats, z2=None):
+    """glnn_gat_scores_f32: (el, er) [n, heads] from one read of z [n, heads * out_feats]; z2: z -= z2 in place first."""
+    _need_cuda(z, z2, attn_l, attn_r)
+    _mat(z, "gat_scores z")
+    n = z.shape[0]
+    hf = heads * out_feats
+    if z.shape[1] != hf or attn_l.numel() != hf or attn_r.numel() != hf or not attn_l.is_contiguous() or not attn_r.is_contiguous():
+        raise ValueError("gat_scores: z must be [n, heads * out_feats] and attn_l / attn_r contiguous [1, heads, out_feats]")
+    if z2 is not None:
+        _mat(z2, "gat_scores z2")
+    el = torch.empty((n, heads), dtype=torch.float32, device=z.device)
+    er = torch.empty((n, heads), dtype=torch.float32, device=z.device)
+    rc = _lib.lib().glnn_gat_scores_f32(_p(z), _ld(z), _p(z2), 0 if z2 is None else _ld(z2), n, heads, out_feats, _p(attn_l), _p(attn_r),
+                                        _p(el), _p(er), _stream())
+    _lib.check(rc, "glnn_gat_scores_f32")
+    return el, er
+
+
+def gat_attn_fwd(indptr, indices, nnz, z, el, er, heads, out_feats, negative_slope=0.2, attn_drop=0.0, seed=0, relu=False, want_lse=False,
+                 out=None):
+    """glnn_gat_attn_fwd_f32: (out [n, heads * out_feats], lse [n, heads] or None) -- edge softmax + weighted aggregation of z."""
+    z = as_feat(z)
+    n = z.shape[0]
+    _appnp_check(indptr, indices, z, n, "gat_attn_fwd")
+    _need_cuda(el, er, out)
+    if out is None:
+        out = feat_empty(n, heads * out_feats, z.device)
+    _mat(out, "gat_attn_fwd out")
+    lse = torch.empty((n, heads), dtype=torch.float32, device=z.device) if want_lse else None
+    with _Timed("gat_attn_fwd", d=heads * out_feats, n_dst=n, nnz=int(nnz), attn_drop=float(attn_drop)):
+        rc = _lib.lib().glnn_gat_attn_fwd_f32(_p(indptr), _p(indices), n, int(nnz), _p(z), _ld(z), heads, out_feats,
+                                              _p(_vec(el.view(-1), n * heads, "el")), _p(_vec(er.view(-1), n * heads, "er")),
+                                              float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF, 1 if relu else 0, _p(out),
+                                              _ld(out), _p(lse), _stream())
+    _lib.check(rc, "glnn_gat_attn_fwd_f32")
+    return out, lse
+
+
+def gat_attn_bwd(graph, z, el, er, lse, attn_l, attn_r, g, y, heads, out_feats, negative_slope=0.2, attn_drop=0.0, seed=0,
+                 dattn_l=None, dattn_r=None):
+    """glnn_gat_attn_bwd_f32 over `graph` (CSRGraph: its in-CSR and its cached transpose with edge ids): (dz, dattn_l, dattn_r).
+    g = dL/d out behind the activation mask, y = the forward's stored output.  The [E, heads] score-gradient scratch lives for the call."""
+    z, g, y = as_feat(z), as_feat(g), as_feat(y)
+    n = z.shape[0]
+    _appnp_check(graph.indptr, graph.indices, z, n, "gat_attn_bwd")
+    _need_cuda(el, er, lse, attn_l, attn_r, g, y)
+    tg, t_eids = graph.transposed_eids()
+    nnz = graph.num_edges()
+    dev = z.device
+    hf = heads * out_feats
+    ds = torch.empty((max(nnz, 1), heads), dtype=torch.float32, device=dev)
+    der = torch.empty((n, heads), dtype=torch.float32, device=dev)
+    dl = torch.empty((n, heads), dtype=torch.float32, device=dev)
+    dz = feat_empty(n, hf, dev)
+    if dattn_l is None:
+        dattn_l = torch.empty(hf, dtype=torch.float32, device=dev)
+    if dattn_r is None:
+        dattn_r = torch.empty(hf, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(_lib.lib().glnn_gat_attn_bwd_workspace_floats(n, heads, out_feats)), dtype=torch.float32, device=dev)
+    with _Timed("gat_attn_bwd", d=hf, n_dst=n, nnz=int(nnz), attn_drop=float(attn_drop)):
+        rc = _lib.lib().glnn_gat_attn_bwd_f32(_p(graph.indptr), _p(graph.indices), _p(tg.indptr), _p(tg.indices), _p(t_eids), n, int(nnz),
+                                              _p(z), _ld(z), heads, out_feats, _p(el), _p(er), _p(lse), _p(attn_l), _p(attn_r), _p(g), _ld(g),
+                                              _p(y), _ld(y), float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF, _p(ds), _p(der),
+                                              _p(dl), _p(dz), _ld(dz), _p(dattn_l), _p(dattn_r), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "glnn_gat_attn_bwd_f32")
+    return dz, dattn_l, dattn_r
+
+
+def gat_attn_mask(nnz, heads, attn_drop, seed, device):
+    """glnn_gat_attn_mask_u8: uint8 [nnz, heads], 1 = head h of edge e kept -- the mask the attention kernels evaluate."""
+    mask = torch.empty((max(int(nnz), 1), heads), dtype=torch.uint8, device=device)[:int(nnz)]
+    rc = _lib.lib().glnn_gat_attn_mask_u8(int(nnz), heads, float(attn_drop), int(seed) & 0xFFFFFFFF, _p(mask) if nnz else None, _stream())
+    _lib.check(rc, "glnn_gat_attn_mask_u8")
+    return mask
+
+
+_NONNEG = []          # [(weakref to the tensor, key, answer)]: one entry
+
+
+def is_nonneg(x):
+    """Whether every element of x is >= 0, remembered while the very same unmodified tensor is asked about again (as_feat's identity
+    rule): the reference hands the same `feats` to every epoch, so a GAT teacher looks at its input once."""
+    import weakref
+    key = _pad_key(x)
+    if key is not None and _NONNEG and _NONNEG[0][0]() is x and _NONNEG[0][1] == key:
+        return _NONNEG[0][2]
+    ans = bool((x.detach().min() >= 0).item()) if x.numel() else True
+    _NONNEG[:] = [(weakref.ref(x), key, ans)]
+    return ans

@@ -35,7 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .autograd import appnp_bwd, appnp_fwd, graphconv_bwd, graphconv_fwd
+from .autograd import appnp_bwd, appnp_fwd, gat_layer_bwd, gat_layer_fwd, graphconv_bwd, graphconv_fwd
 from .student import _mix32
 
 
@@ -44,11 +44,11 @@ def _is_relu(act):
 
 
 def check_supported(model, criterion, optimizer):
-    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE / GCN teacher."""
+    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP or GAT teacher."""
     enc = model.encoder
     name = model.model_name
-    if "MLP" in name or not ("SAGE" in name or "GCN" in name or "APPNP" in name):
-        raise NotImplementedError(f"TeacherEngine: SAGE, GCN or APPNP teachers only (got {name})")
+    if "MLP" in name or not ("SAGE" in name or "GCN" in name or "APPNP" in name or "GAT" in name):
+        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP or GAT teachers only (got {name})")
     if not (isinstance(criterion, nn.NLLLoss) and criterion.reduction == "mean" and criterion.weight is None
             and criterion.ignore_index == -100):
         raise NotImplementedError("TeacherEngine: the criterion must be nn.NLLLoss() (reference train_teacher.py:237)")
@@ -61,13 +61,16 @@ def check_supported(model, criterion, optimizer):
     elif "APPNP" in name:
         if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
             raise NotImplementedError("TeacherEngine: APPNP with norm_type none|batch|layer and ReLU (models.py:282-344)")
+    elif "GAT" in name:
+        if not _is_relu(enc.activation) or any(not lay.relu() for lay in enc.layers[:-1]) or enc.layers[-1].relu():
+            raise NotImplementedError("TeacherEngine: GAT with ReLU hidden layers and a linear last layer (models.py:202-279)")
     else:
         if enc.norm_type not in ("none", "batch", "layer"):      # train.conf.yaml: cora-style GCN none, pokec / penn94 GCN batch
             raise NotImplementedError("TeacherEngine: GCN with norm_type none|batch|layer")
         for lay in enc.layers[:-1]:
             if not _is_relu(lay._activation):
                 raise NotImplementedError("TeacherEngine: GraphConv(activation=F.relu) on hidden layers (models.py:170-187)")
-    for bn in enc.norms:
+    for bn in getattr(enc, "norms", ()):
         if isinstance(bn, nn.LayerNorm):
             if not bn.elementwise_affine or len(bn.normalized_shape) != 1:
                 raise NotImplementedError("TeacherEngine: nn.LayerNorm(hidden_dim) with the reference's defaults")
@@ -93,11 +96,12 @@ class _Arena:
 class TeacherEngine:
     def __init__(self, model, optimizer):
         self.model, self.enc, self.opt = model, model.encoder, optimizer
-        self.kind = "sage" if "SAGE" in model.model_name else ("appnp" if "APPNP" in model.model_name else "gcn")
+        name = model.model_name
+        self.kind = "sage" if "SAGE" in name else ("appnp" if "APPNP" in name else ("gat" if "GAT" in name else "gcn"))
         self.L = self.enc.num_layers
-        self.bn = self.enc.norm_type == "batch"
-        self.ln = self.enc.norm_type == "layer"
-        self.p = float(self.enc.dropout.p)
+        self.bn = getattr(self.enc, "norm_type", "none") == "batch"
+        self.ln = getattr(self.enc, "norm_type", "none") == "layer"
+        self.p = float(self.enc.layers[0].feat_drop.p if self.kind == "gat" else self.enc.dropout.p)
         params = list(model.parameters())
         self.params = params
         dev = params[0].device
@@ -496,6 +500,59 @@ class TeacherEngine:
             da = ops.gemm(dz, layer.weight, w_is_kn=True)                        # dz W
             z, stats, seed = saved[l - 1]
             dz = self._appnp_tail_bwd(l - 1, da, z, stats, seed, None)
+        ops.note_param_write()
+
+
+    # ------------------------------------------------------------------------------------------ full-graph GAT
+    def _attn_seed(self, layer):
+        """The attention-dropout seed of `layer` in the current step: a stream of its own, apart from the feature dropout seeds _seed(layer)."""
+        p = float(self.enc.layers[layer].attn_drop.p)
+        return _mix32(self.base_seed ^ 0x47415441 ^ _mix32(self.step_count * 131 + layer + 0x3D)) if p > 0 else 0
+
+    @torch.no_grad()
+    def step_gat(self, g, feats, labels, idx_train, lamb=1.0):
+        """The reference's full-graph `train` (train_and_eval.py:12-29) over GAT (models.py:202-279): per layer the projection with the
+        feature dropout in its operand load, glnn_gat_scores_f32 and glnn_gat_attn_fwd_f32; NLL over idx_train; per layer
+        glnn_gat_attn_bwd_f32 over the graph and its transpose, the weight gradient and the input gradient; Adam."""
+        ops._need_cuda(feats, labels, idx_train, g.indptr)
+        if g.has_zero_in_degree():
+            raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
+                               "(dgl GATConv semantics; add self-loops or set allow_zero_in_degree).")
+        self.step_count += 1
+        try:
+            self._step_gat_body(g, feats, labels, idx_train, lamb)
+        except Exception:
+            self.step_count -= 1          # the step never happened (see step_sage)
+            raise
+        self._adam()
+
+    def _step_gat_body(self, g, feats, labels, idx_train, lamb):
+        enc, L = self.enc, self.L
+        n = g.num_dst_nodes()
+        x = ops.as_feat(feats)
+        signed0 = self.p > 0 and not ops.is_nonneg(feats)
+        acts, saved = [x], []
+        for l, lay in enumerate(enc.layers):
+            fs, as_ = self._seed(l), self._attn_seed(l)
+            y, sv = gat_layer_fwd(g, acts[l], lay.fc.weight, lay.attn_l, lay.attn_r, lay._num_heads, lay._out_feats, lay.negative_slope,
+                                  l != L - 1, lay.feat_drop.p, fs, lay.attn_drop.p, as_, signed0 if l == 0 else False, want_lse=True)
+            saved.append((sv, fs, as_))
+            acts.append(y)
+        logits = acts[L]
+        logits_tr = ops.gather_rows(logits, idx_train)                            # out[idx_train] (train_and_eval.py:22)
+        _, dl = ops.softmax_loss(logits_tr, ops.LOSS_NLL, float(lamb), labels=labels, label_rows=idx_train, loss_out=self.loss_out,
+                                 loss_accum=self.loss_accum, workspace=self.ws_loss)
+        gy = ops.feat_empty(n, logits.shape[1], self.dev, zero=True)
+        ops.scatter_rows(dl, idx_train, gy)
+        for l in range(L - 1, -1, -1):
+            lay = enc.layers[l]
+            sv, fs, as_ = saved[l]
+            da, _, _, _ = gat_layer_bwd(g, gy, acts[l + 1], sv, acts[l], lay.fc.weight, lay.attn_l, lay.attn_r, lay._num_heads,
+                                        lay._out_feats, lay.negative_slope, lay.feat_drop.p, fs, lay.attn_drop.p, as_,
+                                        signed0 if l == 0 else False, need_dx=l > 0, dw=self.grad(lay.fc.weight),
+                                        dattn_l=self.grad(lay.attn_l).view(-1), dattn_r=self.grad(lay.attn_r).view(-1))
+            if l > 0:      # the feature-dropout mask of layer l and the ReLU mask of layer l - 1 (its stored output is post-ReLU)
+                gy = ops.bn_relu_bwd(da, acts[l], dz=da, drop_p=lay.feat_drop.p, drop_seed=fs)[0]
         ops.note_param_write()
 
 

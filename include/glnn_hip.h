@@ -706,6 +706,39 @@ GLNN_API int glnn_csr_transpose_eids(const int64_t* indptr, const int32_t* indic
  * (edge_drop, seed) -- the role glnn_dropout_mask_u8 plays for the feature dropout (parity tests feed it to the oracle). */
 GLNN_API int glnn_edge_drop_mask_u8(int64_t nnz, int t, float edge_drop, uint32_t seed, uint8_t* mask, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GAT attention (dgl 0.6.1 GATConv of the reference GAT teacher, models.py:202-279): per-destination edge softmax with per-edge scores
+ * from two per-node scalars per head.  docs/GAT_SEMANTICS.md states the arithmetic.  Square graph of n nodes, indptr / indices the in-CSR
+ * (rows = destinations, edge id = CSR position); z [n, heads * out_feats] the projected rows, head-major columns.  heads <= 64,
+ * heads * out_feats <= 256, nnz < 2^31.  Attention dropout: edge e, head h kept iff glnn_gat_attn_mask_u8(...)[e * heads + h], weight
+ * 1 / (1 - attn_drop), applied AFTER the normalisation; attn_drop = 0 disables it.  Deterministic (no float atomics).
+ *
+ * glnn_gat_scores_f32: el[r, h] = <z[r, h, :], attn_l[h, :]>, er likewise with attn_r, from one read of z.  z2 != NULL: z -= z2 first
+ *   (stored back into z): the two half-products of a signed input behind the feature dropout. */
+GLNN_API int glnn_gat_scores_f32(float* z, int64_t ldz, const float* z2, int64_t ldz2, int64_t n, int heads, int out_feats,
+                                 const float* attn_l, const float* attn_r, float* el, float* er, void* stream);
+/* out[i] = act( sum_{e = (j -> i)} a_ij w_ij z[j] ),  a_ij = softmax over ALL in-edges of i of leaky_relu(el[j] + er[i], negative_slope)
+ *   per head, w_ij the dropout weight; relu != 0: ReLU epilogue.  lse (optional, [n, heads]): max + log(denominator) of every row and
+ *   head, what the backward recomputes a_ij from.  A row without in-edges gives zeros. */
+GLNN_API int glnn_gat_attn_fwd_f32(const int64_t* indptr, const int32_t* indices, int64_t n, int64_t nnz, const float* z, int64_t ldz,
+                                   int heads, int out_feats, const float* el, const float* er, float negative_slope, float attn_drop,
+                                   uint32_t seed, int relu, float* out, int64_t ldo, float* lse, void* stream);
+/* Backward of glnn_gat_attn_fwd_f32 + glnn_gat_scores_f32 with respect to z, attn_l and attn_r.  g = dL/d out behind the activation
+ * mask, y = the forward's stored output (D_i = <g_i, y_i> per head).  Pass 1 (in-CSR): ds [nnz, heads] scratch and der [n, heads];
+ * pass 2 (transposed CSR with original edge ids, glnn_csr_transpose_eids): dz [n, heads * out_feats] and del [n, heads]; then
+ * dattn_l = sum_j del_j z_j, dattn_r = sum_i der_i z_i through per-workgroup partials in `workspace`
+ * (>= glnn_gat_attn_bwd_workspace_floats floats), folded in fixed order. */
+GLNN_API int64_t glnn_gat_attn_bwd_workspace_floats(int64_t n, int heads, int out_feats);
+GLNN_API int glnn_gat_attn_bwd_f32(const int64_t* indptr, const int32_t* indices, const int64_t* t_indptr, const int32_t* t_indices,
+                                   const int32_t* t_eids, int64_t n, int64_t nnz, const float* z, int64_t ldz, int heads, int out_feats,
+                                   const float* el, const float* er, const float* lse, const float* attn_l, const float* attn_r,
+                                   const float* g, int64_t ldg, const float* y, int64_t ldy, float negative_slope, float attn_drop,
+                                   uint32_t seed, float* ds, float* der, float* del_, float* dz, int64_t lddz, float* dattn_l,
+                                   float* dattn_r, float* workspace, int64_t workspace_floats, void* stream);
+/* The attention keep-mask the GAT kernels evaluate on the fly: mask[e * heads + h] = 1 iff head h of edge e is kept under
+ * (attn_drop, seed) -- the role glnn_edge_drop_mask_u8 plays for APPNP (parity tests feed it to the oracle). */
+GLNN_API int glnn_gat_attn_mask_u8(int64_t nnz, int heads, float attn_drop, uint32_t seed, uint8_t* mask, void* stream);
+
 /* K7  row gather: out[i,:] = x[rows[i],:]  (feats[idx], reference train_and_eval.py:42,76,
  *     models.py:136) and scatter y[rows[i],:] = x[i,:] (models.py:145). */
 GLNN_API int glnn_gather_rows_f32(const float* x, int64_t ldx, const int64_t* rows, int64_t n_rows,
