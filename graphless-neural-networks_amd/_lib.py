@@ -97,6 +97,8 @@ SIGNATURES = {
     "glnn_gat_attn_mask_u8": [c_i64, c_int, c_f32, c_u32, c_vp, c_vp],
     "glnn_gather_rows_f32": [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp],
     "glnn_scatter_rows_f32": [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp],
+    "glnn_gemm_bf16": [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_int, c_vp],
+    "glnn_mlp_forward_bf16": [c_vp, c_vp, c_i64, c_int, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp],
 }
 
 MLP_MAX_LAYERS = 8
@@ -185,6 +187,12 @@ class SageLnDesc(ctypes.Structure):
     _fields_ = [("eps", c_f32), ("reserved", ctypes.c_int32), ("layer", SageLnLayer * SAGE_MAX_LAYERS)]
 
 
+class MlpServeDesc(ctypes.Structure):
+    """glnn_mlp_serve_desc of include/glnn_hip.h (field for field)."""
+    _fields_ = [("num_layers", ctypes.c_int32), ("reserved", ctypes.c_int32), ("dims", ctypes.c_int32 * (MLP_MAX_LAYERS + 1)),
+                ("reserved2", ctypes.c_int32), ("w", _F), ("ldw", c_i64 * MLP_MAX_LAYERS), ("ep_scale", _F), ("ep_shift", _F)]
+
+
 _lib = None
 
 
@@ -223,7 +231,7 @@ def lib():
         if h.glnn_abi_version() != ABI_VERSION:
             raise GlnnError(f"{LIB_PATH}: ABI version {h.glnn_abi_version()} != {ABI_VERSION} expected by this package; rebuild")
         for which, mirror in ((0, MlpStepDesc), (1, SageStepDesc), (2, SageLayer), (3, AdamDesc), (4, HubPlanDesc), (5, ChunkSignalsDesc),
-                              (6, SageLnDesc)):
+                              (6, SageLnDesc), (7, MlpServeDesc)):
             if h.glnn_struct_bytes(which) != ctypes.sizeof(mirror):
                 raise GlnnError(f"{LIB_PATH}: sizeof({mirror.__name__}) is {h.glnn_struct_bytes(which)} in the library, "
                                 f"{ctypes.sizeof(mirror)} in this binding")

@@ -76,7 +76,12 @@ def get_teacher_args(argv=None):
 
 
 def get_student_args(argv=None):
-    return _parser(_COMMON + _STUDENT_ONLY, "GLNN student distillation (HIP hot path)").parse_args(argv)
+    p = _parser(_COMMON + _STUDENT_ONLY, "GLNN student distillation (HIP hot path)")
+    # not a reference flag: the storage of the student's evaluation / serving passes (train_and_eval.evaluate_mini_batch(dtype=...)),
+    # bfloat16 = weights and hidden activations stored as bf16, bf16 MFMA products, fp32 accumulation and saved log-probs (glnn_amd.serve)
+    p.add_argument("--serve_dtype", type=str, default="float32", choices=["float32", "bfloat16"],
+                   help="Storage of the MLP student's evaluation passes (bfloat16: norm_type none / batch)")
+    return p.parse_args(argv)
 
 
 def _device(args):

@@ -45,6 +45,7 @@ static void load_options(Options& o) {
   o.signal_fence = env_ll("GLNN_SIGNAL_NO_FENCE", 0) ? 0 : 1;
   o.bn0_in_gemm = (int)env_ll("GLNN_STUDENT_BN0_IN_GEMM", 1);
   o.bn0_consts_in_gemm = (int)env_ll("GLNN_STUDENT_BN0_CONSTS_IN_GEMM", 1);
+  o.gemm_bf16_mfma16 = (int)env_ll("GLNN_GEMM_BF16_MFMA16", 1);
 }
 static Options g_opts;
 static std::once_flag g_opts_once;
@@ -108,6 +109,7 @@ extern "C" int64_t glnn_struct_bytes(int which) {
   if (which == 4) return (int64_t)sizeof(glnn_hub_plan);
   if (which == 5) return (int64_t)sizeof(glnn_chunk_signals);
   if (which == 6) return (int64_t)sizeof(glnn_sage_ln_desc);
+  if (which == 7) return (int64_t)sizeof(glnn_mlp_serve_desc);
   return -1;
 }
 

@@ -45,6 +45,7 @@ struct Options {
   int bn0_in_gemm;          // GLNN_STUDENT_BN0_IN_GEMM=0: the first hidden layer's BatchNorm backward stays partial + apply launches behind a plain input-gradient GEMM
   int signal_fence;         // GLNN_SIGNAL_NO_FENCE=1: glnn_stream_wait_value32 without the empty kernel behind the wait (tests: the negative control)
   int cls_fused;            // GLNN_STUDENT_CLS_FUSED=0: the large-batch classifier stays a split-K GEMM launch + a loss launch (cls_block.hip off)
+  int gemm_bf16_mfma16;     // GLNN_GEMM_BF16_MFMA16=0: the bf16 serving GEMM on v_mfma_f32_32x32x16_bf16 instead of 16x16x32 (same per-wave tile; 3 % slower on 2048 x 2048)
   int sage_fuse_ln_bwd;     // GLNN_SAGE_FUSE_LN_BWD=0: the LayerNorm teacher's transposed aggregation writes dh and glnn_layernorm_bwd_f32 follows
 };
 const Options& opts();

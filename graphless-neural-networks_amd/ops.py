@@ -1369,3 +1369,47 @@ def is_nonneg(x):
     ans = bool((x.detach().min() >= 0).item()) if x.numel() else True
     _NONNEG[:] = [(weakref.ref(x), key, ans)]
     return ans
+
+
+# ---------------------------------------------------------------------------------------------
+# bf16 serving GEMM of the MLP student (csrc/gemm_bf16.hip)
+def round64(d):
+    return (d + 63) // 64 * 64
+
+
+def pack_weight_bf16(w):
+    """W [n, k] fp32 (torch Linear layout) -> the bf16 [n, round64(k)] operand of gemm_bf16, zeros behind column k (glnn_cast_f32_bf16
+    into a zeroed buffer).  Returns the [n, k] view."""
+    _need_cuda(w)
+    _mat(w, "pack_weight_bf16 w")
+    n, k = w.shape
+    buf = torch.zeros((n, round64(k)), dtype=torch.bfloat16, device=w.device)
+    return to_bf16(w.detach(), out=buf[:, :k])
+
+
+def _bf16_weight(w, k, name):
+    _bf16_mat(w, name)
+    if w.shape[1] != k or _ld(w) % 64 or w.data_ptr() % 16:
+        raise ValueError(f"{name}: expected a bf16 [n, {k}] view of rows padded to a multiple of 64 (ops.pack_weight_bf16)")
+    return w
+
+
+def gemm_bf16(a, w, ep_scale=None, ep_shift=None, relu=False, out=None, out_dtype=None, log_softmax=False):
+    """glnn_gemm_bf16: out = epi(A @ W^T) on the bf16 MFMA with fp32 accumulation.  a: [m, k] fp32 (rounded to bf16 while it is staged) or
+    bf16; w: bf16 [n, k] from pack_weight_bf16; out: `out`'s dtype, else out_dtype (default fp32).  log_softmax (n <= 64, fp32 out):
+    the rows' log-probabilities instead of the logits."""
+    _need_cuda(a, w, ep_scale, ep_shift, out)
+    if a.dtype == torch.bfloat16:
+        a = as_bf16_feat(a)
+    else:
+        _mat(a, "gemm_bf16 a")
+    m, k = a.shape
+    n = w.shape[0]
+    _bf16_weight(w, k, "gemm_bf16 w")
+    out = _out_like(out, out_dtype, torch.float32, m, n, a.device, "gemm_bf16 out")
+    with _Timed("gemm_bf16", m=m, k=k, n=n):
+        rc = _lib.lib().glnn_gemm_bf16(_p(a), _ld(a), _dtype_code(a), m, k, _p(w), _ld(w), n, _p(_vec(ep_scale, n, "ep_scale")),
+                                       _p(_vec(ep_shift, n, "ep_shift")), 1 if relu else 0, _p(out), _ld(out), _dtype_code(out),
+                                       1 if log_softmax else 0, _stream())
+    _lib.check(rc, "glnn_gemm_bf16")
+    return out[:m] if out.shape[0] != m else out

@@ -43,7 +43,7 @@ GLNN_API int glnn_abi_version(void);               /* bumped on any signature ch
 GLNN_API const char* glnn_last_error(void);        /* thread-local, never NULL */
 GLNN_API int glnn_device_info(int* cu_count, int* xcd_count, char* arch_buf, int arch_buf_len);
 /* sizeof of the descriptor structs below as THIS build sees them (0 = glnn_mlp_step_desc, 1 = glnn_sage_step_desc,
- * 2 = glnn_sage_layer, 3 = glnn_adam_desc, 4 = glnn_hub_plan, 5 = glnn_chunk_signals, 6 = glnn_sage_ln_desc; -1 otherwise): lets a binding in another language check its mirror of the layout at load time. */
+ * 2 = glnn_sage_layer, 3 = glnn_adam_desc, 4 = glnn_hub_plan, 5 = glnn_chunk_signals, 6 = glnn_sage_ln_desc, 7 = glnn_mlp_serve_desc; -1 otherwise): lets a binding in another language check its mirror of the layout at load time. */
 GLNN_API int64_t glnn_struct_bytes(int which);
 /* The library reads its GLNN_* environment switches (csrc/glnn_common.h, glnn::Options: choices between supported, equal-result
  * forms of a launch sequence, for tests and A/B timing) ONCE, at the first call.  This re-reads them; not for concurrent use. */
@@ -781,6 +781,41 @@ GLNN_API int glnn_sage_fused_bf16(const int64_t* indptr, const int32_t* indices,
                                   int d_out, const float* ep_scale, const float* ep_shift, int relu,
                                   void* out, int64_t ldo, int out_dtype, const float* w2_packed, int d_out2,
                                   void* out2, int64_t ldo2, int out2_dtype, const int32_t* tile_order, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * bf16 serving of the MLP student (csrc/gemm_bf16.hip): opt-in inference with weights and hidden activations STORED as bf16, every
+ * product on the bf16 MFMA (v_mfma_f32_16x16x32_bf16) with fp32 accumulation in a fixed order, an fp32 epilogue, fp32 logits.
+ *   out[m, n] = epi( A[m, k] . W[n, k]^T ),  epi(v) = relu?( v * ep_scale[n] + ep_shift[n] ),  then optionally log_softmax of each row.
+ * A: bf16 [m, lda] (a_dtype GLNN_DTYPE_BF16: lda a multiple of 8, 16-byte aligned; whatever sits in columns [k, lda) is ignored) or fp32
+ *    [m, lda] (GLNN_DTYPE_F32, any lda >= k), rounded to bf16 as glnn_cast_f32_bf16 rounds while it is staged.
+ * W: bf16 [n, ldw], ldw a multiple of 64 and >= k, 16-byte aligned, ZEROS in columns [k, ldw) (glnn_cast_f32_bf16 into a zeroed buffer).
+ * out: bf16 (ldo a multiple of 8, columns [n, n rounded up to 8) written as 0) or fp32 (any ldo >= n).  ep_scale / ep_shift may be NULL
+ *    (1 / 0).  log_softmax (n <= 64, fp32 out): `out` receives log-probabilities (max, expf sum, subtract); the logits are not stored.
+ * No split-K, no float atomics: bit-equal run to run, a row's result does not depend on the other rows of the call, and the fp32-A and
+ * bf16-A forms of one call agree bit for bit.  m == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------ */
+GLNN_API int glnn_gemm_bf16(const void* a, int64_t lda, int a_dtype, int64_t m, int k, const uint16_t* w, int64_t ldw,
+                            int n, const float* ep_scale, const float* ep_shift, int relu, void* out, int64_t ldo,
+                            int out_dtype, int log_softmax, void* stream);
+
+/* The eval-mode chain of a student (norm "none" or BatchNorm folded into ep_scale / ep_shift; ReLU behind every layer but the last). */
+typedef struct glnn_mlp_serve_desc {        /* glnn_struct_bytes(7) */
+  int32_t num_layers;                       /* 1 .. GLNN_MLP_MAX_LAYERS */
+  int32_t reserved;
+  int32_t dims[GLNN_MLP_MAX_LAYERS + 1];    /* dims[l] -> dims[l + 1] is layer l */
+  int32_t reserved2;
+  const uint16_t* w[GLNN_MLP_MAX_LAYERS];   /* bf16 [dims[l + 1], ldw[l]], see glnn_gemm_bf16 */
+  int64_t ldw[GLNN_MLP_MAX_LAYERS];
+  const float* ep_scale[GLNN_MLP_MAX_LAYERS];   /* fp32 [dims[l + 1]] or NULL */
+  const float* ep_shift[GLNN_MLP_MAX_LAYERS];
+} glnn_mlp_serve_desc;
+
+/* logits (or log-probabilities: log_softmax, dims[num_layers] <= 64) of x [m, dims[0]] (x_dtype as a_dtype above) into fp32 out [m, ldo]:
+ * num_layers glnn_gemm_bf16 launches on `stream`.  Hidden rows ping-pong between the caller's bf16 buffers buf0 / buf1, each [m, ld_buf]
+ * (ld_buf a multiple of 8 and >= every hidden width; buf1 may be NULL for <= 2 layers, both for 1).  Never allocates or synchronises. */
+GLNN_API int glnn_mlp_forward_bf16(const glnn_mlp_serve_desc* desc, const void* x, int64_t ldx, int x_dtype, int64_t m,
+                                   uint16_t* buf0, uint16_t* buf1, int64_t ld_buf, float* out, int64_t ldo,
+                                   int log_softmax, void* stream);
 
 #ifdef __cplusplus
 }
