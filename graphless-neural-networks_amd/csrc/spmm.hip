@@ -188,6 +188,14 @@ __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<floa
 #define GLNN_NT_STREAMS 1
 #endif
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld4_stream(const float* p) {
+#if GLNN_NT_STREAMS
+  const f32x4_t t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
+  return make_float4(t.x, t.y, t.z, t.w);
+#else
+  return ld4(p);
+#endif
+}
 __device__ __forceinline__ void st4_stream(float* p, float4 v) {
 #if GLNN_NT_STREAMS
   f32x4_t t = {v.x, v.y, v.z, v.w};
@@ -1110,9 +1118,17 @@ struct FusedArgs {
   const int32_t* tile_order;                            // optional permutation of the tile ids (heaviest tiles first)
   HubPlan hub;                                          // n_hub == 0: hub rows are summed by the tile's own workgroup
   ChunkMap cm;                                          // n == 0: off (the kernel's CM = false instantiation never reads it)
+  // the aggregate (sum x[u] + x_self) / (deg+1) of an input that stays the same from call to call (the AGG instantiations only; last, so
+  // that every other field keeps its offset): agg_out -- phase A also streams the rows it parks in LDS to agg_out[v, 0:ld_agg];
+  // agg_in -- phase A is a copy of those rows back into LDS (no graph, no x)
+  float* agg_out; const float* agg_in; int64_t ld_agg;
 };
 
-template <int LPR, int U, int RT, bool CM = false>      // RT = 32-row sub-tiles per workgroup: each W fragment load feeds RT MFMA chains; CM: chunk map
+constexpr int kAggNone = 0, kAggOut = 1, kAggIn = 2;
+
+// AGG: kAggOut / kAggIn, the two forms of phase A around a kept aggregate (FusedArgs); phases B, C and the epilogue are the same code in all
+// three, so the outputs of an agg_in launch are the bits of the gathering launch that wrote its matrix
+template <int LPR, int U, int RT, bool CM = false, int AGG = kAggNone>      // RT = 32-row sub-tiles per workgroup: each W fragment load feeds RT MFMA chains; CM: chunk map
 __global__ __launch_bounds__(kFusedBlock) void sage_fused_kernel(const FusedArgs a) {
   constexpr int kFusedRows = 32 * RT;
   extern __shared__ __attribute__((aligned(16))) float lds_a[];      // [kFusedRows][kpad + 4]
@@ -1123,7 +1139,7 @@ __global__ __launch_bounds__(kFusedBlock) void sage_fused_kernel(const FusedArgs
   const bool col_ok = col4 < a.d_in;
   const int kpad = a.kgroups * 8;
   const int lda = kpad + 4;
-  const int tile_id = a.tile_order ? a.tile_order[blockIdx.x] : (int)blockIdx.x;
+  const int tile_id = (AGG != kAggIn && a.tile_order) ? a.tile_order[blockIdx.x] : (int)blockIdx.x;
   const int64_t row0 = (int64_t)tile_id * kFusedRows;
   int chunk = 0;
   int64_t self_shift = 0, out_shift = 0;
@@ -1139,10 +1155,23 @@ __global__ __launch_bounds__(kFusedBlock) void sage_fused_kernel(const FusedArgs
   //      4-rows-per-wave split leaves most waves idle at the barrier behind the heaviest one) ---------
   __shared__ int s_next;
   __shared__ int s_arrived;                            // (CM: waves of this workgroup that are done)
+  if constexpr (AGG == kAggIn) {
+    // the kept aggregate instead: the tile's rows stream into LDS, 16 bytes per lane, consecutive lanes on consecutive float4 of a row and
+    // then of the next one (ld_agg == the padded width: one contiguous run per tile).  Rows past n_dst and columns past the stored width
+    // are the zeros the gathering phase parks there.
+    const int kv = kpad / 4, dpad = (a.d_in + 3) & ~3;
+    for (int i = threadIdx.x; i < kFusedRows * kv; i += kFusedBlock) {
+      const int lr = i / kv, c4 = (i - lr * kv) * 4;
+      const int64_t v = row0 + lr;
+      float4 y = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (v < a.n_dst && c4 < dpad) y = ld4_stream(a.agg_in + v * a.ld_agg + c4);
+      st4(lds_a + lr * lda + c4, y);
+    }
+  }
   if (threadIdx.x == 0) { s_next = 0; if (CM) s_arrived = 0; }
   __syncthreads();
 #pragma unroll 1
-  while (true) {
+  while (AGG != kAggIn) {
     int lr = 0;
     if (lane == 0) lr = atomicAdd(&s_next, 1);
     lr = __builtin_amdgcn_readfirstlane(lr);
@@ -1166,12 +1195,16 @@ __global__ __launch_bounds__(kFusedBlock) void sage_fused_kernel(const FusedArgs
         }
       }
     }
-    if (!deferred && lane < LPR && col4 < kpad) st4(lds_a + lr * lda + col4, y);
+    if (!deferred && lane < LPR && col4 < kpad) {
+      st4(lds_a + lr * lda + col4, y);
+      if constexpr (AGG == kAggOut)
+        if (v < a.n_dst && col4 < a.ld_agg) st4_stream(a.agg_out + v * a.ld_agg + col4, y);
+    }
   }
   __syncthreads();
   // long rows of this tile: all 8 waves on one row at a time (uniform loop: every wave sees the same degrees)
 #pragma unroll 1
-  for (int lr = 0; lr < kFusedRows; ++lr) {
+  for (int lr = 0; AGG != kAggIn && lr < kFusedRows; ++lr) {
     const int64_t v = row0 + lr;
     if (v >= a.n_dst) break;
     const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
@@ -1196,6 +1229,8 @@ __global__ __launch_bounds__(kFusedBlock) void sage_fused_kernel(const FusedArgs
         if (col4 + 3 >= a.d_in) y.w = 0.f;
       }
       st4(lds_a + lr * lda + col4, y);
+      if constexpr (AGG == kAggOut)
+        if (col4 < a.ld_agg) st4_stream(a.agg_out + v * a.ld_agg + col4, y);
     }
     __syncthreads();
   }
@@ -1702,12 +1737,47 @@ extern "C" int glnn_pack_weight_f32(const float* w, int64_t ldw, int d_out, int 
   return glnn::check_launch("glnn_pack_weight_f32");
 }
 
+// The hit path of a kept aggregate (glnn_sage_fused_agg_f32 with agg_in): the gathering launch's phases B and C over rows read back from
+// `agg`.  No graph and no x: the tiles run in id order, one 32-row tile per workgroup like the launch that wrote the matrix.
+static int sage_fused_agg_in(int64_t n_dst, int d_in, const float* w_packed, int d_out, const float* ep_scale, const float* ep_shift,
+                             int relu, float* out, int64_t ldo, const float* w2_packed, int d_out2, float* out2, int64_t ldo2,
+                             const float* agg_in, int64_t ld_agg, void* stream) {
+  GLNN_REQUIRE(w_packed && (out || w2_packed), "glnn_sage_fused_agg_f32: null pointer");
+  GLNN_REQUIRE(!w2_packed || (out2 && d_out2 >= 1 && d_out2 <= 256 && ldo2 >= d_out2 && glnn::aligned16(w2_packed)),
+               "glnn_sage_fused_agg_f32: the chained projection needs out2 with ldo2 >= d_out2 in [1,256]");
+  GLNN_REQUIRE(n_dst >= 0, "glnn_sage_fused_agg_f32: bad n_dst");
+  GLNN_REQUIRE(d_in >= 1 && d_in <= 256 && d_out >= 1 && d_out <= 256, "glnn_sage_fused_agg_f32: d_in and d_out must be in [1,256]");
+  const int dpad = (d_in + 3) & ~3;
+  GLNN_REQUIRE(ld_agg % 4 == 0 && ld_agg >= dpad && (!out || ldo >= d_out),
+               "glnn_sage_fused_agg_f32: leading dimensions (ld_agg a multiple of 4 and >= %d; ldo >= d_out)", dpad);
+  GLNN_REQUIRE(glnn::aligned16(agg_in) && glnn::aligned16(w_packed), "glnn_sage_fused_agg_f32: 16-byte alignment required");
+  FusedArgs a = {};
+  a.n_dst = n_dst; a.d_in = d_in; a.w_packed = w_packed; a.d_out = d_out; a.kgroups = (d_in + 7) / 8; a.ep_scale = ep_scale;
+  a.ep_shift = ep_shift; a.relu = relu; a.out = out; a.ldo = ldo;
+  a.w2_packed = w2_packed; a.d_out2 = w2_packed ? d_out2 : 0; a.kgroups2 = w2_packed ? (d_out + 7) / 8 : 0; a.out2 = out2; a.ldo2 = ldo2;
+  a.agg_in = agg_in; a.ld_agg = ld_agg;
+  // one 32-row sub-tile per workgroup like the gathering launch: RT = 2 measured 1.47 ms against 1.52 on the products layer-1 shape and
+  // RT = 4 1.57 (profiles/agg_cache_ab.txt) -- the launch is bound by its serial load -> MFMA -> store per workgroup, not by the W reads
+  constexpr int rt = 1;
+  const int64_t blocks = (n_dst + 32 * rt - 1) / (32 * rt);
+  GLNN_REQUIRE(blocks < ((int64_t)1 << 31), "glnn_sage_fused_agg_f32: n_dst too large for one launch");
+  const int kg_lds = a.kgroups2 > a.kgroups ? a.kgroups2 : a.kgroups;
+  const size_t smem = sizeof(float) * 32 * rt * (kg_lds * 8 + 4);
+  // (LPR is the gathering phase's lane mapping: the copy does not use it, one instantiation serves every width)
+  hipLaunchKernelGGL((sage_fused_kernel<64, GLNN_FUSED_U, rt, false, kAggIn>), dim3((unsigned)blocks), dim3(kFusedBlock), smem,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  return glnn::check_launch("glnn_sage_fused_agg_f32");
+}
+
 static int sage_fused_impl(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, const float* x,
                            int64_t ldx, int d_in, const float* x_self, int64_t ld_self, const float* w_packed,
                            int d_out, const float* ep_scale, const float* ep_shift, int relu, float* out,
                            int64_t ldo, const float* w2_packed, int d_out2, float* out2, int64_t ldo2, const int32_t* tile_order,
-                           const glnn_hub_plan* plan, void* stream, const glnn_chunk_signals* chunks = nullptr) {
+                           const glnn_hub_plan* plan, void* stream, const glnn_chunk_signals* chunks = nullptr,
+                           float* agg_out = nullptr, const float* agg_in = nullptr, int64_t ld_agg = 0) {
   if (n_dst == 0) return GLNN_OK;
+  if (agg_in) return sage_fused_agg_in(n_dst, d_in, w_packed, d_out, ep_scale, ep_shift, relu, out, ldo, w2_packed, d_out2, out2, ldo2,
+                                       agg_in, ld_agg, stream);
   GLNN_REQUIRE(indptr && x && x_self && w_packed && (out || w2_packed), "glnn_sage_fused_f32: null pointer");   // indices NULL iff no edges
   GLNN_REQUIRE(!w2_packed || (out2 && d_out2 >= 1 && d_out2 <= 256 && ldo2 >= d_out2 && glnn::aligned16(w2_packed)),
                "glnn_sage_fused_f32: the chained projection needs out2 with ldo2 >= d_out2 in [1,256]");
@@ -1717,8 +1787,11 @@ static int sage_fused_impl(const int64_t* indptr, const int32_t* indices, int64_
   GLNN_REQUIRE(ldx % 4 == 0 && ldx >= dpad && ld_self % 4 == 0 && ld_self >= dpad && (!out || ldo >= d_out),
                "glnn_sage_fused_f32: leading dimensions (ldx, ld_self multiples of 4 and >= %d; ldo >= d_out)", dpad);
   GLNN_REQUIRE(glnn::aligned16(x) && glnn::aligned16(x_self) && glnn::aligned16(w_packed), "glnn_sage_fused_f32: 16-byte alignment required");
+  GLNN_REQUIRE(!agg_out || (ld_agg % 4 == 0 && ld_agg >= dpad && glnn::aligned16(agg_out) && !chunks),
+               "glnn_sage_fused_agg_f32: agg_out needs ld_agg a multiple of 4 and >= %d, 16-byte alignment, no chunks", dpad);
   if (n_dst == 0) return GLNN_OK;
   FusedArgs a;
+  a.agg_out = agg_out; a.agg_in = nullptr; a.ld_agg = ld_agg;
   a.indptr = indptr; a.indices = indices; a.n_dst = n_dst; a.x = x; a.ldx = ldx; a.d_in = d_in; a.x_self = x_self;
   a.ld_self = ld_self; a.w_packed = w_packed; a.d_out = d_out; a.kgroups = (d_in + 7) / 8; a.ep_scale = ep_scale;
   a.ep_shift = ep_shift; a.relu = relu; a.out = out; a.ldo = ldo;
@@ -1758,6 +1831,8 @@ static int sage_fused_impl(const int64_t* indptr, const int32_t* indices, int64_
 #define GLNN_FUSED_LAUNCH(LPR_, RT_)                                                                                                          \
   do {                                                                                                                                        \
     if (a.cm.n) hipLaunchKernelGGL((sage_fused_kernel<LPR_, GLNN_FUSED_U, RT_, true>), dim3((unsigned)blocks), dim3(kFusedBlock), smem, st, a); \
+    else if (a.agg_out)                                                                                                                       \
+      hipLaunchKernelGGL((sage_fused_kernel<LPR_, GLNN_FUSED_U, RT_, false, kAggOut>), dim3((unsigned)blocks), dim3(kFusedBlock), smem, st, a); \
     else hipLaunchKernelGGL((sage_fused_kernel<LPR_, GLNN_FUSED_U, RT_>), dim3((unsigned)blocks), dim3(kFusedBlock), smem, st, a);             \
   } while (0)
   if (kv <= 16 && dv <= 16) GLNN_FUSED_LAUNCH(16, 1); else if (kv <= 32) GLNN_FUSED_LAUNCH(32, 1); else GLNN_FUSED_LAUNCH(64, 1);
@@ -1791,6 +1866,16 @@ extern "C" int glnn_sage_fused_chunks_f32(const int64_t* indptr, const int32_t* 
   GLNN_REQUIRE(chunks, "glnn_sage_fused_chunks_f32: chunks is NULL (use glnn_sage_fused_plan_f32)");
   return sage_fused_impl(indptr, indices, n_dst, n_src, x, ldx, d_in, x_self, ld_self, w_packed, d_out, ep_scale, ep_shift, relu, out, ldo,
                          w2_packed, d_out2, out2, ldo2, tile_order, plan, stream, chunks);
+}
+
+extern "C" int glnn_sage_fused_agg_f32(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, const float* x,
+                                       int64_t ldx, int d_in, const float* x_self, int64_t ld_self, const float* w_packed,
+                                       int d_out, const float* ep_scale, const float* ep_shift, int relu, float* out,
+                                       int64_t ldo, const float* w2_packed, int d_out2, float* out2, int64_t ldo2, const int32_t* tile_order,
+                                       const glnn_hub_plan* plan, float* agg_out, const float* agg_in, int64_t ld_agg, void* stream) {
+  GLNN_REQUIRE((agg_out != nullptr) != (agg_in != nullptr), "glnn_sage_fused_agg_f32: exactly one of agg_out and agg_in must be given");
+  return sage_fused_impl(indptr, indices, n_dst, n_src, x, ldx, d_in, x_self, ld_self, w_packed, d_out, ep_scale, ep_shift, relu, out, ldo,
+                         w2_packed, d_out2, out2, ldo2, tile_order, plan, stream, nullptr, agg_out, agg_in, ld_agg);
 }
 
 extern "C" int glnn_signal_alloc(uint32_t** signal) {

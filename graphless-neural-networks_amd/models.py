@@ -198,6 +198,7 @@ class SAGE(nn.Module):
         return h_list, h
 
     CHAIN_NEXT_PROJECTION = True      # A/B switch of the chained projection in `inference`
+    CACHE_INPUT_AGGREGATE = True      # A/B switch of the kept layer-1 neighbour aggregate in `inference` (_input_aggregate)
 
     def _tail(self, l):
         """Fused eval tail of layer l: (ep_scale, ep_shift, relu) = BN(eval) o (+bias) o ReLU; dropout is a no-op."""
@@ -241,14 +242,17 @@ class SAGE(nn.Module):
 
     def release_placed(self):
         """Drop the placed buffers this encoder keeps across inference calls (the hidden layers' rows per (graph, layer) and the placed copy
-        of the input features): a long-lived process that is done with a graph gets its memory back."""
+        of the input features, the kept layer-1 aggregate): a long-lived process that is done with a graph gets its memory back."""
         self.__dict__.pop("_placed", None)
         self.__dict__.pop("_placed_x", None)
+        self.__dict__.pop("_agg_x", None)
         torch.cuda.empty_cache()
 
-    def _whole_graph_layer(self, l, g, x, projected, place=True):
+    def _whole_graph_layer(self, l, g, x, projected, place=True, agg=None):
         """Layer l of the whole-graph sweep: (y, projected for layer l+1 or None).  place=False: plain allocations (the launch is being
-        used as the PROBE that places the buffer it gathers from -- see _placed_buffer)."""
+        used as the PROBE that places the buffer it gathers from -- see _placed_buffer).  agg (layer 0): {"agg_out": m} / {"agg_in": m} of
+        _input_aggregate for the fused launch."""
+        agg = agg or {}
         layer = self.layers[l]
         post_ln = self.norm_type == "layer" and l != self.num_layers - 1
         ep_scale, ep_shift, relu = (None, layer.fc_neigh.bias, False) if post_ln else self._tail(l)
@@ -264,7 +268,7 @@ class SAGE(nn.Module):
             out_next = self._placed_buffer(g, ("proj", l), n, nxt._out_feats, x.device) if place else None
             _, proj = ops.sage_fused(g.indptr, g.indices, x, n, layer.fc_neigh.weight, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu,
                                      x_self=x[:n], w_next=nxt.fc_neigh.weight, want_out=False, tile_order=g.fused_tile_order(),
-                                     out_next=out_next)
+                                     out_next=out_next, **agg)
             return x, proj                                               # (y is not read: the next layer consumes `proj`)
         out = None
         if place and nxt is not None and not post_ln:
@@ -272,7 +276,7 @@ class SAGE(nn.Module):
             # the NEXT layer's own launch on each candidate allocation
             out = self._placed_buffer(g, ("y", l), n, layer._out_feats, x.device,
                                       probe=lambda cand: self._whole_graph_layer(l + 1, g, cand, None, place=False))
-        y = layer(g, (x, x[:n]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, out=out)
+        y = layer(g, (x, x[:n]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, out=out, **agg)
         if post_ln:
             y = _eval_tail(self, l, y)
         return y, None
@@ -288,6 +292,35 @@ class SAGE(nn.Module):
         px = ops.place_for_gather(x, g.indptr, g.indices, g.num_dst_nodes(), what="SAGE.inference features")
         self.__dict__["_placed_x"] = (weakref.ref(feats), sig, px)
         return px
+
+    def _input_aggregate(self, g, feats, x):
+        """Layer 0 aggregates first in the fused kernel: its gather computes A1 = (A x + x) / (deg+1), which depends on the graph and the
+        input features only -- not on any parameter -- and the callers of `inference` (train_and_eval's evaluate once per eval_interval,
+        the final soft-label pass) come back with the same graph and the same unmodified `feats` while the weights change.  The first
+        forward over a (graph, feats) stores A1 beside its own output (ops.sage_fused(agg_out=...)); later ones read it back instead of
+        gathering (agg_in: the same projection code over the same rows, so the same bits).  Remembered under the key of _placed_input --
+        the graph and the tensor themselves (weak), its data pointer, shape and in-place version -- and never under the weights.
+        Returns (the launch's keyword, the entry to remember once that launch has run or None).  No room (free memory under twice the
+        matrix, or the allocation fails): the forward runs as it always did."""
+        layer, n = self.layers[0], g.num_dst_nodes()
+        if not SAGE.CACHE_INPUT_AGGREGATE or not layer.fused_eligible() or x.shape[0] < n or n == 0:
+            return {}, None
+        try:
+            sig = (feats.data_ptr(), tuple(feats.shape), feats._version)
+        except RuntimeError:          # tensors created under torch.inference_mode() have no version counter: never kept
+            return {}, None
+        ent = self.__dict__.get("_agg_x")
+        if ent is not None and ent[0]() is g and ent[1]() is feats and ent[2] == sig and ent[3].device == x.device:
+            return {"agg_in": ent[3]}, None
+        self.__dict__.pop("_agg_x", None)                  # (the stale matrix goes before its successor is allocated)
+        import weakref
+        try:
+            if torch.cuda.mem_get_info(x.device)[0] < 2 * 4 * n * ops.round4(layer._in_feats):
+                return {}, None
+            buf = ops.feat_empty(n, layer._in_feats, x.device)
+        except torch.cuda.OutOfMemoryError:
+            return {}, None
+        return {"agg_out": buf}, (weakref.ref(g), weakref.ref(feats), sig, buf)
 
     def _whole_graph_layer_bf16(self, l, g, x, projected):
         """Layer l of the whole-graph sweep with bf16 activation storage: (y, projected for layer l+1 or None).  A matrix is stored as bf16
@@ -347,15 +380,19 @@ class SAGE(nn.Module):
         whole_graph = whole_graph and getattr(dataloader, "graph", None) is not None     # loaders that do not sweep arange(N)
         with torch.no_grad():
             x = ops.as_feat(feats)
+            agg, agg_ent = {}, None
             if whole_graph:
                 x = self._placed_input(dataloader.graph, feats, x)
+                agg, agg_ent = self._input_aggregate(dataloader.graph, feats, x)
             projected = None          # x @ W_l^T handed over by the previous (fused) layer when layer l projects first
             ln = self.norm_type == "layer"
             for l, layer in enumerate(self.layers):
                 post_ln = ln and l != self.num_layers - 1      # LayerNorm -> ReLU as a pass of its own behind the conv (+ bias)
                 ep_scale, ep_shift, relu = (None, layer.fc_neigh.bias, False) if post_ln else self._tail(l)
                 if whole_graph:
-                    y, projected = self._whole_graph_layer(l, dataloader.graph, x, projected)
+                    y, projected = self._whole_graph_layer(l, dataloader.graph, x, projected, agg=agg if l == 0 else None)
+                    if l == 0 and agg_ent is not None:
+                        self.__dict__["_agg_x"] = agg_ent
                 else:
                     d_out = self.hidden_dim if l != self.num_layers - 1 else self.output_dim
                     y = ops.feat_empty(x.shape[0], d_out, x.device, zero=True)           # models.py:129-132

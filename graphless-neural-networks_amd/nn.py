@@ -36,12 +36,13 @@ class SAGEConv(nn.Module):
         """Aggregate-first layers with d_in, d_out <= 256 run on the single-launch K1F kernel."""
         return self._in_feats <= self._out_feats and self._in_feats <= FUSED_SAGE_MAX_IN and self._out_feats <= 256
 
-    def forward(self, graph, feat, ep_scale=None, ep_shift=None, relu=False, w_packed=None, out=None):
+    def forward(self, graph, feat, ep_scale=None, ep_shift=None, relu=False, w_packed=None, out=None, agg_out=None, agg_in=None):
         """out = fc_neigh((sum_{u->v} h[u] + h_dst[v]) / (deg(v)+1)).  ep_* / relu: optional fused tail
         (eval-mode BatchNorm + ReLU of the caller) used by SAGE.inference; bias is folded by the caller then.
         w_packed: ops.pack_weight(fc_neigh.weight) of a caller that sweeps many blocks with the same weights (the chunked
         inference loop packs once per layer instead of once per chunk).  out (inference only): where the layer's rows go
-        (SAGE.inference hands a placed buffer, ops.placed_for_gather, to the layers whose output the next layer gathers)."""
+        (SAGE.inference hands a placed buffer, ops.placed_for_gather, to the layers whose output the next layer gathers).
+        agg_out / agg_in (inference, fused-eligible layers only): the kept neighbour aggregate of ops.sage_fused."""
         h_src, h_dst = feat if isinstance(feat, tuple) else (feat, feat)
         n_dst = graph.num_dst_nodes()
         if h_dst.shape[0] != n_dst:
@@ -53,6 +54,8 @@ class SAGEConv(nn.Module):
             return linear_fn(agg, w, b)
         fused_tail = ep_scale is not None or ep_shift is not None or relu
         shift = ep_shift if fused_tail else b
+        if (agg_out is not None or agg_in is not None) and not self.fused_eligible():
+            raise ValueError("SAGEConv: agg_out / agg_in belong to the fused launch (fused_eligible())")
         # (no ops.HubPlan here: a whole-graph launch is long enough to hide its hub rows behind the heaviest-first tile order -- measured on
         #  the arxiv-shaped graph the extra launch costs 10-60 us per layer and gains nothing; row shards use one: glnn_amd/dist.py)
         if self._in_feats > self._out_feats:
@@ -64,7 +67,7 @@ class SAGEConv(nn.Module):
             # aggregation + projection + epilogue in one launch: the aggregated rows never reach HBM
             order = graph.fused_tile_order() if n_dst == graph.n_dst else None
             return ops.sage_fused(graph.indptr, graph.indices, h_src, n_dst, w, ep_scale=ep_scale, ep_shift=shift, relu=relu,
-                                  x_self=h_dst, w_packed=w_packed, tile_order=order, out=out)
+                                  x_self=h_dst, w_packed=w_packed, tile_order=order, out=out, agg_out=agg_out, agg_in=agg_in)
         agg = ops.spmm(graph.indptr, graph.indices, h_src, n_dst, ops.AGG_SAGE_GCN)
         return ops.gemm(agg, w, ep_scale=ep_scale, ep_shift=shift, relu=relu, out=out)
 

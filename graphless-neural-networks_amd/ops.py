@@ -461,15 +461,32 @@ class ChunkSignals:
 
 
 def sage_fused(indptr, indices, x, n_dst, w, ep_scale=None, ep_shift=None, relu=False, out=None, x_self=None, w_packed=None,
-               w_next=None, out_next=None, want_out=True, tile_order=None, hub=None, chunks=None, out_dtype=None, out_next_dtype=None):
+               w_next=None, out_next=None, want_out=True, tile_order=None, hub=None, chunks=None, out_dtype=None, out_next_dtype=None,
+               agg_out=None, agg_in=None):
     """K1F glnn_sage_fused_f32: epi(((A x + x_self)/(deg+1)) @ w.T) in one launch (d_in, d_out <= 256).
     w_next [d_out2, d_out]: also returns (.. , out @ w_next.T) -- the projection of the NEXT layer when it projects first;
     with want_out=False the hidden rows themselves are not written at all (returns (None, projected)).
     chunks (ChunkSignals.launch(...)): the launch covers the chunks of a row range -- x_self / out / out_next are then WHOLE buffers
     addressed through the descriptor's per-chunk rows (they must be given), and every chunk signals its completion.
     bf16 x (and x_self): glnn_sage_fused_bf16, the same fp32 MFMA on the fp32 aggregate; out / out_next are stored in their own dtype, else
-    in out_dtype / out_next_dtype (default bf16); no hub / chunks."""
-    _need_cuda(indptr, indices, x, w, ep_scale, ep_shift, out, x_self, w_next, out_next)
+    in out_dtype / out_next_dtype (default bf16); no hub / chunks.
+    agg_out / agg_in (glnn_sage_fused_agg_f32; fp32, no chunks; a feat_empty(n_dst, d_in) matrix): the aggregate
+    (A x + x_self)/(deg+1) depends on the graph and on x only.  agg_out: this launch also stores it there (same out / out_next bits).
+    agg_in: the launch reads it back instead of gathering -- indptr, indices, x, x_self, tile_order and hub are not used -- and stores the
+    bits the agg_out launch with these weights stores; set_timing records it as a "gemm" (m rows, k = d_in, n = d_out), which is what it
+    is."""
+    _need_cuda(indptr, indices, x, w, ep_scale, ep_shift, out, x_self, w_next, out_next, agg_out, agg_in)
+    agg = agg_out if agg_out is not None else agg_in
+    if agg is not None:
+        if agg_out is not None and agg_in is not None:
+            raise ValueError("sage_fused: agg_out and agg_in exclude each other")
+        if chunks is not None or (x is not None and x.dtype != torch.float32):
+            raise ValueError("sage_fused: agg_out / agg_in belong to the fp32 launch without chunks")
+        _mat(agg, "sage_fused agg")
+        if agg.shape[0] < n_dst or agg.shape[1] != w.shape[1]:
+            raise ValueError("sage_fused: the aggregate must hold n_dst rows of d_in columns")
+    if agg_in is not None:
+        return _sage_fused_agg_in(agg_in, n_dst, w, ep_scale, ep_shift, relu, out, w_packed, w_next, out_next, want_out)
     if x.dtype == torch.bfloat16:
         return _sage_fused_bf16(indptr, indices, x, n_dst, w, ep_scale, ep_shift, relu, out, x_self, w_packed, w_next, out_next, want_out,
                                 tile_order, hub, chunks, out_dtype, out_next_dtype)
@@ -504,11 +521,35 @@ def sage_fused(indptr, indices, x, n_dst, w, ep_scale=None, ep_shift=None, relu=
         plan = hub.desc_for(d_in, x.device) if hub is not None else None
         if chunks is not None:
             rc = _lib.lib().glnn_sage_fused_chunks_f32(*args, plan, ctypes.byref(chunks), _stream())
+        elif agg_out is not None:
+            rc = _lib.lib().glnn_sage_fused_agg_f32(*args, plan, _p(agg_out), None, _ld(agg_out), _stream())
         elif plan is not None:
             rc = _lib.lib().glnn_sage_fused_plan_f32(*args, plan, _stream())
         else:
             rc = _lib.lib().glnn_sage_fused_f32(*args, _stream())
     _lib.check(rc, "glnn_sage_fused_f32")
+    return out if w_next is None else (out, out_next)
+
+
+def _sage_fused_agg_in(agg, n_dst, w, ep_scale, ep_shift, relu, out, w_packed, w_next, out_next, want_out):
+    d_out, d_in = w.shape
+    if w_packed is None:
+        w_packed = pack_weight(w)
+    if out is None and (want_out or w_next is None):
+        out = feat_empty(n_dst, d_out, agg.device)
+    w2p, d_out2 = None, 0
+    if w_next is not None:
+        if w_next.shape[1] != d_out:
+            raise ValueError("sage_fused: w_next must be [d_out2, d_out]")
+        w2p, d_out2 = pack_weight(w_next), w_next.shape[0]
+        if out_next is None:
+            out_next = feat_empty(n_dst, d_out2, agg.device)
+    with _Timed("gemm", m=n_dst, k=d_in, n=d_out):
+        rc = _lib.lib().glnn_sage_fused_agg_f32(
+            None, None, n_dst, 0, None, 0, d_in, None, 0, _p(w_packed), d_out, _p(_vec(ep_scale, d_out, "ep_scale")),
+            _p(_vec(ep_shift, d_out, "ep_shift")), 1 if relu else 0, _p(out), _ld(out) if out is not None else 0,
+            _p(w2p), d_out2, _p(out_next), _ld(out_next) if out_next is not None else 0, None, None, None, _p(agg), _ld(agg), _stream())
+    _lib.check(rc, "glnn_sage_fused_agg_f32")
     return out if w_next is None else (out, out_next)
 
 

@@ -141,6 +141,22 @@ GLNN_API int glnn_sage_fused_plan_f32(const int64_t* indptr, const int32_t* indi
                                       float* out, int64_t ldo, const float* w2_packed, int d_out2,
                                       float* out2, int64_t ldo2, const int32_t* tile_order,
                                       const glnn_hub_plan* plan, void* stream);
+/* The same launch around a KEPT aggregate.  A1 = (sum_{u->v} x[u] + x_self[v]) / (deg+1) depends on the graph and on x only: a caller whose
+ * layer aggregates the same input call after call (the teacher's layer 1 over a dataset's features, once per evaluation) keeps it.
+ * Exactly one of agg_out / agg_in is non-NULL; ld_agg is a multiple of 4 and >= d_in rounded up to 4; both are 16-byte aligned.
+ *   agg_out  the launch of glnn_sage_fused_plan_f32, which also streams every normalised row to agg_out[v, 0:ld_agg) (columns at or beyond
+ *            d_in are written as 0, up to d_in rounded up to 8 where ld_agg reaches that far); out / out2 are the bits of the plain launch
+ *   agg_in   the gather is replaced by a copy of agg_in[v, 0:d_in rounded up to 4) into the tile; indptr, indices, x, x_self, tile_order
+ *            and plan are not read (may be NULL).  The projection, epilogue and chained projection are the same code, so out / out2 are
+ *            bit for bit what the agg_out launch with these weights stores. */
+GLNN_API int glnn_sage_fused_agg_f32(const int64_t* indptr, const int32_t* indices, int64_t n_dst,
+                                     int64_t n_src, const float* x, int64_t ldx, int d_in,
+                                     const float* x_self, int64_t ld_self, const float* w_packed,
+                                     int d_out, const float* ep_scale, const float* ep_shift, int relu,
+                                     float* out, int64_t ldo, const float* w2_packed, int d_out2,
+                                     float* out2, int64_t ldo2, const int32_t* tile_order,
+                                     const glnn_hub_plan* plan, float* agg_out, const float* agg_in,
+                                     int64_t ld_agg, void* stream);
 
 /* ABI 12 (round 6): ONE fused launch over the CHUNKS of a row shard, with a completion signal per chunk.  A rank of the sharded forward
  * (no reference counterpart: the reference is single-device, train_teacher.py:162-165) produces its rows chunk by chunk so that each
