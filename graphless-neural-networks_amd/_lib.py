@@ -97,6 +97,9 @@ SIGNATURES = {
     "glnn_gat_attn_bwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                               c_vp, c_i64, c_vp, c_i64, c_f32, c_f32, c_u32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp],
     "glnn_gat_attn_mask_u8": [c_i64, c_int, c_f32, c_u32, c_vp, c_vp],
+    "glnn_sage_mean_fused_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp,
+                                 c_i64, c_vp, c_vp],
+    "glnn_spmm_sage_mean_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64, c_vp],
     "glnn_gather_rows_f32": [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp],
     "glnn_scatter_rows_f32": [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp],
     "glnn_gemm_bf16": [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_int, c_vp],

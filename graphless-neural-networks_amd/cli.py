@@ -69,9 +69,17 @@ def get_teacher_args(argv=None):
     # bfloat16 = the gathered matrices stored as bf16, arithmetic and the saved log-probs fp32
     p.add_argument("--inference_dtype", type=str, default="float32", choices=["float32", "bfloat16"],
                    help="Activation storage of the SAGE teacher's evaluation forward (bfloat16: SAGE only)")
+    # not a reference flag: the SAGE teacher's aggregator (conf key `sage_aggregator`, read by Model): "gcn" is what the reference builds,
+    # "mean" dgl's default form with a separate fc_self (docs/SAGE_MEAN_SEMANTICS.md; trained through the differentiable ops, fp32 inference)
+    p.add_argument("--sage_aggregator", type=str, default="gcn", choices=["gcn", "mean"],
+                   help="Aggregator of the SAGE teacher's SAGEConv layers (mean: separate fc_self; fp32, single device)")
     args = p.parse_args(argv)
     if args.inference_dtype != "float32" and "SAGE" not in args.teacher:
         p.error(f"--inference_dtype {args.inference_dtype} is implemented for the SAGE teacher only (got --teacher {args.teacher})")
+    if args.sage_aggregator != "gcn" and "SAGE" not in args.teacher:
+        p.error(f"--sage_aggregator {args.sage_aggregator} applies to the SAGE teacher only (got --teacher {args.teacher})")
+    if args.sage_aggregator != "gcn" and args.inference_dtype != "float32":
+        p.error(f"--sage_aggregator {args.sage_aggregator} runs its inference in float32 only")
     return args
 
 

@@ -384,6 +384,12 @@ def _refuse_gat(encoder, who):
                                   "scores of the remote sources, an exchange the sharded forward does not have (whole-graph GAT only)")
 
 
+def _refuse_mean(encoder, who):
+    if getattr(encoder, "aggregator_type", "gcn") != "gcn":
+        raise NotImplementedError(f"{who}: the sharded teacher forward implements the SAGE 'gcn' aggregator only -- a SAGE "
+                                  f"{encoder.aggregator_type!r} teacher (separate fc_self) runs on one device (SAGE.inference)")
+
+
 class ShardedTeacher:
     """SAGE layer-wise inference over a row-sharded graph.  `graph_shard` = full graph's rows [lo,hi)
     (glnn_amd.graph.CSRGraph.row_range), column indices global.
@@ -403,6 +409,7 @@ class ShardedTeacher:
                   the two: `shards` is replaced by shards.mixed(mixed_fraction) (whole chunks of either kind).
         All are chunked and overlapped when shards.chunks > 1; results are identical."""
         _refuse_gat(encoder, "ShardedTeacher")
+        _refuse_mean(encoder, "ShardedTeacher")
         if widening_exchange not in ("narrow", "wide", "mixed"):
             raise ValueError("ShardedTeacher: widening_exchange must be 'narrow', 'wide' or 'mixed'")
         if widening_exchange == "mixed":
@@ -994,6 +1001,7 @@ class HaloShardedTeacher:
         being exchanged runs in two passes over the split CSR of HaloPlan.split_csr (local-source edges + self first, then the
         remote-source edges once the halo has landed).  Same sums, local edges before remote ones (results equal to rounding)."""
         _refuse_gat(encoder, "HaloShardedTeacher")
+        _refuse_mean(encoder, "HaloShardedTeacher")
         self.enc, self.g, self.sh, self.be, self.group, self.overlap = encoder, graph_shard, shards, be, group, overlap
         if graph_shard.n_dst != shards.rows:
             raise ValueError(f"HaloShardedTeacher: the graph shard has {graph_shard.n_dst} rows, the shard range {shards.rows}")

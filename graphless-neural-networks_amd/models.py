@@ -40,6 +40,14 @@ def _check_tail(module):
     act = getattr(module, "activation", F.relu)
     if act is not F.relu and getattr(act, "__name__", "") != "relu":
         raise NotImplementedError("only ReLU hidden activations (what the reference constructs, models.py:371,381)")
+    agg = getattr(module, "aggregator_type", None)
+    if agg is not None:
+        # a SAGE encoder: every path below dispatches on the encoder's aggregator, so the layers must all be of that kind -- a "mean" layer
+        # (separate fc_self) must never run through the "gcn" engine, which would silently drop its self weight
+        if agg not in ("gcn", "mean"):
+            raise NotImplementedError(f"SAGE aggregator_type {agg!r}: 'gcn' (the reference's, models.py:84-99) or 'mean'")
+        if any(getattr(lay, "_aggre_type", "gcn") != agg for lay in module.layers):
+            raise NotImplementedError(f"SAGE(aggregator_type={agg!r}): every SAGEConv layer must use that aggregator")
     for bn in module.norms:
         if isinstance(bn, nn.LayerNorm):
             if not bn.elementwise_affine or len(bn.normalized_shape) != 1:
@@ -149,25 +157,28 @@ class MLP(nn.Module):
 class SAGE(nn.Module):
     """reference models.py:62-148"""
 
-    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none"):
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", aggregator_type="gcn"):
+        """aggregator_type: "gcn" (what the reference builds) or "mean" (dgl's default SAGE form with a separate fc_self,
+        docs/SAGE_MEAN_SEMANTICS.md); anything else raises in SAGEConv."""
         super().__init__()
         self.num_layers = num_layers
         self.hidden_dim = hidden_dim
         self.output_dim = output_dim
         self.norm_type = norm_type
         self.activation = activation
+        self.aggregator_type = aggregator_type
         self.dropout = nn.Dropout(dropout_ratio)
         self.layers = nn.ModuleList()
         self.norms = nn.ModuleList()
         if num_layers == 1:
-            self.layers.append(SAGEConv(input_dim, output_dim, "gcn"))
+            self.layers.append(SAGEConv(input_dim, output_dim, aggregator_type))
         else:
-            self.layers.append(SAGEConv(input_dim, hidden_dim, "gcn"))
+            self.layers.append(SAGEConv(input_dim, hidden_dim, aggregator_type))
             self._add_norm(hidden_dim)
             for _ in range(num_layers - 2):
-                self.layers.append(SAGEConv(hidden_dim, hidden_dim, "gcn"))
+                self.layers.append(SAGEConv(hidden_dim, hidden_dim, aggregator_type))
                 self._add_norm(hidden_dim)
-            self.layers.append(SAGEConv(hidden_dim, output_dim, "gcn"))
+            self.layers.append(SAGEConv(hidden_dim, output_dim, aggregator_type))
 
     def _add_norm(self, hidden_dim):
         if self.norm_type == "batch":
@@ -202,7 +213,8 @@ class SAGE(nn.Module):
 
     def _tail(self, l):
         """Fused eval tail of layer l: (ep_scale, ep_shift, relu) = BN(eval) o (+bias) o ReLU; dropout is a no-op."""
-        bias = self.layers[l].fc_neigh.bias
+        mean = self.aggregator_type == "mean"
+        bias = self.layers[l].mean_bias() if mean else self.layers[l].fc_neigh.bias      # ("mean": fc_self.bias + fc_neigh.bias)
         if l == self.num_layers - 1:
             return None, bias, False
         if self.activation is not F.relu and getattr(self.activation, "__name__", "") != "relu":
@@ -212,6 +224,8 @@ class SAGE(nn.Module):
             # version counters + ops.PARAM_EPOCH, which this library's raw-pointer writers bump)
             bn = self.norms[l]
             ts = (bn.weight, bn.bias, bn.running_mean, bn.running_var) + ((bias,) if bias is not None else ())
+            if mean and bias is not None:      # (the summed bias is a derived tensor: key on the two parameters it came from)
+                ts = ts[:-1] + (self.layers[l].fc_self.bias, self.layers[l].fc_neigh.bias)
             key = (ops.PARAM_EPOCH, bn.eps) + tuple((t.data_ptr(), t._version) for t in ts)
             cache = self.__dict__.setdefault("_tail_cache", {})
             ent = cache.get(l)
@@ -254,6 +268,9 @@ class SAGE(nn.Module):
         _input_aggregate for the fused launch."""
         agg = agg or {}
         layer = self.layers[l]
+        if self.aggregator_type != "gcn":
+            raise NotImplementedError("SAGE._whole_graph_layer: the chained next-layer projection and the placed buffers belong to the 'gcn' "
+                                      f"engine, not to aggregator_type {self.aggregator_type!r}")
         post_ln = self.norm_type == "layer" and l != self.num_layers - 1
         ep_scale, ep_shift, relu = (None, layer.fc_neigh.bias, False) if post_ln else self._tail(l)
         n = g.num_dst_nodes()
@@ -303,6 +320,9 @@ class SAGE(nn.Module):
         Returns (the launch's keyword, the entry to remember once that launch has run or None).  No room (free memory under twice the
         matrix, or the allocation fails): the forward runs as it always did."""
         layer, n = self.layers[0], g.num_dst_nodes()
+        if self.aggregator_type != "gcn":
+            raise NotImplementedError("SAGE._input_aggregate: the kept layer-1 neighbour aggregate is the 'gcn' aggregate (A x + x)/(deg+1), "
+                                      f"not implemented for aggregator_type {self.aggregator_type!r}")
         if not SAGE.CACHE_INPUT_AGGREGATE or not layer.fused_eligible() or x.shape[0] < n or n == 0:
             return {}, None
         try:
@@ -327,6 +347,8 @@ class SAGE(nn.Module):
         exactly when an aggregation gathers it -- the chained projection, a project-first layer's x @ W^T, and a hidden layer's output
         when the next layer aggregates first; all sums, MFMA and epilogues are fp32 and the logits come out fp32."""
         layer = self.layers[l]
+        if self.aggregator_type != "gcn":
+            raise NotImplementedError(f"SAGE bf16 activation storage: 'gcn' aggregator only, not aggregator_type {self.aggregator_type!r}")
         ep_scale, ep_shift, relu = self._tail(l)
         n = g.num_dst_nodes()
         nxt = self.layers[l + 1] if l + 1 < self.num_layers else None
@@ -361,6 +383,50 @@ class SAGE(nn.Module):
                 x, projected = self._whole_graph_layer_bf16(l, g, x, projected)
             return x
 
+    def _inference_mean(self, dataloader, feats, whole_graph, dtype):
+        """`inference` of a "mean" encoder, fp32: per layer ONE launch over all rows of the resident CSR (whole_graph) or one per chunk of
+        the loader's sweep over global-id row ranges (the same kernels on the same rows: bit-identical), the tail as in `_tail` with the
+        summed bias, LayerNorm as its own pass behind the conv.  The "gcn" engine's extras -- the chained next-layer projection, the kept
+        layer-1 aggregate, bf16 storage -- are not implemented for this aggregator and raise when asked for."""
+        if dtype != torch.float32:
+            raise NotImplementedError("SAGE.inference(dtype=torch.bfloat16): bf16 activation storage is implemented for the 'gcn' aggregator "
+                                      "only, not for aggregator_type 'mean'")
+        g = getattr(dataloader, "graph", None)
+        if g is None or not hasattr(dataloader, "global_blocks"):
+            raise NotImplementedError("SAGE.inference(aggregator_type 'mean'): a glnn_amd.graph.FullNeighborLoader over the resident graph")
+        ln = self.norm_type == "layer"
+        with torch.no_grad():
+            x = ops.as_feat(feats)
+            n = g.num_dst_nodes()
+            for l, layer in enumerate(self.layers):
+                post_ln = ln and l != self.num_layers - 1
+                ep_scale, ep_shift, relu = (None, layer.mean_bias(), False) if post_ln else self._tail(l)
+                if whole_graph:
+                    y = layer(g, (x, x[:n]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu)
+                else:
+                    y = ops.feat_empty(n, layer._out_feats, x.device, zero=True)
+                    form = layer.mean_form()
+                    wp = ops.pack_weight_pair(layer.fc_neigh.weight, layer.fc_self.weight) if form == "fused" else None
+                    r4 = ops.round4(layer._out_feats)
+                    # a layer that projects first projects x ONCE, not once per chunk
+                    p = ops.gemm(x, ops.stack_weight_pair(layer.fc_neigh.weight, layer.fc_self.weight)) if form == "project" else None
+                    dataloader.global_blocks = True
+                    try:
+                        for _, _, blocks in dataloader:
+                            block = blocks[0]
+                            s_, e_ = block.dst_range
+                            if p is not None:
+                                ops.spmm_sage_mean(block.indptr, block.indices, p[:, :layer._out_feats], p[s_:e_, r4:], e_ - s_,
+                                                   ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, out=y[s_:e_])
+                            else:
+                                layer(block, (x, x[s_:e_]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, w_packed=wp, out=y[s_:e_])
+                    finally:
+                        dataloader.global_blocks = False
+                if post_ln:
+                    y = _eval_tail(self, l, y)
+                x = y
+            return x
+
     def inference(self, dataloader, feats, whole_graph=True, dtype=torch.float32):
         """Layer-wise full-neighbour inference (reference models.py:121-148).
 
@@ -375,6 +441,9 @@ class SAGE(nn.Module):
         _need_hip(feats, "SAGE.inference")
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"SAGE.inference: dtype must be torch.float32 or torch.bfloat16, not {dtype}")
+        if self.aggregator_type != "gcn":
+            _check_tail(self)
+            return self._inference_mean(dataloader, feats, whole_graph, dtype)
         if dtype == torch.bfloat16:
             return self._inference_bf16(dataloader, feats, whole_graph)
         whole_graph = whole_graph and getattr(dataloader, "graph", None) is not None     # loaders that do not sweep arange(N)
@@ -594,7 +663,8 @@ class Model(nn.Module):
         if "MLP" in conf["model_name"]:
             self.encoder = MLP(norm_type=conf["norm_type"], **common).to(conf["device"])
         elif "SAGE" in conf["model_name"]:
-            self.encoder = SAGE(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
+            self.encoder = SAGE(activation=F.relu, norm_type=conf["norm_type"], aggregator_type=conf.get("sage_aggregator", "gcn"),
+                                **common).to(conf["device"])
         elif "GCN" in conf["model_name"]:
             self.encoder = GCN(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
         elif "APPNP" in conf["model_name"]:

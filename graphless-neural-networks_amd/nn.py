@@ -20,21 +20,106 @@ FUSED_SAGE_MAX_IN = 256   # aggregate-first layers with d_in, d_out <= 256 take 
                           # 128->256 11.4 vs 12.2 ms, 256->256 23.6 vs 25.1 ms (fused vs aggregation + GEMM)
 
 
+MEAN_COMPOSE_SHAPES = frozenset()      # (d_in, d_out) of "mean" layers that the fused launch does NOT win on a GPU measurement and that
+                                       # therefore take the composition (scripts/bench_sage_mean.py; DESIGN.md "SAGE mean")
+
+
+def mean_row_scale(graph):
+    """1 / max(in_deg, 1) per destination row (fp32, cached on the graph): the row scale that turns GLNN_AGG_SUM into the mean."""
+    if "inv_deg_clamp1" not in graph._cache:
+        graph._cache["inv_deg_clamp1"] = (1.0 / graph.in_degrees().clamp(min=1).to(torch.float32)).contiguous()
+    return graph._cache["inv_deg_clamp1"]
+
+
+def _add_epilogue(y, s, ep_scale, ep_shift, relu, out):
+    """epi(y + s) of the composed "mean" form (plumbing of the fallback: the hot forms fuse it)."""
+    y = y + s
+    if ep_scale is not None:
+        y = y * ep_scale
+    if ep_shift is not None:
+        y = y + ep_shift
+    if relu:
+        y = torch.relu_(y)
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y
+
+
 class SAGEConv(nn.Module):
     def __init__(self, in_feats, out_feats, aggregator_type, bias=True):
         super().__init__()
-        if aggregator_type != "gcn":
-            raise NotImplementedError("the reference only builds SAGEConv(..., 'gcn') (models.py:84-99)")
+        if aggregator_type not in ("gcn", "mean"):
+            raise NotImplementedError(f"SAGEConv(..., {aggregator_type!r}): only the 'gcn' aggregator the reference builds (models.py:84-99) and "
+                                      "the 'mean' aggregator (docs/SAGE_MEAN_SEMANTICS.md) are implemented")
         self._in_feats, self._out_feats = in_feats, out_feats
+        self._aggre_type = aggregator_type
+        if aggregator_type == "mean":
+            self.fc_self = nn.Linear(in_feats, out_feats, bias=bias)      # (registered first, as dgl 0.6.1 does)
         self.fc_neigh = nn.Linear(in_feats, out_feats, bias=bias)
         self.reset_parameters()
 
     def reset_parameters(self):
+        if self._aggre_type == "mean":
+            nn.init.xavier_uniform_(self.fc_self.weight, gain=nn.init.calculate_gain("relu"))
         nn.init.xavier_uniform_(self.fc_neigh.weight, gain=nn.init.calculate_gain("relu"))
 
+    def mean_bias(self):
+        """The "mean" layer's effective bias fc_self.bias + fc_neigh.bias (None without biases), remembered while both are unmodified."""
+        bs, bn = self.fc_self.bias, self.fc_neigh.bias
+        if bs is None:
+            return None
+        key = (ops.PARAM_EPOCH, bs.data_ptr(), bs._version, bn.data_ptr(), bn._version)
+        ent = self.__dict__.get("_mean_bias")
+        if ent is None or ent[0] != key:
+            self.__dict__["_mean_bias"] = ent = (key, (bs.detach() + bn.detach()).contiguous())
+        return ent[1]
+
+    def mean_form(self):
+        """Which eval form a "mean" layer takes: "fused" (one launch, d_in <= d_out <= 256), "project" (d_in > d_out, d_out <= 256:
+        one GEMM against the stacked weights, then the aggregation at the narrower width) or "compose" (aggregation with a row scale
+        plus two GEMMs)."""
+        if self._in_feats <= self._out_feats <= 256 and (self._in_feats, self._out_feats) not in MEAN_COMPOSE_SHAPES:
+            return "fused"
+        if self._in_feats > self._out_feats and self._out_feats <= 256:
+            return "project"
+        return "compose"
+
+    def forward_mean(self, graph, feat, ep_scale=None, ep_shift=None, relu=False, w_packed=None, out=None, form=None):
+        """out = fc_self(h_dst) + fc_neigh(mean_{u->v} h[u]) (deg 0: the mean is 0).  ep_* / relu: the fused tail of SAGE.inference, which
+        then folds the summed bias itself.  form: force "fused" / "project" / "compose" (tests and A/B timing; default mean_form())."""
+        h_src, h_dst = feat if isinstance(feat, tuple) else (feat, feat)
+        n_dst = graph.num_dst_nodes()
+        if h_dst.shape[0] != n_dst:
+            raise ValueError("SAGEConv: h_dst must hold the block's destination rows")
+        wn, ws = self.fc_neigh.weight, self.fc_self.weight
+        if torch.is_grad_enabled() and (h_src.requires_grad or h_dst.requires_grad or wn.requires_grad or ws.requires_grad):
+            agg = SpmmFn.apply(graph, h_src, ops.AGG_SUM, mean_row_scale(graph))
+            return linear_fn(h_dst, ws, self.fc_self.bias) + linear_fn(agg, wn, self.fc_neigh.bias)
+        fused_tail = ep_scale is not None or ep_shift is not None or relu
+        shift = ep_shift if fused_tail else self.mean_bias()
+        form = form or self.mean_form()
+        if form == "fused":
+            order = graph.fused_tile_order() if n_dst == graph.n_dst else None
+            return ops.sage_mean_fused(graph.indptr, graph.indices, h_src, n_dst, wn, ws, ep_scale=ep_scale, ep_shift=shift, relu=relu,
+                                       x_self=h_dst, w_packed=w_packed, tile_order=order, out=out)
+        if form == "project":
+            # project first (linear commutes with the mean): ONE product against [W_neigh; W_self], aggregate at the narrower width
+            r4 = ops.round4(self._out_feats)
+            p = ops.gemm(ops.as_feat(h_src), ops.stack_weight_pair(wn, ws))
+            return ops.spmm_sage_mean(graph.indptr, graph.indices, p[:, :self._out_feats], p[:, r4:], n_dst, ep_scale=ep_scale,
+                                      ep_shift=shift, relu=relu, out=out)
+        if form != "compose":
+            raise ValueError(f"SAGEConv.forward_mean: unknown form {form!r}")
+        agg = ops.spmm(graph.indptr, graph.indices, h_src, n_dst, ops.AGG_SUM, row_scale=mean_row_scale(graph))
+        y = ops.gemm(agg, wn)
+        s = ops.gemm(ops.as_feat(h_dst), ws)
+        return _add_epilogue(y, s, ep_scale, shift, relu, out)
+
     def fused_eligible(self):
-        """Aggregate-first layers with d_in, d_out <= 256 run on the single-launch K1F kernel."""
-        return self._in_feats <= self._out_feats and self._in_feats <= FUSED_SAGE_MAX_IN and self._out_feats <= 256
+        """Aggregate-first layers with d_in, d_out <= 256 run on the single-launch K1F kernel ("gcn" only: the "mean" forms are
+        mean_form()'s)."""
+        return self._aggre_type == "gcn" and self._in_feats <= self._out_feats and self._in_feats <= FUSED_SAGE_MAX_IN and self._out_feats <= 256
 
     def forward(self, graph, feat, ep_scale=None, ep_shift=None, relu=False, w_packed=None, out=None, agg_out=None, agg_in=None):
         """out = fc_neigh((sum_{u->v} h[u] + h_dst[v]) / (deg(v)+1)).  ep_* / relu: optional fused tail
@@ -43,6 +128,10 @@ class SAGEConv(nn.Module):
         inference loop packs once per layer instead of once per chunk).  out (inference only): where the layer's rows go
         (SAGE.inference hands a placed buffer, ops.placed_for_gather, to the layers whose output the next layer gathers).
         agg_out / agg_in (inference, fused-eligible layers only): the kept neighbour aggregate of ops.sage_fused."""
+        if self._aggre_type == "mean":
+            if agg_out is not None or agg_in is not None:
+                raise NotImplementedError("SAGEConv 'mean': the kept neighbour aggregate (agg_out / agg_in) belongs to the 'gcn' launch")
+            return self.forward_mean(graph, feat, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, w_packed=w_packed, out=out)
         h_src, h_dst = feat if isinstance(feat, tuple) else (feat, feat)
         n_dst = graph.num_dst_nodes()
         if h_dst.shape[0] != n_dst:
@@ -75,6 +164,8 @@ class SAGEConv(nn.Module):
         """Eval-mode layer with bf16 activation STORAGE (SAGE.inference(..., dtype=torch.bfloat16)): the forms `forward` picks, where every
         matrix an aggregation gathers is bf16 and all arithmetic is fp32.  h_src / h_dst: bf16 rows when the layer aggregates first, fp32
         when it projects first (a GEMM is then their only reader).  out_dtype: torch.bfloat16 when the next layer gathers the result."""
+        if self._aggre_type == "mean":
+            raise NotImplementedError("SAGEConv 'mean': bf16 activation storage is implemented for the 'gcn' aggregator only")
         n_dst = graph.num_dst_nodes()
         w, b = self.fc_neigh.weight, self.fc_neigh.bias
         fused_tail = ep_scale is not None or ep_shift is not None or relu

@@ -590,6 +590,127 @@ def _sage_fused_bf16(indptr, indices, x, n_dst, w, ep_scale, ep_shift, relu, out
     return out if w_next is None else (out, out_next)
 
 
+# ---- the GraphSAGE "mean" aggregator (csrc/sage_mean.hip, docs/SAGE_MEAN_SEMANTICS.md) -------------------------------------------
+_PAIRS = []           # [(kind, weakref(w_neigh), weakref(w_self), key, derived)], most recent first
+
+
+def _pair_cached(kind, w_neigh, w_self, build):
+    """`build()` of a (fc_neigh.weight, fc_self.weight) pair, remembered like pack_weight remembers a packed weight: while the same two
+    unmodified tensors come back (identity, torch version, data pointer, PARAM_EPOCH) -- a parameter write re-derives."""
+    key = tuple((w.data_ptr(), tuple(w.shape), w.stride(0), w._version) for w in (w_neigh, w_self)) + (PARAM_EPOCH,)
+    for i, (kd, rn, rs, k, val) in enumerate(_PAIRS):
+        if kd == kind and rn() is w_neigh and rs() is w_self and k == key:
+            if i:
+                _PAIRS.insert(0, _PAIRS.pop(i))
+            return val
+    val = build()
+    import weakref
+    _PAIRS[:] = [e for e in _PAIRS if e[1]() is not None and e[2]() is not None
+                 and not (e[0] == kind and e[1]() is w_neigh and e[2]() is w_self)][:15]
+    _PAIRS.insert(0, (kind, weakref.ref(w_neigh), weakref.ref(w_self), key, val))
+    return val
+
+
+def _check_pair(w_neigh, w_self, who):
+    _need_cuda(w_neigh, w_self)
+    _mat(w_neigh, who + " w_neigh")
+    _mat(w_self, who + " w_self")
+    if w_neigh.shape != w_self.shape:
+        raise ValueError(f"{who}: fc_neigh.weight and fc_self.weight must have the same [d_out, d_in] shape")
+
+
+def pack_weight_pair(w_neigh, w_self):
+    """The packed W_cat of sage_mean_fused: glnn_pack_weight_f32 of the [d_out, 2 kpad] matrix [W_neigh | 0 | W_self | 0], kpad = d_in
+    rounded up to 8, so that the fused launch is ONE MFMA product over [mean | self] tiles.  Keyed like pack_weight (parameter writes
+    re-pack); READ-ONLY for the caller."""
+    _check_pair(w_neigh, w_self, "pack_weight_pair")
+
+    def build():
+        d_out, d_in = w_neigh.shape
+        kpad = round8(d_in)
+        cat = torch.zeros(d_out, 2 * kpad, dtype=torch.float32, device=w_neigh.device)
+        cat[:, :d_in] = w_neigh.detach()
+        cat[:, kpad:kpad + d_in] = w_self.detach()
+        return _pack_weight(cat)
+    return _pair_cached("cat", w_neigh, w_self, build)
+
+
+def stack_weight_pair(w_neigh, w_self):
+    """[W_neigh; 0; W_self] as ONE [round4(d_out) + d_out, d_in] matrix for the project-first form: gemm(x, stacked) gives the two halves
+    spmm_sage_mean reads, the second one starting at the float4-aligned column round4(d_out).  Keyed like pack_weight_pair."""
+    _check_pair(w_neigh, w_self, "stack_weight_pair")
+
+    def build():
+        d_out, d_in = w_neigh.shape
+        r4 = round4(d_out)
+        st = torch.zeros(r4 + d_out, d_in, dtype=torch.float32, device=w_neigh.device)
+        st[:d_out] = w_neigh.detach()
+        st[r4:] = w_self.detach()
+        return st
+    return _pair_cached("stack", w_neigh, w_self, build)
+
+
+def sage_mean_fused(indptr, indices, x, n_dst, w_neigh, w_self, ep_scale=None, ep_shift=None, relu=False, out=None, x_self=None,
+                    self_rows=None, w_packed=None, tile_order=None):
+    """glnn_sage_mean_fused_f32: epi(fc_neigh(mean of the in-neighbours' rows) + fc_self(own row)) in one launch, d_in <= d_out <= 256.
+    x [n_src, d_in]; x_self: the destination rows' own features, default x[:n_dst]; self_rows (int64 [n_dst]): destination v's own row is
+    x_self[self_rows[v]].  w_packed: pack_weight_pair(w_neigh, w_self) of a caller that sweeps many blocks.  Returns [n_dst, d_out]."""
+    _need_cuda(indptr, indices, x, ep_scale, ep_shift, out, x_self, self_rows, w_packed, tile_order)
+    _check_pair(w_neigh, w_self, "sage_mean_fused")
+    x = as_feat(x)
+    x_self = x if x_self is None else as_feat(x_self)
+    n_src, d_in = x.shape
+    d_out = w_neigh.shape[0]
+    if w_neigh.shape[1] != d_in or x_self.shape[1] != d_in:
+        raise ValueError("sage_mean_fused: weights must be [d_out, d_in] and x_self as wide as x")
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or indptr.numel() < n_dst + 1:
+        raise ValueError("sage_mean_fused: indptr must be int64 with n_dst + 1 entries and indices int32")
+    if self_rows is not None:
+        if self_rows.dtype != torch.int64 or not self_rows.is_contiguous() or self_rows.numel() < n_dst:
+            raise ValueError("sage_mean_fused: self_rows must be a contiguous int64 vector of n_dst row ids")
+    elif x_self.shape[0] < n_dst:
+        raise ValueError("sage_mean_fused: x_self must hold n_dst rows")
+    if tile_order is not None and (tile_order.dtype != torch.int32 or not tile_order.is_contiguous() or tile_order.numel() != (n_dst + 31) // 32):
+        raise ValueError("sage_mean_fused: tile_order must be a contiguous int32 permutation of the ceil(n_dst / 32) tile ids")
+    if w_packed is None:
+        w_packed = pack_weight_pair(w_neigh, w_self)
+    if out is None:
+        out = feat_empty(n_dst, d_out, x.device)
+    _mat(out, "sage_mean_fused out")
+    if out.shape[0] < n_dst or out.shape[1] != d_out:
+        raise ValueError("sage_mean_fused: out must hold n_dst rows of d_out columns")
+    with _Timed("sage_mean_fused", d=d_in, n_dst=n_dst, d_out=d_out):
+        rc = _lib.lib().glnn_sage_mean_fused_f32(
+            _p(indptr), _p(indices), n_dst, n_src, _p(x), _ld(x), d_in, _p(x_self), _ld(x_self), _p(self_rows), _p(w_packed), d_out,
+            _p(_vec(ep_scale, d_out, "ep_scale")), _p(_vec(ep_shift, d_out, "ep_shift")), 1 if relu else 0, _p(out), _ld(out),
+            _p(tile_order), _stream())
+    _lib.check(rc, "glnn_sage_mean_fused_f32")
+    return out
+
+
+def spmm_sage_mean(indptr, indices, x, s, n_dst, ep_scale=None, ep_shift=None, relu=False, out=None):
+    """glnn_spmm_sage_mean_f32: out[v] = epi(mean_{u->v} x[u] + s[v]), d <= 256.  x [n_src, d] and s [>= n_dst, d]: the two halves of
+    gemm(h, stack_weight_pair(w_neigh, w_self)) (column views keep their leading dimension).  Returns [n_dst, d]."""
+    _need_cuda(indptr, indices, x, s, ep_scale, ep_shift, out)
+    x, s = as_feat(x), as_feat(s)
+    n_src, d = x.shape
+    if s.shape[1] != d or s.shape[0] < n_dst:
+        raise ValueError("spmm_sage_mean: s must hold n_dst rows as wide as x")
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or indptr.numel() < n_dst + 1:
+        raise ValueError("spmm_sage_mean: indptr must be int64 with n_dst + 1 entries and indices int32")
+    if out is None:
+        out = feat_empty(n_dst, d, x.device)
+    _mat(out, "spmm_sage_mean out")
+    if out.shape[0] < n_dst or out.shape[1] != d:
+        raise ValueError("spmm_sage_mean: out must hold n_dst rows of d columns")
+    with _Timed("spmm_sage_mean", d=d, n_dst=n_dst):
+        rc = _lib.lib().glnn_spmm_sage_mean_f32(
+            _p(indptr), _p(indices), n_dst, n_src, _p(x), _ld(x), d, _p(s), _ld(s), _p(_vec(ep_scale, d, "ep_scale")),
+            _p(_vec(ep_shift, d, "ep_shift")), 1 if relu else 0, _p(out), _ld(out), _stream())
+    _lib.check(rc, "glnn_spmm_sage_mean_f32")
+    return out
+
+
 class RowRangeLaunch:
     """A PREPARED SAGE-"gcn" launch over row ranges [s, e) of one resident CSR whose column ids are rows of `x` (the engine-mode chunked
     sweep of SAGE.inference, reference models.py:133-145): everything that does not change from chunk to chunk -- the checks of sage_fused /

@@ -56,6 +56,9 @@ def check_supported(model, criterion, optimizer):
     if type(optimizer) is not torch.optim.Adam or len(grp) != 1 or grp[0].get("amsgrad") or grp[0].get("maximize"):
         raise NotImplementedError("TeacherEngine: torch.optim.Adam, one param group, no amsgrad/maximize (train_teacher.py:234-236)")
     if "SAGE" in name:
+        if getattr(enc, "aggregator_type", "gcn") != "gcn":
+            raise NotImplementedError(f"TeacherEngine: the one-call SAGE step implements the 'gcn' aggregator only; a SAGE "
+                                      f"{enc.aggregator_type!r} teacher trains through SAGE.forward's differentiable ops (train_sage)")
         if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
             raise NotImplementedError("TeacherEngine: SAGE with norm_type none|batch|layer and ReLU (the reference's configs)")
     elif "APPNP" in name:

@@ -51,6 +51,8 @@ def train_sage(model, dataloader, feats, labels, criterion, optimizer, lamb=1):
     `dataloader` (glnn_amd.graph.NodeDataLoader: blocks sampled and relabelled on the device; the outermost block gathers
     straight from `feats`, so `feats[input_nodes]` is never materialised).  The per-step `loss.item()` of the reference
     (:49) is a device-side running sum read ONCE per epoch; the returned mean of the per-batch losses is the same number."""
+    if "SAGE" in model.model_name and getattr(model.encoder, "aggregator_type", "gcn") == "mean":
+        return _train_sage_autograd(model, dataloader, feats, labels, criterion, optimizer, lamb)
     teacher.check_supported(model, criterion, optimizer)
     if "SAGE" not in model.model_name:
         raise NotImplementedError("train_sage(): GraphSAGE teachers only")
@@ -72,6 +74,34 @@ def train_sage(model, dataloader, feats, labels, criterion, optimizer, lamb=1):
             dataloader.global_first_block = had
     eng.sync_optimizer_state()
     return eng.loss_accum.item() / max(steps, 1)
+
+
+def _train_sage_autograd(model, dataloader, feats, labels, criterion, optimizer, lamb):
+    """train_sage for a SAGE "mean" teacher: the reference's literal step (train_and_eval.py:39-54) per batch of the same loader --
+    SAGE.forward in training mode (the differentiable HIP ops of glnn_amd.autograd: aggregation, both Linear layers, the hidden tails),
+    log-softmax, the criterion, backward, optimizer.step().  The one-call TeacherEngine.step_sage is "gcn"-only; the loss and the
+    optimiser on this path are torch's own.  `global_first_block` stays off: the forward gathers feats[input_nodes] like the reference.
+    One host read of the summed loss per epoch."""
+    _need = next(model.parameters())
+    if not _need.is_cuda or not feats.is_cuda:
+        raise RuntimeError("train_sage needs the model and the features on the GPU (HIP path only)")
+    model.train()
+    total, steps = None, 0
+    for input_nodes, output_nodes, blocks in dataloader:
+        if input_nodes is None:
+            raise RuntimeError("train_sage(SAGE 'mean'): the loader must yield input_nodes (global_first_block off)")
+        batch_feats = ops.gather_rows(ops.as_feat(feats), input_nodes)
+        logits = model(blocks, batch_feats)
+        out = logits.log_softmax(dim=1)
+        loss = criterion(out, labels[output_nodes])
+        total = loss.detach() if total is None else total + loss.detach()
+        loss = loss * lamb
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        ops.note_param_write()      # (torch's step bumps the version counters too; kept for optimisers that write through .data)
+        steps += 1
+    return total.item() / steps if steps else 0.0
 
 
 def _batch_indices(n, batch_size):

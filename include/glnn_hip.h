@@ -755,6 +755,32 @@ GLNN_API int glnn_gat_attn_bwd_f32(const int64_t* indptr, const int32_t* indices
  * (attn_drop, seed) -- the role glnn_edge_drop_mask_u8 plays for APPNP (parity tests feed it to the oracle). */
 GLNN_API int glnn_gat_attn_mask_u8(int64_t nnz, int heads, float attn_drop, uint32_t seed, uint8_t* mask, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GraphSAGE "mean" aggregator (csrc/sage_mean.hip; docs/SAGE_MEAN_SEMANTICS.md states the arithmetic):
+ *   h_neigh[v] = (1 / max(deg(v), 1)) * sum_{u->v} x[u]        out[v] = fc_neigh(h_neigh[v]) + fc_self(x_self[v])
+ * Both entries: CSR over destination rows as glnn_spmm_csr_f32, n_src < 2^31, float4-addressable rows (leading dimensions multiples of 4
+ * and >= the width rounded up to 4, 16-byte aligned bases), epi(t) = relu?(t * ep_scale[j] + ep_shift[j]) with NULL = 1 / 0.  No float
+ * atomics, no grid barrier: bit-identical run to run, and a row's result does not depend on the other rows of the launch.  A shape
+ * outside the stated contract returns GLNN_ERR_UNSUPPORTED with nothing launched.  n_dst == 0 is a no-op.
+ *
+ * glnn_sage_mean_fused_f32 replaces dgl 0.6.1 SAGEConv(in, out, "mean").forward of an aggregate-first layer (the reference has no call
+ *   site: it only builds "gcn") in ONE launch, d_in <= d_out <= 256:  out = epi([h_neigh | x_self] . W_cat^T), one fp32 MFMA product over
+ *   K = 2 kpad, kpad = d_in rounded up to 8.  w_cat_packed = glnn_pack_weight_f32 of the [d_out, 2 kpad] matrix whose columns [0, d_in) are
+ *   fc_neigh.weight, [kpad, kpad + d_in) fc_self.weight and the rest zeros.  self_rows (optional, int64 [n_dst]): the self row of
+ *   destination v is x_self[self_rows[v]], else x_self[v].  tile_order (optional): a permutation of the ceil(n_dst / 32) tile ids (same
+ *   bits).  out: ldo >= d_out; columns [d_out, min(d_out rounded up to 4, ldo)) are written as 0. */
+GLNN_API int glnn_sage_mean_fused_f32(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, const float* x,
+                                      int64_t ldx, int d_in, const float* x_self, int64_t ld_self, const int64_t* self_rows,
+                                      const float* w_cat_packed, int d_out, const float* ep_scale, const float* ep_shift, int relu,
+                                      float* out, int64_t ldo, const int32_t* tile_order, void* stream);
+/* glnn_spmm_sage_mean_f32 replaces the aggregation half of dgl 0.6.1 SAGEConv(in, out, "mean").forward when the layer projects first
+ *   (in > out; the reference has no call site), and is the general fallback:  out[v, :d] = epi(h_neigh[v, :d] + s[v, :d]),  d <= 256.
+ *   After ONE product of the source rows against the stacked [W_neigh; W_self], x is the first half of that matrix and s the second half
+ *   of the same rows (own pointer and leading dimension).  out: columns [d, d rounded up to 4) are written as 0. */
+GLNN_API int glnn_spmm_sage_mean_f32(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, const float* x,
+                                     int64_t ldx, int d, const float* s, int64_t lds, const float* ep_scale, const float* ep_shift,
+                                     int relu, float* out, int64_t ldo, void* stream);
+
 /* K7  row gather: out[i,:] = x[rows[i],:]  (feats[idx], reference train_and_eval.py:42,76,
  *     models.py:136) and scatter y[rows[i],:] = x[i,:] (models.py:145). */
 GLNN_API int glnn_gather_rows_f32(const float* x, int64_t ldx, const int64_t* rows, int64_t n_rows,
