@@ -69,6 +69,8 @@ SIGNATURES = {
     "glnn_sage_fwd_bwd_ln_f32": [c_vp, c_vp, c_vp],
     "glnn_sage_train_step_ln_f32": [c_vp, c_vp, c_vp, c_vp],
     "glnn_sage_step_ws_ln_floats": [c_i64, c_int],
+    "glnn_sage_mean_fwd_bwd_f32": [c_vp, c_vp, c_vp, c_vp],
+    "glnn_sage_mean_train_step_f32": [c_vp, c_vp, c_vp, c_vp, c_vp],
     "glnn_act_fwd_f32": [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_f32, c_u32, c_vp, c_i64, c_vp],
     "glnn_norm_drop_fwd_f32": [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_int, c_f32, c_u32, c_vp, c_i64, c_vp],
     "glnn_bn_bwd_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_f32, c_u32, c_vp, c_i64,
@@ -192,6 +194,17 @@ class SageLnDesc(ctypes.Structure):
     _fields_ = [("eps", c_f32), ("reserved", ctypes.c_int32), ("layer", SageLnLayer * SAGE_MAX_LAYERS)]
 
 
+class SageMeanLayer(ctypes.Structure):
+    """glnn_sage_mean_layer of include/glnn_hip.h (field for field)."""
+    _fields_ = [("w_self", c_vp), ("b_self", c_vp), ("gw_self", c_vp), ("gb_self", c_vp), ("cat", c_vp), ("ld_cat", c_i64),
+                ("wcat", c_vp), ("bsum", c_vp), ("dcat", c_vp), ("ld_dcat", c_i64)]
+
+
+class SageMeanDesc(ctypes.Structure):
+    """glnn_sage_mean_desc of include/glnn_hip.h (field for field)."""
+    _fields_ = [("num_layers", ctypes.c_int32), ("reserved", ctypes.c_int32), ("layer", SageMeanLayer * SAGE_MAX_LAYERS)]
+
+
 class MlpServeDesc(ctypes.Structure):
     """glnn_mlp_serve_desc of include/glnn_hip.h (field for field)."""
     _fields_ = [("num_layers", ctypes.c_int32), ("reserved", ctypes.c_int32), ("dims", ctypes.c_int32 * (MLP_MAX_LAYERS + 1)),
@@ -236,7 +249,7 @@ def lib():
         if h.glnn_abi_version() != ABI_VERSION:
             raise GlnnError(f"{LIB_PATH}: ABI version {h.glnn_abi_version()} != {ABI_VERSION} expected by this package; rebuild")
         for which, mirror in ((0, MlpStepDesc), (1, SageStepDesc), (2, SageLayer), (3, AdamDesc), (4, HubPlanDesc), (5, ChunkSignalsDesc),
-                              (6, SageLnDesc), (7, MlpServeDesc)):
+                              (6, SageLnDesc), (7, MlpServeDesc), (8, SageMeanDesc)):
             if h.glnn_struct_bytes(which) != ctypes.sizeof(mirror):
                 raise GlnnError(f"{LIB_PATH}: sizeof({mirror.__name__}) is {h.glnn_struct_bytes(which)} in the library, "
                                 f"{ctypes.sizeof(mirror)} in this binding")

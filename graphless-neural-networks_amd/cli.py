@@ -73,7 +73,14 @@ def get_teacher_args(argv=None):
     # "mean" dgl's default form with a separate fc_self (docs/SAGE_MEAN_SEMANTICS.md; trained through the differentiable ops, fp32 inference)
     p.add_argument("--sage_aggregator", type=str, default="gcn", choices=["gcn", "mean"],
                    help="Aggregator of the SAGE teacher's SAGEConv layers (mean: separate fc_self; fp32, single device)")
+    # not a reference flag: how a SAGE "mean" teacher steps (train_sage(mean_step=...)): "autograd" = the differentiable ops + torch's loss and
+    # optimiser, "native" = TeacherEngine.step_sage_mean, the whole step as one C call (csrc/sage_mean_step.hip)
+    p.add_argument("--sage_mean_step", type=str, default="autograd", choices=["autograd", "native"],
+                   help="Training step of a SAGE 'mean' teacher (native: one C call per batch; needs --sage_aggregator mean)")
     args = p.parse_args(argv)
+    if args.sage_mean_step != "autograd" and ("SAGE" not in args.teacher or args.sage_aggregator != "mean"):
+        p.error(f"--sage_mean_step {args.sage_mean_step} applies to --teacher SAGE --sage_aggregator mean only "
+                f"(got --teacher {args.teacher} --sage_aggregator {args.sage_aggregator})")
     if args.inference_dtype != "float32" and "SAGE" not in args.teacher:
         p.error(f"--inference_dtype {args.inference_dtype} is implemented for the SAGE teacher only (got --teacher {args.teacher})")
     if args.sage_aggregator != "gcn" and "SAGE" not in args.teacher:

@@ -110,6 +110,7 @@ extern "C" int64_t glnn_struct_bytes(int which) {
   if (which == 5) return (int64_t)sizeof(glnn_chunk_signals);
   if (which == 6) return (int64_t)sizeof(glnn_sage_ln_desc);
   if (which == 7) return (int64_t)sizeof(glnn_mlp_serve_desc);
+  if (which == 8) return (int64_t)sizeof(glnn_sage_mean_desc);
   return -1;
 }
 

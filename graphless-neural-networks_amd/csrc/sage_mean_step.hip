@@ -1,0 +1,481 @@
+// The sampled-block training step of the GraphSAGE "mean" teacher for gfx950 (MI355X) -- docs/SAGE_MEAN_SEMANTICS.md; the "gcn" step's
+// launch sequence (csrc/sage_step.hip) with the two aggregations that step cannot express, issued from C++ for the same reason: the step
+// is host-bound when its launches come from Python.
+//
+//   z_l = [mean_l | self_l] [W_neigh | W_self]^T + (b_neigh + b_self)        mean_l[v] = (1 / max(deg v, 1)) sum_{u->v} h_l[u],  self_l[v] = h_l[v]
+//
+//   sage_mean_cat_kernel   forward aggregation: per destination row the operand pair [mean | self] in ONE buffer of leading dimension
+//     2 round4(d_in) (second half at the float4-aligned column round4(d_in); padding columns written as zeros).  Sources: plain local rows,
+//     the global feature matrix through global ids + self_rows (outermost block), or pre-activations z of the hidden layer in front with
+//     its tail (BatchNorm affine / LayerNorm -> ReLU -> dropout, the counter-based mask keyed by the ACTIVATION's row and column) applied
+//     to every gathered row and to the self row -- xf_apply of csrc/spmm.hip, so the step is bit-identical to the materialised-h form.
+//   sage_mean_bwd_kernel   backward aggregation over the PLAIN transposed block (glnn_csr_transpose, add_self = 0):
+//     dh[u] = sum_{v: u->v} inv(v) dcat[v, :d] + (u < n_dst ? dcat[u, off : off + d] : 0),  inv(v) from the forward block's indptr.
+//     Every source row is written -- a row no edge references gets exact zeros (+ its self term).
+//   pack_pair_kernel       W_cat = [W_neigh | W_self] ([d_out, 2 round4(d_in)], zero padding) and b_neigh + b_self, re-packed every step
+//     because the parameters change every step.
+//
+// Both aggregations take the row split of csrc/sage_mean.hip: rows of more than 128 entries are summed by all eight waves of the workgroup
+// (64-entry chunks dealt round-robin, the partials folded through LDS in a fixed order), shorter rows by one wave.  No float atomics, no
+// grid barrier: bit-identical run to run.  Rows wider than 256 floats are cut into 256-column slabs (blockIdx.y).
+// The projections, weight gradients, loss, tails and Adam are the library's existing launches.
+#include <hip/hip_runtime.h>
+#include "glnn_common.h"
+
+#define GLNN_TRY(expr)              \
+  do {                              \
+    const int rc_ = (expr);         \
+    if (rc_ != GLNN_OK) return rc_; \
+  } while (0)
+
+namespace {
+
+constexpr int kWaves = 8;
+constexpr int kBlock = 64 * kWaves;
+constexpr int kTileRows = 32;
+constexpr int kLongRow = 128;      // entries above which the whole workgroup takes a row (csrc/sage_mean.hip)
+constexpr int kU = 8;              // row loads in flight per lane group
+constexpr int kMaxTailD = 256;     // widest hidden layer whose tail the gather evaluates (the limit of glnn::spmm_csr_tail)
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ int ld_idx_stream(const int32_t* p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
+  return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
+}
+// columns [d, ..) of a lane's four are padding: exact zeros whatever the row held there
+__device__ __forceinline__ float4 mask_cols(float4 y, int col4, int d) {
+  if (col4 + 0 >= d) y.x = 0.f;
+  if (col4 + 1 >= d) y.y = 0.f;
+  if (col4 + 2 >= d) y.z = 0.f;
+  if (col4 + 3 >= d) y.w = 0.f;
+  return y;
+}
+
+// The hidden tail of the layer in front, per lane: its four columns' scale / shift (BatchNorm a_scale / a_shift, or LayerNorm gamma / beta)
+struct TailCols { float s[4], h[4]; uint32_t thr, seed; float dscale; int col; bool affine; const float* mean; const float* rstd; };
+// XF == 1: drop(relu(z * s + h)) (BatchNorm affine / none);  XF == 2: drop(relu(((z - mean_r) * rstd_r) * s + h)) (LayerNorm) -- the
+// arithmetic of glnn_act_fwd_f32 / glnn_layernorm_fwd_f32 per element, roundings pinned as csrc/spmm.hip's xf_apply pins them
+template <int XF>
+__device__ __forceinline__ float4 tail_apply(const TailCols& x, float4 v, uint32_t row) {
+  if (XF == 0) return v;
+  float o[4] = {v.x, v.y, v.z, v.w};
+  float mu = 0.f, rs = 1.f;
+  if (XF == 2) { mu = x.mean[row]; rs = x.rstd[row]; }
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    float y;
+    if (XF == 2) {
+      y = (o[t] - mu) * rs;
+      asm volatile("" : "+v"(y));
+      y = fmaf(y, x.s[t], x.h[t]);
+    } else {
+      y = x.affine ? fmaf(o[t], x.s[t], x.h[t]) : o[t];
+    }
+    y = fmaxf(y, 0.f);
+    if (x.thr) y = glnn::drop_keep(x.seed, x.thr, row, (uint32_t)(x.col + t)) ? y * x.dscale : 0.f;
+    asm volatile("" : "+v"(y));        // the ROUNDED tail value is what gets summed (the materialised form stored it)
+    o[t] = y;
+  }
+  return make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// Sum of ld.row(indices[e], ld.weight(indices[e])) over this wave's share of the entries [e0, e1): the 64-entry chunks
+// e0 + 64 (wave_id + k n_waves).  A row is covered by LPR lanes; the G = 64 / LPR lane groups take different entries of a chunk (group g:
+// positions % G == g, ascending), kU loads in flight each, and are folded with cross-lane adds.  The total is in lanes < LPR.
+template <int LPR, class Ld>
+__device__ __forceinline__ float4 wave_row_sum(const int32_t* __restrict__ indices, int64_t e0, int64_t e1, int wave_id, int n_waves, int lane,
+                                               const Ld& ld) {
+  constexpr int G = 64 / LPR;
+  const int g = lane / LPR;
+  float4 acc = zero4();
+  for (int64_t base = e0 + (int64_t)wave_id * 64; base < e1; base += (int64_t)n_waves * 64) {
+    const int64_t rem = e1 - base;
+    const int cnt = rem < 64 ? (int)rem : 64;
+    const int my_idx = lane < cnt ? ld_idx_stream(indices + base + lane) : 0;
+    const float my_w = ld.weight(my_idx, lane < cnt);
+    for (int j = 0; j < cnt; j += G * kU) {
+      float4 v[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int ei = j + u * G + g;
+        const int src = __shfl(my_idx, ei & 63);
+        const float w = __shfl(my_w, ei & 63);
+        v[u] = ei < cnt ? ld.row(src, w) : zero4();
+      }
+#pragma unroll
+      for (int u = 0; u < kU; ++u) acc = add4(acc, v[u]);
+    }
+  }
+  if (G >= 2) acc = add4(acc, shfl_xor4(acc, 32));
+  if (G >= 4) acc = add4(acc, shfl_xor4(acc, 16));
+  return acc;
+}
+
+// One 32-row tile of a CSR.  finish(v, n_entries, sum) is called by ONE whole wave per row v < n_rows; `sum` is in the lanes < LPR.
+// s_next must be 0 and visible on entry.
+template <int LPR, class Ld, class Fin>
+__device__ __forceinline__ void aggregate_tile(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows,
+                                               int64_t row0, int lane, int wave, int* s_next, float4* s_part, const Ld& ld, Fin&& finish) {
+#pragma unroll 1
+  while (true) {
+    int lr = 0;
+    if (lane == 0) lr = atomicAdd(s_next, 1);
+    lr = __builtin_amdgcn_readfirstlane(lr);
+    if (lr >= kTileRows) break;
+    const int64_t v = row0 + lr;
+    if (v >= n_rows) continue;
+    const int64_t e0 = indptr[v], e1 = indptr[v + 1];
+    if (e1 - e0 > kLongRow) continue;
+    finish(v, e1 - e0, wave_row_sum<LPR>(indices, e0, e1, 0, 1, lane, ld));
+  }
+  __syncthreads();
+  // long rows of this tile: all 8 waves on one row at a time (uniform loop: every wave sees the same row lengths)
+#pragma unroll 1
+  for (int lr = 0; lr < kTileRows; ++lr) {
+    const int64_t v = row0 + lr;
+    if (v >= n_rows) break;
+    const int64_t e0 = indptr[v], e1 = indptr[v + 1];
+    if (e1 - e0 <= kLongRow) continue;
+    const float4 acc = wave_row_sum<LPR>(indices, e0, e1, wave, kWaves, lane, ld);
+    // fold the 8 wave partials through 4 LDS slots in a fixed order: waves 4-7 park, waves 0-3 add theirs, wave 0 sums the four
+    if (wave >= 4 && lane < LPR) s_part[(wave - 4) * 64 + lane] = acc;
+    __syncthreads();
+    if (wave < 4 && lane < LPR) s_part[wave * 64 + lane] = add4(acc, s_part[wave * 64 + lane]);
+    __syncthreads();
+    if (wave == 0) {
+      float4 t = zero4();
+      if (lane < LPR) t = add4(add4(s_part[lane], s_part[64 + lane]), add4(s_part[128 + lane], s_part[192 + lane]));
+      finish(v, e1 - e0, t);
+    }
+    __syncthreads();
+  }
+}
+
+struct CatArgs {
+  const int64_t* indptr; const int32_t* indices; int64_t n_dst;
+  const float* x; int64_t ldx; int d;                       // the gathered rows (plain rows, or pre-activations z with `tail`)
+  const int64_t* self_rows;                                 // outermost block with global ids: the self row of v is x[self_rows[v]]
+  const float* t_scale; const float* t_shift; const float* t_mean; const float* t_rstd; uint32_t t_thr, t_seed; float t_dscale;
+  float* cat; int64_t ld_cat;                               // [n_dst, 2 round4(d)]
+};
+
+template <int XF>
+struct CatLoad {
+  const float* x; int64_t ldx; int col4; bool col_ok; TailCols tc;
+  __device__ __forceinline__ float weight(int, bool) const { return 0.f; }
+  __device__ __forceinline__ float4 row(int src, float) const {
+    return col_ok ? tail_apply<XF>(tc, ld4(x + (int64_t)src * ldx + col4), (uint32_t)src) : zero4();
+  }
+};
+
+template <int LPR, int XF>
+__global__ __launch_bounds__(kBlock) void sage_mean_cat_kernel(const CatArgs a) {
+  __shared__ float4 s_part[4 * 64];
+  __shared__ int s_next;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col4 = ((int)blockIdx.y * LPR + lane % LPR) * 4;
+  const int dpad = (a.d + 3) & ~3;
+  const bool col_ok = col4 < dpad;
+  CatLoad<XF> ld;
+  ld.x = a.x; ld.ldx = a.ldx; ld.col4 = col4; ld.col_ok = col_ok;
+  TailCols& tc = ld.tc;
+  tc.thr = a.t_thr; tc.seed = a.t_seed; tc.dscale = a.t_dscale; tc.col = col4; tc.affine = a.t_scale != nullptr;
+  tc.mean = a.t_mean; tc.rstd = a.t_rstd;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const bool ok = XF != 0 && tc.affine && col4 + t < a.d;
+    tc.s[t] = ok ? a.t_scale[col4 + t] : (XF == 2 ? 0.f : 1.f);
+    tc.h[t] = ok ? a.t_shift[col4 + t] : 0.f;
+  }
+  if (threadIdx.x == 0) s_next = 0;
+  __syncthreads();
+  aggregate_tile<LPR>(a.indptr, a.indices, a.n_dst, (int64_t)blockIdx.x * kTileRows, lane, wave, &s_next, s_part, ld,
+                      [&](int64_t v, int64_t deg, float4 sum) {
+                        if (lane >= LPR || !col_ok) return;
+                        const float inv = 1.0f / (float)(deg > 1 ? deg : 1);      // one IEEE division per row
+                        const float4 m = mask_cols(make_float4(sum.x * inv, sum.y * inv, sum.z * inv, sum.w * inv), col4, a.d);
+                        const int64_t sr = a.self_rows ? a.self_rows[v] : v;
+                        const float4 s = mask_cols(tail_apply<XF>(tc, ld4(a.x + sr * a.ldx + col4), (uint32_t)v), col4, a.d);
+                        st4(a.cat + v * a.ld_cat + col4, m);
+                        st4(a.cat + v * a.ld_cat + dpad + col4, s);
+                      });
+}
+
+struct BwdArgs {
+  const int64_t* t_indptr; const int32_t* t_indices; int64_t n_src;      // the plain transposed block: a row per SOURCE, entries = destinations
+  const int64_t* indptr; int64_t n_dst;                                  // the forward block: inv(v) = 1 / max(indptr[v + 1] - indptr[v], 1)
+  const float* dcat; int64_t ld_dcat; int d;                             // [n_dst, 2 round4(d)]: dmean | dself
+  float* dh; int64_t ld_dh;                                              // [n_src, >= round4(d)]
+};
+
+struct BwdLoad {
+  const float* dcat; int64_t ld; const int64_t* indptr; int col4; bool col_ok;
+  __device__ __forceinline__ float weight(int v, bool ok) const {
+    if (!ok) return 0.f;
+    const int64_t deg = indptr[v + 1] - indptr[v];
+    return 1.0f / (float)(deg > 1 ? deg : 1);
+  }
+  __device__ __forceinline__ float4 row(int v, float w) const {
+    if (!col_ok) return zero4();
+    const float4 t = ld4(dcat + (int64_t)v * ld + col4);
+    return make_float4(t.x * w, t.y * w, t.z * w, t.w * w);
+  }
+};
+
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void sage_mean_bwd_kernel(const BwdArgs a) {
+  __shared__ float4 s_part[4 * 64];
+  __shared__ int s_next;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col4 = ((int)blockIdx.y * LPR + lane % LPR) * 4;
+  const int dpad = (a.d + 3) & ~3;
+  const bool col_ok = col4 < dpad;
+  BwdLoad ld;
+  ld.dcat = a.dcat; ld.ld = a.ld_dcat; ld.indptr = a.indptr; ld.col4 = col4; ld.col_ok = col_ok;
+  if (threadIdx.x == 0) s_next = 0;
+  __syncthreads();
+  aggregate_tile<LPR>(a.t_indptr, a.t_indices, a.n_src, (int64_t)blockIdx.x * kTileRows, lane, wave, &s_next, s_part, ld,
+                      [&](int64_t u, int64_t, float4 sum) {
+                        if (lane >= LPR || !col_ok) return;
+                        if (u < a.n_dst) sum = add4(sum, ld4(a.dcat + u * a.ld_dcat + dpad + col4));
+                        st4(a.dh + u * a.ld_dh + col4, mask_cols(sum, col4, a.d));
+                      });
+}
+
+struct PackLayer { const float* wn; const float* ws; const float* bn; const float* bs; float* wcat; float* bsum; int d_in, d_out; };
+struct PackArgs { PackLayer layer[GLNN_SAGE_MAX_LAYERS]; };
+
+__global__ __launch_bounds__(256) void pack_pair_kernel(const PackArgs a) {
+  const PackLayer& y = a.layer[blockIdx.y];
+  const int dpad = (y.d_in + 3) & ~3;
+  const int64_t total = (int64_t)y.d_out * 2 * dpad;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int o = (int)(i / (2 * dpad));
+    const int c = (int)(i - (int64_t)o * 2 * dpad);
+    const int cc = c < dpad ? c : c - dpad;
+    const float* w = c < dpad ? y.wn : y.ws;
+    y.wcat[i] = cc < y.d_in ? w[(int64_t)o * y.d_in + cc] : 0.f;
+    if (c == 0) y.bsum[o] = y.bn[o] + y.bs[o];
+  }
+}
+
+template <int XF>
+int launch_cat(const CatArgs& a, hipStream_t st) {
+  const int dv = ((a.d + 3) & ~3) / 4;
+  const unsigned tiles = (unsigned)((a.n_dst + kTileRows - 1) / kTileRows);
+  if (dv <= 16) hipLaunchKernelGGL((sage_mean_cat_kernel<16, XF>), dim3(tiles, 1), dim3(kBlock), 0, st, a);
+  else if (dv <= 32) hipLaunchKernelGGL((sage_mean_cat_kernel<32, XF>), dim3(tiles, 1), dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL((sage_mean_cat_kernel<64, XF>), dim3(tiles, (unsigned)((dv + 63) / 64)), dim3(kBlock), 0, st, a);
+  return glnn::check_launch("glnn_sage_mean_fwd_bwd_f32: forward aggregation");
+}
+
+int launch_bwd(const BwdArgs& a, hipStream_t st) {
+  const int dv = ((a.d + 3) & ~3) / 4;
+  const unsigned tiles = (unsigned)((a.n_src + kTileRows - 1) / kTileRows);
+  if (dv <= 16) hipLaunchKernelGGL((sage_mean_bwd_kernel<16>), dim3(tiles, 1), dim3(kBlock), 0, st, a);
+  else if (dv <= 32) hipLaunchKernelGGL((sage_mean_bwd_kernel<32>), dim3(tiles, 1), dim3(kBlock), 0, st, a);
+  else hipLaunchKernelGGL((sage_mean_bwd_kernel<64>), dim3(tiles, (unsigned)((dv + 63) / 64)), dim3(kBlock), 0, st, a);
+  return glnn::check_launch("glnn_sage_mean_fwd_bwd_f32: backward aggregation");
+}
+
+inline int r4(int c) { return (c + 3) & ~3; }
+
+// every argument check of the step, before any launch
+int check_desc(const glnn_sage_step_desc* d, const glnn_sage_mean_desc* m, const glnn_sage_ln_desc* ln) {
+  GLNN_REQUIRE(d && m, "glnn_sage_mean_fwd_bwd_f32: null descriptor");
+  GLNN_REQUIRE(d->x && d->labels && d->dlogits && d->loss_out, "glnn_sage_mean_fwd_bwd_f32: null pointer");
+  const int L = d->num_layers;
+  GLNN_REQUIRE(L >= 1 && L <= GLNN_SAGE_MAX_LAYERS, "glnn_sage_mean_fwd_bwd_f32: num_layers=%d outside [1,%d]", L, GLNN_SAGE_MAX_LAYERS);
+  GLNN_REQUIRE(m->num_layers == L, "glnn_sage_mean_fwd_bwd_f32: the mean descriptor has %d layers, the step descriptor %d", m->num_layers, L);
+  for (int l = 0; l <= L; ++l) GLNN_REQUIRE(d->dims[l] >= 1, "glnn_sage_mean_fwd_bwd_f32: dims[%d] must be positive", l);
+  GLNN_REQUIRE(d->dropout_p >= 0.f && d->dropout_p < 1.f, "glnn_sage_mean_fwd_bwd_f32: dropout_p outside [0, 1)");
+  if (ln) {
+    GLNN_REQUIRE(!d->batchnorm && ln->eps > 0.f, "glnn_sage_mean_fwd_bwd_f32: LayerNorm tails need batchnorm == 0 and eps > 0");
+    for (int l = 0; l < L - 1; ++l) {
+      const glnn_sage_ln_layer& q = ln->layer[l];
+      GLNN_REQUIRE(q.gamma && q.beta && q.ggamma && q.gbeta && q.mean && q.rstd, "glnn_sage_mean_fwd_bwd_f32: LayerNorm of hidden layer %d: null pointer", l);
+    }
+  }
+  GLNN_REQUIRE(d->ldx % 4 == 0 && d->ldx >= r4(d->dims[0]) && glnn::aligned16(d->x),
+               "glnn_sage_mean_fwd_bwd_f32: x needs float4 rows (ldx a multiple of 4, >= %d; 16-byte aligned)", r4(d->dims[0]));
+  GLNN_REQUIRE(d->ld_dlogits >= d->dims[L], "glnn_sage_mean_fwd_bwd_f32: ld_dlogits < dims[%d]", L);
+  int max_hidden = 0;
+  for (int l = 0; l < L; ++l) {
+    const glnn_sage_layer& y = d->layer[l];
+    const glnn_sage_mean_layer& q = m->layer[l];
+    const int d_in = d->dims[l], d_out = d->dims[l + 1];
+    GLNN_REQUIRE(y.indptr && y.w && y.b && y.gw && y.gb && y.z && q.w_self && q.b_self && q.gw_self && q.gb_self && q.cat && q.wcat && q.bsum,
+                 "glnn_sage_mean_fwd_bwd_f32: layer %d: null pointer", l);
+    GLNN_REQUIRE(y.indices || y.nnz == 0, "glnn_sage_mean_fwd_bwd_f32: layer %d: null indices with %lld edges", l, (long long)y.nnz);
+    GLNN_REQUIRE(y.n_dst >= 1 && y.nnz >= 0, "glnn_sage_mean_fwd_bwd_f32: layer %d: bad block sizes", l);
+    GLNN_REQUIRE(y.n_src >= y.n_dst, "glnn_sage_mean_fwd_bwd_f32: layer %d: n_src=%lld < n_dst=%lld (destinations come first among the sources)",
+                 l, (long long)y.n_src, (long long)y.n_dst);
+    GLNN_REQUIRE(y.n_src < ((int64_t)1 << 31), "glnn_sage_mean_fwd_bwd_f32: layer %d: n_src too large", l);
+    GLNN_REQUIRE(l == 0 || y.n_src == d->layer[l - 1].n_dst, "glnn_sage_mean_fwd_bwd_f32: block %d has %lld sources, block %d %lld destinations",
+                 l, (long long)y.n_src, l - 1, (long long)d->layer[l - 1].n_dst);
+    GLNN_REQUIRE(q.ld_cat == 2ll * r4(d_in), "glnn_sage_mean_fwd_bwd_f32: layer %d: ld_cat=%lld must be 2 * round4(d_in) = %d", l,
+                 (long long)q.ld_cat, 2 * r4(d_in));
+    GLNN_REQUIRE(y.ldz % 4 == 0 && y.ldz >= r4(d_out), "glnn_sage_mean_fwd_bwd_f32: layer %d: ldz=%lld must be a multiple of 4 and >= %d", l,
+                 (long long)y.ldz, r4(d_out));
+    GLNN_REQUIRE(glnn::aligned16(q.cat) && glnn::aligned16(q.wcat) && glnn::aligned16(y.z), "glnn_sage_mean_fwd_bwd_f32: layer %d: 16-byte alignment required", l);
+    if (l < L - 1) {
+      max_hidden = d_out > max_hidden ? d_out : max_hidden;
+      if (y.h) GLNN_REQUIRE(y.ldh % 4 == 0 && y.ldh >= r4(d_out) && glnn::aligned16(y.h),
+                            "glnn_sage_mean_fwd_bwd_f32: layer %d: ldh=%lld must be a multiple of 4 and >= %d", l, (long long)y.ldh, r4(d_out));
+      if (d->batchnorm)
+        GLNN_REQUIRE(y.gamma && y.beta && y.ggamma && y.gbeta && y.running_mean && y.running_var && y.mean && y.rstd && y.a_scale && y.a_shift,
+                     "glnn_sage_mean_fwd_bwd_f32: BatchNorm of hidden layer %d: null pointer", l);
+      if (!y.h && d_out > kMaxTailD)
+        return glnn::fail(GLNN_ERR_UNSUPPORTED, "glnn_sage_mean_fwd_bwd_f32: hidden layer %d is %d wide: the tail-in-gather form takes at most %d "
+                          "columns, give the layer an h buffer", l, d_out, kMaxTailD);
+    }
+    if (l >= 1) {
+      GLNN_REQUIRE(y.t_indptr && (y.t_indices || y.nnz == 0) && q.dcat, "glnn_sage_mean_fwd_bwd_f32: layer %d needs the transpose buffers and dcat", l);
+      GLNN_REQUIRE(q.ld_dcat == q.ld_cat && glnn::aligned16(q.dcat), "glnn_sage_mean_fwd_bwd_f32: layer %d: ld_dcat=%lld must equal ld_cat=%lld", l,
+                   (long long)q.ld_dcat, (long long)q.ld_cat);
+    }
+  }
+  if (L > 1)
+    GLNN_REQUIRE(d->dh && d->ld_dh % 4 == 0 && d->ld_dh >= r4(max_hidden) && glnn::aligned16(d->dh),
+                 "glnn_sage_mean_fwd_bwd_f32: backward scratch dh missing, or ld_dh=%lld not a multiple of 4 >= %d", (long long)d->ld_dh, r4(max_hidden));
+  return GLNN_OK;
+}
+
+int sage_mean_fwd_bwd_impl(const glnn_sage_step_desc* d, const glnn_sage_mean_desc* m, const glnn_sage_ln_desc* ln, void* stream) {
+  GLNN_TRY(check_desc(d, m, ln));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int L = d->num_layers;
+  const float p = d->dropout_p;
+  // ---- W_cat = [W_neigh | W_self] and b_neigh + b_self of every layer, ONE launch ----------------------------------------------------------
+  {
+    PackArgs pa = {};
+    int64_t most = 1;
+    for (int l = 0; l < L; ++l) {
+      const glnn_sage_mean_layer& q = m->layer[l];
+      pa.layer[l] = {d->layer[l].w, q.w_self, d->layer[l].b, q.b_self, q.wcat, q.bsum, d->dims[l], d->dims[l + 1]};
+      const int64_t tot = (int64_t)d->dims[l + 1] * q.ld_cat;
+      most = tot > most ? tot : most;
+    }
+    int64_t blocks = (most + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(pack_pair_kernel, dim3((unsigned)blocks, (unsigned)L), dim3(256), 0, st, pa);
+    GLNN_TRY(glnn::check_launch("glnn_sage_mean_fwd_bwd_f32: weight pair packing"));
+  }
+  // ---- forward ---------------------------------------------------------------------------------------------------------------------------
+  for (int l = 0; l < L; ++l) {
+    const glnn_sage_layer& y = d->layer[l];
+    const glnn_sage_mean_layer& q = m->layer[l];
+    const int d_in = d->dims[l], d_out = d->dims[l + 1];
+    CatArgs a = {};
+    a.indptr = y.indptr; a.indices = y.indices; a.n_dst = y.n_dst; a.d = d_in; a.cat = q.cat; a.ld_cat = q.ld_cat;
+    if (l == 0) {
+      a.x = d->x; a.ldx = d->ldx; a.self_rows = y.self_rows;
+      GLNN_TRY(launch_cat<0>(a, st));
+    } else if (d->layer[l - 1].h) {
+      a.x = d->layer[l - 1].h; a.ldx = d->layer[l - 1].ldh;
+      GLNN_TRY(launch_cat<0>(a, st));
+    } else {
+      // the hidden layer in front left only z: its tail is evaluated on every gathered row and on the self row
+      const glnn_sage_layer& pv = d->layer[l - 1];
+      a.x = pv.z; a.ldx = pv.ldz;
+      a.t_thr = glnn::drop_threshold(p); a.t_seed = pv.drop_seed; a.t_dscale = 1.0f / (1.0f - p);
+      if (ln) {
+        const glnn_sage_ln_layer& g = ln->layer[l - 1];
+        a.t_scale = g.gamma; a.t_shift = g.beta; a.t_mean = g.mean; a.t_rstd = g.rstd;
+        GLNN_TRY(launch_cat<2>(a, st));
+      } else {
+        a.t_scale = d->batchnorm ? pv.a_scale : nullptr; a.t_shift = d->batchnorm ? pv.a_shift : nullptr;
+        GLNN_TRY(launch_cat<1>(a, st));
+      }
+    }
+    // z = [mean | self] W_cat^T + (b_neigh + b_self): ONE product over K = 2 round4(d_in) (padding columns are zeros on both sides)
+    const int k = (int)q.ld_cat;
+    glnn::ColStats cs = {d->ws_bn, d->ws_bn_floats, 0, 0, 0, nullptr, nullptr, nullptr};
+    if (l < L - 1 && d->batchnorm && glnn::opts().gemm_stats)
+      GLNN_TRY(glnn::gemm_stats(q.cat, q.ld_cat, y.n_dst, k, q.wcat, q.ld_cat, d_out, q.bsum, y.z, y.ldz, d->ws_gemm, d->ws_gemm_floats, stream, &cs));
+    else
+      GLNN_TRY(glnn_gemm_f32(q.cat, q.ld_cat, nullptr, nullptr, nullptr, 0.f, 0u, y.n_dst, k, q.wcat, q.ld_cat, 0, d_out, nullptr, nullptr, q.bsum, 0,
+                             y.z, y.ldz, d->ws_gemm, d->ws_gemm_floats, stream));
+    if (l == L - 1) break;
+    if (ln) {
+      const glnn_sage_ln_layer& g = ln->layer[l];
+      GLNN_TRY(glnn_layernorm_fwd_f32(y.z, y.ldz, y.n_dst, d_out, g.gamma, g.beta, ln->eps, 1, p, y.drop_seed, y.h, y.ldh, g.mean, g.rstd, stream));
+      continue;
+    }
+    if (d->batchnorm)
+      GLNN_TRY(glnn::bn_stats(y.z, y.ldz, y.n_dst, d_out, y.gamma, y.beta, d->bn_eps, d->bn_momentum, y.running_mean, y.running_var, y.nbt,
+                              y.mean, y.rstd, y.a_scale, y.a_shift, d->ws_bn, d->ws_bn_floats, stream, nullptr, nullptr, nullptr, 0, nullptr,
+                              cs.done ? &cs : nullptr));
+    if (y.h)
+      GLNN_TRY(glnn_act_fwd_f32(y.z, y.ldz, y.n_dst, d_out, d->batchnorm ? y.a_scale : nullptr, d->batchnorm ? y.a_shift : nullptr, p,
+                                y.drop_seed, y.h, y.ldh, stream));
+  }
+  // ---- loss + dlogits (labels indexed by the batch's output nodes) -------------------------------------------------------------------------
+  const glnn_sage_layer& top = d->layer[L - 1];
+  GLNN_TRY(glnn::softmax_loss(top.z, top.ldz, top.n_dst, d->dims[L], GLNN_LOSS_NLL, d->labels, d->label_rows, nullptr, 0, nullptr, d->lamb,
+                              d->dlogits, d->ld_dlogits, nullptr, 0, d->loss_out, d->loss_accum, d->ws_loss, d->ws_loss_floats, stream, nullptr, nullptr));
+  // ---- backward --------------------------------------------------------------------------------------------------------------------------
+  const float* dz = d->dlogits;
+  int64_t ld_dz = d->ld_dlogits;
+  for (int l = L - 1; l >= 0; --l) {
+    const glnn_sage_layer& y = d->layer[l];
+    const glnn_sage_mean_layer& q = m->layer[l];
+    const int d_in = d->dims[l], d_out = d->dims[l + 1];
+    const int64_t half = q.ld_cat / 2;
+    // dW_neigh = dz^T mean, dW_self = dz^T self: the two halves of the operand buffer, straight into the two gradient tensors
+    // (the last layer's two bias gradients are both colsum(dz); hidden layers get theirs from the tail backward below)
+    GLNN_TRY(glnn_gemm_tn_f32(dz, ld_dz, y.n_dst, d_out, q.cat, q.ld_cat, nullptr, nullptr, nullptr, 0.f, 0u, d_in, y.gw, d_in,
+                              l == L - 1 ? y.gb : nullptr, d->ws_tn, d->ws_tn_floats, stream));
+    GLNN_TRY(glnn_gemm_tn_f32(dz, ld_dz, y.n_dst, d_out, q.cat + half, q.ld_cat, nullptr, nullptr, nullptr, 0.f, 0u, d_in, q.gw_self, d_in,
+                              l == L - 1 ? q.gb_self : nullptr, d->ws_tn, d->ws_tn_floats, stream));
+    if (l == 0) break;                                     // the outermost block's input is feats: no gradient needed
+    // dcat = dz [W_neigh | W_self] = [dmean | dself]
+    GLNN_TRY(glnn_gemm_f32(dz, ld_dz, nullptr, nullptr, nullptr, 0.f, 0u, y.n_dst, d_out, q.wcat, q.ld_cat, 1, (int)q.ld_cat, nullptr, nullptr, nullptr,
+                           0, q.dcat, q.ld_dcat, nullptr, 0, stream));
+    if (y.tr_ws)                                           // not prebuilt by the caller: the PLAIN transpose (no identity term in "mean")
+      GLNN_TRY(glnn_csr_transpose(y.indptr, y.indices, y.n_dst, y.n_src, y.nnz, 0, y.t_indptr, y.t_indices, y.tr_ws, y.tr_ws_bytes, stream));
+    BwdArgs b = {y.t_indptr, y.t_indices, y.n_src, y.indptr, y.n_dst, q.dcat, q.ld_dcat, d_in, d->dh, d->ld_dh};
+    GLNN_TRY(launch_bwd(b, st));
+    // the tail of the layer in front produced h_l: dz_{l-1} in place on dh (+ the norm's gradients and db_{l-1})
+    const glnn_sage_layer& prev = d->layer[l - 1];
+    if (ln) {
+      const glnn_sage_ln_layer& g = ln->layer[l - 1];
+      GLNN_TRY(glnn_layernorm_bwd_f32(d->dh, d->ld_dh, prev.z, prev.ldz, prev.n_dst, d_in, g.gamma, g.beta, g.mean, g.rstd, 1, p, prev.drop_seed,
+                                      d->dh, d->ld_dh, g.ggamma, g.gbeta, prev.gb, d->ws_bn, d->ws_bn_floats, stream));
+    } else {
+      GLNN_TRY(glnn::bn_relu_bwd(d->dh, d->ld_dh, prev.z, prev.ldz, prev.n_dst, d_in, d->batchnorm ? prev.gamma : nullptr, prev.mean, prev.rstd,
+                                 d->batchnorm ? prev.a_scale : nullptr, d->batchnorm ? prev.a_shift : nullptr, p, prev.drop_seed, d->dh,
+                                 d->ld_dh, prev.ggamma, prev.gbeta, prev.gb, d->ws_bn, d->ws_bn_floats, stream, nullptr));
+    }
+    // db_self = db_neigh = colsum(dz_{l-1})
+    if (hipMemcpyAsync(m->layer[l - 1].gb_self, prev.gb, sizeof(float) * (size_t)d_in, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      (void)hipGetLastError();
+      return glnn::fail(GLNN_ERR_HIP, "glnn_sage_mean_fwd_bwd_f32: copying the bias gradient of layer %d failed", l - 1);
+    }
+    dz = d->dh;
+    ld_dz = d->ld_dh;
+  }
+  return GLNN_OK;
+}
+
+}  // namespace
+
+extern "C" int glnn_sage_mean_fwd_bwd_f32(const glnn_sage_step_desc* d, const glnn_sage_mean_desc* m, const glnn_sage_ln_desc* ln, void* stream) {
+  return sage_mean_fwd_bwd_impl(d, m, ln, stream);
+}
+
+// The whole optimisation step in ONE call: the entry above followed by the fused Adam launch on the same stream.  The gradient partials are
+// folded by launches of their own (nothing is left pending for Adam), so the two-call form gives the same bits trivially.
+extern "C" int glnn_sage_mean_train_step_f32(const glnn_sage_step_desc* d, const glnn_sage_mean_desc* m, const glnn_sage_ln_desc* ln,
+                                             const glnn_adam_desc* adam, void* stream) {
+  GLNN_REQUIRE(adam && adam->params && adam->grads && adam->exp_avg && adam->exp_avg_sq && adam->sizes && adam->grads_host,
+               "glnn_sage_mean_train_step_f32: the Adam descriptor is incomplete");
+  GLNN_TRY(sage_mean_fwd_bwd_impl(d, m, ln, stream));
+  return glnn::adam_step(adam->params, adam->grads, adam->exp_avg, adam->exp_avg_sq, adam->sizes, adam->num_tensors, adam->max_size, adam->lr,
+                         adam->beta1, adam->beta2, adam->eps, adam->weight_decay, adam->step, adam->grads_host, nullptr, stream);
+}

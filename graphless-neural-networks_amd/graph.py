@@ -22,6 +22,7 @@ class CSRGraph:
         self.gindices = None       # outermost training block only: the edges' GLOBAL source ids (see NodeDataLoader)
         self.dst_nodes = None
         self.t_indptr = self.t_indices = self.inv_deg = None      # inner training blocks of an engine-mode loader: the transposed block (+ self) and 1/(deg+1)
+        self.t_add_self = None     # how t_indptr / t_indices were built: True = with a self entry per destination (SAGE "gcn"), False = plain ("mean")
 
     # ---- construction -------------------------------------------------------------------------
     @classmethod
@@ -266,6 +267,9 @@ class NodeDataLoader:
         # edges' global source ids; no frontier table, no local relabelling, `input_nodes` is yielded as None -- because TeacherEngine
         # gathers layer 0 straight from the feature matrix.  That block is the widest of a batch: 60 % of the sampler's device time.
         self.global_first_block = False
+        # True (set by train_sage(mean_step="native") together with global_first_block): the engine-mode transposes of the inner blocks are
+        # the PLAIN ones (no self entry, no 1 / (deg + 1)) -- what TeacherEngine.step_sage_mean's backward reads.  Default: as before.
+        self.plain_transpose = False
         # the whole-graph path of SAGE.inference is only valid when the loader sweeps EVERY node in id order
         if isinstance(sampler, MultiLayerFullNeighborSampler) and sampler.n_layers == 1 and not shuffle \
                 and self.nids.numel() == g.num_dst_nodes() and bool((self.nids.cpu() == torch.arange(g.num_dst_nodes())).all()):
@@ -296,12 +300,13 @@ class NodeDataLoader:
             block.gindices, block.dst_nodes = gidx, seeds       # the same edges with global source ids (TeacherEngine, layer 0)
         return input_nodes, block
 
-    def _batch(self, b, idx, fanouts, epoch=None, global_first=None):
+    def _batch(self, b, idx, fanouts, epoch=None, global_first=None, plain_transpose=None):
         """global_first: the value of `global_first_block` the ITERATOR was created under (snapshotted by __iter__, like `epoch`): a worker
         thread that is still building batches when the consumer flips the flag back keeps building the shape its consumer expects."""
         dev = self.g.device
         epoch = self._epoch if epoch is None else epoch
         gfb = self.global_first_block if global_first is None else global_first
+        plain = self.plain_transpose if plain_transpose is None else plain_transpose
         output_nodes = self.nids[idx].to(dev) if self.nids.device != dev else self.nids[idx.to(dev)]
         seeds, blocks = output_nodes, []
         for l in reversed(range(len(fanouts))):          # last layer's block is sampled first
@@ -312,8 +317,10 @@ class NodeDataLoader:
                 # entry per destination, 1 / (in-degree + 1) -- depends on the block alone, so it is built HERE, beside the previous step,
                 # instead of by ten launches on the step's own stream (the same two library calls: the same bits)
                 from . import ops
-                blk.t_indptr, blk.t_indices = ops.csr_transpose(blk.indptr, blk.indices, blk.n_dst, blk.n_src, blk.num_edges(), add_self=True)
-                blk.inv_deg, _ = ops.degrees(blk.indptr, None, blk.n_dst, blk.n_src, 0, want_out=False, transform=ops.DEG_INV_PLUS1)
+                blk.t_indptr, blk.t_indices = ops.csr_transpose(blk.indptr, blk.indices, blk.n_dst, blk.n_src, blk.num_edges(), add_self=not plain)
+                blk.t_add_self = not plain
+                if not plain:      # (the "mean" step takes 1 / max(deg, 1) from the forward block's indptr)
+                    blk.inv_deg, _ = ops.degrees(blk.indptr, None, blk.n_dst, blk.n_src, 0, want_out=False, transform=ops.DEG_INV_PLUS1)
             blocks.insert(0, blk)
         return seeds, output_nodes, blocks
 
@@ -325,6 +332,7 @@ class NodeDataLoader:
         for the reference, here as stream-level concurrency on the GPU)."""
         self._epoch += 1
         gfb = bool(self.global_first_block)      # snapshot: this iterator's batches keep the shape its consumer asked for (see _batch)
+        plain = bool(self.plain_transpose)
         n = self.nids.numel()
         from . import ops
         order = ops.randperm_cpu(n) if self.shuffle else torch.arange(n)
@@ -334,7 +342,7 @@ class NodeDataLoader:
             chunks.pop()
         if not self.g.indptr.is_cuda or not self.prefetch:
             for b, idx in enumerate(chunks):
-                yield self._batch(b, idx, fanouts, global_first=gfb)
+                yield self._batch(b, idx, fanouts, global_first=gfb, plain_transpose=plain)
             return
         main = torch.cuda.current_stream(self.g.device)
         if self._side is None:
@@ -354,7 +362,7 @@ class NodeDataLoader:
 
         def build(b):
             with torch.cuda.stream(side):
-                batch = self._batch(b, chunks[b], fanouts, epoch, gfb)
+                batch = self._batch(b, chunks[b], fanouts, epoch, gfb, plain)
                 ev = torch.cuda.Event()
                 ev.record(side)
             return batch, ev

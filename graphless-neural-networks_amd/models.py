@@ -392,7 +392,9 @@ class SAGE(nn.Module):
             raise NotImplementedError("SAGE.inference(dtype=torch.bfloat16): bf16 activation storage is implemented for the 'gcn' aggregator "
                                       "only, not for aggregator_type 'mean'")
         g = getattr(dataloader, "graph", None)
-        if g is None or not hasattr(dataloader, "global_blocks"):
+        # whole graph: any loader that sweeps every node of a resident graph in id order (FullNeighborLoader, or the NodeDataLoader the
+        # teacher CLI evaluates with: it carries `.graph` exactly then); the chunked sweep also needs the loader's global-id blocks
+        if g is None or not (whole_graph or hasattr(dataloader, "global_blocks")):
             raise NotImplementedError("SAGE.inference(aggregator_type 'mean'): a glnn_amd.graph.FullNeighborLoader over the resident graph")
         ln = self.norm_type == "layer"
         with torch.no_grad():

@@ -84,6 +84,39 @@ def check_supported(model, criterion, optimizer):
                            "selects the CPU: pass --device 0)")
 
 
+def check_supported_mean(model, criterion, optimizer):
+    """Raise unless (model, criterion, optimizer) is a SAGE "mean" teacher that TeacherEngine.step_sage_mean trains: norm_type
+    none | batch | layer, ReLU, nn.NLLLoss(), plain single-group Adam, on the GPU.  (check_supported stays the gate of the "gcn" step and
+    keeps refusing a "mean" model.)"""
+    enc = model.encoder
+    name = model.model_name
+    if "SAGE" not in name:
+        raise NotImplementedError(f"TeacherEngine.step_sage_mean: SAGE teachers only (got {name})")
+    if getattr(enc, "aggregator_type", "gcn") != "mean":
+        raise NotImplementedError(f"TeacherEngine.step_sage_mean: the 'mean' aggregator only (got {getattr(enc, 'aggregator_type', 'gcn')!r}; "
+                                  "a 'gcn' teacher trains through step_sage)")
+    if enc.norm_type not in ("none", "batch", "layer"):
+        raise NotImplementedError(f"TeacherEngine.step_sage_mean: norm_type none|batch|layer (got {enc.norm_type!r})")
+    if not _is_relu(enc.activation):
+        raise NotImplementedError("TeacherEngine.step_sage_mean: the hidden activation must be ReLU")
+    if any(lay.fc_self.bias is None or lay.fc_neigh.bias is None for lay in enc.layers):
+        raise NotImplementedError("TeacherEngine.step_sage_mean: SAGEConv(bias=True) layers only")
+    if not (isinstance(criterion, nn.NLLLoss) and criterion.reduction == "mean" and criterion.weight is None
+            and criterion.ignore_index == -100):
+        raise NotImplementedError("TeacherEngine.step_sage_mean: the criterion must be nn.NLLLoss()")
+    grp = optimizer.param_groups
+    if type(optimizer) is not torch.optim.Adam or len(grp) != 1 or grp[0].get("amsgrad") or grp[0].get("maximize"):
+        raise NotImplementedError("TeacherEngine.step_sage_mean: torch.optim.Adam, one param group, no amsgrad/maximize")
+    for bn in getattr(enc, "norms", ()):
+        if isinstance(bn, nn.LayerNorm):
+            if not bn.elementwise_affine or len(bn.normalized_shape) != 1:
+                raise NotImplementedError("TeacherEngine.step_sage_mean: nn.LayerNorm(hidden_dim) with the reference's defaults")
+        elif bn.momentum is None or not bn.affine or not bn.track_running_stats:
+            raise NotImplementedError("TeacherEngine.step_sage_mean: BatchNorm1d with the reference's defaults")
+    if next(model.parameters()).device.type != "cuda":
+        raise RuntimeError("TeacherEngine.step_sage_mean needs the model on the GPU (HIP path only; pass --device 0)")
+
+
 class _Arena:
     """Bump allocator over one device buffer (base None: sizing pass); 256-byte granules keep every sub-buffer float4-aligned."""
 
@@ -134,6 +167,8 @@ class TeacherEngine:
         self.loss_accum = torch.zeros(1, **f32)
         self._sage_desc = self._arena = self._arena_stream = None      # step_sage: persistent descriptor and scratch arena
         self._sage_ln = None                                           # step_sage, norm_type "layer": the LayerNorm side descriptor
+        self._sage_mean = None                                         # step_sage_mean: the fc_self / operand-buffer side descriptor
+        self.mean = self.kind == "sage" and getattr(self.enc, "aggregator_type", "gcn") == "mean"
         self.ws_loss = torch.empty(1024, **f32)
         # step_sage: the hidden layers' h = dropout(relu(norm(z))) is NOT written -- the next layer's aggregation applies that tail to the z
         # rows it gathers (glnn::spmm_csr_tail; same arithmetic per element, so the step is bit-identical to the materialised form, one pass
@@ -194,6 +229,9 @@ class TeacherEngine:
         for l, layer in enumerate(enc.layers):
             w, b = layer.fc_neigh.weight, layer.fc_neigh.bias
             sig += [ptr(w), ptr(b), ptr(self.grad(w)), ptr(self.grad(b))]
+            if self.mean:
+                w, b = layer.fc_self.weight, layer.fc_self.bias
+                sig += [ptr(w), ptr(b), ptr(self.grad(w)), ptr(self.grad(b))]
             if l != len(enc.layers) - 1 and self.bn:
                 bn = enc.norms[l]
                 sig += [ptr(bn.weight), ptr(bn.bias), ptr(self.grad(bn.weight)), ptr(self.grad(bn.bias)), ptr(bn.running_mean), ptr(bn.running_var),
@@ -209,6 +247,9 @@ class TeacherEngine:
         otherwise feats[input_nodes] is gathered once (blocks that came from elsewhere).  The whole forward + loss + backward
         is ONE C call (glnn_sage_fwd_bwd_f32, csrc/sage_step.hip) over buffers allocated here; Adam follows."""
         enc, L = self.enc, self.L
+        if self.mean:      # (this step has no fc_self term: it would silently train another model)
+            raise NotImplementedError("TeacherEngine.step_sage implements the 'gcn' aggregator; a SAGE 'mean' teacher steps through "
+                                      "TeacherEngine.step_sage_mean")
         ops._need_cuda(feats, labels, output_nodes, input_nodes)
         if len(blocks) != L:
             raise ValueError(f"TeacherEngine.step_sage: {len(blocks)} blocks for {L} layers")
@@ -291,7 +332,8 @@ class TeacherEngine:
                     if self.ln:          # per-ROW statistics of z_l (written by the forward, read by the backward)
                         q = self._sage_ln.layer[l]
                         q.mean, q.rstd = A.take(4 * n_dst), A.take(4 * n_dst)
-                if l >= 1 and getattr(blk, "t_indptr", None) is not None:      # transposed by the loader (NodeDataLoader.global_first_block)
+                # transposed by the loader (NodeDataLoader.global_first_block) -- with the self entries, not the "mean" step's plain form
+                if l >= 1 and getattr(blk, "t_indptr", None) is not None and getattr(blk, "t_add_self", True) is not False:
                     y.t_indptr, y.t_indices, y.inv_deg = ptr(blk.t_indptr), ptr(blk.t_indices), ptr(blk.inv_deg)
                     y.tr_ws, y.tr_ws_bytes = None, 0
                 elif l >= 1:
@@ -361,6 +403,164 @@ class TeacherEngine:
         if rc != 0:
             self.step_count -= 1          # the step never happened: Adam's bias correction and the dropout seeds stay where they were
         _lib.check(rc, ("glnn_sage_train_step" if one_call else "glnn_sage_fwd_bwd") + ("_ln_f32" if self.ln else "_f32"))
+        if not one_call:
+            self._adam()
+
+    def step_sage_mean(self, blocks, feats, labels, output_nodes, lamb=1.0, input_nodes=None):
+        """step_sage for a SAGE "mean" teacher (docs/SAGE_MEAN_SEMANTICS.md): the same contract -- in place on the parameters, the BatchNorm
+        buffers and the optimiser's moments; `feats` global, gathered through blocks[0]'s global ids when it carries them -- as ONE C call,
+        glnn_sage_mean_train_step_f32 (csrc/sage_mean_step.hip): per layer the [mean | self] operand pair and one projection against the
+        packed [W_neigh | W_self]; backward over the PLAIN transposed blocks.  grad_sync set (or GLNN_TEACHER_ONE_CALL=0):
+        glnn_sage_mean_fwd_bwd_f32, then Adam."""
+        enc, L = self.enc, self.L
+        if not self.mean:
+            raise NotImplementedError("TeacherEngine.step_sage_mean: SAGE 'mean' teachers only; a 'gcn' teacher steps through step_sage")
+        ops._need_cuda(feats, labels, output_nodes, input_nodes)
+        if len(blocks) != L:
+            raise ValueError(f"TeacherEngine.step_sage_mean: {len(blocks)} blocks for {L} layers")
+        if L > _lib.SAGE_MAX_LAYERS:
+            raise NotImplementedError(f"TeacherEngine: at most {_lib.SAGE_MAX_LAYERS} layers")
+        if labels.dtype != torch.int64 or output_nodes.dtype != torch.int64 or not output_nodes.is_contiguous():
+            raise ValueError("TeacherEngine.step_sage_mean: labels / output_nodes must be int64 (output_nodes contiguous)")
+        x = ops.as_feat(feats)
+        dev = self.dev
+        if blocks[0].gindices is None:
+            if input_nodes is None:
+                raise ValueError("TeacherEngine.step_sage_mean: blocks without global ids need input_nodes")
+            x = ops.gather_rows(x, input_nodes)
+        for l in range(1, L):
+            if blocks[l].num_src_nodes() != blocks[l - 1].num_dst_nodes():
+                raise ValueError(f"TeacherEngine.step_sage_mean: block {l} has {blocks[l].num_src_nodes()} sources, block {l - 1} "
+                                 f"{blocks[l - 1].num_dst_nodes()} destinations")
+        if x.shape[0] < (blocks[0].num_src_nodes() if blocks[0].gindices is None else 1):
+            raise ValueError("TeacherEngine.step_sage_mean: the layer-0 source matrix is smaller than the outermost block")
+        self.step_count += 1
+        r4 = lambda c: (c + 3) // 4 * 4
+        ptr = lambda t: None if t is None else t.data_ptr()
+        d, md = self._sage_desc, self._sage_mean
+        if d is None:       # everything that does not depend on the batch, written once (see step_sage)
+            d, md = _lib.SageStepDesc(), _lib.SageMeanDesc()
+            self._sage_desc, self._sage_mean = d, md
+            self._sage_dims = [enc.layers[0].fc_neigh.weight.shape[1]] + [lay.fc_neigh.weight.shape[0] for lay in enc.layers]
+            self.p = float(enc.dropout.p)
+            d.num_layers, d.batchnorm, d.dropout_p = L, 1 if self.bn else 0, self.p
+            md.num_layers = L
+            for i, v in enumerate(self._sage_dims):
+                d.dims[i] = v
+            for l, layer in enumerate(enc.layers):
+                y, q = d.layer[l], md.layer[l]
+                w, b = layer.fc_neigh.weight, layer.fc_neigh.bias
+                y.w, y.b, y.gw, y.gb = ptr(w), ptr(b), ptr(self.grad(w)), ptr(self.grad(b))
+                w, b = layer.fc_self.weight, layer.fc_self.bias
+                q.w_self, q.b_self, q.gw_self, q.gb_self = ptr(w), ptr(b), ptr(self.grad(w)), ptr(self.grad(b))
+                if l != L - 1 and self.bn:
+                    bn = enc.norms[l]
+                    d.bn_eps, d.bn_momentum = bn.eps, bn.momentum
+                    y.gamma, y.beta, y.ggamma, y.gbeta = ptr(bn.weight), ptr(bn.bias), ptr(self.grad(bn.weight)), ptr(self.grad(bn.bias))
+                    y.running_mean, y.running_var, y.nbt = ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked)
+            self._sage_ln = None
+            if self.ln and L > 1:          # (a one-layer encoder has no hidden tail and no norm module)
+                lnd = self._sage_ln = _lib.SageLnDesc()
+                lnd.eps = enc.norms[0].eps
+                for l in range(L - 1):
+                    ln, q = enc.norms[l], lnd.layer[l]
+                    if ctypes.c_float(ln.eps).value != lnd.eps:
+                        raise NotImplementedError("TeacherEngine: the hidden LayerNorms of a SAGE teacher must share one eps")
+                    q.gamma, q.beta, q.ggamma, q.gbeta = ptr(ln.weight), ptr(ln.bias), ptr(self.grad(ln.weight)), ptr(self.grad(ln.bias))
+            self._sage_static = self._sage_signature(enc)
+        elif self._sage_static != self._sage_signature(enc):
+            self._sage_desc = self._sage_mean = None        # something the descriptors captured was replaced: rebuild them
+            self.step_count -= 1
+            return self.step_sage_mean(blocks, feats, labels, output_nodes, lamb, input_nodes)
+        dims = self._sage_dims
+        d.lamb = float(lamb)
+
+        def layout(A):      # ONE pass hands out the step's scratch from the arena (see step_sage)
+            max_rows, max_hidden = 1, 4
+            for l, blk in enumerate(blocks):
+                y, q = d.layer[l], md.layer[l]
+                n_dst, n_src, nnz = blk.num_dst_nodes(), blk.num_src_nodes(), blk.num_edges()
+                q.ld_cat = 2 * r4(dims[l])
+                q.cat = A.take(4 * n_dst * q.ld_cat)
+                q.wcat, q.bsum = A.take(4 * dims[l + 1] * q.ld_cat), A.take(4 * dims[l + 1])
+                y.z, y.ldz = A.take(4 * n_dst * r4(dims[l + 1])), r4(dims[l + 1])
+                if l != L - 1:
+                    if self.gather_tail and dims[l + 1] <= 256:      # (the tail-in-gather form: hidden width <= 256, as in step_sage)
+                        y.h, y.ldh = None, 0
+                    else:
+                        y.h, y.ldh = A.take(4 * n_dst * r4(dims[l + 1])), r4(dims[l + 1])
+                    max_rows, max_hidden = max(max_rows, n_dst), max(max_hidden, dims[l + 1])
+                    if self.bn:
+                        y.mean, y.rstd, y.a_scale, y.a_shift = (A.take(4 * dims[l + 1]) for _ in range(4))
+                    if self.ln:
+                        g = self._sage_ln.layer[l]
+                        g.mean, g.rstd = A.take(4 * n_dst), A.take(4 * n_dst)
+                # the PLAIN transpose: the loader's when it built that one (t_add_self False), else built inside the C call -- never one
+                # that carries the "gcn" step's self entries
+                if l >= 1 and getattr(blk, "t_indptr", None) is not None and getattr(blk, "t_add_self", None) is False:
+                    y.t_indptr, y.t_indices = ptr(blk.t_indptr), ptr(blk.t_indices)
+                    y.tr_ws, y.tr_ws_bytes = None, 0
+                elif l >= 1:
+                    wsb = int(_lib.lib().glnn_csr_transpose_workspace_bytes(n_src, nnz))
+                    y.t_indptr, y.t_indices = A.take(8 * (n_src + 1)), A.take(4 * max(nnz, 1))
+                    y.tr_ws, y.tr_ws_bytes = A.take(wsb + 8), (wsb + 7) // 8 * 8
+            n_out = blocks[-1].num_dst_nodes()
+            d.dlogits, d.ld_dlogits = A.take(4 * n_out * r4(dims[-1])), r4(dims[-1])
+            if L > 1:
+                wd = r4(max(dims[1:L]))
+                dcat = A.take(4 * max(blocks[l].num_dst_nodes() * 2 * r4(dims[l]) for l in range(1, L)))      # one buffer, layer by layer
+                for l in range(1, L):
+                    md.layer[l].dcat, md.layer[l].ld_dcat = dcat, 2 * r4(dims[l])
+                d.dh, d.ld_dh = A.take(4 * max(b.num_src_nodes() for b in blocks[1:]) * wd), wd
+            nchunks = (max_rows + 127) // 128
+            d.ws_bn_floats = (3 * nchunks + 2 + 3 * ((nchunks + 63) // 64)) * max_hidden + 1024
+            if self.ln:
+                for l in range(L - 1):
+                    n_l = blocks[l].num_dst_nodes()
+                    d.ws_bn_floats = max(d.ws_bn_floats, int(_lib.lib().glnn_sage_step_ws_ln_floats(n_l, dims[l + 1])),
+                                         int(_lib.lib().glnn_layernorm_bwd_workspace_floats(n_l, dims[l + 1])))
+            d.ws_tn_floats = 64 * max(dims) + 256 * 128 * 128 + 2 * max(dims) * max(dims)
+            d.ws_gemm_floats = min(max(16 * max(b.num_dst_nodes() for b in blocks) * min(dims[1:]), 1 << 20), 512 * 128 * 128)
+            d.ws_bn, d.ws_tn, d.ws_gemm = A.take(4 * d.ws_bn_floats), A.take(4 * d.ws_tn_floats), A.take(4 * d.ws_gemm_floats)
+            return A.off
+
+        for l, blk in enumerate(blocks):       # the batch: blocks and dropout seeds
+            y = d.layer[l]
+            glob = l == 0 and blk.gindices is not None
+            y.indptr, y.indices = ptr(blk.indptr), ptr(blk.gindices if glob else blk.indices)
+            y.n_dst, y.n_src, y.nnz = blk.num_dst_nodes(), blk.num_src_nodes(), blk.num_edges()
+            y.self_rows = ptr(blk.dst_nodes) if glob else None
+            if l != L - 1:
+                y.drop_seed = self._seed(l)
+        cur = torch.cuda.current_stream(dev)
+        if self._arena_stream is not None and self._arena_stream != cur:
+            cur.wait_stream(self._arena_stream)            # the previous step used the arena on another stream
+        self._arena_stream = cur
+        arena = self._arena
+        base = 0 if arena is None else (arena.data_ptr() + 255) // 256 * 256
+        total = layout(_Arena(base))
+        if arena is None or total + 256 > arena.numel():    # first step / a bigger batch: (re)allocate with headroom, lay out again
+            arena = self._arena = torch.empty(int(total * 1.25) + 256, dtype=torch.uint8, device=dev)
+            layout(_Arena((arena.data_ptr() + 255) // 256 * 256))
+        d.x, d.ldx, d.x_rows = ptr(x), x.stride(0), x.shape[0]
+        d.labels, d.label_rows = ptr(labels), ptr(output_nodes)
+        d.ws_loss, d.ws_loss_floats = ptr(self.ws_loss), self.ws_loss.numel()
+        d.loss_out, d.loss_accum = ptr(self.loss_out), ptr(self.loss_accum)
+        keep = [x]                                              # alive until the call below is queued (same-stream reuse is ordered)
+        ops.note_param_write()      # (running statistics are written through raw pointers; Adam follows)
+        one_call = self.grad_sync is None and self._one_call
+        lnp = ctypes.byref(self._sage_ln) if self._sage_ln is not None else None
+        if one_call:
+            g_ = self.opt.param_groups[0]
+            ad = self.table.desc
+            ad.lr, ad.beta1, ad.beta2, ad.eps, ad.weight_decay, ad.step = g_["lr"], g_["betas"][0], g_["betas"][1], g_["eps"], g_["weight_decay"], self.step_count
+            rc = _lib.lib().glnn_sage_mean_train_step_f32(ctypes.byref(d), ctypes.byref(md), lnp, ctypes.byref(ad), ops._stream())
+        else:
+            rc = _lib.lib().glnn_sage_mean_fwd_bwd_f32(ctypes.byref(d), ctypes.byref(md), lnp, ops._stream())
+        del keep
+        if rc != 0:
+            self.step_count -= 1          # the step never happened: Adam's bias correction and the dropout seeds stay where they were
+        _lib.check(rc, "glnn_sage_mean_train_step_f32" if one_call else "glnn_sage_mean_fwd_bwd_f32")
         if not one_call:
             self._adam()
 

@@ -46,32 +46,49 @@ def train(model, data, feats, labels, criterion, optimizer, idx_train, lamb=1):
     return eng.loss_out.item()
 
 
-def train_sage(model, dataloader, feats, labels, criterion, optimizer, lamb=1):
+SAGE_MEAN_STEPS = ("autograd", "native")
+
+
+def train_sage(model, dataloader, feats, labels, criterion, optimizer, lamb=1, mean_step="autograd"):
     """Sampled-block GraphSAGE training (reference train_and_eval.py:32-56): one TeacherEngine.step_sage per batch of
     `dataloader` (glnn_amd.graph.NodeDataLoader: blocks sampled and relabelled on the device; the outermost block gathers
     straight from `feats`, so `feats[input_nodes]` is never materialised).  The per-step `loss.item()` of the reference
-    (:49) is a device-side running sum read ONCE per epoch; the returned mean of the per-batch losses is the same number."""
-    if "SAGE" in model.model_name and getattr(model.encoder, "aggregator_type", "gcn") == "mean":
+    (:49) is a device-side running sum read ONCE per epoch; the returned mean of the per-batch losses is the same number.
+    mean_step (SAGE "mean" teachers only; ignored otherwise): "autograd" (default) = the differentiable-op step of
+    _train_sage_autograd, "native" = one TeacherEngine.step_sage_mean per batch, the loader in engine mode with plain transposes."""
+    if mean_step not in SAGE_MEAN_STEPS:
+        raise ValueError(f"train_sage: mean_step must be one of {SAGE_MEAN_STEPS} (got {mean_step!r})")
+    is_mean = "SAGE" in model.model_name and getattr(model.encoder, "aggregator_type", "gcn") == "mean"
+    if is_mean and mean_step == "autograd":
         return _train_sage_autograd(model, dataloader, feats, labels, criterion, optimizer, lamb)
-    teacher.check_supported(model, criterion, optimizer)
+    if is_mean:
+        teacher.check_supported_mean(model, criterion, optimizer)
+    else:
+        teacher.check_supported(model, criterion, optimizer)
     if "SAGE" not in model.model_name:
         raise NotImplementedError("train_sage(): GraphSAGE teachers only")
     model.train()
     eng = teacher.get_engine(model, optimizer)
     eng.loss_accum.zero_()
     steps = 0
+    step = eng.step_sage_mean if is_mean else eng.step_sage
     # the engine gathers layer 0 straight from `feats` through the outermost block's global ids: our loader then builds that block
     # without its frontier table / local relabelling and yields input_nodes = None (60 % of the sampler's device time; other loaders: no-op)
     had = getattr(dataloader, "global_first_block", None)
+    had_plain = getattr(dataloader, "plain_transpose", None)
     if had is not None:
         dataloader.global_first_block = True
+    if had_plain is not None:          # the inner blocks' loader-built transposes: plain for "mean", with the self entries for "gcn"
+        dataloader.plain_transpose = is_mean
     try:
         for input_nodes, output_nodes, blocks in dataloader:
-            eng.step_sage(blocks, feats, labels, output_nodes, float(lamb), input_nodes=input_nodes)
+            step(blocks, feats, labels, output_nodes, float(lamb), input_nodes=input_nodes)
             steps += 1
     finally:
         if had is not None:
             dataloader.global_first_block = had
+        if had_plain is not None:
+            dataloader.plain_transpose = had_plain
     eng.sync_optimizer_state()
     return eng.loss_accum.item() / max(steps, 1)
 
@@ -259,7 +276,7 @@ def run_transductive(conf, model, g, feats, labels, indices, criterion, evaluato
 
     def train_epoch():
         if is_sage:
-            return train_sage(model, data, feats, labels, criterion, optimizer)
+            return train_sage(model, data, feats, labels, criterion, optimizer, mean_step=conf.get("sage_mean_step", "autograd"))
         if is_mlp:
             return train_mini_batch(model, feats_train, labels_train, batch_size, criterion, optimizer)
         return train(model, data, feats, labels, criterion, optimizer, idx_train)
@@ -351,7 +368,7 @@ def run_inductive(conf, model, g, feats, labels, indices, criterion, evaluator, 
 
     def train_epoch():
         if is_sage:
-            return train_sage(model, obs_data, obs_feats, obs_labels, criterion, optimizer)
+            return train_sage(model, obs_data, obs_feats, obs_labels, criterion, optimizer, mean_step=conf.get("sage_mean_step", "autograd"))
         if is_mlp:
             return train_mini_batch(model, feats_train, labels_train, batch_size, criterion, optimizer)
         return train(model, obs_data, obs_feats, obs_labels, criterion, optimizer, obs_idx_train)

@@ -43,7 +43,7 @@ GLNN_API int glnn_abi_version(void);               /* bumped on any signature ch
 GLNN_API const char* glnn_last_error(void);        /* thread-local, never NULL */
 GLNN_API int glnn_device_info(int* cu_count, int* xcd_count, char* arch_buf, int arch_buf_len);
 /* sizeof of the descriptor structs below as THIS build sees them (0 = glnn_mlp_step_desc, 1 = glnn_sage_step_desc,
- * 2 = glnn_sage_layer, 3 = glnn_adam_desc, 4 = glnn_hub_plan, 5 = glnn_chunk_signals, 6 = glnn_sage_ln_desc, 7 = glnn_mlp_serve_desc; -1 otherwise): lets a binding in another language check its mirror of the layout at load time. */
+ * 2 = glnn_sage_layer, 3 = glnn_adam_desc, 4 = glnn_hub_plan, 5 = glnn_chunk_signals, 6 = glnn_sage_ln_desc, 7 = glnn_mlp_serve_desc, 8 = glnn_sage_mean_desc; -1 otherwise): lets a binding in another language check its mirror of the layout at load time. */
 GLNN_API int64_t glnn_struct_bytes(int which);
 /* The library reads its GLNN_* environment switches (csrc/glnn_common.h, glnn::Options: choices between supported, equal-result
  * forms of a launch sequence, for tests and A/B timing) ONCE, at the first call.  This re-reads them; not for concurrent use. */
@@ -587,6 +587,41 @@ GLNN_API int glnn_sage_fwd_bwd_ln_f32(const glnn_sage_step_desc* desc, const gln
 GLNN_API int glnn_sage_train_step_ln_f32(const glnn_sage_step_desc* desc, const glnn_sage_ln_desc* ln, const glnn_adam_desc* adam,
                                          void* stream);
 GLNN_API int64_t glnn_sage_step_ws_ln_floats(int64_t n_dst, int hidden);
+
+/* The same step for SAGE teachers built with the "mean" aggregator (dgl 0.6.1 SAGEConv(in, out, "mean"); docs/SAGE_MEAN_SEMANTICS.md; the
+ * reference only builds "gcn", so this replaces no reference call site -- it is train_and_eval.py:39-53 over that layer):
+ *   z_l = [mean_l | self_l] [W_neigh | W_self]^T + (b_neigh + b_self),  mean_l[v] = (1 / max(deg v, 1)) sum_{u->v} h_l[u],  self_l[v] = h_l[v]
+ * `desc` is the "gcn" step's descriptor with w / b / gw / gb = fc_neigh; agg, ld_agg, dagg, ld_dagg and inv_deg are unused.  `mean` adds,
+ * per layer, fc_self and the step's own scratch:
+ *   w_self/b_self/gw_self/gb_self  fc_self weight [dims[l+1], dims[l]] / bias and their gradients (contiguous)
+ *   cat, ld_cat     the operand pair [mean | self] per destination row, [n_dst, ld_cat] floats, ld_cat == 2 * round4(dims[l]); the self
+ *                   half starts at column round4(dims[l]); padding columns are written as zeros
+ *   wcat, bsum      [dims[l+1], ld_cat] and [dims[l+1]] floats: [W_neigh | W_self] in the same layout and b_neigh + b_self, re-packed on
+ *                   the device by every call (the parameters stay the fc_self / fc_neigh tensors)
+ *   dcat, ld_dcat   (l >= 1) dz [W_neigh | W_self], [n_dst, ld_dcat] floats, ld_dcat == ld_cat; layers may share one buffer
+ * t_indptr / t_indices of layers >= 1 hold (tr_ws == NULL) or receive (tr_ws != NULL) the PLAIN transposed block,
+ * glnn_csr_transpose(..., add_self = 0): "mean" has no identity term.  `ln` NULL: the tails of desc (BatchNorm when desc->batchnorm, else
+ * none); non-NULL: LayerNorm tails as in glnn_sage_fwd_bwd_ln_f32.  h == NULL on a hidden layer (width <= 256, else GLNN_ERR_UNSUPPORTED):
+ * its tail is evaluated inside the next layer's gather, on the gathered rows and on the self row, bit-identical to the stored form.
+ * Backward per layer: two glnn_gemm_tn_f32 over the halves of cat, dcat by glnn_gemm_f32, the transposed aggregation
+ * dh[u] = sum_{v: u->v} dcat[v, :d] / max(deg v, 1) + (u < n_dst ? dcat[u, ld_cat/2 : ld_cat/2 + d] : 0) -- every row of dh is written --
+ * then glnn_bn_relu_bwd_f32 / glnn_layernorm_bwd_f32; both bias gradients of a layer receive colsum(dz).  Workspaces as the "gcn" step
+ * (ws_tn >= 64 * max dims floats).  No float atomics: bit-reproducible.  Bad arguments return GLNN_ERR_INVALID_ARG before any launch. */
+typedef struct glnn_sage_mean_layer {
+  float* w_self; float* b_self; float* gw_self; float* gb_self;
+  float* cat; int64_t ld_cat;
+  float* wcat; float* bsum;
+  float* dcat; int64_t ld_dcat;
+} glnn_sage_mean_layer;
+typedef struct glnn_sage_mean_desc {        /* glnn_struct_bytes(8) */
+  int32_t num_layers; int32_t reserved;
+  glnn_sage_mean_layer layer[GLNN_SAGE_MAX_LAYERS];
+} glnn_sage_mean_desc;
+GLNN_API int glnn_sage_mean_fwd_bwd_f32(const glnn_sage_step_desc* desc, const glnn_sage_mean_desc* mean, const glnn_sage_ln_desc* ln,
+                                        void* stream);
+/* ... followed by the fused Adam launch on the same stream: the same bits as glnn_sage_mean_fwd_bwd_f32 + glnn_adam_step_f32 */
+GLNN_API int glnn_sage_mean_train_step_f32(const glnn_sage_step_desc* desc, const glnn_sage_mean_desc* mean, const glnn_sage_ln_desc* ln,
+                                           const glnn_adam_desc* adam, void* stream);
 
 /* y = dropout(relu(z * a_scale + a_shift)) materialised (a_scale/a_shift NULL: plain ReLU): the `norms[l](h)` ->
  * `activation` -> `dropout` tail of a TRAINING-mode SAGE layer (reference models.py:113-117), whose output the next
