@@ -4,6 +4,7 @@
 //   z [N, H F] = the projected rows (head-major columns), el / er [N, H] = <z, attn_l> / <z, attn_r> per head (gat_scores_kernel)
 //   forward  (in-CSR, row i):     e_ij = leaky_relu(el[j] + er[i]),  a_ij = exp(e_ij - max_i) / sum_i,  out[i] = act(sum_j a_ij w_ij z[j])
 //   backward (in-CSR, row i):     ds_ij = a_ij (w_ij <g_i, z_j> - <g_i, out_i>) * (e_ij > 0 ? 1 : slope)  -> ds [E, H],  der_i = sum_j ds_ij
+//                                 (<g_i, out_i> as sum_k a_ik w_ik <g_i, z_k> / sum_k a_ik in fp64: see bwd_dst_row)
 //   backward (transposed, row j): dz_j = sum_i a_ij w_ij g_i + del_j attn_l + der_j attn_r,   del_j = sum_i ds_ij (read by edge id)
 //   dattn_l / dattn_r = column sums of del z / der z: per-workgroup partials, folded in fixed order
 //
@@ -39,7 +40,7 @@ struct GatArgs {
   float* out; int64_t ldo;                 // forward: out; src pass: dz
   float* lse;                              // forward: optional [N, H] store; backward: the stored values
   const float* g; int64_t ldg;             // backward: gradient of the layer's output (behind the activation mask)
-  const float* y; int64_t ldy;             // backward: the layer's stored output
+  const float* y; int64_t ldy;             // backward: the layer's stored output (kept in the C ABI, not read: see bwd_dst_row)
   float* ds;                               // [E, H] scratch
   float* der; float* del_;                 // [N, H]
   const float* attn_l; const float* attn_r;
@@ -64,23 +65,26 @@ __device__ __forceinline__ bool attn_keep(uint32_t seed, uint32_t thr, uint32_t 
 }
 
 struct Smem {
-  float red[kWaves][64];
+  double red[kWaves][64];                   // holds a float exactly; the backward's per-head sums are doubles
   float4 part[kWaves][64];
   float4 part2[kWaves][64];
 };
 
+__device__ __forceinline__ float max_of(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double max_of(double a, double b) { return fmax(a, b); }
+
 // per-head reduction over the edge slots of a wave (and, for a long row, over the workgroup's waves in wave order)
-template <bool MAX>
-__device__ __forceinline__ float reduce_heads(float v, int HP, int h, int wave_id, int n_waves, int lane, Smem& sm) {
+template <bool MAX, typename T>
+__device__ __forceinline__ T reduce_heads(T v, int HP, int h, int wave_id, int n_waves, int lane, Smem& sm) {
   for (int m = HP; m < 64; m <<= 1) {
-    const float o = __shfl_xor(v, m);
-    v = MAX ? fmaxf(v, o) : v + o;
+    const T o = __shfl_xor(v, m);
+    v = MAX ? max_of(v, o) : v + o;
   }
   if (n_waves > 1) {
     if (lane < HP) sm.red[wave_id][lane] = v;
     __syncthreads();
-    v = sm.red[0][h];
-    for (int w = 1; w < n_waves; ++w) v = MAX ? fmaxf(v, sm.red[w][h]) : v + sm.red[w][h];
+    v = (T)sm.red[0][h];
+    for (int w = 1; w < n_waves; ++w) v = MAX ? max_of(v, (T)sm.red[w][h]) : v + (T)sm.red[w][h];
     __syncthreads();
   }
   return v;
@@ -184,6 +188,11 @@ __device__ __forceinline__ void fwd_row(const GatArgs& a, int64_t v, int wave_id
 }
 
 // ---------------------------------------------------------------------------------------------- backward, destination side (in-CSR)
+// ds_ij = a_ij (c_ij - D_i) with c_ij = w_ij <g_i, z_j> and D_i = <g_i, out_i> = sum_k a_ik c_ik.  On a row whose softmax is close to
+// one-hot (scores of +-40 at heads * out_feats = 256) c_ij - D_i cancels to (1 - a_ij) c_ij, so D_i has to be the mean of the SAME c values
+// under the SAME weights: two sweeps, the first leaves c_ij in ds and sums a and a c per head in fp64, the second reads c_ij back (each lane
+// its own entries) and writes ds.  <g_i, y_i> from the stored output differs from that mean by the forward's rounding (1e-5 of |c|), which
+// the sum over a hub's edges in the source pass then multiplies.
 template <int LPR, bool UNI>
 __device__ __forceinline__ void bwd_dst_row(const GatArgs& a, int64_t v, int wave_id, int n_waves, int lane, Smem& sm) {
   const int HP = 1 << a.hp_shift, EPP = 64 >> a.hp_shift;
@@ -191,24 +200,13 @@ __device__ __forceinline__ void bwd_dst_row(const GatArgs& a, int64_t v, int wav
   const bool hv = h < a.H;
   const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
   const int F = a.F;
-  float der = 0.f;
+  const float er_h = hv ? a.er[v * a.H + h] : 0.f, lse_h = hv ? a.lse[v * a.H + h] : 0.f;
+  double S = 0.0, P = 0.0;
   if (hv) {
-    const float er_h = a.er[v * a.H + h], lse_h = a.lse[v * a.H + h];
     const float* gp = a.g + v * a.ldg + h * F;
-    const float* yp = a.y + v * a.ldy + h * F;
-    float D = 0.f;
-    if (UNI) {
-      for (int f = 0; f < F; f += 4) {
-        const float4 p = ld4(gp + f), q = ld4(yp + f);
-        D = fmaf(p.x, q.x, D); D = fmaf(p.y, q.y, D); D = fmaf(p.z, q.z, D); D = fmaf(p.w, q.w, D);
-      }
-    } else {
-      for (int f = 0; f < F; ++f) D = fmaf(gp[f], yp[f], D);
-    }
     for (int64_t e = e0 + (int64_t)wave_id * EPP + slot; e < e1; e += (int64_t)n_waves * EPP) {
       const int64_t j = a.indices[e];
-      const float s = a.el[j * a.H + h] + er_h;
-      const float at = __expf(lrelu(s, a.slope) - lse_h);
+      const float at = __expf(lrelu(a.el[j * a.H + h] + er_h, a.slope) - lse_h);
       float c = 0.f;
       if (!a.thr || attn_keep(a.seed, a.thr, (uint32_t)e, (uint32_t)h)) {
         const float* zp = a.z + j * a.ldz + h * F;
@@ -222,7 +220,20 @@ __device__ __forceinline__ void bwd_dst_row(const GatArgs& a, int64_t v, int wav
         }
         c *= a.dscale;
       }
-      const float dsv = at * (c - D) * (s > 0.f ? 1.f : a.slope);
+      a.ds[e * a.H + h] = c;
+      S += (double)at;
+      P += (double)at * (double)c;
+    }
+  }
+  S = reduce_heads<false>(S, HP, h, wave_id, n_waves, lane, sm);
+  P = reduce_heads<false>(P, HP, h, wave_id, n_waves, lane, sm);
+  float der = 0.f;
+  if (hv) {
+    const double D = S > 0.0 ? P / S : 0.0;
+    for (int64_t e = e0 + (int64_t)wave_id * EPP + slot; e < e1; e += (int64_t)n_waves * EPP) {
+      const float s = a.el[(int64_t)a.indices[e] * a.H + h] + er_h;
+      const float at = __expf(lrelu(s, a.slope) - lse_h);
+      const float dsv = at * (float)((double)a.ds[e * a.H + h] - D) * (s > 0.f ? 1.f : a.slope);
       a.ds[e * a.H + h] = dsv;
       der += dsv;
     }
@@ -415,8 +426,8 @@ __global__ __launch_bounds__(256) void gat_scores_kernel(float* __restrict__ z, 
     float* zp = z + r * ldz + h * F;
     const float* al = attn_l + h * F;
     const float* ar = attn_r + h * F;
-    float sl = 0.f, sr = 0.f;
-    if (vec4) {                                             // F % 4 == 0 and 16-byte aligned rows: 16-byte loads (and stores)
+    double sl = 0.0, sr = 0.0;                              // fp64 sums: a score of +-40 over 256 columns keeps its last fp32 bits, which
+    if (vec4) {                                             // the softmax's exponentials magnify; F % 4 == 0 and aligned rows: 16-byte moves
       for (int f = 0; f < F; f += 4) {
         float4 x = ld4(zp + f);
         if (z2) {
@@ -425,18 +436,20 @@ __global__ __launch_bounds__(256) void gat_scores_kernel(float* __restrict__ z, 
           st4(zp + f, x);
         }
         const float4 l4 = ld4(al + f), r4 = ld4(ar + f);
-        sl = fmaf(x.x, l4.x, sl); sl = fmaf(x.y, l4.y, sl); sl = fmaf(x.z, l4.z, sl); sl = fmaf(x.w, l4.w, sl);
-        sr = fmaf(x.x, r4.x, sr); sr = fmaf(x.y, r4.y, sr); sr = fmaf(x.z, r4.z, sr); sr = fmaf(x.w, r4.w, sr);
+        sl = fma((double)x.x, (double)l4.x, sl); sl = fma((double)x.y, (double)l4.y, sl);
+        sl = fma((double)x.z, (double)l4.z, sl); sl = fma((double)x.w, (double)l4.w, sl);
+        sr = fma((double)x.x, (double)r4.x, sr); sr = fma((double)x.y, (double)r4.y, sr);
+        sr = fma((double)x.z, (double)r4.z, sr); sr = fma((double)x.w, (double)r4.w, sr);
       }
     } else
     for (int f = 0; f < F; ++f) {
       float x = zp[f];
       if (z2) { x -= z2[r * ldz2 + h * F + f]; zp[f] = x; }
-      sl = fmaf(x, al[f], sl);
-      sr = fmaf(x, ar[f], sr);
+      sl = fma((double)x, (double)al[f], sl);
+      sr = fma((double)x, (double)ar[f], sr);
     }
-    el[r * H + h] = sl;
-    er[r * H + h] = sr;
+    el[r * H + h] = (float)sl;
+    er[r * H + h] = (float)sr;
   }
 }
 

@@ -1483,7 +1483,8 @@ def gat_attn_fwd(indptr, indices, nnz, z, el, er, heads, out_feats, negative_slo
 def gat_attn_bwd(graph, z, el, er, lse, attn_l, attn_r, g, y, heads, out_feats, negative_slope=0.2, attn_drop=0.0, seed=0,
                  dattn_l=None, dattn_r=None):
     """glnn_gat_attn_bwd_f32 over `graph` (CSRGraph: its in-CSR and its cached transpose with edge ids): (dz, dattn_l, dattn_r).
-    g = dL/d out behind the activation mask, y = the forward's stored output.  The [E, heads] score-gradient scratch lives for the call."""
+    g = dL/d out behind the activation mask, y = the forward's stored output (checked, not read: the kernel forms <g_i, out_i> from the row's
+    own edges).  The [E, heads] score-gradient scratch lives for the call."""
     z, g, y = as_feat(z), as_feat(g), as_feat(y)
     n = z.shape[0]
     _appnp_check(graph.indptr, graph.indices, z, n, "gat_attn_bwd")

@@ -775,7 +775,8 @@ GLNN_API int glnn_gat_attn_fwd_f32(const int64_t* indptr, const int32_t* indices
                                    int heads, int out_feats, const float* el, const float* er, float negative_slope, float attn_drop,
                                    uint32_t seed, int relu, float* out, int64_t ldo, float* lse, void* stream);
 /* Backward of glnn_gat_attn_fwd_f32 + glnn_gat_scores_f32 with respect to z, attn_l and attn_r.  g = dL/d out behind the activation
- * mask, y = the forward's stored output (D_i = <g_i, y_i> per head).  Pass 1 (in-CSR): ds [nnz, heads] scratch and der [n, heads];
+ * mask.  y = the forward's stored output: still required and checked like g, but not read (D_i = <g_i, out_i> is formed per head as
+ * sum_k a_ik c_ik / sum_k a_ik from the row's own c_ik = w_ik <g_i, z_k>, in fp64).  Pass 1 (in-CSR, two sweeps): ds [nnz, heads] scratch and der [n, heads];
  * pass 2 (transposed CSR with original edge ids, glnn_csr_transpose_eids): dz [n, heads * out_feats] and del [n, heads]; then
  * dattn_l = sum_j del_j z_j, dattn_r = sum_i der_i z_i through per-workgroup partials in `workspace`
  * (>= glnn_gat_attn_bwd_workspace_floats floats), folded in fixed order. */

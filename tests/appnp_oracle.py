@@ -3,6 +3,8 @@
 checks the reference's recorded masks and the library's counter-hash masks."""
 import numpy as np
 
+from graphgen import segment_reduce
+
 
 def degree_norms(indptr, indices, n):
     """(dst_norm, src_norm) = (in_deg.clamp(1)^-1/2, out_deg.clamp(1)^-1/2)."""
@@ -30,8 +32,7 @@ def propagate(indptr, indices, h0, k, alpha, masks=None, p=0.0):
     h = h0.copy()
     for t in range(1, k + 1):
         w = _weights(masks, t, len(src), p)
-        agg = np.zeros_like(h)
-        np.add.at(agg, dst, w[:, None] * (sn[src, None] * h[src]))
+        agg = segment_reduce(np.add, w[:, None] * (sn[src, None] * h[src]), dst, n, 0.0)
         h = (1 - alpha) * dn[:, None] * agg + alpha * h0
     return h
 
@@ -47,8 +48,7 @@ def propagate_bwd(indptr, indices, g, k, alpha, masks=None, p=0.0):
     for t in range(k, 0, -1):
         acc += alpha * g
         w = _weights(masks, t, len(src), p)
-        nxt = np.zeros_like(g)
-        np.add.at(nxt, src, w[:, None] * (dn[dst, None] * g[dst]))
+        nxt = segment_reduce(np.add, w[:, None] * (dn[dst, None] * g[dst]), src, n, 0.0)
         g = (1 - alpha) * sn[:, None] * nxt
     return g + acc
 

@@ -4,6 +4,8 @@ caller (feature masks [N, in], attention masks [E, H], 1 = kept), so the same fu
 library's counter-hash masks."""
 import numpy as np
 
+from graphgen import segment_reduce
+
 
 def _edges(indptr, indices):
     n = len(indptr) - 1
@@ -24,15 +26,12 @@ def layer_fwd(indptr, indices, x, w, attn_l, attn_r, relu, feat_mask=None, feat_
     el, er = (z * al).sum(-1), (z * ar).sum(-1)
     s = el[src] + er[dst]                                  # [E, H]
     e = np.where(s > 0, s, slope * s)
-    mx = np.full((n, H), -np.inf)
-    np.maximum.at(mx, dst, e)
+    mx = segment_reduce(np.maximum, e, dst, n, -np.inf)
     ex = np.exp(e - mx[dst])
-    den = np.zeros((n, H))
-    np.add.at(den, dst, ex)
+    den = segment_reduce(np.add, ex, dst, n, 0.0)
     a = ex / den[dst]
     wm = np.ones_like(a) if attn_mask is None else np.asarray(attn_mask, np.float64).reshape(a.shape) / (1.0 - attn_p)
-    r = np.zeros((n, H, F))
-    np.add.at(r, dst, (a * wm)[:, :, None] * z[src])
+    r = segment_reduce(np.add, (a * wm)[:, :, None] * z[src], dst, n, 0.0)
     y = np.maximum(r, 0) if relu else r
     cache = dict(dst=dst, src=src, h=h, fm=fm, w=w, al=al, ar=ar, z=z, s=s, a=a, wm=wm, r=r, relu=relu, slope=slope,
                  lse=mx + np.log(den), el=el, er=er)
@@ -50,12 +49,9 @@ def layer_dz(c, gy):
     cij = wm * (g[dst] * z[src]).sum(-1)                    # [E, H]
     de = a * (cij - D[dst])
     ds = de * np.where(c["s"] > 0, 1.0, c["slope"])
-    der = np.zeros((n, H))
-    np.add.at(der, dst, ds)
-    dl = np.zeros((n, H))
-    np.add.at(dl, src, ds)
-    dz = np.zeros((n, H, F))
-    np.add.at(dz, src, (a * wm)[:, :, None] * g[dst])
+    der = segment_reduce(np.add, ds, dst, n, 0.0)
+    dl = segment_reduce(np.add, ds, src, n, 0.0)
+    dz = segment_reduce(np.add, (a * wm)[:, :, None] * g[dst], src, n, 0.0)
     dz += dl[:, :, None] * c["al"] + der[:, :, None] * c["ar"]
     dal = (dl[:, :, None] * z).sum(0)[None]
     dar = (der[:, :, None] * z).sum(0)[None]

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import appnp_oracle as ao
-from graphgen import random_graph
+from graphgen import planted_graph, random_graph, scan_geometry, second_trip_plan
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -82,12 +82,20 @@ def _bwd(g, dy, k, alpha, p, seed):
 
 CASES = [(d, k, alpha, p) for d in (1, 7, 40, 47, 64, 256) for k in (0, 1, 10) for alpha in (0.1, 1.0) for p in (0.0, 0.5)
          if not (alpha == 1.0 and k == 0)]
+# the widths of the remaining appnp_prop_kernel<LPR, ..> instantiations (prop_launch: LPR = pow2 >= ceil(d / 4)): LPR 4, 4, 8, 8, 32, 32
+CASES += [(d, k, 0.1, p) for d in (12, 16, 20, 32, 100, 128) for k in (1, 3) for p in (0.0, 0.5)]
 
 
 @pytest.mark.parametrize("d,k,alpha,p", CASES)
 def test_forward_and_backward_match_the_oracle(graph, d, k, alpha, p):
-    from glnn_amd import ops
     ip, ix, g = graph
+    _check_propagation(ip, ix, g, d, k, alpha, p)
+    deg = np.diff(ip)
+    assert deg.max() > 128 and (deg == 0).any()
+
+
+def _check_propagation(ip, ix, g, d, k, alpha, p):
+    from glnn_amd import ops
     n = len(ip) - 1
     rs = np.random.RandomState(d * 100 + k)
     h0 = rs.standard_normal((n, d)).astype(np.float32)
@@ -96,11 +104,59 @@ def test_forward_and_backward_match_the_oracle(graph, d, k, alpha, p):
     masks = _lib_masks(ops, len(ix), k, p, seed)
     out = _fwd(g, torch.from_numpy(h0).to(DEV), k, alpha, p, seed).cpu().numpy()
     ref = ao.propagate(ip, ix, h0, k, alpha, masks, p)
+    print(f"n={n} d={d} k={k} p={p} forward: max|err| {np.abs(out - ref).max():.3e} max|ref| {np.abs(ref).max():.3e}")
     np.testing.assert_allclose(out, ref, rtol=1e-4, atol=1e-4)
     dh0 = _bwd(g, torch.from_numpy(dy).to(DEV), k, alpha, p, seed).cpu().numpy()
-    np.testing.assert_allclose(dh0, ao.propagate_bwd(ip, ix, dy, k, alpha, masks, p), rtol=1e-4, atol=1e-4)
-    deg = np.diff(ip)
-    assert deg.max() > 128 and (deg == 0).any()
+    ref = ao.propagate_bwd(ip, ix, dy, k, alpha, masks, p)
+    print(f"n={n} d={d} k={k} p={p} backward: max|err| {np.abs(dh0 - ref).max():.3e} max|ref| {np.abs(ref).max():.3e}")
+    np.testing.assert_allclose(dh0, ref, rtol=1e-4, atol=1e-4)
+
+
+# ---------------------------------------------------------------------------------------------------------------- launch geometry
+# The numbers prop_launch and appnp_prop_kernel derive the grid from, mirrored by name (csrc/appnp.hip; gat.hip has the same values, so
+# test_gat_gpu.py plants the same rows):
+K_BLOCK = 512                 # appnp.hip:24  kBlock: the rows one trip of the long-row scan looks at (n_chunks = ceil(n / kBlock), appnp.hip:170)
+K_WAVES = K_BLOCK // 64       # appnp.hip:25  kWaves
+K_ROWS_PER_WAVE = 8           # appnp.hip:26  kRowsPerWave
+K_LONG_ROW = 128              # appnp.hip:27  kLongRow: a row above it is a whole workgroup's
+K_LONG_BLOCK_ROWS = 512       # appnp.hip:28  kLongBlockRows
+K_LONG_BLOCK_CAP = 512        # appnp.hip:29  kLongBlockCap
+BIG_N = K_LONG_BLOCK_ROWS * K_LONG_BLOCK_CAP + 656      # 262 800: just above the size at which every scan chunk has a workgroup of its own
+
+
+def _geometry(n):
+    """(n_chunks, n_long_blocks, rows_per_block) of prop_launch (appnp.hip:243-249) and the scan loop (appnp.hip:170-171)."""
+    return scan_geometry(n, K_BLOCK, K_WAVES, K_ROWS_PER_WAVE, K_LONG_BLOCK_ROWS, K_LONG_BLOCK_CAP)
+
+
+@pytest.fixture(scope="module")
+def big_graph():
+    from glnn_amd.graph import CSRGraph
+    n_chunks, n_long_blocks, _ = _geometry(BIG_N)
+    ip, ix = planted_graph(BIG_N, 17, *second_trip_plan(BIG_N, n_chunks, n_long_blocks, K_LONG_ROW))
+    return ip, ix, CSRGraph(torch.from_numpy(ip).to(DEV), torch.from_numpy(ix).to(DEV), BIG_N)
+
+
+def test_big_graph_has_the_rows_the_launch_geometry_branches_on(big_graph):
+    ip, ix, _ = big_graph
+    n = len(ip) - 1
+    n_chunks, n_long_blocks, rows_per_block = _geometry(n)
+    assert n > K_LONG_BLOCK_ROWS * K_LONG_BLOCK_CAP and n_chunks > n_long_blocks          # the scan loop makes a second trip
+    assert rows_per_block == K_ROWS_PER_WAVE * K_WAVES and n % rows_per_block != 0         # 64 tickets per block; ragged last block
+    deg, out_deg = np.diff(ip), np.bincount(ix, minlength=n)
+    for d in (deg, out_deg):                                                # the forward over the in-CSR, the backward over the transpose
+        long_rows = np.flatnonzero(d > K_LONG_ROW)
+        assert (long_rows % n_chunks >= n_long_blocks).sum() >= 2 and (long_rows % n_chunks < n_long_blocks).sum() >= 2
+        assert {K_LONG_ROW - 1, K_LONG_ROW, K_LONG_ROW + 1} <= set(d.tolist())
+        assert ((d > 64) & (d < K_LONG_ROW)).any()                           # a one-wave row of two 64-entry chunks
+    assert deg.min() == 1 and (deg == 1).sum() > 100 and 2.5 < deg.mean() < 3.5
+
+
+def test_large_n_propagation_matches_the_oracle(big_graph):
+    """The launch geometry a 600-row graph never reaches (appnp.hip prop_launch / appnp_prop_kernel): 64 tickets per row block, a last
+    block that ends before its tickets do, and long rows -- destinations forward, sources backward -- that the scan finds on its second trip."""
+    ip, ix, g = big_graph
+    _check_propagation(ip, ix, g, 8, 2, 0.1, 0.5)
 
 
 def test_wide_rows_are_column_tiled(graph):

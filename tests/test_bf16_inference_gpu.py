@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-4
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WIDTHS = [3, 7, 47, 100, 128, 256]
+WIDTHS = [3, 7, 17, 47, 100, 128, 256]        # 16-byte pieces per row 1, 1, 3, 6, 13, 16, 32: LPR 2, 2, 4, 8, 16, 16, 32 of both dispatchers
 
 
 def _bits(t):

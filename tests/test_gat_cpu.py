@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import gat_oracle as go
-from graphgen import random_graph
+from graphgen import planted_graph, random_graph, segment_reduce
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "gat_teacher.npz")
@@ -160,3 +160,31 @@ def test_gat_layers_refuse_what_is_out_of_scope():
         GAT(3, 8, 16, 4, 0.0, torch.nn.functional.relu, residual=True)
     with pytest.raises(NotImplementedError, match="bipartite"):
         GATConv((8, 8), 4, 2)
+
+
+def test_segment_reduce_is_ufunc_at():
+    """The oracles' scatter (graphgen.segment_reduce) against numpy's own ufunc.at: unsorted indices, rows nobody names, 1-d .. 3-d values."""
+    rs = np.random.RandomState(0)
+    n, m = 50, 400
+    idx = rs.randint(0, n - 5, size=m)                                       # the last rows stay empty
+    idx[idx == 7] = 8                                                        # ... and one in the middle
+    for shape in ((m,), (m, 3), (m, 2, 4)):
+        vals = rs.standard_normal(shape)
+        for ufunc, init in ((np.add, 0.0), (np.maximum, -np.inf)):
+            want = np.full((n,) + shape[1:], init)
+            ufunc.at(want, idx, vals)
+            np.testing.assert_allclose(segment_reduce(ufunc, vals, idx, n, init), want, rtol=1e-14, atol=1e-14)
+            order = np.argsort(idx, kind="stable")
+            np.testing.assert_allclose(segment_reduce(ufunc, vals[order], idx[order], n, init), want, rtol=1e-14, atol=1e-14)
+    assert segment_reduce(np.add, np.zeros((0, 2)), np.zeros(0, np.int64), 3, 0.0).shape == (3, 2)
+
+
+def test_planted_graph_degrees_are_exact():
+    n = 5000
+    in_deg, out_deg, lone = {10: 300, 4999: 129, 77: 128}, {3: 200, 2500: 127}, [0, 1, 4000]
+    ip, ix = planted_graph(n, 1, in_deg, out_deg, lone)
+    deg, out = np.diff(ip), np.bincount(ix, minlength=n)
+    assert ip.dtype == np.int64 and ix.dtype == np.int32 and deg.min() == 1
+    assert all(deg[r] == d for r, d in in_deg.items()) and all(out[r] == d for r, d in out_deg.items())
+    assert (deg[lone] == 1).all() and (ix[ip[lone]] == lone).all()           # the self-loop alone
+    assert 2.5 < deg.mean() < 3.5

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import gat_oracle as go
-from graphgen import csr_from_edges, random_graph
+from graphgen import csr_from_edges, planted_graph, random_graph, scan_geometry, second_trip_plan
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -78,7 +78,21 @@ def _standin_fp32(ip, ix, x, w, al, ar, relu, fm, p_feat, am, p_attn, gy):
     return out.detach().numpy().reshape(n, -1), tx.grad.numpy(), tw.grad.numpy(), tl.grad.numpy(), tr.grad.numpy()
 
 
-SHAPES = [(8, 16), (8, 8), (8, 7), (1, 47), (1, 7), (1, 16)]
+# (H, F) -> gat_rows_kernel<KIND, LPR, UNI> (gat.hip rows_launch: LPR = pow2 >= ceil(H F / 4), at least 4; UNI = F % 4 == 0) and
+# HP = pow2 >= H, the head lanes of the score sweeps.  docs/KERNEL_COVERAGE.md lists which case runs which instantiation.
+SHAPES = [(8, 16), (8, 8), (8, 7), (1, 47), (1, 7), (1, 16),
+          (1, 1),        # LPR 4, one live column
+          (3, 5),        # LPR 4, HP 4 with one dead head lane
+          (2, 12),       # LPR 8, UNI
+          (5, 6),        # LPR 8, HP 8 with three dead head lanes
+          (9, 9),        # LPR 32 without UNI, HP 16 with seven dead head lanes
+          (16, 3),       # LPR 16, a lane's four columns span two heads, HP 16
+          (64, 1),       # LPR 16, four heads per lane, HP 64: one edge per step, no butterfly
+          (6, 40),       # LPR 64, UNI
+          (7, 33),       # LPR 64 with padding lanes
+          (33, 7),       # LPR 64, HP 64 with 31 dead head lanes
+          (64, 4),       # LPR 64, UNI: heads = 64 and heads * out_feats = 256 at once
+          (1, 256)]      # LPR 64, HP 1, the full-width row
 
 
 def test_graph_has_the_rows_the_kernels_branch_on(graph):
@@ -91,15 +105,11 @@ def test_graph_has_the_rows_the_kernels_branch_on(graph):
     assert len(np.unique(pairs, axis=0)) < len(pairs)
 
 
-@pytest.mark.parametrize("H,F", SHAPES)
-@pytest.mark.parametrize("p_attn", [0.0, 0.3])
-def test_layer_forward_and_backward_match_the_oracle(graph, H, F, p_attn):
-    """Scores, attention forward (+ ReLU on the multi-head shapes), attention backward, weight and input gradients against the oracle fed
-    the masks the helpers write: dropping exactly the helper's edges / elements in the oracle reproduces the kernels' output."""
+def _check_layer(ip, ix, g, H, F, p_attn, d_in=20):
+    """One layer on graph (ip, ix, g) against the oracle fed the masks the helpers write; every figure is printed before it is asserted."""
     from glnn_amd import ops
     from glnn_amd.autograd import gat_layer_bwd, gat_layer_fwd
-    ip, ix, g = graph
-    n, nnz, d_in = len(ip) - 1, len(ix), 20
+    n, nnz = len(ip) - 1, len(ix)
     relu = H > 1
     p_feat = 0.4 if p_attn > 0 else 0.0
     fs, as_ = 1234 + H, 99 + F
@@ -125,14 +135,75 @@ def test_layer_forward_and_backward_match_the_oracle(graph, H, F, p_attn):
     standin = {"dW": sdw, "dattn_l": sdl, "dattn_r": sdr, "dx": sdx}
     for name, a, b in got:
         e32 = f" fp32 stand-in max|err| {np.abs(standin[name] - b).max():.3e}" if name in standin else ""
-        print(f"H={H} F={F} p_attn={p_attn} {name}: max|err| {np.abs(a - b).max():.3e} max|ref| {np.abs(b).max():.3e}{e32}")
+        print(f"n={n} H={H} F={F} p_attn={p_attn} {name}: max|err| {np.abs(a - b).max():.3e} max|ref| {np.abs(b).max():.3e}{e32}")
     for name, a, b in got:
-        # the APPNP kernel bound, or -- where fp32 accumulation over the 600 rows of these unscaled inputs costs more than that -- 4x the
+        # the APPNP kernel bound, or -- where fp32 accumulation over the graph's rows of these unscaled inputs costs more than that -- 4x the
         # error the fp32 stand-in itself shows against the oracle on the same inputs (docs/GAT_SEMANTICS.md, Tolerances).  dz: APPNP bound only.
         e32 = np.abs(standin[name] - b).max() if name in standin else 0.0
         tol = np.maximum(1e-4 + 1e-4 * np.abs(b), 4.0 * e32)
         bad = np.abs(a - b) > tol
         assert not bad.any(), f"{name}: {bad.sum()} elements, max|err| {np.abs(a - b).max():.3e}, fp32 stand-in max|err| {e32:.3e}"
+
+
+@pytest.mark.parametrize("H,F", SHAPES)
+@pytest.mark.parametrize("p_attn", [0.0, 0.3])
+def test_layer_forward_and_backward_match_the_oracle(graph, H, F, p_attn):
+    """Scores, attention forward (+ ReLU on the multi-head shapes), attention backward, weight and input gradients against the oracle fed
+    the masks the helpers write: dropping exactly the helper's edges / elements in the oracle reproduces the kernels' output.
+
+    (H, F) = (1, 256) is the hard case for the backward's arithmetic: one head of 256 unscaled features gives scores of +-40 and rows
+    whose softmax is nearly one-hot, and a hub source sums 700 ds (docs/GAT_SEMANTICS.md, D_i)."""
+    ip, ix, g = graph
+    _check_layer(ip, ix, g, H, F, p_attn)
+
+
+# ---------------------------------------------------------------------------------------------------------------- launch geometry
+# The numbers rows_launch and gat_rows_kernel derive the grid from, mirrored by name (csrc/gat.hip):
+K_BLOCK = 512                 # gat.hip `constexpr int kBlock`: the rows one trip of the long-row scan looks at (n_chunks = ceil(n / kBlock) in gat_rows_kernel)
+K_WAVES = K_BLOCK // 64       # gat.hip `constexpr int kWaves`
+K_ROWS_PER_WAVE = 8           # gat.hip `constexpr int kRowsPerWave`
+K_LONG_ROW = 128              # gat.hip `constexpr int kLongRow`: a row above it is a whole workgroup's
+K_LONG_BLOCK_ROWS = 512       # gat.hip `constexpr int kLongBlockRows`
+K_LONG_BLOCK_CAP = 512        # gat.hip `constexpr int kLongBlockCap`
+BIG_N = K_LONG_BLOCK_ROWS * K_LONG_BLOCK_CAP + 656      # 262 800: just above the size at which every scan chunk has a workgroup of its own
+
+
+def _geometry(n):
+    """(n_chunks, n_long_blocks, rows_per_block) as gat.hip's rows_launch sets them and the scan loop `for (chunk = blockIdx.x; ...)` of gat_rows_kernel uses them."""
+    return scan_geometry(n, K_BLOCK, K_WAVES, K_ROWS_PER_WAVE, K_LONG_BLOCK_ROWS, K_LONG_BLOCK_CAP)
+
+
+@pytest.fixture(scope="module")
+def big_graph():
+    from glnn_amd.graph import CSRGraph
+    n_chunks, n_long_blocks, _ = _geometry(BIG_N)
+    ip, ix = planted_graph(BIG_N, 17, *second_trip_plan(BIG_N, n_chunks, n_long_blocks, K_LONG_ROW))
+    return ip, ix, CSRGraph(torch.from_numpy(ip).to(DEV), torch.from_numpy(ix).to(DEV), BIG_N)
+
+
+def test_big_graph_has_the_rows_the_launch_geometry_branches_on(big_graph):
+    ip, ix, _ = big_graph
+    n = len(ip) - 1
+    n_chunks, n_long_blocks, rows_per_block = _geometry(n)
+    assert n > K_LONG_BLOCK_ROWS * K_LONG_BLOCK_CAP and n_chunks > n_long_blocks          # the scan loop makes a second trip
+    assert rows_per_block == K_ROWS_PER_WAVE * K_WAVES and n % rows_per_block != 0         # a wave takes eight rows; ragged last block
+    deg, out_deg = np.diff(ip), np.bincount(ix, minlength=n)
+    for d in (deg, out_deg):                                                # the in-CSR passes and the source pass over the transpose
+        long_rows = np.flatnonzero(d > K_LONG_ROW)
+        assert (long_rows % n_chunks >= n_long_blocks).sum() >= 2 and (long_rows % n_chunks < n_long_blocks).sum() >= 2
+        assert {K_LONG_ROW - 1, K_LONG_ROW, K_LONG_ROW + 1} <= set(d.tolist())
+        assert ((d > 64) & (d < K_LONG_ROW)).any()                           # a one-wave row of two 64-entry chunks
+    assert deg.min() == 1 and (deg == 1).sum() > 100 and 2.5 < deg.mean() < 3.5
+    last_block = np.arange(n - n % rows_per_block, n)
+    assert len(last_block) < rows_per_block and (deg[last_block] > 0).all()
+
+
+def test_large_n_layer_matches_the_oracle(big_graph):
+    """The launch geometry a 600-row graph never reaches (gat.hip rows_launch / gat_rows_kernel): eight rows per wave, a last block that
+    ends before its rows do, and long rows -- destinations and, for the source pass, sources -- that the scan finds on its second trip.
+    dattn_l / dattn_r sum over all 262 800 rows: the 4x-stand-in clause of the tolerance rule is the one that decides them."""
+    ip, ix, g = big_graph
+    _check_layer(ip, ix, g, 2, 4, 0.3, d_in=8)
 
 
 def test_attention_mask_helper_keep_fraction_and_independence():
@@ -147,7 +218,7 @@ def test_attention_mask_helper_keep_fraction_and_independence():
     assert ops.gat_attn_mask(nnz, H, 0.0, 7, DEV).all()
 
 
-@pytest.mark.parametrize("H,F", [(8, 16), (1, 47), (8, 7)])
+@pytest.mark.parametrize("H,F", [(8, 16), (1, 47), (8, 7), (5, 6), (33, 7)])
 def test_two_runs_are_bit_identical(H, F):
     from glnn_amd import ops
     from glnn_amd.autograd import gat_layer_bwd, gat_layer_fwd
@@ -316,6 +387,18 @@ def test_zero_in_degree_raises_and_the_refusals(gold):
         dist.ShardedTeacher(m.encoder, g, None, None)
     with pytest.raises(NotImplementedError, match="not sharded"):
         dist.HaloShardedTeacher(m.encoder, g, None, None)
+    # the attention kernels' own limits, through ops: heads <= 64 and heads * out_feats <= 256 (gat.hip set_shape)
+    from glnn_amd import ops
+    from glnn_amd._lib import GlnnError
+    loops = CSRGraph(torch.arange(4, dtype=torch.int64, device=DEV), torch.arange(3, dtype=torch.int32, device=DEV), 3)
+    for H, F in ((65, 1), (1, 257), (64, 5)):
+        z, al, s3 = torch.zeros(3, H * F, device=DEV), torch.zeros(1, H, F, device=DEV), torch.zeros(3, H, device=DEV)
+        with pytest.raises(GlnnError, match=r"heads <= 64 and heads \* out_feats <= 256"):
+            ops.gat_scores(z, al, al, H, F)
+        with pytest.raises(GlnnError, match=r"heads <= 64 and heads \* out_feats <= 256"):
+            ops.gat_attn_fwd(loops.indptr, loops.indices, 3, z, s3, s3, H, F)
+        with pytest.raises(GlnnError, match=r"heads <= 64 and heads \* out_feats <= 256"):
+            ops.gat_attn_bwd(loops, z, s3, s3, s3, al, al, z, z, H, F)
 
 
 # ---------------------------------------------------------------------------------------------------------------- command lines

@@ -607,7 +607,13 @@ def test_softmax_loss_indexed_targets_and_accum(n, rows, c):
     np.testing.assert_allclose(d2.cpu().numpy(), g2, atol=1e-6, rtol=1e-4)
 
 
-@pytest.mark.parametrize("rows,k,c,p", [(4096, 2048, 47, 0.2), (4001, 256, 40, 0.5), (1030, 512, 7, 0.0), (2500, 1024, 48, 0.3), (4096, 768, 1, 0.1)])
+# k -> cls_fwd_kernel<XF, STEPS> (cls_block.hip cls_fwd: STEPS = k / 256 unrolled for 1, 2, 4, 8, 16, else the generic loop; XF = 2 with
+# dropout, 1 with the affine tail alone, 0 for the stored-tail calls of (b)).  The second row: STEPS 16 under all three transforms (k = 4096,
+# 53 KB of static + 32 KB of dynamic LDS) and the generic loop at 9 and 5 steps, rows just above the kernel's floor of 1024.
+# The third row: the pairs no other row reaches (docs/KERNEL_COVERAGE.md), <1, 1>, <1, 4>, <1, 8> and <2, 2>.
+@pytest.mark.parametrize("rows,k,c,p", [(4096, 2048, 47, 0.2), (4001, 256, 40, 0.5), (1030, 512, 7, 0.0), (2500, 1024, 48, 0.3), (4096, 768, 1, 0.1),
+                                        (1030, 4096, 47, 0.2), (1100, 4096, 7, 0.0), (1500, 2304, 40, 0.3), (1030, 1280, 48, 0.0),
+                                        (1030, 256, 7, 0.0), (1030, 1024, 7, 0.0), (1030, 2048, 7, 0.0), (1030, 512, 7, 0.3)])
 @pytest.mark.parametrize("kind", ["nll", "kl"])
 def test_classifier_loss_one_launch_vs_oracle_and_the_two_launch_form(rows, k, c, p, kind):
     """glnn_classifier_loss_f32 (cls_block.hip): logits = dropout(relu(z * a_scale + a_shift)) . W^T + b by 16-row workgroups with the
@@ -637,6 +643,8 @@ def test_classifier_loss_one_launch_vs_oracle_and_the_two_launch_form(rows, k, c
     # (a)
     act = ops.act_fwd(z, sc, sh, p, seed)
     ref = act.double() @ w.double().t() + b.double()
+    print(f"rows={rows} k={k} c={c} p={p} {kind}: max|logits - fp64| {float((logits.double() - ref).abs().max()):.3e}, plain fp32 matmul "
+          f"{float(((act @ w.t() + b).double() - ref).abs().max()):.3e}")
     assert float((logits.double() - ref).abs().max()) < TOL
     tgt = y_all[idx.cpu().numpy()] if kind == "nll" else t_all[idx.cpu().numpy()]
     loss_w, dz_w = so.loss_and_dlogits(logits.cpu().numpy(), tgt, kind, lamb)

@@ -21,7 +21,9 @@ N_SRC = 300
 HUB, HUB_EDGES = 17, 3000          # far above the kernels' long-row threshold (128 in-edges: the whole workgroup takes the row)
 LONG, LONG_EDGES = 50, 130         # just above it
 ISOLATED = (3, 40, 69, 200, 299)
-WIDTHS = [(100, 256), (256, 256), (256, 47), (12, 40), (5, 3)]
+# d_in picks sage_mean_fused_kernel<LPR> (16 / 32 / 64 up to 64 / 128 / 256 columns), d_out picks spmm_sage_mean_kernel<dv> of the
+# project-first form in the same way: (12, 65) is the smallest d_out on its <32> (docs/KERNEL_COVERAGE.md)
+WIDTHS = [(100, 256), (256, 256), (256, 47), (12, 40), (5, 3), (12, 65)]
 
 
 @functools.lru_cache(maxsize=None)

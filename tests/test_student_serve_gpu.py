@@ -35,6 +35,18 @@ def _product_inputs(k, n, seed):
 @pytest.mark.parametrize("n", NS)
 @pytest.mark.parametrize("k", KS)
 def test_gemm_bf16_against_fp64(k, n):
+    _check_gemm_bf16(k, n, MS)
+
+
+@pytest.mark.parametrize("n", [47, 256])
+def test_gemm_bf16_on_the_32x32_mfma_against_fp64(monkeypatch, n):
+    """GLNN_GEMM_BF16_MFMA16=0: the MF = 32 instantiations of gemm_bf16_kernel (v_mfma_f32_32x32x16_bf16), both tile widths, every
+    operand / output type and the log-softmax epilogue, under the bounds of the default shape."""
+    monkeypatch.setenv("GLNN_GEMM_BF16_MFMA16", "0")
+    _check_gemm_bf16(100, n, [31, 257])
+
+
+def _check_gemm_bf16(k, n, ms):
     from glnn_amd import ops
     a, w, es, eh, prod = _product_inputs(k, n, seed=1000 * k + n)
     a16 = ops.as_bf16_feat(a.to(DEV))
@@ -43,7 +55,7 @@ def test_gemm_bf16_against_fp64(k, n):
     assert wp.stride(0) % 64 == 0 and np.array_equal(br.bits(wp), br.bits(w))        # the pack is the plain rounding (exact here)
     est, eht = torch.from_numpy(es).to(DEV), torch.from_numpy(eh).to(DEV)
     worst32, worst_lsm = 0.0, 0.0
-    for m in MS:
+    for m in ms:
         for epi in (False, True):
             want = np.maximum(prod[:m] * es.astype(np.float64) + eh.astype(np.float64), 0.0) if epi else prod[:m]
             kw = dict(ep_scale=est, ep_shift=eht, relu=True) if epi else {}
