@@ -92,6 +92,9 @@ SIGNATURES = {
                                 c_vp, c_i64, c_vp, c_i64, c_vp],
     "glnn_csr_transpose_eids": [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "glnn_edge_drop_mask_u8": [c_i64, c_int, c_f32, c_u32, c_vp, c_vp],
+    "glnn_gpr_prop_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp,
+                          c_i64, c_vp, c_vp],
+    "glnn_gpr_fold_f32": [c_vp, c_int, c_i64, c_vp, c_vp, c_i64, c_vp],
     "glnn_gat_scores_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "glnn_gat_attn_fwd_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_u32, c_int, c_vp, c_i64,
                               c_vp, c_vp],
@@ -109,6 +112,7 @@ SIGNATURES = {
 }
 
 MLP_MAX_LAYERS = 8
+GPR_FOLD_CHUNK = 4096          # GLNN_GPR_FOLD_CHUNK of include/glnn_hip.h
 MLP_COUNTERS = 1024
 _F = ctypes.c_void_p * MLP_MAX_LAYERS
 

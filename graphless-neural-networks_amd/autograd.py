@@ -253,6 +253,72 @@ def appnp_propagate(graph, h0, k, alpha, edge_drop, training):
         return appnp_fwd(graph, h0, int(k), float(alpha), p, seed)
 
 
+# ------------------------------------------------------------------------------------------ GPR-GNN propagation (docs/GPR_SEMANTICS.md)
+def _gpr_run(csr, nnz, x0, gamma, k, first_norm, row_norm, h0=None):
+    """acc = sum_{j <= k} gamma[j] Q^j x0 over `csr` (Q = diag(row_norm) A diag(first_norm)): K launches of glnn_gpr_prop_f32 ping-ponging
+    two buffers (the step-K row is not stored), or the k = 0 entry alone.  h0: also the per-row scalars <Q^j x0, h0>; returns (acc, row_dot)."""
+    n, d = x0.shape
+    acc = ops.feat_empty(n, d, x0.device)
+    row_dot = None
+    if h0 is not None:
+        row_dot = torch.empty((k + 1) * ops.gpr_col_tiles(d) * n, dtype=torch.float32, device=x0.device)
+    if k == 0:
+        ops.gpr_prop(None, None, 0, x0, 0, None, None, None, gamma, acc, h0=h0, row_dot=row_dot)
+        return acc, row_dot
+    bufs = [ops.feat_empty(n, d, x0.device) for _ in range(min(k - 1, 2))]
+    x = x0
+    for j in range(1, k + 1):
+        x = ops.gpr_prop(csr.indptr, csr.indices, nnz, x, j, first_norm if j == 1 else None, row_norm, first_norm, gamma, acc,
+                         out=None if j == k else bufs[j % len(bufs)], h0=h0, row_dot=row_dot)
+    return acc, row_dot
+
+
+def gpr_fwd(g, h0, gamma, k):
+    """out = sum_{j = 0..K} gamma[j] P^j h0,  P = D_in^-1/2 A D_out^-1/2 (APPNP's operator; A[i, j] = the number of edges j -> i).  gamma
+    [K + 1] is read on the device."""
+    h0 = ops.as_feat(h0)
+    in_norm, out_norm = g.degree_norms()
+    return _gpr_run(g, g.num_edges(), h0, gamma, int(k), out_norm, in_norm)[0]
+
+
+def gpr_bwd(g, dy, h0, gamma, k):
+    """(dL/dh0, dL/dgamma) from dy = dL/dout:  G_0 = dy, G_j = P^T G_{j-1} (a gather over the transposed CSR with the norms swapped);
+    dh0 = sum gamma[j] G_j, dgamma[j] = <G_j, h0>.  No forward iterate is saved: the per-row dots leave the K launches' epilogues and
+    glnn_gpr_fold_f32 sums them in a fixed order."""
+    dy, h0 = ops.as_feat(dy), ops.as_feat(h0)
+    n, d = dy.shape
+    k = int(k)
+    in_norm, out_norm = g.degree_norms()
+    tg = g.transposed(False)
+    dh0, row_dot = _gpr_run(tg, g.num_edges(), dy, gamma, k, in_norm, out_norm, h0=h0)
+    return dh0, ops.gpr_fold(row_dot, k + 1, ops.gpr_col_tiles(d) * n)
+
+
+class GprPropFn(torch.autograd.Function):
+    """GPRConv as a differentiable op on the HIP path: gradients for the trunk's logits and for the K + 1 coefficients."""
+
+    @staticmethod
+    def forward(ctx, graph, h0, gamma, k):
+        h0 = ops.as_feat(h0.detach())
+        ctx.graph, ctx.k = graph, k
+        ctx.save_for_backward(h0, gamma)
+        return gpr_fwd(graph, h0, gamma.detach(), k)
+
+    @staticmethod
+    def backward(ctx, dy):
+        h0, gamma = ctx.saved_tensors
+        dh0, dgamma = gpr_bwd(ctx.graph, dy.contiguous(), h0, gamma.detach(), ctx.k)
+        return None, dh0 if ctx.needs_input_grad[1] else None, dgamma if ctx.needs_input_grad[2] else None, None
+
+
+def gpr_propagate(graph, h0, gamma, k, training):
+    """GPRConv forward: differentiable in training mode (appnp_propagate's rule); the eval forward keeps nothing for a backward."""
+    if training and torch.is_grad_enabled() and (h0.requires_grad or gamma.requires_grad):
+        return GprPropFn.apply(graph, h0, gamma, int(k))
+    with torch.no_grad():
+        return gpr_fwd(graph, h0, gamma, int(k))
+
+
 # ------------------------------------------------------------------------------------------ GAT layer (dgl 0.6.1 GATConv)
 def gat_layer_fwd(g, x, w, attn_l, attn_r, heads, out_feats, slope, relu, feat_p=0.0, feat_seed=0, attn_p=0.0, attn_seed=0, signed=True,
                   want_lse=False):

@@ -384,6 +384,12 @@ def _refuse_gat(encoder, who):
                                   "scores of the remote sources, an exchange the sharded forward does not have (whole-graph GAT only)")
 
 
+def _refuse_gpr(encoder, who):
+    if type(encoder).__name__ == "GPRGNN":
+        raise NotImplementedError(f"{who}: the GPRGNN teacher is not sharded -- each of its K propagation steps needs the previous step's "
+                                  "rows of the remote sources, an exchange the sharded forward does not have (whole-graph GPRGNN only)")
+
+
 def _refuse_mean(encoder, who):
     if getattr(encoder, "aggregator_type", "gcn") != "gcn":
         raise NotImplementedError(f"{who}: the sharded teacher forward implements the SAGE 'gcn' aggregator only -- a SAGE "
@@ -409,6 +415,7 @@ class ShardedTeacher:
                   the two: `shards` is replaced by shards.mixed(mixed_fraction) (whole chunks of either kind).
         All are chunked and overlapped when shards.chunks > 1; results are identical."""
         _refuse_gat(encoder, "ShardedTeacher")
+        _refuse_gpr(encoder, "ShardedTeacher")
         _refuse_mean(encoder, "ShardedTeacher")
         if widening_exchange not in ("narrow", "wide", "mixed"):
             raise ValueError("ShardedTeacher: widening_exchange must be 'narrow', 'wide' or 'mixed'")
@@ -1001,6 +1008,7 @@ class HaloShardedTeacher:
         being exchanged runs in two passes over the split CSR of HaloPlan.split_csr (local-source edges + self first, then the
         remote-source edges once the halo has landed).  Same sums, local edges before remote ones (results equal to rounding)."""
         _refuse_gat(encoder, "HaloShardedTeacher")
+        _refuse_gpr(encoder, "HaloShardedTeacher")
         _refuse_mean(encoder, "HaloShardedTeacher")
         self.enc, self.g, self.sh, self.be, self.group, self.overlap = encoder, graph_shard, shards, be, group, overlap
         if graph_shard.n_dst != shards.rows:

@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .autograd import appnp_propagate, linear_fn, norm_act_drop
-from .nn import GATConv, GraphConv, SAGEConv
+from .nn import GATConv, GPRConv, GraphConv, SAGEConv
 
 
 def _bn_eval_fold(bn, bias):
@@ -609,6 +609,25 @@ class APPNP(MLP):
         return h_list, appnp_propagate(g, h, self.k, self.alpha, self.edge_drop, self.training)
 
 
+class GPRGNN(MLP):
+    """GPR-GNN (Chien et al., ICLR 2021; docs/GPR_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it): APPNP's MLP trunk (same
+    layers, norms and state_dict keys) followed by GPRConv(k, alpha, init) -- K propagation steps over APPNP's operator whose K + 1
+    mixing coefficients `propagate.gamma` are learned.  No edge dropout and no dropout in front of the propagation."""
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", k=10, alpha=0.1,
+                 init="PPR"):
+        super().__init__(num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, norm_type)
+        self.activation = activation
+        for layer in self.layers:          # (APPNP's trunk, draw for draw: its Linears are initialised once more)
+            layer.reset_parameters()
+        self.propagate = GPRConv(k, alpha, init)      # "Random" draws from torch's generator here, after the trunk's layers
+        self.k, self.alpha = self.propagate.k, self.propagate.alpha
+
+    def forward(self, g, feats):
+        h_list, h = super().forward(feats)
+        return h_list, self.propagate(g, h)
+
+
 class GAT(nn.Module):
     """reference models.py:202-279: num_layers GATConv layers, `num_heads` heads of hidden_dim // num_heads features on every hidden layer
     (ReLU inside the conv, outputs flattened to [N, hidden_dim] and kept in h_list), one head of output_dim features on the last (its
@@ -681,6 +700,9 @@ class Model(nn.Module):
             if heads < 1 or conf["hidden_dim"] < heads or conf["hidden_dim"] % heads:
                 raise ValueError(f"GAT: hidden_dim ({conf['hidden_dim']}) must be a positive multiple of num_heads ({heads})")
             self.encoder = GAT(activation=F.relu, num_heads=heads, attn_drop=conf["attn_dropout_ratio"], **common).to(conf["device"])
+        elif "GPRGNN" in conf["model_name"]:
+            self.encoder = GPRGNN(activation=F.relu, norm_type=conf["norm_type"], k=conf.get("gpr_k", 10), alpha=conf.get("gpr_alpha", 0.1),
+                                  init=conf.get("gpr_init", "PPR"), **common).to(conf["device"])
         else:
             raise ValueError(f"Unknown model_name {conf['model_name']}")
 

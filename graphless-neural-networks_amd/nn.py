@@ -3,6 +3,7 @@
   SAGEConv(in, out, "gcn")(block, (h, h_dst))   <- dgl.nn.SAGEConv, reference models.py:84-99,112,138
   GraphConv(in, out, activation=)(g, h)          <- dgl.nn.GraphConv, reference models.py:170-187,193
   GATConv(in, out, heads, ...)(g, h)             <- dgl.nn.GATConv, reference models.py:228-267 (docs/GAT_SEMANTICS.md)
+  GPRConv(k, alpha, init)(g, h)                  <- GPR-GNN's learned K-step propagation (no dgl counterpart; docs/GPR_SEMANTICS.md)
 
 Parameter names follow dgl 0.6.1 so that a reference `model.pth` loads: SAGEConv.fc_neigh.{weight,bias}
 (weight [out,in], xavier_uniform gain=relu; no fc_self for "gcn"), GraphConv.{weight [in,out] xavier_uniform,
@@ -12,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import GraphConvFn, SpmmFn, gat_conv, graphconv_fwd, linear_fn
+from .autograd import GraphConvFn, SpmmFn, gat_conv, gpr_propagate, graphconv_fwd, linear_fn
 
 
 FUSED_SAGE_MAX_IN = 256   # aggregate-first layers with d_in, d_out <= 256 take the single-launch K1F kernel.  Interleaved
@@ -268,3 +269,44 @@ class GATConv(nn.Module):
                      self.relu(), self.feat_drop.p, self.attn_drop.p, self.training, signed=not nonneg)
         return y.view(y.shape[0], self._num_heads, self._out_feats) if y.is_contiguous() else y.reshape(y.shape[0], self._num_heads,
                                                                                                         self._out_feats)
+
+
+GPR_INITS = ("PPR", "NPPR", "Random")
+
+
+class GPRConv(nn.Module):
+    """GPR-GNN propagation (Chien et al., ICLR 2021; docs/GPR_SEMANTICS.md): out = sum_{j = 0..K} gamma[j] P^j h with ONE parameter,
+    gamma [K + 1] fp32, and P = D_in^-1/2 A D_out^-1/2 (APPNP's operator).  No edge dropout, no dropout of its own, no zero-in-degree
+    error (a row without in-edges keeps gamma[0] h alone).  init: the paper's released initialisations "PPR" | "NPPR" | "Random"."""
+
+    def __init__(self, k=10, alpha=0.1, init="PPR"):
+        super().__init__()
+        if init not in GPR_INITS:
+            raise ValueError(f"GPRConv: init must be one of {GPR_INITS} (got {init!r})")
+        if int(k) < 0:
+            raise ValueError(f"GPRConv: k must be >= 0 (got {k})")
+        self.k, self.alpha, self.init = int(k), float(alpha), init
+        self.gamma = nn.Parameter(torch.empty(self.k + 1, dtype=torch.float32))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        k, a = self.k, self.alpha
+        j = torch.arange(k + 1, dtype=torch.float64)
+        with torch.no_grad():
+            if self.init == "PPR":               # APPNP's teleport weights: they sum to 1
+                g = a * (1.0 - a) ** j
+                g[k] = (1.0 - a) ** k
+            elif self.init == "NPPR":
+                g = a ** j
+                g = g / g.abs().sum()
+            else:                                # "Random": uniform(-b, b), b = sqrt(3 / (K + 1)), from torch's default generator
+                b = (3.0 / (k + 1)) ** 0.5
+                g = nn.init.uniform_(torch.empty(k + 1, dtype=torch.float32), -b, b).to(torch.float64)
+                g = g / g.abs().sum()
+            self.gamma.copy_(g.to(torch.float32))
+
+    def forward(self, graph, feat):
+        if (isinstance(graph, (list, tuple)) or isinstance(feat, tuple) or graph.num_dst_nodes() != graph.num_src_nodes()
+                or feat.shape[0] != graph.num_dst_nodes()):
+            raise NotImplementedError("GPRConv: block (bipartite) inputs are not implemented: GPR-GNN propagates over the whole graph")
+        return gpr_propagate(graph, feat, self.gamma, self.k, self.training)

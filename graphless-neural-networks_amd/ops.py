@@ -1374,6 +1374,67 @@ def appnp_propagate_bwd(t_indptr, t_indices, t_eids, x, nnz, t, first, dst_norm,
     return out
 
 
+# --------------------------------------------------------------------------------------------- GPR-GNN propagation
+def gpr_col_tiles(d):
+    """The 256-column tiles of a d-wide row: row_dot of gpr_prop holds one scalar per coefficient, tile and row."""
+    return (int(d) + 255) // 256
+
+
+def gpr_prop(indptr, indices, nnz, x, k, x_norm, row_norm, out_norm, gamma, acc, out=None, h0=None, row_dot=None):
+    """ONE step k of GPR-GNN propagation, glnn_gpr_prop_f32 (square graph, n = x.shape[0]), forward or backward by what the caller passes
+    (in-CSR with x_norm = out_norm = src_norm, row_norm = dst_norm; transposed CSR with the norms swapped):
+    row = row_norm * A (x_norm * x at k = 1, the pre-scaled x after it); acc = (gamma[0] * x at k = 1, else acc) + gamma[k] * row, in
+    place; out = out_norm * row unless out is None (the last step).  h0 + row_dot (the backward): row_dot[k] = the per-row <row, h0>, and
+    row_dot[0] = <x, h0> at k <= 1.  k = 0: acc = gamma[0] * x without a graph.  gamma is read on the device.  Returns out."""
+    _need_cuda(indptr, indices, x, x_norm, row_norm, out_norm, gamma, acc, out, h0, row_dot)
+    x = as_feat(x)
+    n, d = x.shape
+    k = int(k)
+    _mat(acc, "gpr_prop acc")
+    if tuple(acc.shape) != (n, d):
+        raise ValueError("gpr_prop: acc must have x's shape")
+    if gamma.dtype != torch.float32 or gamma.dim() != 1 or gamma.numel() < k + 1 or not gamma.is_contiguous():
+        raise ValueError(f"gpr_prop: gamma must be a contiguous float32 vector of >= {k + 1} coefficients")
+    if k > 0:
+        _appnp_check(indptr, indices, x, n, "gpr_prop")
+        _vec(row_norm, n, "row_norm")
+    if out is not None:
+        _mat(out, "gpr_prop out")
+        if tuple(out.shape) != (n, d):
+            raise ValueError("gpr_prop: out must have x's shape")
+    if (h0 is None) != (row_dot is None):
+        raise ValueError("gpr_prop: h0 and row_dot go together")
+    if h0 is not None:
+        h0 = as_feat(h0)
+        if tuple(h0.shape) != (n, d):
+            raise ValueError("gpr_prop: h0 must have x's shape")
+        if row_dot.dtype != torch.float32 or not row_dot.is_contiguous() or row_dot.numel() < (k + 1) * gpr_col_tiles(d) * n:
+            raise ValueError("gpr_prop: row_dot must be contiguous float32 with >= (k + 1) * ceil(d / 256) * n elements")
+    with _Timed("gpr_prop", d=d, n_dst=n, nnz=int(nnz), k=k):
+        rc = _lib.lib().glnn_gpr_prop_f32(_p(indptr), _p(indices), n, int(nnz), _p(x), _ld(x), d, _p(_vec(x_norm, n, "x_norm")),
+                                          _p(row_norm), _p(_vec(out_norm, n, "out_norm")), _p(gamma), k, _p(acc), _ld(acc), _p(out),
+                                          0 if out is None else _ld(out), _p(h0), 0 if h0 is None else _ld(h0), _p(row_dot), _stream())
+    _lib.check(rc, "glnn_gpr_prop_f32")
+    return out
+
+
+def gpr_fold(row_dot, rows, m, out=None):
+    """dgamma [rows] = the fixed-order fp64 row sums of row_dot [rows, m] (glnn_gpr_fold_f32: chunks of _lib.GPR_FOLD_CHUNK entries, then
+    the chunk partials)."""
+    _need_cuda(row_dot, out)
+    rows, m = int(rows), int(m)
+    if row_dot.dtype != torch.float32 or not row_dot.is_contiguous() or row_dot.numel() < rows * m:
+        raise ValueError("gpr_fold: row_dot must be contiguous float32 with >= rows * m elements")
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=row_dot.device)
+    _vec(out, rows, "gpr_fold out")
+    chunks = (m + _lib.GPR_FOLD_CHUNK - 1) // _lib.GPR_FOLD_CHUNK
+    ws = torch.empty(max(rows * chunks, 1), dtype=torch.float64, device=row_dot.device)
+    rc = _lib.lib().glnn_gpr_fold_f32(_p(row_dot), rows, m, _p(out), _p(ws), ws.numel() * 8, _stream())
+    _lib.check(rc, "glnn_gpr_fold_f32")
+    return out
+
+
 def csr_transpose_eids(indptr, indices, n_dst, n_src, nnz):
     """glnn_csr_transpose_eids: (t_indptr [n_src+1], t_indices [nnz], t_eids [nnz]) -- csr_transpose plus the original edge id (CSR
     position) of every transposed entry."""

@@ -35,7 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .autograd import appnp_bwd, appnp_fwd, gat_layer_bwd, gat_layer_fwd, graphconv_bwd, graphconv_fwd
+from .autograd import appnp_bwd, appnp_fwd, gat_layer_bwd, gat_layer_fwd, gpr_bwd, gpr_fwd, graphconv_bwd, graphconv_fwd
 from .student import _mix32
 
 
@@ -44,11 +44,11 @@ def _is_relu(act):
 
 
 def check_supported(model, criterion, optimizer):
-    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP or GAT teacher."""
+    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT or GPRGNN teacher."""
     enc = model.encoder
     name = model.model_name
-    if "MLP" in name or not ("SAGE" in name or "GCN" in name or "APPNP" in name or "GAT" in name):
-        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP or GAT teachers only (got {name})")
+    if "MLP" in name or not ("SAGE" in name or "GCN" in name or "APPNP" in name or "GAT" in name or "GPRGNN" in name):
+        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT or GPRGNN teachers only (got {name})")
     if not (isinstance(criterion, nn.NLLLoss) and criterion.reduction == "mean" and criterion.weight is None
             and criterion.ignore_index == -100):
         raise NotImplementedError("TeacherEngine: the criterion must be nn.NLLLoss() (reference train_teacher.py:237)")
@@ -64,6 +64,9 @@ def check_supported(model, criterion, optimizer):
     elif "APPNP" in name:
         if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
             raise NotImplementedError("TeacherEngine: APPNP with norm_type none|batch|layer and ReLU (models.py:282-344)")
+    elif "GPRGNN" in name:
+        if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
+            raise NotImplementedError("TeacherEngine: GPRGNN with norm_type none|batch|layer and ReLU (docs/GPR_SEMANTICS.md)")
     elif "GAT" in name:
         if not _is_relu(enc.activation) or any(not lay.relu() for lay in enc.layers[:-1]) or enc.layers[-1].relu():
             raise NotImplementedError("TeacherEngine: GAT with ReLU hidden layers and a linear last layer (models.py:202-279)")
@@ -133,7 +136,8 @@ class TeacherEngine:
     def __init__(self, model, optimizer):
         self.model, self.enc, self.opt = model, model.encoder, optimizer
         name = model.model_name
-        self.kind = "sage" if "SAGE" in name else ("appnp" if "APPNP" in name else ("gat" if "GAT" in name else "gcn"))
+        self.kind = "sage" if "SAGE" in name else ("appnp" if "APPNP" in name else ("gat" if "GAT" in name else
+                                                                                     ("gpr" if "GPRGNN" in name else "gcn")))
         self.L = self.enc.num_layers
         self.bn = getattr(self.enc, "norm_type", "none") == "batch"
         self.ln = getattr(self.enc, "norm_type", "none") == "layer"
@@ -674,9 +678,9 @@ class TeacherEngine:
             return dh
         return self._tail_bwd(l, dh, z, stats, seed, bias_grad)
 
-    def _step_appnp_body(self, g, feats, labels, idx_train, lamb):
+    def _trunk_fwd(self, feats):
+        """The MLP trunk of APPNP / GPRGNN in training mode: (trunk logits, layer inputs, saved tails)."""
         enc, L = self.enc, self.L
-        n = g.num_dst_nodes()
         a = ops.as_feat(feats)
         acts, saved = [a], []
         for l, layer in enumerate(enc.layers):
@@ -687,14 +691,11 @@ class TeacherEngine:
                 acts.append(a)
             else:
                 a = z
-        seed_e = self._edge_seed()
-        logits = appnp_fwd(g, a, enc.k, enc.alpha, enc.edge_drop, seed_e)
-        logits_tr = ops.gather_rows(logits, idx_train)                            # out[idx_train] (train_and_eval.py:22)
-        _, dl = ops.softmax_loss(logits_tr, ops.LOSS_NLL, float(lamb), labels=labels, label_rows=idx_train, loss_out=self.loss_out,
-                                 loss_accum=self.loss_accum, workspace=self.ws_loss)
-        dlog = ops.feat_empty(n, logits.shape[1], self.dev, zero=True)
-        ops.scatter_rows(dl, idx_train, dlog)
-        dz = appnp_bwd(g, dlog, enc.k, enc.alpha, enc.edge_drop, seed_e)         # d/d(trunk logits)
+        return a, acts, saved
+
+    def _trunk_bwd(self, dz, acts, saved):
+        """Gradients of every trunk parameter from dz = d/d(trunk logits)."""
+        enc, L = self.enc, self.L
         for l in range(L - 1, -1, -1):
             layer = enc.layers[l]
             ops.gemm_tn(dz, acts[l], out=self.grad(layer.weight), col_sum_a=self.grad(layer.bias))    # dW = dz^T a, db = sum dz
@@ -703,7 +704,48 @@ class TeacherEngine:
             da = ops.gemm(dz, layer.weight, w_is_kn=True)                        # dz W
             z, stats, seed = saved[l - 1]
             dz = self._appnp_tail_bwd(l - 1, da, z, stats, seed, None)
+
+    def _loss_grad(self, logits, labels, idx_train, lamb, n):
+        """NLL over out[idx_train] (train_and_eval.py:22) and its gradient scattered back to [n, C]."""
+        logits_tr = ops.gather_rows(logits, idx_train)
+        _, dl = ops.softmax_loss(logits_tr, ops.LOSS_NLL, float(lamb), labels=labels, label_rows=idx_train, loss_out=self.loss_out,
+                                 loss_accum=self.loss_accum, workspace=self.ws_loss)
+        dlog = ops.feat_empty(n, logits.shape[1], self.dev, zero=True)
+        ops.scatter_rows(dl, idx_train, dlog)
+        return dlog
+
+    def _step_appnp_body(self, g, feats, labels, idx_train, lamb):
+        enc = self.enc
+        a, acts, saved = self._trunk_fwd(feats)
+        seed_e = self._edge_seed()
+        logits = appnp_fwd(g, a, enc.k, enc.alpha, enc.edge_drop, seed_e)
+        dlog = self._loss_grad(logits, labels, idx_train, lamb, g.num_dst_nodes())
+        dz = appnp_bwd(g, dlog, enc.k, enc.alpha, enc.edge_drop, seed_e)         # d/d(trunk logits)
+        self._trunk_bwd(dz, acts, saved)
         ops.note_param_write()
+
+    # ------------------------------------------------------------------------------------------ full-graph GPR-GNN
+    @torch.no_grad()
+    def step_gpr(self, g, feats, labels, idx_train, lamb=1.0):
+        """The full-graph `train` step over GPRGNN (docs/GPR_SEMANTICS.md): the MLP trunk with its norm / ReLU / dropout tails, K launches
+        of glnn_gpr_prop_f32, NLL over idx_train, K launches over the transposed graph whose epilogues leave the per-row <G_k, h0>,
+        glnn_gpr_fold_f32 into grad(gamma), the trunk backward, and the ONE Adam launch (gamma is one more tensor of its table)."""
+        ops._need_cuda(feats, labels, idx_train, g.indptr)
+        self.step_count += 1
+        try:
+            enc = self.enc
+            gamma = enc.propagate.gamma
+            h0, acts, saved = self._trunk_fwd(feats)
+            logits = gpr_fwd(g, h0, gamma, enc.k)
+            dlog = self._loss_grad(logits, labels, idx_train, lamb, g.num_dst_nodes())
+            dz, dgamma = gpr_bwd(g, dlog, h0, gamma, enc.k)
+            self.grad(gamma).copy_(dgamma)
+            self._trunk_bwd(dz, acts, saved)
+            ops.note_param_write()
+        except Exception:
+            self.step_count -= 1          # the step never happened (see step_sage)
+            raise
+        self._adam()
 
 
     # ------------------------------------------------------------------------------------------ full-graph GAT

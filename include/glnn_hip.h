@@ -758,6 +758,34 @@ GLNN_API int glnn_csr_transpose_eids(const int64_t* indptr, const int32_t* indic
 GLNN_API int glnn_edge_drop_mask_u8(int64_t nnz, int t, float edge_drop, uint32_t seed, uint8_t* mask, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GPR-GNN propagation (Chien et al., ICLR 2021): result = sum_{k = 0..K} gamma[k] P^k x0 with K + 1 learned coefficients and APPNP's
+ * operator P = D_in^-1/2 A D_out^-1/2.  docs/GPR_SEMANTICS.md states the arithmetic.  ONE entry serves both directions, one call per
+ * step k = 1..K (k = 0 alone when K = 0); square graph of n nodes, nnz = indptr[n] < 2^31 (GLNN_ERR_UNSUPPORTED otherwise), no edge
+ * dropout.  Deterministic (no float atomics).
+ *   forward:   indptr / indices = the in-CSR,          x_norm = src_norm, row_norm = dst_norm, out_norm = src_norm, x0 = h0
+ *   backward:  indptr / indices = glnn_csr_transpose,  x_norm = dst_norm, row_norm = src_norm, out_norm = dst_norm, x0 = dL/dresult
+ *
+ * Step k >= 1:  row[i] = row_norm[i] sum_{e = (j -> i)} xs[j],  xs[j] = x_norm[j] x[j] at k = 1 (x = x0 unscaled; x_norm required), else
+ *   x[j] (x = the previous call's `out`, already scaled; x_norm must be NULL).
+ *     acc[i] = (k = 1 ? gamma[0] x[i] : acc[i]) + gamma[k] row[i]        -- after step K, acc is the result
+ *     out[i] = out_norm[i] row[i]                                          -- out may be NULL (step K: the row is not needed again)
+ *   h0 / row_dot (both or neither; the backward): row_dot[(k T + c) n + i] = sum over the columns of 256-column tile c of row[i] h0[i],
+ *     T = ceil(d / 256), and at k = 1 also row_dot[c n + i] from x; row_dot holds (K + 1) T n floats.
+ * k = 0 (K = 0, no propagation launch, the graph arguments are ignored): acc = gamma[0] x, row_dot[c n + i] as above.
+ * gamma [K + 1] is read on the device.  Padding columns [d, ld) of acc and out are written as 0.  acc and out alias no input. */
+GLNN_API int glnn_gpr_prop_f32(const int64_t* indptr, const int32_t* indices, int64_t n, int64_t nnz, const float* x, int64_t ldx,
+                               int d, const float* x_norm, const float* row_norm, const float* out_norm, const float* gamma, int k,
+                               float* acc, int64_t ldacc, float* out, int64_t ldo, const float* h0, int64_t ldh0, float* row_dot,
+                               void* stream);
+/* dgamma[r] = sum of row_dot[r m .. r m + m) for r < rows (rows = K + 1, m = T n), accumulated in fp64 in a geometry that depends on m
+ * alone: stage 1 sums chunks of GLNN_GPR_FOLD_CHUNK entries (thread t of 256 takes entries t, t + 256, ...; xor tree over the lanes, the
+ * four waves in order), stage 2 sums the chunk partials the same way.  workspace: rows * ceil(m / GLNN_GPR_FOLD_CHUNK) * 8 bytes, 8-byte
+ * aligned.  m = 0 writes zeros. */
+#define GLNN_GPR_FOLD_CHUNK 4096
+GLNN_API int glnn_gpr_fold_f32(const float* row_dot, int rows, int64_t m, float* dgamma, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * GAT attention (dgl 0.6.1 GATConv of the reference GAT teacher, models.py:202-279): per-destination edge softmax with per-edge scores
  * from two per-node scalars per head.  docs/GAT_SEMANTICS.md states the arithmetic.  Square graph of n nodes, indptr / indices the in-CSR
  * (rows = destinations, edge id = CSR position); z [n, heads * out_feats] the projected rows, head-major columns.  heads <= 64,
