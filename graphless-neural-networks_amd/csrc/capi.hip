@@ -46,6 +46,7 @@ static void load_options(Options& o) {
   o.bn0_in_gemm = (int)env_ll("GLNN_STUDENT_BN0_IN_GEMM", 1);
   o.bn0_consts_in_gemm = (int)env_ll("GLNN_STUDENT_BN0_CONSTS_IN_GEMM", 1);
   o.gemm_bf16_mfma16 = (int)env_ll("GLNN_GEMM_BF16_MFMA16", 1);
+  o.agg_in_rowwalk = (int)env_ll("GLNN_AGG_IN_ROWWALK", 1);
 }
 static Options g_opts;
 static std::once_flag g_opts_once;

@@ -41,6 +41,10 @@ struct RpArgs {
   // optional column statistics of C (BatchNorm training): workgroup (x, y) leaves, for each of its 128 columns, the count / mean / M2 of
   // the rows it wrote at st_*[x * n + col] -- accumulated in registers along its walk, from the very values it stores
   float* st_cnt; float* st_mean; float* st_m2;
+  // the wave-walk kernel only: wp_kgroups != 0 -- `w` is not W [n, ldw] but its MFMA B-fragment packing (pack_weight_kernel of spmm.hip):
+  // wp[nt][kg][lane][t] = W[32 nt + (lane & 31)][8 kg + 4 (lane >> 5) + t], wp_ntiles = ceil(n / 32) tiles of wp_kgroups == KG k-groups,
+  // zero behind n and behind the packed width
+  int wp_kgroups; int wp_ntiles;
 };
 
 __device__ __forceinline__ float4 rp_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -243,7 +247,8 @@ __global__ __launch_bounds__(kRpThreads) void gemm_rowpanel_kernel(const RpArgs 
 // ---------------------------------------------------------------------------------------------
 // K3w (round 5): the WAVE-WALK form.  Same product, same k order per output element (bit-identical results), but no workgroup
 // tile, no LDS staging of A and no barrier in the walk at all:
-//   * a workgroup still shares ONE thing: the 128-column panel of W in LDS, loaded once (one barrier, before the walk);
+//   * a workgroup still shares ONE thing: the 128-column panel of W in LDS, loaded once (one barrier, before the walk) -- from W [n, k]
+//     or, for the kept-aggregate hit path of glnn_sage_fused_agg_f32 (glnn::gemm_rowwalk_packed), from its MFMA B-fragment packing;
 //   * every WAVE walks its own sequence of 32-row tiles of A and owns the whole 32 x 128 output tile (four 32 x 32 MFMA blocks:
 //     every A value feeds four MFMAs, every ds_read_b128 of a W fragment feeds four);
 //   * A never touches LDS: lane (li, kk) of the 32x32x2 MFMA needs A[row li][8 kg + 4 kk .. +3] -- one float4 per k-group, loaded
@@ -354,14 +359,29 @@ __global__ __launch_bounds__(64 * kRwWaves) void gemm_rowwalk_kernel(const RpArg
       else RW_BLOAD(af[kg], a_voff, rs0, kg * 32);
     });
   }
-  if (g.k < KP) {
-    for (int r = tid; r < kRpCols; r += 64 * kRwWaves) *reinterpret_cast<float4*>(lds + r * KS + g.k) = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  for (int f = tid; f < kRpCols * kv; f += 64 * kRwWaves) {
-    const int row = f / kv, c = f - row * kv;
-    int ng = n0 + row;
-    if (ng > g.n - 1) ng = g.n - 1;              // columns past n: a valid row re-read, never stored
-    *reinterpret_cast<float4*>(lds + row * KS + 4 * c) = rp_ld4(g.w + (int64_t)ng * g.ldw + 4 * c);
+  if (g.wp_kgroups == 0) {
+    if (g.k < KP) {
+      for (int r = tid; r < kRpCols; r += 64 * kRwWaves) *reinterpret_cast<float4*>(lds + r * KS + g.k) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int f = tid; f < kRpCols * kv; f += 64 * kRwWaves) {
+      const int row = f / kv, c = f - row * kv;
+      int ng = n0 + row;
+      if (ng > g.n - 1) ng = g.n - 1;              // columns past n: a valid row re-read, never stored
+      *reinterpret_cast<float4*>(lds + row * KS + 4 * c) = rp_ld4(g.w + (int64_t)ng * g.ldw + 4 * c);
+    }
+  } else {
+    // the packed panel: float4 (kg, lane) of 32-column tile nt is W[32 nt + (lane & 31)][8 kg + 4 (lane >> 5) .. + 3] -- panel row
+    // 32 ntl + (lane & 31), floats 8 kg + 4 (lane >> 5) on.  Consecutive threads read consecutive float4 of the buffer; the 32 rows a
+    // half-wave writes are KS floats apart (conflict-free, as the fragment reads).  The packing holds all KG k-groups with zeros behind
+    // the packed width: every float of [0, KP) of every panel row is written, nothing to zero first.
+    const float4* wp = reinterpret_cast<const float4*>(g.w);
+    for (int f = tid; f < kRpCols * 2 * KG; f += 64 * kRwWaves) {
+      const int ntl = f / (64 * KG), rem = f - ntl * (64 * KG);
+      const int kgq = rem >> 6, l = rem & 63;
+      int nt = (n0 >> 5) + ntl;
+      if (nt > g.wp_ntiles - 1) nt = g.wp_ntiles - 1;      // tiles past the packed buffer: a valid tile re-read, never stored (its columns are >= n)
+      *reinterpret_cast<float4*>(lds + (32 * ntl + (l & 31)) * KS + 8 * kgq + 4 * (l >> 5)) = wp[((int64_t)nt * KG + kgq) * 64 + l];
+    }
   }
   __syncthreads();
 
@@ -519,10 +539,12 @@ int launch_rowpanel(const RpArgs& g, int grid_x, int panels, hipStream_t st) {
 // GLNN_ERR_UNSUPPORTED = nothing launched (the caller takes the tiled kernels): plain float4-addressable operands, W [n, k] with
 // 36 <= k <= 128 (k % 4 == 0) -- from k = 129 on the pipelined k loop of gemm.hip amortises its prologue -- and enough rows that every
 // workgroup walks >= 2 tiles of a full-chip grid.
-int glnn::gemm_rowpanel(const float* a, int64_t lda, int64_t m, int k, const float* w, int64_t ldw, int n, const float* ep_scale,
-                        const float* ep_shift, int relu, float* c, int64_t ldc, void* stream, glnn::ColStats* cs) {
+// wp_kgroups != 0: `w` is the packed form (RpArgs) and ldw is not used -- the wave-walk kernel or nothing
+static int rowpanel_impl(const float* a, int64_t lda, int64_t m, int k, const float* w, int64_t ldw, int n, const float* ep_scale,
+                         const float* ep_shift, int relu, float* c, int64_t ldc, void* stream, glnn::ColStats* cs, int wp_kgroups) {
   if (k < 36 || k > 128 || (k & 3) || m < 2048 || n < 96) return GLNN_ERR_UNSUPPORTED;
-  if ((lda & 3) || (ldw & 3) || lda < k || ldw < k || ldc < n || !glnn::aligned16(a) || !glnn::aligned16(w)) return GLNN_ERR_UNSUPPORTED;
+  if ((lda & 3) || lda < k || ldc < n || !glnn::aligned16(a) || !glnn::aligned16(w)) return GLNN_ERR_UNSUPPORTED;
+  if (wp_kgroups == 0 && ((ldw & 3) || ldw < k)) return GLNN_ERR_UNSUPPORTED;
   if (lda >= (1 << 22) || ldc >= (1 << 22)) return GLNN_ERR_UNSUPPORTED;      // a 64-row tile must fit a 2 GiB buffer window
   RpArgs g;
   g.a = a; g.lda = lda; g.m = m; g.k = k; g.w = w; g.ldw = ldw; g.n = n; g.ep_scale = ep_scale; g.ep_shift = ep_shift; g.relu = relu;
@@ -531,6 +553,8 @@ int glnn::gemm_rowpanel(const float* a, int64_t lda, int64_t m, int k, const flo
   const int kg = (k + 7) / 8;
   const int panels = (n + kRpCols - 1) / kRpCols;
   if (panels > 65535) return GLNN_ERR_UNSUPPORTED;
+  g.wp_kgroups = wp_kgroups; g.wp_ntiles = (n + 31) / 32;
+  if (wp_kgroups != 0 && (wp_kgroups != kg || cs || glnn::opts().gemm_rowpanel == 2)) return GLNN_ERR_UNSUPPORTED;
   // which form: the wave-walk kernel (round 5) takes the plain products; a product whose epilogue also leaves BatchNorm statistics stays on the
   // workgroup-tile kernel of round 4 (the statistics' VALU work next to the walk's asm-managed registers made the compiler spill them;
   // measured slower as well: 336 vs 309 us on 0.5 M x 100 x 256).  GLNN_GEMM_ROWPANEL=2: everything on the round-4 form (A/B, tests).
@@ -581,4 +605,15 @@ int glnn::gemm_rowpanel(const float* a, int64_t lda, int64_t m, int k, const flo
     cs->nparts = (int)gx; cs->chunk_rows = 0; cs->done = 1;
   }
   return rc;
+}
+
+int glnn::gemm_rowpanel(const float* a, int64_t lda, int64_t m, int k, const float* w, int64_t ldw, int n, const float* ep_scale,
+                        const float* ep_shift, int relu, float* c, int64_t ldc, void* stream, glnn::ColStats* cs) {
+  return rowpanel_impl(a, lda, m, k, w, ldw, n, ep_scale, ep_shift, relu, c, ldc, stream, cs, 0);
+}
+
+int glnn::gemm_rowwalk_packed(const float* a, int64_t lda, int64_t m, int d_in, const float* w_packed, int n, const float* ep_scale,
+                              const float* ep_shift, int relu, float* c, int64_t ldc, void* stream) {
+  if (glnn::opts().gemm_rowpanel == 0 || d_in < 1) return GLNN_ERR_UNSUPPORTED;
+  return rowpanel_impl(a, lda, m, (d_in + 3) & ~3, w_packed, 0, n, ep_scale, ep_shift, relu, c, ldc, stream, nullptr, (d_in + 7) / 8);
 }

@@ -47,6 +47,7 @@ struct Options {
   int cls_fused;            // GLNN_STUDENT_CLS_FUSED=0: the large-batch classifier stays a split-K GEMM launch + a loss launch (cls_block.hip off)
   int gemm_bf16_mfma16;     // GLNN_GEMM_BF16_MFMA16=0: the bf16 serving GEMM on v_mfma_f32_32x32x16_bf16 instead of 16x16x32 (same per-wave tile; 3 % slower on 2048 x 2048)
   int sage_fuse_ln_bwd;     // GLNN_SAGE_FUSE_LN_BWD=0: the LayerNorm teacher's transposed aggregation writes dh and glnn_layernorm_bwd_f32 follows
+  int agg_in_rowwalk;       // GLNN_AGG_IN_ROWWALK=0: the kept-aggregate hit path of glnn_sage_fused_agg_f32 stays on sage_fused_kernel<.., kAggIn> (no wave-walk GEMM)
 };
 const Options& opts();
 
@@ -267,6 +268,12 @@ struct ColStats {
 };
 int gemm_rowpanel(const float* a, int64_t lda, int64_t m, int k, const float* w, int64_t ldw, int n, const float* ep_scale,
                   const float* ep_shift, int relu, float* c, int64_t ldc, void* stream, ColStats* cs = nullptr);
+// The same product on the wave-walk form alone, with W given in the MFMA B-fragment order of glnn_pack_weight_f32 (d_in columns packed
+// into ceil(d_in / 8) k-groups; k = d_in rounded up to 4, A's columns [d_in, k) zero): the kept-aggregate hit path of
+// glnn_sage_fused_agg_f32.  Only the panel's way into LDS differs from gemm_rowpanel's walk; same bits.  GLNN_ERR_UNSUPPORTED = nothing
+// launched (shape, alignment, GLNN_GEMM_ROWPANEL=0/2, LDS attribute refused) and no HIP error left behind.
+int gemm_rowwalk_packed(const float* a, int64_t lda, int64_t m, int d_in, const float* w_packed, int n, const float* ep_scale,
+                        const float* ep_shift, int relu, float* c, int64_t ldc, void* stream);
 // glnn_gemm_f32 (plain A) + column statistics partials when the kernel that takes the shape can produce them (cs->done)
 int gemm_stats(const float* a, int64_t lda, int64_t m, int k, const float* w, int64_t ldw, int n, const float* bias, float* c, int64_t ldc,
                float* workspace, int64_t workspace_floats, void* stream, ColStats* cs);

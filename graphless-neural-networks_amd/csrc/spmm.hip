@@ -1739,6 +1739,23 @@ extern "C" int glnn_pack_weight_f32(const float* w, int64_t ldw, int d_out, int 
 
 // The hit path of a kept aggregate (glnn_sage_fused_agg_f32 with agg_in): the gathering launch's phases B and C over rows read back from
 // `agg`.  No graph and no x: the tiles run in id order, one 32-row tile per workgroup like the launch that wrote the matrix.
+//
+// An unchained hit is a plain GEMM out = epi(A1 . W^T), and the wave-walk kernel (K3w, gemm_rowpanel.hip) takes it when the shape is in
+// its range: it keeps every wave's next tile in flight under the current tile's MFMAs, where a workgroup here is serial per tile (load,
+// barrier, MFMA, store).  Its output is the bits of phases B / C here BY CONSTRUCTION, not by observation -- per output element
+// (row, col) both kernels issue the same chain of v_mfma_f32_32x32x2_f32:
+//   * both run kg ascending and t = 0..3 inside it, one MFMA per (kg, t), all into one accumulator;
+//   * in both, lane half kk of MFMA (kg, t) multiplies A[row][8 kg + 4 kk + t] by W[col][8 kg + 4 kk + t] (the MFMA sums its two halves
+//     itself, the same way in both): phase B reads av = lds_a[li * lda + kk * 4 + kg * 8 + t] against the packed
+//     wp[nt][kg][lane][t] = W[nt * 32 + (lane & 31)][kg * 8 + (lane >> 5) * 4 + t]; K3w loads af[kg][t] = A[li][8 kg + 4 kk + t] and reads
+//     the W fragment from panel row 32 j + li at floats 8 kg + 4 kk + t, which the packed prologue fills with that very W value;
+//   * both start from a zero accumulator (K3w's first MFMA takes C = 0: 0 + a.b, as accumulating into zeroed registers);
+//   * both see exact zeros behind d_in: the stored pad columns [d_in, round4(d_in)) of A1 are zeros, the columns behind them read 0 (LDS
+//     zeros here, out-of-range buffer loads there), and the packing is zero behind d_in -- ceil(round4(d_in) / 8) = ceil(d_in / 8)
+//     k-groups in both;
+//   * both finish with fmaf(acc, scale, shift) (1 / 0 without them) and fmaxf(., 0) under relu, and store rows < n_dst, cols < d_out.
+// tests/test_agg_in_rowwalk_gpu.py holds the two routes and the gathering launch to torch.equal.  GLNN_AGG_IN_ROWWALK=0 keeps the launch
+// below for every shape (A/B runs, tests); so does any shape or device K3w does not take (GLNN_ERR_UNSUPPORTED: nothing was launched).
 static int sage_fused_agg_in(int64_t n_dst, int d_in, const float* w_packed, int d_out, const float* ep_scale, const float* ep_shift,
                              int relu, float* out, int64_t ldo, const float* w2_packed, int d_out2, float* out2, int64_t ldo2,
                              const float* agg_in, int64_t ld_agg, void* stream) {
@@ -1756,6 +1773,11 @@ static int sage_fused_agg_in(int64_t n_dst, int d_in, const float* w_packed, int
   a.ep_shift = ep_shift; a.relu = relu; a.out = out; a.ldo = ldo;
   a.w2_packed = w2_packed; a.d_out2 = w2_packed ? d_out2 : 0; a.kgroups2 = w2_packed ? (d_out + 7) / 8 : 0; a.out2 = out2; a.ldo2 = ldo2;
   a.agg_in = agg_in; a.ld_agg = ld_agg;
+  if (!w2_packed && out && d_out >= 96 && n_dst >= 2048 && glnn::opts().agg_in_rowwalk) {
+    const int rc = glnn::gemm_rowwalk_packed(agg_in, ld_agg, n_dst, d_in, w_packed, d_out, ep_scale, ep_shift, relu, out, ldo, stream);
+    if (rc != GLNN_ERR_UNSUPPORTED) return rc;
+    (void)hipGetLastError();      // (a refused LDS attribute on a smaller part: nothing was launched, nothing may stay behind)
+  }
   // one 32-row sub-tile per workgroup like the gathering launch: RT = 2 measured 1.47 ms against 1.52 on the products layer-1 shape and
   // RT = 4 1.57 (profiles/agg_cache_ab.txt) -- the launch is bound by its serial load -> MFMA -> store per workgroup, not by the W reads
   constexpr int rt = 1;

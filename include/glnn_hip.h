@@ -148,7 +148,9 @@ GLNN_API int glnn_sage_fused_plan_f32(const int64_t* indptr, const int32_t* indi
  *            d_in are written as 0, up to d_in rounded up to 8 where ld_agg reaches that far); out / out2 are the bits of the plain launch
  *   agg_in   the gather is replaced by a copy of agg_in[v, 0:d_in rounded up to 4) into the tile; indptr, indices, x, x_self, tile_order
  *            and plan are not read (may be NULL).  The projection, epilogue and chained projection are the same code, so out / out2 are
- *            bit for bit what the agg_out launch with these weights stores. */
+ *            bit for bit what the agg_out launch with these weights stores.  Without a chained projection, with 36 <= d_in rounded up to 4
+ *            <= 128, d_out >= 96 and n_dst >= 2048 the launch is the wave-walk GEMM reading w_packed (the same MFMA chain per output
+ *            element: the same bits); GLNN_AGG_IN_ROWWALK=0 keeps the fused launch for every shape. */
 GLNN_API int glnn_sage_fused_agg_f32(const int64_t* indptr, const int32_t* indices, int64_t n_dst,
                                      int64_t n_src, const float* x, int64_t ldx, int d_in,
                                      const float* x_self, int64_t ld_self, const float* w_packed,
