@@ -95,6 +95,10 @@ SIGNATURES = {
     "glnn_gpr_prop_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp,
                           c_i64, c_vp, c_vp],
     "glnn_gpr_fold_f32": [c_vp, c_int, c_i64, c_vp, c_vp, c_i64, c_vp],
+    "glnn_gcnii_layer_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_vp, c_f32, c_u32,
+                             c_vp, c_i64, c_vp, c_i64, c_vp, c_vp],
+    "glnn_gcnii_layer_bwd_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_f32, c_u32, c_f32,
+                                 c_f32, c_vp, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp],
     "glnn_gat_scores_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "glnn_gat_attn_fwd_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_f32, c_f32, c_u32, c_int, c_vp, c_i64,
                               c_vp, c_vp],

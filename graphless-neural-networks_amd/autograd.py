@@ -3,6 +3,8 @@
 keep working on HIP for callers that differentiate `Model.forward` themselves: the dense projections, the neighbour
 aggregation and the norm/ReLU/dropout tails run on libglnn_hip.so in both directions.  The training loops of this package
 do not go through autograd at all -- see student.py (StudentEngine) and teacher.py (TeacherEngine)."""
+import math
+
 import torch
 
 from . import ops
@@ -317,6 +319,102 @@ def gpr_propagate(graph, h0, gamma, k, training):
         return GprPropFn.apply(graph, h0, gamma, int(k))
     with torch.no_grad():
         return gpr_fwd(graph, h0, gamma, int(k))
+
+
+# ------------------------------------------------------------------------------------------ GCNII conv stack (docs/GCNII_SEMANTICS.md)
+def gcnii_betas(num_layers, lamda):
+    """beta_l = log(lamda / l + 1) for l = 1..L (the paper's identity-mapping weights)."""
+    return [math.log(float(lamda) / l + 1.0) for l in range(1, int(num_layers) + 1)]
+
+
+def gcnii_fwd(g, h0, weights, alpha, betas, drop_p=0.0, seeds=None, save=False):
+    """The L conv layers over h0 = H_0: L launches of glnn_gcnii_layer_f32, each gathering the previous layer's UNSCALED rows (every H_l
+    is an output of the model; x_norm = src_norm rides in the gather).  seeds (training, drop_p > 0): seeds[l] keys drop_l, l = 1..L.
+    Returns ([H_1..H_L], [S_1..S_L] when save else None)."""
+    h0 = ops.as_feat(h0)
+    n, d = h0.shape
+    in_norm, out_norm = g.degree_norms()
+    nnz = g.num_edges()
+    hs, ss = [], [] if save else None
+    x = h0
+    for l, w in enumerate(weights, 1):
+        s = ops.feat_empty(n, d, h0.device) if save else None
+        x = ops.gcnii_layer(g.indptr, g.indices, nnz, x, h0, w, alpha, betas[l - 1], in_norm, x_norm=out_norm,
+                            drop_p=drop_p, drop_seed=seeds[l] if drop_p > 0 else 0, s_out=s)
+        hs.append(x)
+        if save:
+            ss.append(s)
+    return hs, ss
+
+
+def gcnii_bwd(g, da, hs, ss, weights, alpha, betas, dws, drop_p=0.0, seeds=None, drop_last=True):
+    """dL/dH_0 (before H_0's own ReLU mask) from da = dL/d drop_{L+1}(H_L): L launches of glnn_gcnii_layer_bwd_f32 over the transposed
+    graph -- layer L in the plain form, the others gathering the previous launch's dS, stored PRE-SCALED by dst_norm so that no gather of
+    the chain multiplies per edge -- each followed by dW_l = (beta_l dZ_l)^T S_l (glnn_gemm_tn_f32 into dws[l - 1]), and one launch
+    without a product for H_0.  seeds[l] keys drop_l (l = 1..L + 1); drop_last False: da is already behind drop_{L+1}'s mask (autograd)."""
+    da = ops.as_feat(da)
+    n, d = da.shape
+    L = len(weights)
+    in_norm, out_norm = g.degree_norms()
+    tg = g.transposed(False)
+    nnz = g.num_edges()
+    dz, acc = ops.feat_empty(n, d, da.device), ops.feat_empty(n, d, da.device)
+    bufs = [ops.feat_empty(n, d, da.device) for _ in range(min(L, 2))]
+    seed = lambda s: seeds[s] if drop_p > 0 else 0
+    x = da
+    for l in range(L, 0, -1):
+        p_l = drop_p if (l < L or drop_last) else 0.0
+        x = ops.gcnii_layer_bwd(tg.indptr, tg.indices, nnz, x, hs[l - 1], weights[l - 1].t().contiguous(), alpha, betas[l - 1], dz, acc,
+                                first=l == L, row_norm=out_norm, out_norm=in_norm, plain=l == L, drop_p=p_l, drop_seed=seed(l + 1),
+                                dz_scale=betas[l - 1], ds_out=bufs[l % len(bufs)])
+        ops.gemm_tn(dz, ss[l - 1], out=dws[l - 1])
+    return ops.gcnii_layer_bwd(tg.indptr, tg.indices, nnz, x, None, None, alpha, 0.0, dz, acc, first=False, row_norm=out_norm,
+                               drop_p=drop_p, drop_seed=seed(1))
+
+
+class GcniiStackFn(torch.autograd.Function):
+    """The GCNII conv stack as ONE differentiable op on the HIP path: H_L carries the gradient (to H_0 and to every W_l); H_1..H_{L-1} are
+    returned for the callers that list hidden states and are not differentiable.  The backward replays the dropout masks from the seeds."""
+
+    @staticmethod
+    def forward(ctx, graph, h0, alpha, betas, drop_p, seeds, *weights):
+        h0 = ops.as_feat(h0.detach())
+        ws = [w.detach() for w in weights]
+        hs, ss = gcnii_fwd(graph, h0, ws, alpha, betas, drop_p, seeds, save=True)
+        ctx.graph, ctx.cfg, ctx.L = graph, (alpha, betas, drop_p, seeds), len(ws)
+        ctx.save_for_backward(*hs, *ss, *weights)
+        ctx.mark_non_differentiable(*hs[:-1])
+        return tuple(hs)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        L = ctx.L
+        saved = ctx.saved_tensors
+        hs, ss, ws = saved[:L], saved[L:2 * L], [w.detach() for w in saved[2 * L:]]
+        alpha, betas, drop_p, seeds = ctx.cfg
+        dws = [torch.empty_like(w) for w in ws]
+        dh0 = gcnii_bwd(ctx.graph, dys[-1].contiguous(), hs, ss, ws, alpha, betas, dws, drop_p, seeds, drop_last=False)
+        return (None, dh0 if ctx.needs_input_grad[1] else None, None, None, None, None) + tuple(dws)
+
+
+def gcnii_stack_seeds(count, sites):
+    """The seeds of the dropout sites 0..sites-1 of the count-th dropout draw of this process (tests replay the masks from them)."""
+    base = int(torch.initial_seed()) * 0x85EBCA77 + count * 0x9E3779B1 + 0x47434E32
+    return [(base + s * 0x632BE5AB) & 0xFFFFFFFF for s in range(sites)]
+
+
+def gcnii_stack(graph, h0, weights, alpha, betas, drop_p, training):
+    """[H_1..H_L] of the conv stack: differentiable in training mode (appnp_propagate's rule; the per-layer dropout only then, its
+    counter-based seeds drawn like norm_act_drop's); the eval forward keeps nothing for a backward."""
+    p = float(drop_p) if training else 0.0
+    seeds = None
+    if p > 0:
+        _drop_counter[0] += 1
+        seeds = gcnii_stack_seeds(_drop_counter[0], len(weights) + 2)
+    if training and torch.is_grad_enabled() and (h0.requires_grad or any(w.requires_grad for w in weights)):
+        return list(GcniiStackFn.apply(graph, h0, float(alpha), tuple(betas), p, seeds, *weights))
+    with torch.no_grad():
+        return gcnii_fwd(graph, h0, list(weights), float(alpha), betas, p, seeds)[0]
 
 
 # ------------------------------------------------------------------------------------------ GAT layer (dgl 0.6.1 GATConv)

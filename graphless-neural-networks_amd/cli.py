@@ -77,7 +77,14 @@ def get_teacher_args(argv=None):
     # optimiser, "native" = TeacherEngine.step_sage_mean, the whole step as one C call (csrc/sage_mean_step.hip)
     p.add_argument("--sage_mean_step", type=str, default="autograd", choices=["autograd", "native"],
                    help="Training step of a SAGE 'mean' teacher (native: one C call per batch; needs --sage_aggregator mean)")
+    # not reference flags: the GCNII teacher's teleport and identity-mapping strengths (conf keys `gcnii_alpha`, `gcnii_lamda`, read by
+    # Model; docs/GCNII_SEMANTICS.md).  Unset = the conf's value or the paper's defaults 0.1 / 0.5
+    p.add_argument("--gcnii_alpha", type=float, default=None, help="alpha of the GCNII teacher's initial residual (default 0.1)")
+    p.add_argument("--gcnii_lamda", type=float, default=None, help="lamda of the GCNII teacher's beta_l = log(lamda / l + 1) (default 0.5)")
     args = p.parse_args(argv)
+    for flag in ("gcnii_alpha", "gcnii_lamda"):
+        if getattr(args, flag) is not None and "GCNII" not in args.teacher:
+            p.error(f"--{flag} applies to the GCNII teacher only (got --teacher {args.teacher})")
     if args.sage_mean_step != "autograd" and ("SAGE" not in args.teacher or args.sage_aggregator != "mean"):
         p.error(f"--sage_mean_step {args.sage_mean_step} applies to --teacher SAGE --sage_aggregator mean only "
                 f"(got --teacher {args.teacher} --sage_aggregator {args.sage_aggregator})")

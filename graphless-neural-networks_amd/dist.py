@@ -390,6 +390,12 @@ def _refuse_gpr(encoder, who):
                                   "rows of the remote sources, an exchange the sharded forward does not have (whole-graph GPRGNN only)")
 
 
+def _refuse_gcnii(encoder, who):
+    if type(encoder).__name__ == "GCNII":
+        raise NotImplementedError(f"{who}: the GCNII teacher is not sharded -- each of its conv layers needs the previous layer's hidden "
+                                  "rows of the remote sources, an exchange the sharded forward does not have (whole-graph GCNII only)")
+
+
 def _refuse_mean(encoder, who):
     if getattr(encoder, "aggregator_type", "gcn") != "gcn":
         raise NotImplementedError(f"{who}: the sharded teacher forward implements the SAGE 'gcn' aggregator only -- a SAGE "
@@ -416,6 +422,7 @@ class ShardedTeacher:
         All are chunked and overlapped when shards.chunks > 1; results are identical."""
         _refuse_gat(encoder, "ShardedTeacher")
         _refuse_gpr(encoder, "ShardedTeacher")
+        _refuse_gcnii(encoder, "ShardedTeacher")
         _refuse_mean(encoder, "ShardedTeacher")
         if widening_exchange not in ("narrow", "wide", "mixed"):
             raise ValueError("ShardedTeacher: widening_exchange must be 'narrow', 'wide' or 'mixed'")
@@ -1009,6 +1016,7 @@ class HaloShardedTeacher:
         remote-source edges once the halo has landed).  Same sums, local edges before remote ones (results equal to rounding)."""
         _refuse_gat(encoder, "HaloShardedTeacher")
         _refuse_gpr(encoder, "HaloShardedTeacher")
+        _refuse_gcnii(encoder, "HaloShardedTeacher")
         _refuse_mean(encoder, "HaloShardedTeacher")
         self.enc, self.g, self.sh, self.be, self.group, self.overlap = encoder, graph_shard, shards, be, group, overlap
         if graph_shard.n_dst != shards.rows:

@@ -16,8 +16,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .autograd import appnp_propagate, linear_fn, norm_act_drop
-from .nn import GATConv, GPRConv, GraphConv, SAGEConv
+from .autograd import appnp_propagate, gcnii_stack, linear_fn, norm_act_drop
+from .nn import GATConv, GCNIIConv, GPRConv, GraphConv, SAGEConv
 
 
 def _bn_eval_fold(bn, bias):
@@ -628,6 +628,53 @@ class GPRGNN(MLP):
         return h_list, self.propagate(g, h)
 
 
+GCNII_MAX_LAYERS = 64
+
+
+class GCNII(nn.Module):
+    """GCNII (Chen, Wei, Huang, Ding, Li, ICML 2020; docs/GCNII_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it):
+    H_0 = relu(fc_in(drop(x))), num_layers GCNIIConv layers over H_0 and APPNP's operator with a dropout in front of each,
+    logits = fc_out(drop(H_L)).  forward returns ([H_1..H_L], logits)."""
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", alpha=0.1, lamda=0.5):
+        super().__init__()
+        if hidden_dim > ops.GCNII_MAX_HIDDEN:
+            raise NotImplementedError(f"GCNII: hidden_dim of at most {ops.GCNII_MAX_HIDDEN} (the fused kernel's tile width; got {hidden_dim})")
+        if norm_type != "none":
+            raise NotImplementedError(f"GCNII: norm_type 'none' only (the paper's model has no norm layers; got {norm_type!r})")
+        if not 1 <= num_layers <= GCNII_MAX_LAYERS:
+            raise NotImplementedError(f"GCNII: 1 to {GCNII_MAX_LAYERS} conv layers (got num_layers {num_layers})")
+        if activation is not F.relu and getattr(activation, "__name__", "") != "relu":
+            raise NotImplementedError("GCNII: only the ReLU activation (the fused layer kernel's epilogue)")
+        self.num_layers, self.norm_type, self.activation = num_layers, norm_type, activation
+        self.hidden_dim, self.alpha, self.lamda = hidden_dim, float(alpha), float(lamda)
+        self.dropout = nn.Dropout(dropout_ratio)
+        self.fc_in = nn.Linear(input_dim, hidden_dim)
+        self.layers = nn.ModuleList(GCNIIConv(hidden_dim, l, alpha, lamda) for l in range(1, num_layers + 1))
+        self.fc_out = nn.Linear(hidden_dim, output_dim)
+
+    def betas(self):
+        return [layer.beta for layer in self.layers]
+
+    def forward(self, g, feats):
+        _need_hip(feats, "GCNII.forward")
+        if (isinstance(g, (list, tuple)) or isinstance(feats, tuple) or g.num_dst_nodes() != g.num_src_nodes()
+                or feats.shape[0] != g.num_dst_nodes()):
+            raise NotImplementedError("GCNII: block (bipartite) inputs are not implemented: GCNII runs on the whole graph")
+        weights = [layer.weight for layer in self.layers]
+        if not self.training:
+            with torch.no_grad():
+                h0 = ops.gemm(ops.as_feat(feats), self.fc_in.weight, ep_shift=self.fc_in.bias, relu=True)
+                hs = gcnii_stack(g, h0, weights, self.alpha, self.betas(), 0.0, False)
+                return hs, ops.gemm(hs[-1], self.fc_out.weight, ep_shift=self.fc_out.bias)
+        p = self.dropout.p
+        x = norm_act_drop(feats, None, p, relu=False) if p > 0 else feats
+        h0 = norm_act_drop(linear_fn(x, self.fc_in.weight, self.fc_in.bias), None, 0.0)
+        hs = gcnii_stack(g, h0, weights, self.alpha, self.betas(), p, True)
+        h = norm_act_drop(hs[-1], None, p, relu=False) if p > 0 else hs[-1]
+        return hs, linear_fn(h, self.fc_out.weight, self.fc_out.bias)
+
+
 class GAT(nn.Module):
     """reference models.py:202-279: num_layers GATConv layers, `num_heads` heads of hidden_dim // num_heads features on every hidden layer
     (ReLU inside the conv, outputs flattened to [N, hidden_dim] and kept in h_list), one head of output_dim features on the last (its
@@ -686,6 +733,10 @@ class Model(nn.Module):
         elif "SAGE" in conf["model_name"]:
             self.encoder = SAGE(activation=F.relu, norm_type=conf["norm_type"], aggregator_type=conf.get("sage_aggregator", "gcn"),
                                 **common).to(conf["device"])
+        elif "GCNII" in conf["model_name"]:          # (tested before "GCN", which it contains)
+            alpha, lamda = conf.get("gcnii_alpha"), conf.get("gcnii_lamda")          # (absent or None: the paper's defaults)
+            self.encoder = GCNII(activation=F.relu, norm_type=conf["norm_type"], alpha=0.1 if alpha is None else alpha,
+                                 lamda=0.5 if lamda is None else lamda, **common).to(conf["device"])
         elif "GCN" in conf["model_name"]:
             self.encoder = GCN(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
         elif "APPNP" in conf["model_name"]:
@@ -725,6 +776,9 @@ class Model(nn.Module):
     def inference(self, data, feats, dtype=torch.float32):
         """dtype=torch.bfloat16: bf16 activation storage, the SAGE teacher's whole-graph forward only (SAGE.inference)."""
         if dtype != torch.float32:
+            if "GCNII" in self.model_name:
+                raise NotImplementedError(f"GCNII.inference(dtype={dtype}): bf16 activation storage is not implemented for the GCNII teacher "
+                                          "(csrc/gcnii.hip gathers and stores fp32 rows; docs/GCNII_SEMANTICS.md, Out of scope)")
             if "SAGE" not in self.model_name:
                 raise NotImplementedError(f"{self.model_name}.inference(dtype={dtype}): bf16 activation storage is implemented for the SAGE "
                                           "teacher's whole-graph forward only")

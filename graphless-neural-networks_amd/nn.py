@@ -4,16 +4,19 @@
   GraphConv(in, out, activation=)(g, h)          <- dgl.nn.GraphConv, reference models.py:170-187,193
   GATConv(in, out, heads, ...)(g, h)             <- dgl.nn.GATConv, reference models.py:228-267 (docs/GAT_SEMANTICS.md)
   GPRConv(k, alpha, init)(g, h)                  <- GPR-GNN's learned K-step propagation (no dgl counterpart; docs/GPR_SEMANTICS.md)
+  GCNIIConv(hidden, layer, alpha, lamda)(g, h, h0) <- one GCNII conv layer (dgl 0.6.1 has none; docs/GCNII_SEMANTICS.md)
 
 Parameter names follow dgl 0.6.1 so that a reference `model.pth` loads: SAGEConv.fc_neigh.{weight,bias}
 (weight [out,in], xavier_uniform gain=relu; no fc_self for "gcn"), GraphConv.{weight [in,out] xavier_uniform,
 bias zeros}.  Only what the reference constructs is implemented; anything else raises."""
 
+import math
+
 import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import GraphConvFn, SpmmFn, gat_conv, gpr_propagate, graphconv_fwd, linear_fn
+from .autograd import GraphConvFn, SpmmFn, gat_conv, gcnii_stack, gpr_propagate, graphconv_fwd, linear_fn
 
 
 FUSED_SAGE_MAX_IN = 256   # aggregate-first layers with d_in, d_out <= 256 take the single-launch K1F kernel.  Interleaved
@@ -310,3 +313,43 @@ class GPRConv(nn.Module):
                 or feat.shape[0] != graph.num_dst_nodes()):
             raise NotImplementedError("GPRConv: block (bipartite) inputs are not implemented: GPR-GNN propagates over the whole graph")
         return gpr_propagate(graph, feat, self.gamma, self.k, self.training)
+
+
+class GCNIIConv(nn.Module):
+    """One GCNII conv layer (Chen et al., ICML 2020, eq. 5; docs/GCNII_SEMANTICS.md):
+    relu((1 - beta) S + beta S W^T),  S = (1 - alpha) P h + alpha h0,  beta = log(lamda / layer + 1),  P = D_in^-1/2 A D_out^-1/2.
+    ONE parameter, `weight` [hidden, hidden] (nn.Linear orientation, no bias), uniform(-1 / sqrt(hidden), 1 / sqrt(hidden)) as in the
+    paper's released code.  `layer` is 1-based.  No dropout of its own: the encoder (models.GCNII) owns the dropout sites."""
+
+    def __init__(self, hidden, layer, alpha=0.1, lamda=0.5):
+        super().__init__()
+        if int(hidden) > ops.GCNII_MAX_HIDDEN:
+            raise NotImplementedError(f"GCNIIConv: GCNII hidden widths of at most {ops.GCNII_MAX_HIDDEN} (the fused kernel's tile; got {hidden})")
+        if int(hidden) < 1 or int(layer) < 1:
+            raise ValueError(f"GCNIIConv: hidden and layer must be >= 1 (got {hidden}, {layer})")
+        self.hidden, self.layer, self.alpha, self.lamda = int(hidden), int(layer), float(alpha), float(lamda)
+        self.weight = nn.Parameter(torch.empty(self.hidden, self.hidden, dtype=torch.float32))
+        self.reset_parameters()
+
+    @property
+    def beta(self):
+        return math.log(self.lamda / self.layer + 1.0)
+
+    def reset_parameters(self):
+        b = 1.0 / math.sqrt(self.hidden)
+        nn.init.uniform_(self.weight, -b, b)
+
+    def forward(self, graph, feat, h0):
+        """feat = H_{l-1}, h0 = H_0 (both [n, hidden]).  Differentiable in training mode when feat IS h0 (a one-layer stack); deeper
+        stacks differentiate as a whole (models.GCNII -> autograd.gcnii_stack), so a layer in the middle runs without a graph."""
+        if (isinstance(graph, (list, tuple)) or isinstance(feat, tuple) or graph.num_dst_nodes() != graph.num_src_nodes()
+                or feat.shape[0] != graph.num_dst_nodes()):
+            raise NotImplementedError("GCNIIConv: block (bipartite) inputs are not implemented: GCNII runs on the whole graph")
+        if feat is h0:
+            return gcnii_stack(graph, h0, [self.weight], self.alpha, [self.beta], 0.0, self.training)[0]
+        if self.training and torch.is_grad_enabled() and (feat.requires_grad or h0.requires_grad or self.weight.requires_grad):
+            raise NotImplementedError("GCNIIConv: a GCNII layer behind another one is differentiated by the whole stack "
+                                      "(glnn_amd.autograd.gcnii_stack); call it under torch.no_grad()")
+        in_norm, out_norm = graph.degree_norms()
+        return ops.gcnii_layer(graph.indptr, graph.indices, graph.num_edges(), feat, h0, self.weight, self.alpha, self.beta, in_norm,
+                               x_norm=out_norm)

@@ -1435,6 +1435,96 @@ def gpr_fold(row_dot, rows, m, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------------------- GCNII conv layer
+GCNII_MAX_HIDDEN = 256          # kMaxD of csrc/gcnii.hip: the kernel's tile width
+
+
+def _gcnii_check(name, indptr, indices, n, d, tile_order):
+    if d > GCNII_MAX_HIDDEN:
+        raise NotImplementedError(f"{name}: GCNII hidden widths of at most {GCNII_MAX_HIDDEN} (the fused kernel's tile; got {d})")
+    if indptr is not None and (indptr.dtype != torch.int64 or indices.dtype != torch.int32 or indptr.numel() < n + 1):
+        raise ValueError(f"{name}: indptr must be int64 with n + 1 entries and indices int32")
+    if tile_order is not None and (tile_order.dtype != torch.int32 or not tile_order.is_contiguous() or tile_order.numel() != (n + 31) // 32):
+        raise ValueError(f"{name}: tile_order must be a contiguous int32 permutation of the ceil(n / 32) tile ids")
+
+
+def _gcnii_rows(name, what, t, n, d):
+    if t is None:
+        return None
+    _mat(t, f"{name} {what}")
+    if tuple(t.shape) != (n, d) or _ld(t) % 4 or t.data_ptr() % 16:
+        raise ValueError(f"{name}: {what} must be [n, d] float32 with float4-addressable rows (ops.feat_empty)")
+    return t
+
+
+def gcnii_layer(indptr, indices, nnz, x, h0, w, alpha, beta, row_norm, x_norm=None, out_norm=None, drop_p=0.0, drop_seed=0, s_out=None,
+                out=None, w_packed=None, tile_order=None):
+    """ONE GCNII conv layer forward, glnn_gcnii_layer_f32 (square graph, n = x.shape[0], d <= 256):
+    S = (1 - alpha) row_norm * A (x_norm * drop(x)) + alpha h0;  out = out_norm * relu((1 - beta) S + beta S w^T).  x_norm None: x is the
+    previous layer's output already scaled by it (that launch's out_norm); out_norm None: unscaled rows.  drop: the feature dropout keyed
+    by the source row (dropout_mask(n, d, drop_p, drop_seed)).  s_out (optional, [n, d]) receives S.  w [d, d] in nn.Linear orientation
+    (w_packed: pack_weight(w) of a caller that has it).  Returns out."""
+    _need_cuda(indptr, indices, x, h0, w, row_norm, x_norm, out_norm, s_out, out, w_packed, tile_order)
+    x, h0 = as_feat(x), as_feat(h0)
+    n, d = h0.shape
+    _gcnii_check("gcnii_layer", indptr, indices, n, d, tile_order)
+    if tuple(x.shape) != (n, d) or tuple(w.shape) != (d, d):
+        raise ValueError("gcnii_layer: x and h0 must be [n, d] and w [d, d]")
+    if w_packed is None:
+        w_packed = pack_weight(w)
+    if out is None:
+        out = feat_empty(n, d, x.device)
+    _gcnii_rows("gcnii_layer", "out", out, n, d)
+    _gcnii_rows("gcnii_layer", "s_out", s_out, n, d)
+    with _Timed("gcnii_layer", d=d, n_dst=n, nnz=int(nnz), train=s_out is not None):
+        rc = _lib.lib().glnn_gcnii_layer_f32(
+            _p(indptr), _p(indices), n, int(nnz), _p(x), _ld(x), d, _p(_vec(x_norm, n, "x_norm")), _p(_vec(row_norm, n, "row_norm")),
+            _p(_vec(out_norm, n, "out_norm")), _p(h0), _ld(h0), float(alpha), float(beta), _p(w_packed), float(drop_p),
+            int(drop_seed) & 0xFFFFFFFF, _p(s_out), 0 if s_out is None else _ld(s_out), _p(out), _ld(out), _p(tile_order), _stream())
+    _lib.check(rc, "glnn_gcnii_layer_f32")
+    return out
+
+
+def gcnii_layer_bwd(t_indptr, t_indices, nnz, g, h, wt, alpha, beta, dz_out, dh0_acc, first, row_norm=None, x_norm=None, out_norm=None,
+                    plain=False, drop_p=0.0, drop_seed=0, dz_scale=1.0, ds_out=None, wt_packed=None, tile_order=None):
+    """ONE GCNII conv layer backward, glnn_gcnii_layer_bwd_f32, over the transposed CSR (norms swapped):
+    dZ = [h > 0] * drop'(plain ? g : (1 - alpha) row_norm * A^T (x_norm * g)), drop' keyed by the own row; dz_out = dz_scale dZ;
+    dS = (1 - beta) dZ + beta dZ W with wt = W^T (wt_packed: pack_weight(wt)); returns ds_out = out_norm * dS;
+    dh0_acc = (0 if first else dh0_acc) + alpha dS.  wt None (the launch behind layer 1): dz_out = drop'(...) + dh0_acc = dL/dH_0 (h None; a given h masks the SUM: [h > 0] (drop'(...) + dh0_acc)),
+    nothing else is written, returns dz_out."""
+    _need_cuda(t_indptr, t_indices, g, h, wt, dz_out, dh0_acc, row_norm, x_norm, out_norm, ds_out, wt_packed, tile_order)
+    g = as_feat(g)
+    h = None if h is None else as_feat(h)
+    n, d = g.shape
+    _gcnii_check("gcnii_layer_bwd", None if plain else t_indptr, t_indices, n, d, tile_order)
+    tail = wt is None and wt_packed is None
+    if not tail:
+        if wt_packed is None:
+            if tuple(wt.shape) != (d, d):
+                raise ValueError("gcnii_layer_bwd: wt must be [d, d]")
+            wt_packed = pack_weight(wt)
+        if ds_out is None:
+            ds_out = feat_empty(n, d, g.device)
+        if h is None:
+            raise ValueError("gcnii_layer_bwd: a layer launch needs the saved h")
+    elif ds_out is not None or plain or first:
+        raise ValueError("gcnii_layer_bwd: the dH_0 launch (wt None) is a gather behind a layer launch and writes dz_out alone")
+    if dz_out is None or dh0_acc is None:
+        raise ValueError("gcnii_layer_bwd: dz_out and dh0_acc are required")
+    if h is not None and tuple(h.shape) != (n, d):
+        raise ValueError("gcnii_layer_bwd: h must have g's shape")
+    for what, t in (("dz_out", dz_out), ("ds_out", ds_out), ("dh0_acc", dh0_acc)):
+        _gcnii_rows("gcnii_layer_bwd", what, t, n, d)
+    with _Timed("gcnii_layer_bwd", d=d, n_dst=n, nnz=int(nnz), plain=bool(plain)):
+        rc = _lib.lib().glnn_gcnii_layer_bwd_f32(
+            _p(t_indptr), _p(t_indices), n, int(nnz), _p(g), _ld(g), d, _p(_vec(x_norm, n, "x_norm")), _p(_vec(row_norm, n, "row_norm")),
+            _p(_vec(out_norm, n, "out_norm")), 1 if plain else 0, _p(h), 0 if h is None else _ld(h), float(drop_p),
+            int(drop_seed) & 0xFFFFFFFF, float(alpha), float(beta), _p(wt_packed), float(dz_scale), _p(dz_out), _ld(dz_out), _p(ds_out),
+            0 if ds_out is None else _ld(ds_out), _p(dh0_acc), _ld(dh0_acc), 1 if first else 0, _p(tile_order), _stream())
+    _lib.check(rc, "glnn_gcnii_layer_bwd_f32")
+    return dz_out if tail else ds_out
+
+
 def csr_transpose_eids(indptr, indices, n_dst, n_src, nnz):
     """glnn_csr_transpose_eids: (t_indptr [n_src+1], t_indices [nnz], t_eids [nnz]) -- csr_transpose plus the original edge id (CSR
     position) of every transposed entry."""

@@ -35,7 +35,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .autograd import appnp_bwd, appnp_fwd, gat_layer_bwd, gat_layer_fwd, gpr_bwd, gpr_fwd, graphconv_bwd, graphconv_fwd
+from .autograd import (appnp_bwd, appnp_fwd, gat_layer_bwd, gat_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd,
+                       graphconv_fwd)
 from .student import _mix32
 
 
@@ -44,18 +45,21 @@ def _is_relu(act):
 
 
 def check_supported(model, criterion, optimizer):
-    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT or GPRGNN teacher."""
+    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GPRGNN or GCNII teacher."""
     enc = model.encoder
     name = model.model_name
     if "MLP" in name or not ("SAGE" in name or "GCN" in name or "APPNP" in name or "GAT" in name or "GPRGNN" in name):
-        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT or GPRGNN teachers only (got {name})")
+        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GPRGNN or GCNII teachers only (got {name})")
     if not (isinstance(criterion, nn.NLLLoss) and criterion.reduction == "mean" and criterion.weight is None
             and criterion.ignore_index == -100):
         raise NotImplementedError("TeacherEngine: the criterion must be nn.NLLLoss() (reference train_teacher.py:237)")
     grp = optimizer.param_groups
     if type(optimizer) is not torch.optim.Adam or len(grp) != 1 or grp[0].get("amsgrad") or grp[0].get("maximize"):
         raise NotImplementedError("TeacherEngine: torch.optim.Adam, one param group, no amsgrad/maximize (train_teacher.py:234-236)")
-    if "SAGE" in name:
+    if "GCNII" in name:          # (tested before "GCN", which it contains; the encoder's constructor refused everything else)
+        if enc.norm_type != "none" or not _is_relu(enc.activation):
+            raise NotImplementedError("TeacherEngine: GCNII with norm_type none and ReLU (docs/GCNII_SEMANTICS.md)")
+    elif "SAGE" in name:
         if getattr(enc, "aggregator_type", "gcn") != "gcn":
             raise NotImplementedError(f"TeacherEngine: the one-call SAGE step implements the 'gcn' aggregator only; a SAGE "
                                       f"{enc.aggregator_type!r} teacher trains through SAGE.forward's differentiable ops (train_sage)")
@@ -136,8 +140,8 @@ class TeacherEngine:
     def __init__(self, model, optimizer):
         self.model, self.enc, self.opt = model, model.encoder, optimizer
         name = model.model_name
-        self.kind = "sage" if "SAGE" in name else ("appnp" if "APPNP" in name else ("gat" if "GAT" in name else
-                                                                                     ("gpr" if "GPRGNN" in name else "gcn")))
+        self.kind = ("gcnii" if "GCNII" in name else "sage" if "SAGE" in name else "appnp" if "APPNP" in name else "gat" if "GAT" in name
+                     else "gpr" if "GPRGNN" in name else "gcn")
         self.L = self.enc.num_layers
         self.bn = getattr(self.enc, "norm_type", "none") == "batch"
         self.ln = getattr(self.enc, "norm_type", "none") == "layer"
@@ -747,6 +751,50 @@ class TeacherEngine:
             raise
         self._adam()
 
+    # ------------------------------------------------------------------------------------------ full-graph GCNII
+    def _gcnii_seed(self, site, step=None):
+        """The seed of dropout site `site` (0: the input, l = 1..L: in front of conv layer l, L + 1: in front of fc_out) in step `step`
+        (default: the current one): a stream of its own, apart from _seed, _edge_seed and _attn_seed.  site < 131, so no two (step, site)
+        pairs share a counter."""
+        step = self.step_count if step is None else step
+        return _mix32(self.base_seed ^ 0x47434E32 ^ _mix32(step * 131 + site + 0x51)) if self.p > 0 else 0
+
+    @torch.no_grad()
+    def step_gcnii(self, g, feats, labels, idx_train, lamb=1.0):
+        """The full-graph `train` step over GCNII (docs/GCNII_SEMANTICS.md): fc_in (+ ReLU) behind the input dropout, L launches of
+        glnn_gcnii_layer_f32 that keep S_l and H_l, fc_out, NLL over idx_train, fc_out's backward, L launches of
+        glnn_gcnii_layer_bwd_f32 over the transposed graph with one glnn_gemm_tn_f32 each (beta_l folded into its stored operand), the
+        launch for dH_0, H_0's ReLU backward, fc_in's backward, and the ONE Adam launch."""
+        ops._need_cuda(feats, labels, idx_train, g.indptr)
+        self.step_count += 1
+        try:
+            self._step_gcnii_body(g, feats, labels, idx_train, lamb)
+        except Exception:
+            self.step_count -= 1          # the step never happened (see step_sage)
+            raise
+        self._adam()
+
+    def _step_gcnii_body(self, g, feats, labels, idx_train, lamb):
+        enc, L, p = self.enc, self.L, self.p
+        n = g.num_dst_nodes()
+        fc_in, fc_out = enc.fc_in, enc.fc_out
+        seeds = [self._gcnii_seed(s) for s in range(L + 2)]
+        weights = [lay.weight for lay in enc.layers]
+        betas = enc.betas()
+        x = ops.as_feat(feats)
+        # drop_0(x) is materialised once per step (signed features: the GEMM's operand-load dropout carries a ReLU) and read twice
+        xd = ops.act_fwd(x, drop_p=p, drop_seed=seeds[0], relu=False) if p > 0 else x
+        h0 = ops.gemm(xd, fc_in.weight, ep_shift=fc_in.bias, relu=True)
+        hs, ss = gcnii_fwd(g, h0, weights, enc.alpha, betas, p, seeds, save=True)
+        a = ops.act_fwd(hs[-1], drop_p=p, drop_seed=seeds[L + 1], relu=False) if p > 0 else hs[-1]
+        logits = ops.gemm(a, fc_out.weight, ep_shift=fc_out.bias)
+        dlog = self._loss_grad(logits, labels, idx_train, lamb, n)
+        ops.gemm_tn(dlog, a, out=self.grad(fc_out.weight), col_sum_a=self.grad(fc_out.bias))
+        da = ops.gemm(dlog, fc_out.weight, w_is_kn=True)                          # dlog W_out: d/d drop_{L+1}(H_L)
+        dh0 = gcnii_bwd(g, da, hs, ss, weights, enc.alpha, betas, [self.grad(w) for w in weights], p, seeds)
+        dz0, _, _ = ops.bn_relu_bwd(dh0, h0, dz=dh0, dz_col_sum=self.grad(fc_in.bias))     # h0 = relu(z0): h0 > 0 <=> z0 > 0
+        ops.gemm_tn(dz0, xd, out=self.grad(fc_in.weight))
+        ops.note_param_write()
 
     # ------------------------------------------------------------------------------------------ full-graph GAT
     def _attn_seed(self, layer):

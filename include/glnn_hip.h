@@ -788,6 +788,38 @@ GLNN_API int glnn_gpr_fold_f32(const float* row_dot, int rows, int64_t m, float*
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GCNII conv layer (Chen, Wei, Huang, Ding, Li, "Simple and Deep Graph Convolutional Networks", ICML 2020), one launch per layer and
+ * direction over APPNP's operator P = D_in^-1/2 A D_out^-1/2.  docs/GCNII_SEMANTICS.md states the arithmetic.  Square graph of n nodes,
+ * nnz = indptr[n] < 2^31 and d <= 256 (GLNN_ERR_UNSUPPORTED otherwise); every row pointer 16-byte aligned with a leading dimension
+ * % 4 == 0 and >= round4(d); padding columns [d, round4(d)) of every output are written as 0.  Deterministic (no float atomics), and
+ * independent of tile_order (optional: an int32 permutation of the ceil(n / 32) row tiles).  n == 0 is a no-op.
+ *
+ * glnn_gcnii_layer_f32 -- the paper's eq. (5), section 3 (initial residual + identity mapping), forward:
+ *     S[i]   = (1 - alpha) row_norm[i] sum_{e = (j -> i)} xs[j] + alpha h0[i],   xs[j] = x_norm[j] drop(x)[j] (x_norm NULL: x is already
+ *              scaled by it);  drop = the package's feature dropout under (drop_p, drop_seed), keyed by the SOURCE row and the column
+ *              (glnn_dropout_mask_u8(n, d, ...)[j]), drop_p = 0: none
+ *     out[i] = out_norm[i] relu((1 - beta) S[i] + beta S[i] W^T)      (out_norm NULL: unscaled);  w_packed = glnn_pack_weight_f32 of W [d, d]
+ *     s_out (optional) = S, what the weight gradient is taken against. */
+GLNN_API int glnn_gcnii_layer_f32(const int64_t* indptr, const int32_t* indices, int64_t n, int64_t nnz, const float* x, int64_t ldx,
+                                  int d, const float* x_norm, const float* row_norm, const float* out_norm, const float* h0,
+                                  int64_t ldh0, float alpha, float beta, const float* w_packed, float drop_p, uint32_t drop_seed,
+                                  float* s_out, int64_t lds, float* out, int64_t ldo, const int32_t* tile_order, void* stream);
+/* glnn_gcnii_layer_bwd_f32 -- the backward of eq. (5), section 3, over glnn_csr_transpose of the graph (norms swapped):
+ *     T[i]  = plain ? g[i] : (1 - alpha) row_norm[i] sum_{e} x_norm[j] g[j]      (g = the previous call's ds_out, or dL/dH_L when plain)
+ *     dZ[i] = [h[i] > 0] drop'(T)[i]        drop' = the mask of (drop_p, drop_seed) keyed by the OWN row i;  h = the saved H_l
+ *     dz_out = dz_scale dZ                  (dz_scale = beta_l: dW_l = dz_out^T S_l)
+ *     dS[i] = (1 - beta) dZ[i] + beta dZ[i] W,   wt_packed = glnn_pack_weight_f32 of W^T;   ds_out[i] = out_norm[i] dS[i] (NULL: unscaled)
+ *     dh0_acc[i] = (first ? 0 : dh0_acc[i]) + alpha dS[i]
+ *   wt_packed == NULL and ds_out == NULL (the launch behind layer 1; gather form, first == 0, h optional):
+ *     dz_out[i] = drop'(T)[i] + dh0_acc[i] = dL/dH_0 (h NULL; with h given the mask covers the sum: [h[i] > 0] (drop'(T)[i] + dh0_acc[i]));
+ *     dh0_acc is only read. */
+GLNN_API int glnn_gcnii_layer_bwd_f32(const int64_t* t_indptr, const int32_t* t_indices, int64_t n, int64_t nnz, const float* g,
+                                      int64_t ldg, int d, const float* x_norm, const float* row_norm, const float* out_norm, int plain,
+                                      const float* h, int64_t ldh, float drop_p, uint32_t drop_seed, float alpha, float beta,
+                                      const float* wt_packed, float dz_scale, float* dz_out, int64_t lddz, float* ds_out, int64_t ldds,
+                                      float* dh0_acc, int64_t ldacc, int first, const int32_t* tile_order, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * GAT attention (dgl 0.6.1 GATConv of the reference GAT teacher, models.py:202-279): per-destination edge softmax with per-edge scores
  * from two per-node scalars per head.  docs/GAT_SEMANTICS.md states the arithmetic.  Square graph of n nodes, indptr / indices the in-CSR
  * (rows = destinations, edge id = CSR position); z [n, heads * out_feats] the projected rows, head-major columns.  heads <= 64,
