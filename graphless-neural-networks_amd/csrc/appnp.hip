@@ -13,20 +13,10 @@
 // dropped edge's feature row is never loaded -- the kept entries of a 64-edge index chunk are compacted with ds_permute before the loads.
 // Every kept edge carries the same weight 1 / (1 - p), so the sum runs over the plain rows and dscale goes into the row's coefficient.
 //
-// Mapping (the ideas of spmm.hip, narrow rows): a row of d <= 256 floats is LPR = 1..64 lanes moving float4; the G = 64 / LPR lane groups
-// take different edges of the same row and are folded with cross-lane adds at the end (fixed order).  One wave per row of <= kLongRow
-// entries (rows pulled from an LDS ticket); longer rows go to the first n_long_blocks workgroups, eight waves per row, folded in LDS in
-// fixed order.  No float atomics: bit-reproducible.  Wider rows: blockIdx.y = the 256-column tile.
-#include "glnn_common.h"
+// Mapping: row_gather_dev.h's wave gather under the two-role scan, rows pulled from an LDS ticket.  Wider rows: blockIdx.y = the 256-column tile.
+#include "row_gather_dev.h"
 
 namespace {
-
-constexpr int kBlock = 512;                // 8 waves
-constexpr int kWaves = kBlock / 64;
-constexpr int kRowsPerWave = 8;
-constexpr int kLongRow = 128;              // in-degree above which a whole workgroup takes the row
-constexpr int kLongBlockRows = 512;        // rows scanned per long-role step
-constexpr int kLongBlockCap = 512;
 
 __device__ __forceinline__ bool edge_keep(uint32_t seed, uint32_t thr, uint32_t t, uint32_t eid) {
   return (glnn::drop_hash(seed, eid, t) & 0xFFFFu) >= thr;
@@ -45,69 +35,27 @@ struct PropArgs {
   const float* h0; int64_t ldh0;                    // forward: the teleport term
   float* acc; int64_t ldacc; int first, last;       // backward: the running alpha-sum
   float* out; int64_t ldo;
-  int n_long_blocks; int rows_per_block;
+  ScanGrid sg;
 };
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 fma4(float s, float4 v, float4 a) {
-  return make_float4(fmaf(s, v.x, a.x), fmaf(s, v.y, a.y), fmaf(s, v.z, a.z), fmaf(s, v.w, a.w));
-}
-__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
-  return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
-}
-template <int LPR>
-__device__ __forceinline__ float4 fold_groups(float4 acc) {
-#pragma unroll
-  for (int m = 32; m >= LPR; m >>= 1) acc = add4(acc, shfl_xor4(acc, m));
-  return acc;
-}
-
-// Running per-group sums over this wave's 64-edge chunks of [e0, e1): chunks e0 + 64 (wave_id + k n_waves).  Inside a chunk the kept
-// entries are moved to the low lanes in ascending order (ds_permute), then group g takes kept entries g, g + G, ...
-template <int LPR, bool XN>
-__device__ __forceinline__ float4 gather_acc(const PropArgs& a, int64_t e0, int64_t e1, int wave_id, int n_waves, int col4, bool col_ok,
-                                             int lane, float4 acc) {
-  constexpr int G = 64 / LPR;
-  constexpr int U = G >= 8 ? (64 / G < 8 ? 64 / G : 8) : 8;    // edges in flight per group (G U <= 64: one chunk)
-  const int g = lane / LPR;
-  for (int64_t base = e0 + (int64_t)wave_id * 64; base < e1; base += (int64_t)n_waves * 64) {
-    const int64_t rem = e1 - base;
-    const int cnt = rem < 64 ? (int)rem : 64;
+// The gathered rows, with the edge mask of step t as the per-chunk hook: the kept entries of a 64-entry chunk are moved to the low lanes in
+// ascending order (ds_permute), so that group g takes kept entries g, g + G, ... and a dropped edge's row is never loaded.
+template <bool XN>
+struct PropRows : NormRows<XN> {
+  const int32_t* eids; uint32_t thr, seed, t;
+  __device__ __forceinline__ int chunk(int64_t base, int lane, int cnt, int& my_idx) const {
+    if (!thr) return cnt;                                               // (uniform)
     const bool in = lane < cnt;
-    int my_idx = in ? __builtin_nontemporal_load(a.indices + base + lane) : 0;
-    bool keep = in;
-    int n_keep = cnt;
-    if (a.thr) {                                                        // (uniform)
-      const uint32_t eid = a.eids ? (uint32_t)(in ? a.eids[base + lane] : 0) : (uint32_t)(base + lane);
-      keep = in && edge_keep(a.seed, a.thr, a.t, eid);
-      const uint64_t m = __ballot(keep);
-      const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-      n_keep = __popcll(m);
-      const int dst = keep ? below : n_keep + (lane - below);          // a permutation: kept entries first, in ascending order
-      my_idx = __builtin_amdgcn_ds_permute(dst << 2, my_idx);
-    }
-    float my_cs = 0.f;
-    if (XN) my_cs = lane < n_keep ? a.x_norm[my_idx] : 0.f;
-    for (int j = 0; j < n_keep; j += G * U) {
-      float4 v[U];
-      float s[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int ei = j + u * G + g;
-        const int src = (G == 1) ? __builtin_amdgcn_readlane(my_idx, ei & 63) : __shfl(my_idx, ei & 63);
-        if (XN) s[u] = (G == 1) ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_cs), ei & 63))
-                                : __shfl(my_cs, ei & 63);
-        const bool ok = ei < n_keep && col_ok;
-        v[u] = ok ? ld4(a.x + (int64_t)src * a.ldx + col4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc = XN ? fma4(s[u], v[u], acc) : add4(acc, v[u]);
-    }
+    const uint32_t eid = eids ? (uint32_t)(in ? eids[base + lane] : 0) : (uint32_t)(base + lane);
+    const bool keep = in && edge_keep(seed, thr, t, eid);
+    const uint64_t m = __ballot(keep);
+    const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const int n_keep = __popcll(m);
+    const int dst = keep ? below : n_keep + (lane - below);            // a permutation: kept entries first, in ascending order
+    my_idx = __builtin_amdgcn_ds_permute(dst << 2, my_idx);
+    return n_keep;
   }
-  return acc;
-}
+};
 
 // the fused epilogue of one row (lanes < LPR with col_ok): norms, teleport / running sum, zeroed padding columns
 template <bool BWD>
@@ -160,68 +108,19 @@ __global__ __launch_bounds__(kBlock) void appnp_prop_kernel(const PropArgs a0) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int col4 = (lane % LPR) * 4;
   const bool col_ok = col4 < a.d;
-  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-
-  if ((int)blockIdx.x < a.n_long_blocks) {
-    // ---- long rows: scan chunk c's rows (c, c + n_chunks, ... : a degree-sorted order is dealt round-robin), whole workgroup per row ----
-    __shared__ int64_t s_rows[kBlock];
-    __shared__ int s_count;
-    __shared__ float4 s_part[kWaves][64];
-    const int64_t n_chunks = (a.n + kBlock - 1) / kBlock;
-    for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += a.n_long_blocks) {
-      if (threadIdx.x == 0) s_count = 0;
-      __syncthreads();
-      const int64_t r = (int64_t)threadIdx.x * n_chunks + chunk;
-      if (r < a.n && (a.indptr[r + 1] - a.indptr[r]) > kLongRow) s_rows[atomicAdd(&s_count, 1)] = r;
-      __syncthreads();
-      const int n_found = s_count;
-      for (int i = 0; i < n_found; ++i) {               // (the order rows are taken in does not matter: each row is one workgroup's)
-        const int64_t v = s_rows[i];
-        const float4 acc = fold_groups<LPR>(gather_acc<LPR, XN>(a, a.indptr[v], a.indptr[v + 1], wave, kWaves, col4, col_ok, lane, zero));
-        if (lane < LPR) s_part[wave][lane] = acc;
-        __syncthreads();
-        if (wave == 0 && lane < LPR && col_ok) {
-          float4 t = s_part[0][lane];
-#pragma unroll
-          for (int w = 1; w < kWaves; ++w) t = add4(t, s_part[w][lane]);
-          finish_row<BWD>(a, v, t, col4);
-        }
-        __syncthreads();
-      }
-    }
-    return;
-  }
-
-  __shared__ int s_ticket;
-  if (threadIdx.x == 0) s_ticket = 0;
-  __syncthreads();
-  const int64_t row_base = ((int64_t)blockIdx.x - a.n_long_blocks) * a.rows_per_block;
-#pragma unroll 1
-  while (true) {
-    int lr = 0;
-    if (lane == 0) lr = atomicAdd(&s_ticket, 1);
-    lr = __builtin_amdgcn_readfirstlane(lr);
-    if (lr >= a.rows_per_block) break;
-    const int64_t v = row_base + lr;
-    if (v >= a.n) break;
-    const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
-    if (e1 - e0 > kLongRow) continue;
-    const float4 acc = fold_groups<LPR>(gather_acc<LPR, XN>(a, e0, e1, 0, 1, col4, col_ok, lane, zero));
-    if (lane < LPR && col_ok) finish_row<BWD>(a, v, acc, col4);
-  }
+  PropRows<XN> ld;
+  ld.x = a.x; ld.ldx = a.ldx; ld.x_norm = a.x_norm; ld.col4 = col4; ld.col_ok = col_ok;
+  ld.eids = a.eids; ld.thr = a.thr; ld.seed = a.seed; ld.t = a.t;
+  scan_rows(a.indptr, a.n, a.sg, lane, wave, [&](int64_t v, int wave_id, int n_waves) {
+    float4 sum = wave_row_sum<LPR>(a.indices, a.indptr[v], a.indptr[v + 1], wave_id, n_waves, lane, ld);
+    if (n_waves > 1) sum = sum_waves_in_order<LPR>(sum, wave_id, lane);
+    if (wave_id == 0 && lane < LPR && col_ok) finish_row<BWD>(a, v, sum, col4);
+  });
 }
 
 template <bool BWD, bool XN>
 void launch_lpr(int lpr, dim3 grid, hipStream_t st, const PropArgs& a) {
-  switch (lpr) {
-    case 1: hipLaunchKernelGGL((appnp_prop_kernel<1, BWD, XN>), grid, dim3(kBlock), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((appnp_prop_kernel<2, BWD, XN>), grid, dim3(kBlock), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((appnp_prop_kernel<4, BWD, XN>), grid, dim3(kBlock), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((appnp_prop_kernel<8, BWD, XN>), grid, dim3(kBlock), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((appnp_prop_kernel<16, BWD, XN>), grid, dim3(kBlock), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((appnp_prop_kernel<32, BWD, XN>), grid, dim3(kBlock), 0, st, a); break;
-    default: hipLaunchKernelGGL((appnp_prop_kernel<64, BWD, XN>), grid, dim3(kBlock), 0, st, a); break;
-  }
+  with_lpr<1>(lpr, [&](auto L) { hipLaunchKernelGGL((appnp_prop_kernel<decltype(L)::value, BWD, XN>), grid, dim3(kBlock), 0, st, a); });
 }
 
 int prop_launch(PropArgs& a, int64_t nnz, int bwd, const char* what, void* stream) {
@@ -230,25 +129,14 @@ int prop_launch(PropArgs& a, int64_t nnz, int bwd, const char* what, void* strea
   if (a.n == 0) return GLNN_OK;
   GLNN_REQUIRE(a.indptr && (a.indices || nnz == 0) && a.x && a.out && a.row_norm, "%s: null pointer", what);
   GLNN_REQUIRE(bwd ? (a.acc != nullptr || (a.first && a.last)) : a.h0 != nullptr, "%s: null pointer", what);
-  const int64_t d4 = (a.d + 3) / 4 * 4;
-  auto ld_ok = [&](const float* p, int64_t ld) { return p == nullptr || (glnn::aligned16(p) && ld % 4 == 0 && ld >= d4); };
-  GLNN_REQUIRE(ld_ok(a.x, a.ldx) && ld_ok(a.out, a.ldo) && ld_ok(a.h0, a.ldh0) && ld_ok(a.acc, a.ldacc),
-               "%s: rows must be 16-byte aligned with a leading dimension %% 4 == 0 and >= round4(d)", what);
+  GLNN_REQUIRE(rows_ok(a.x, a.ldx, a.d) && rows_ok(a.out, a.ldo, a.d) && rows_ok(a.h0, a.ldh0, a.d) &&
+               rows_ok(a.acc, a.ldacc, a.d), "%s: rows must be 16-byte aligned with a leading dimension %% 4 == 0 and >= round4(d)", what);
   GLNN_REQUIRE(a.out != a.x && (!a.h0 || a.out != a.h0) && (!a.acc || (a.acc != a.out && a.acc != a.x)),
                "%s: out must not alias the input, h0 or acc", what);
-  const int dt = a.d < 256 ? a.d : 256;
-  const int lanes = (dt + 3) / 4;
-  int lpr = 1;
-  while (lpr < lanes) lpr <<= 1;
-  int64_t n_long = (a.n + kLongBlockRows - 1) / kLongBlockRows;
-  if (n_long > kLongBlockCap) n_long = kLongBlockCap;
-  a.n_long_blocks = (int)n_long;
-  int64_t rpw = a.n / (2048 * kWaves);
-  if (rpw < 1) rpw = 1;
-  if (rpw > kRowsPerWave) rpw = kRowsPerWave;
-  a.rows_per_block = (int)(rpw * kWaves);
-  const int64_t row_blocks = (a.n + a.rows_per_block - 1) / a.rows_per_block;
-  const dim3 grid((unsigned)(n_long + row_blocks), (unsigned)((a.d + 255) / 256));
+  const int lpr = lpr_for(((a.d < 256 ? a.d : 256) + 3) / 4, 1);
+  const int rc = scan_grid(a.n, what, &a.sg);
+  if (rc != GLNN_OK) return rc;
+  const dim3 grid(a.sg.grid_x, (unsigned)((a.d + 255) / 256));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool xn = a.x_norm != nullptr;
   if (bwd) { if (xn) launch_lpr<true, true>(lpr, grid, st, a); else launch_lpr<true, false>(lpr, grid, st, a); }

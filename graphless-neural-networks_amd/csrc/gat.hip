@@ -14,19 +14,13 @@
 //
 // Two lane layouts.  Scores: lane = (edge slot, head) with HP = pow2 >= H heads per slot, 64 / HP edges per step, 4 H bytes gathered per edge;
 // per-head reductions are xor butterflies over the slots.  Values: a row of H F <= 256 floats is LPR lanes moving float4, the G = 64 / LPR
-// lane groups take different edges and are folded with cross-lane adds (appnp.hip's mapping); each lane recomputes the weight of its own
-// head from el[j] (4 bytes, the same 32-byte segment for the whole group).  One wave per row of <= kLongRow entries (static assignment);
-// longer rows go to the first n_long_blocks workgroups, eight waves per row, folded through LDS in wave order.  No float atomics.
-#include "glnn_common.h"
+// lane groups take different edges and are folded with cross-lane adds (row_gather_dev.h's mapping); each lane recomputes the weight of its
+// own head from el[j] (4 bytes, the same 32-byte segment for the whole group).  Rows go to waves by that header's two-role scan with the
+// static assignment of short rows; a long row's eight partials are folded through LDS in wave order.  No float atomics.
+#include "row_gather_dev.h"
 
 namespace {
 
-constexpr int kBlock = 512;                // 8 waves
-constexpr int kWaves = kBlock / 64;
-constexpr int kRowsPerWave = 8;
-constexpr int kLongRow = 128;              // in-degree above which a whole workgroup takes the row
-constexpr int kLongBlockRows = 512;
-constexpr int kLongBlockCap = 512;
 constexpr int kU = 4;                      // edges in flight per lane group
 constexpr float kNegBig = -3.0e38f;
 
@@ -44,21 +38,9 @@ struct GatArgs {
   float* ds;                               // [E, H] scratch
   float* der; float* del_;                 // [N, H]
   const float* attn_l; const float* attn_r;
-  int n_long_blocks, rows_per_block;
+  ScanGrid sg;
 };
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
-  return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
-}
-template <int LPR>
-__device__ __forceinline__ float4 fold_groups(float4 acc) {
-#pragma unroll
-  for (int m = 32; m >= LPR; m >>= 1) acc = add4(acc, shfl_xor4(acc, m));
-  return acc;
-}
 __device__ __forceinline__ float lrelu(float s, float slope) { return s > 0.f ? s : s * slope; }
 __device__ __forceinline__ bool attn_keep(uint32_t seed, uint32_t thr, uint32_t eid, uint32_t head) {
   return (glnn::drop_hash(seed, eid, head) & 0xFFFFu) >= thr;
@@ -337,27 +319,22 @@ __global__ __launch_bounds__(kBlock) void gat_rows_kernel(const GatArgs a) {
   __shared__ Smem sm;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if ((int)blockIdx.x < a.n_long_blocks) {
-    // long rows: scan chunk c's rows (c, c + n_chunks, ...), the whole workgroup per row (appnp.hip's role split)
-    __shared__ int64_t s_rows[kBlock];
-    __shared__ int s_count;
+  // row_gather_dev.h's two roles with the loops written out: behind scan_rows' callback the KIND 2 kernels take 107..120 VGPRs for
+  // 84..96 and drop from 5 waves per SIMD to 4.  Short rows are assigned statically.
+  if ((int)blockIdx.x < a.sg.n_long_blocks) {
     const int64_t n_chunks = (a.n + kBlock - 1) / kBlock;
-    for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += a.n_long_blocks) {
-      if (threadIdx.x == 0) s_count = 0;
-      __syncthreads();
-      const int64_t r = (int64_t)threadIdx.x * n_chunks + chunk;
-      if (r < a.n && (a.indptr[r + 1] - a.indptr[r]) > kLongRow) s_rows[atomicAdd(&s_count, 1)] = r;
-      __syncthreads();
-      const int n_found = s_count;
-      for (int i = 0; i < n_found; ++i) {               // (the order rows are taken in does not matter: each row is one workgroup's)
-        do_row<KIND, LPR, UNI>(a, s_rows[i], wave, kWaves, lane, sm);
+    for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += a.sg.n_long_blocks) {
+      const int64_t* rows;
+      const int n_found = find_long_rows(a.indptr, a.n, n_chunks, chunk, &rows);
+      for (int i = 0; i < n_found; ++i) {
+        do_row<KIND, LPR, UNI>(a, rows[i], wave, kWaves, lane, sm);
         __syncthreads();
       }
     }
     return;
   }
-  const int64_t row_base = ((int64_t)blockIdx.x - a.n_long_blocks) * a.rows_per_block;
-  for (int lr = wave; lr < a.rows_per_block; lr += kWaves) {
+  const int64_t row_base = ((int64_t)blockIdx.x - a.sg.n_long_blocks) * a.sg.rows_per_block;
+  for (int lr = wave; lr < a.sg.rows_per_block; lr += kWaves) {
     const int64_t v = row_base + lr;
     if (v >= a.n) break;
     if (a.indptr[v + 1] - a.indptr[v] > kLongRow) continue;
@@ -367,13 +344,7 @@ __global__ __launch_bounds__(kBlock) void gat_rows_kernel(const GatArgs a) {
 
 template <int KIND, bool UNI>
 void launch_lpr(int lpr, dim3 grid, hipStream_t st, const GatArgs& a) {
-  switch (lpr) {
-    case 4: hipLaunchKernelGGL((gat_rows_kernel<KIND, 4, UNI>), grid, dim3(kBlock), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((gat_rows_kernel<KIND, 8, UNI>), grid, dim3(kBlock), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((gat_rows_kernel<KIND, 16, UNI>), grid, dim3(kBlock), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((gat_rows_kernel<KIND, 32, UNI>), grid, dim3(kBlock), 0, st, a); break;
-    default: hipLaunchKernelGGL((gat_rows_kernel<KIND, 64, UNI>), grid, dim3(kBlock), 0, st, a); break;
-  }
+  with_lpr<4>(lpr, [&](auto L) { hipLaunchKernelGGL((gat_rows_kernel<KIND, decltype(L)::value, UNI>), grid, dim3(kBlock), 0, st, a); });
 }
 
 int set_shape(GatArgs& a, int64_t n, int64_t nnz, int heads, int f, float p, const char* what) {
@@ -389,21 +360,11 @@ int set_shape(GatArgs& a, int64_t n, int64_t nnz, int heads, int f, float p, con
   return GLNN_OK;
 }
 
-bool row_ok(const float* p, int64_t ld, int hf) { return glnn::aligned16(p) && ld % 4 == 0 && ld >= (hf + 3) / 4 * 4; }
-
 int rows_launch(GatArgs& a, int kind, const char* what, void* stream) {
-  const int lanes = (a.HF + 3) / 4;
-  int lpr = 4;
-  while (lpr < lanes) lpr <<= 1;
-  int64_t n_long = (a.n + kLongBlockRows - 1) / kLongBlockRows;
-  if (n_long > kLongBlockCap) n_long = kLongBlockCap;
-  a.n_long_blocks = (int)n_long;
-  int64_t rpw = a.n / (2048 * kWaves);
-  if (rpw < 1) rpw = 1;
-  if (rpw > kRowsPerWave) rpw = kRowsPerWave;
-  a.rows_per_block = (int)(rpw * kWaves);
-  const int64_t row_blocks = (a.n + a.rows_per_block - 1) / a.rows_per_block;
-  const dim3 grid((unsigned)(n_long + row_blocks));
+  const int lpr = lpr_for((a.HF + 3) / 4, 4);
+  const int rc = scan_grid(a.n, what, &a.sg);
+  if (rc != GLNN_OK) return rc;
+  const dim3 grid(a.sg.grid_x);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool uni = a.F % 4 == 0;
   if (kind == 0) { if (uni) launch_lpr<0, true>(lpr, grid, st, a); else launch_lpr<0, false>(lpr, grid, st, a); }
@@ -526,7 +487,7 @@ extern "C" int glnn_gat_attn_fwd_f32(const int64_t* indptr, const int32_t* indic
   if (rc != GLNN_OK) return rc;
   if (n == 0) return GLNN_OK;
   GLNN_REQUIRE(indptr && (indices || nnz == 0) && z && el && er && out, "glnn_gat_attn_fwd_f32: null pointer");
-  GLNN_REQUIRE(row_ok(z, ldz, a.HF) && row_ok(out, ldo, a.HF) && out != z,
+  GLNN_REQUIRE(rows_ok(z, ldz, a.HF) && rows_ok(out, ldo, a.HF) && out != z,
                "glnn_gat_attn_fwd_f32: rows must be 16-byte aligned with a leading dimension %% 4 == 0 and >= round4(heads * out_feats); out != z");
   a.indptr = indptr; a.indices = indices; a.z = z; a.ldz = ldz; a.el = el; a.er = er; a.slope = negative_slope; a.seed = seed;
   a.relu = relu ? 1 : 0; a.out = out; a.ldo = ldo; a.lse = lse;
@@ -555,7 +516,7 @@ extern "C" int glnn_gat_attn_bwd_f32(const int64_t* indptr, const int32_t* indic
   }
   GLNN_REQUIRE(indptr && t_indptr && (nnz == 0 || (indices && t_indices && t_eids && ds)) && z && el && er && lse && attn_l && attn_r && g && y &&
                der && del_ && dz && workspace, "glnn_gat_attn_bwd_f32: null pointer");
-  GLNN_REQUIRE(row_ok(z, ldz, a.HF) && row_ok(g, ldg, a.HF) && row_ok(y, ldy, a.HF) && row_ok(dz, lddz, a.HF) && dz != g && dz != z,
+  GLNN_REQUIRE(rows_ok(z, ldz, a.HF) && rows_ok(g, ldg, a.HF) && rows_ok(y, ldy, a.HF) && rows_ok(dz, lddz, a.HF) && dz != g && dz != z,
                "glnn_gat_attn_bwd_f32: rows must be 16-byte aligned with a leading dimension %% 4 == 0 and >= round4(heads * out_feats); dz must "
                "not alias g or z");
   GLNN_REQUIRE(workspace_floats >= glnn_gat_attn_bwd_workspace_floats(n, heads, out_feats), "glnn_gat_attn_bwd_f32: workspace too small");

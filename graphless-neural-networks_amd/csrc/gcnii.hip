@@ -7,13 +7,11 @@
 //             dS = (1 - beta) dZ + beta dZ W,   dh0_acc (+)= alpha dS
 //
 //   gcnii_layer_kernel   A workgroup of 8 waves owns a tile of 32 rows:
-//       phase A  the waves pull the tile's rows from an LDS ticket; a wave gathers and sums one row's neighbours (16 bytes per lane,
-//                coalesced; the column indices read 64 at a time with the non-temporal hint and handed round with cross-lane moves; the
-//                per-source norm, when the rows are not pre-scaled, rides along the same way), applies the row's own terms (norm,
-//                dropout mask keyed by the own row, residual row, ReLU mask) and parks the row T in LDS columns [0, kpad); the training
-//                forward streams it to `t_out` (S, for the weight gradient), the backward stores t_scale T (beta dZ, the other operand).
-//                Rows of more than kLongRow entries are then taken by all 8 waves together, their partial sums folded through LDS in a
-//                fixed order.  The plain form loads the tile's own rows instead of gathering;
+//       phase A  row_gather_dev.h's 32-row tile: a wave gathers and sums one row's neighbours (the per-source norm, when the rows are not
+//                pre-scaled, rides along with the index), applies the row's own terms (norm, dropout mask keyed by the own row, residual
+//                row, ReLU mask) and parks the row T in LDS columns [0, kpad); the training forward streams it to `t_out` (S, for the
+//                weight gradient), the backward stores t_scale T (beta dZ, the other operand).  The plain form loads the tile's own rows
+//                instead of gathering: a ticket loop of its own, since it reads no CSR;
 //       phase B  wave w multiplies the [32 x kpad] tile with the w-th 32-column panel of the packed weight (glnn_pack_weight_f32 of W
 //                forward, of W^T backward) on the fp32 MFMA (v_mfma_f32_32x32x2_f32), one coalesced 1 KiB load per k-group from L2;
 //       epilogue (1 - beta) T + beta acc with T read back from LDS at the accumulator's (row, col); ReLU (forward); the backward also
@@ -22,39 +20,15 @@
 //
 // No float atomics and no grid barrier: a row's value is a fixed-order sum over its own edges (one wave, or eight waves with a fixed split
 // and fold), so results are bit-identical run to run and do not depend on which other rows are in the launch or on the tile order.
-#include "glnn_common.h"
+#include "row_gather_dev.h"
 
 namespace {
 
-constexpr int kWaves = 8;
-constexpr int kBlock = 64 * kWaves;
-constexpr int kTileRows = 32;
-constexpr int kLongRow = 128;      // entries above which the whole workgroup takes a row (spmm.hip's threshold, measured there)
-constexpr int kU = 8;              // row loads in flight per lane group
 constexpr int kMaxD = 256;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ int ld_idx_stream(const int32_t* p) { return __builtin_nontemporal_load(p); }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 mul4(float s, float4 v) { return make_float4(s * v.x, s * v.y, s * v.z, s * v.w); }
-__device__ __forceinline__ float4 fma4(float s, float4 v, float4 a) {
-  return make_float4(fmaf(s, v.x, a.x), fmaf(s, v.y, a.y), fmaf(s, v.z, a.z), fmaf(s, v.w, a.w));
-}
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
-  return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
-}
-// columns [d, ..) of a lane's four are padding: exact zeros whatever the row held there
-__device__ __forceinline__ float4 mask_cols(float4 y, int col4, int d) {
-  if (col4 + 0 >= d) y.x = 0.f;
-  if (col4 + 1 >= d) y.y = 0.f;
-  if (col4 + 2 >= d) y.z = 0.f;
-  if (col4 + 3 >= d) y.w = 0.f;
-  return y;
-}
 // the feature dropout of the package on four adjacent columns of `row` (col4 % 4 == 0: two hashes, 16 bits per element)
 __device__ __forceinline__ float4 drop4(float4 v, uint32_t seed, uint32_t thr, float dscale, uint32_t row, int col4) {
   const uint32_t h0 = glnn::drop_hash(seed, row, (uint32_t)col4 >> 1), h1 = glnn::drop_hash(seed, row, ((uint32_t)col4 >> 1) + 1u);
@@ -77,45 +51,15 @@ struct GcniiArgs {
   const int32_t* tile_order; int plain;
 };
 
-// Sum of xs[indices[e], col4 .. col4 + 3] over this wave's share of the edges [e0, e1): the 64-edge chunks e0 + 64 (wave_id + k n_waves).
-// A row of d floats is covered by LPR lanes; the G = 64 / LPR lane groups take different edges of a chunk (group g: the edges with
-// position % G == g, ascending), kU loads in flight each, and are folded with cross-lane adds.  The total is in lanes < LPR.
-template <int LPR, bool XN, bool DROP>
-__device__ __forceinline__ float4 wave_row_sum(const GcniiArgs& a, int64_t e0, int64_t e1, int wave_id, int n_waves, int col4, bool col_ok,
-                                               int lane) {
-  constexpr int G = 64 / LPR;
-  const int g = lane / LPR;
-  float4 acc = zero4();
-  for (int64_t base = e0 + (int64_t)wave_id * 64; base < e1; base += (int64_t)n_waves * 64) {
-    const int64_t rem = e1 - base;
-    const int cnt = rem < 64 ? (int)rem : 64;
-    const int my_idx = lane < cnt ? ld_idx_stream(a.indices + base + lane) : 0;
-    float my_cs = 1.f;
-    if (XN) my_cs = lane < cnt ? a.x_norm[my_idx] : 0.f;
-    for (int j = 0; j < cnt; j += G * kU) {
-      float4 v[kU];
-      float s[kU];
-      int src[kU];
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int ei = j + u * G + g;
-        src[u] = (G == 1) ? __builtin_amdgcn_readlane(my_idx, ei & 63) : __shfl(my_idx, ei & 63);
-        if (XN) s[u] = (G == 1) ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_cs), ei & 63))
-                                : __shfl(my_cs, ei & 63);
-        v[u] = (ei < cnt && col_ok) ? ld4(a.x + (int64_t)src[u] * a.ldx + col4) : zero4();
-      }
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        float4 t = v[u];
-        if (DROP) t = drop4(t, a.seed, a.src_thr, a.dscale, (uint32_t)src[u], col4);
-        acc = XN ? fma4(s[u], t, acc) : add4(acc, t);
-      }
-    }
+// the gathered rows; DROP: the training forward's mask, keyed by the SOURCE row, on every loaded element before it enters the sum
+template <bool XN, bool DROP>
+struct LayerRows : NormRows<XN> {
+  uint32_t seed, thr; float dscale;
+  __device__ __forceinline__ float4 add(float4 acc, float4 v, int src, float w) const {
+    if (DROP) v = drop4(v, seed, thr, dscale, (uint32_t)src, this->col4);
+    return NormRows<XN>::add(acc, v, src, w);
   }
-  if (G >= 2) acc = add4(acc, shfl_xor4(acc, 32));
-  if (G >= 4) acc = add4(acc, shfl_xor4(acc, 16));
-  return acc;
-}
+};
 
 // dynamic LDS (all of the kernel's LDS, so that its base stays 16-byte aligned): [tile floats][4 x 64 float4 fold slots][ticket]
 __host__ __device__ inline size_t fold_bytes() { return sizeof(float4) * 4 * 64 + 16; }
@@ -138,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void gcnii_layer_kernel(const GcniiArgs a) 
 
   // ---- phase A ------------------------------------------------------------------------------------------------------------------
   // called by ONE whole wave per tile row lr (valid == false: the row is past n); `sum` is in the lanes < LPR
-  auto finish = [&](int lr, int64_t v, float4 sum, bool valid) {
+  auto finish = [&](int lr, int64_t v, int64_t, float4 sum, bool valid) {
     if (lane >= LPR || col4 >= kpad) return;      // (LPR * 4 >= kpad: the lanes < LPR cover the padded row)
     float4 t = zero4();
     if (valid && col_ok) {
@@ -154,41 +98,18 @@ __global__ __launch_bounds__(kBlock) void gcnii_layer_kernel(const GcniiArgs a) 
     }
     st4(lds_a + lr * lda + col4, t);
   };
+  if (a.plain) {
 #pragma unroll 1
-  while (true) {
-    int lr = 0;
-    if (lane == 0) lr = atomicAdd(s_next, 1);
-    lr = __builtin_amdgcn_readfirstlane(lr);
-    if (lr >= kTileRows) break;
-    const int64_t v = row0 + lr;
-    if (v >= a.n) { finish(lr, v, zero4(), false); continue; }
-    if (a.plain) { finish(lr, v, (lane < LPR && col_ok) ? ld4(a.x + v * a.ldx + col4) : zero4(), true); continue; }
-    const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
-    if (e1 - e0 > kLongRow) continue;
-    finish(lr, v, wave_row_sum<LPR, XN, DROP>(a, e0, e1, 0, 1, col4, col_ok, lane), true);
-  }
-  __syncthreads();
-  if (!a.plain) {
-    // long rows of this tile: all 8 waves on one row at a time (uniform loop: every wave sees the same degrees)
-#pragma unroll 1
-    for (int lr = 0; lr < kTileRows; ++lr) {
+    for (int lr = tile_ticket(s_next, lane); lr < kTileRows; lr = tile_ticket(s_next, lane)) {
       const int64_t v = row0 + lr;
-      if (v >= a.n) break;
-      const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
-      if (e1 - e0 <= kLongRow) continue;
-      const float4 acc = wave_row_sum<LPR, XN, DROP>(a, e0, e1, wave, kWaves, col4, col_ok, lane);
-      // fold the 8 wave partials through 4 LDS slots in a fixed order: waves 4-7 park, waves 0-3 add theirs, wave 0 sums the four
-      if (wave >= 4 && lane < LPR) s_part[(wave - 4) * 64 + lane] = acc;
-      __syncthreads();
-      if (wave < 4 && lane < LPR) s_part[wave * 64 + lane] = add4(acc, s_part[wave * 64 + lane]);
-      __syncthreads();
-      if (wave == 0) {
-        float4 t = zero4();
-        if (lane < LPR) t = add4(add4(s_part[lane], s_part[64 + lane]), add4(s_part[128 + lane], s_part[192 + lane]));
-        finish(lr, v, t, true);
-      }
-      __syncthreads();
+      finish(lr, v, 0, (v < a.n && lane < LPR && col_ok) ? ld4(a.x + v * a.ldx + col4) : zero4(), v < a.n);
     }
+    __syncthreads();
+  } else {
+    LayerRows<XN, DROP> ld;
+    ld.x = a.x; ld.ldx = a.ldx; ld.x_norm = a.x_norm; ld.col4 = col4; ld.col_ok = col_ok;
+    ld.seed = a.seed; ld.thr = a.src_thr; ld.dscale = a.dscale;
+    gather_tile<LPR>(a.indptr, a.indices, a.n, row0, lane, wave, s_next, s_part, ld, finish);
   }
   if (!a.w_packed) return;      // the dH_0 launch: T (stored through t_out) is the result
 
@@ -248,10 +169,10 @@ __global__ __launch_bounds__(kBlock) void gcnii_layer_kernel(const GcniiArgs a) 
 
 template <bool XN, bool DROP>
 void launch_lpr(const GcniiArgs& a, unsigned blocks, size_t smem, hipStream_t st) {
-  const int kv = a.kgroups * 2;      // float4 per padded row: LPR * 4 >= kpad
-  if (kv <= 16) hipLaunchKernelGGL((gcnii_layer_kernel<16, XN, DROP>), dim3(blocks), dim3(kBlock), smem, st, a);
-  else if (kv <= 32) hipLaunchKernelGGL((gcnii_layer_kernel<32, XN, DROP>), dim3(blocks), dim3(kBlock), smem, st, a);
-  else hipLaunchKernelGGL((gcnii_layer_kernel<64, XN, DROP>), dim3(blocks), dim3(kBlock), smem, st, a);
+  // float4 per padded row: LPR * 4 >= kpad
+  with_lpr<16>(lpr_for(a.kgroups * 2, 16), [&](auto L) {
+    hipLaunchKernelGGL((gcnii_layer_kernel<decltype(L)::value, XN, DROP>), dim3(blocks), dim3(kBlock), smem, st, a);
+  });
 }
 
 // the geometry depends on d alone (LPR, the LDS tile) and on ceil(n / 32): no branch on n
@@ -268,8 +189,6 @@ int launch(GcniiArgs& a, const char* what, void* stream) {
   }
   return glnn::check_launch(what);
 }
-
-bool rows_ok(const float* p, int64_t ld, int d) { return p == nullptr || (glnn::aligned16(p) && ld % 4 == 0 && ld >= ((d + 3) & ~3)); }
 
 }  // namespace
 

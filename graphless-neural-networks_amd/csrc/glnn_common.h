@@ -69,6 +69,8 @@ inline int check_launch(const char* what) {
 }
 
 __host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// float4-addressable rows of d floats (or no buffer at all): 16-byte aligned, ld % 4 == 0, ld >= round4(d)
+inline bool rows_ok(const float* p, int64_t ld, int d) { return p == nullptr || (aligned16(p) && ld % 4 == 0 && ld >= ((d + 3) & ~3)); }
 
 #define GLNN_REQUIRE(cond, ...)                                     \
   do {                                                              \

@@ -12,20 +12,12 @@
 //            geometry -- the row tickets below are dynamic, so per-workgroup partials would not be reproducible; per-row scalars are.
 //   gamma is read from device memory (the parameter tensor Adam updates in place): no host read.
 //
-// Mapping: appnp_prop_kernel's.  A row of d <= 256 floats is LPR = 1..64 lanes moving float4; the G = 64 / LPR lane groups take different
-// edges of the same row and are folded with cross-lane adds (fixed order).  One wave per row of <= kLongRow entries (rows pulled from an
-// LDS ticket); longer rows go to the first n_long_blocks workgroups, eight waves per row, folded through LDS in wave order.  Wider rows:
-// blockIdx.y = the 256-column tile (row_dot then holds one scalar per tile and row).  No float atomics, no grid barrier.
-#include "glnn_common.h"
+// Mapping: row_gather_dev.h's wave gather under the two-role scan, rows pulled from an LDS ticket.  Wider rows: blockIdx.y = the
+// 256-column tile (row_dot then holds one scalar per tile and row).  No float atomics, no grid barrier.
+#include "row_gather_dev.h"
 
 namespace {
 
-constexpr int kBlock = 512;                // 8 waves
-constexpr int kWaves = kBlock / 64;
-constexpr int kRowsPerWave = 8;
-constexpr int kLongRow = 128;              // row length above which a whole workgroup takes the row
-constexpr int kLongBlockRows = 512;        // rows scanned per long-role step
-constexpr int kLongBlockCap = 512;
 constexpr int kFoldChunk = GLNN_GPR_FOLD_CHUNK;      // row_dot entries per stage-1 partial of the fold
 constexpr int kFoldBlock = 256;
 
@@ -40,63 +32,15 @@ struct GprArgs {
   float* acc; int64_t ldacc;
   float* out; int64_t ldo;   // NULL at the last step: the row itself is not needed again
   const float* h0; int64_t ldh0; float* row_dot;    // backward: row_dot[(k * tiles + tile) * n + row]
-  int n_long_blocks; int rows_per_block;
+  ScanGrid sg;
 };
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 fma4(float s, float4 v, float4 a) {
-  return make_float4(fmaf(s, v.x, a.x), fmaf(s, v.y, a.y), fmaf(s, v.z, a.z), fmaf(s, v.w, a.w));
-}
-__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
-  return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
-}
-template <int LPR>
-__device__ __forceinline__ float4 fold_groups(float4 acc) {
-#pragma unroll
-  for (int m = 32; m >= LPR; m >>= 1) acc = add4(acc, shfl_xor4(acc, m));
-  return acc;
-}
 // sum over the LPR lanes of a row (every lane of the wave calls it; lanes outside the row's columns pass 0)
 template <int LPR>
 __device__ __forceinline__ float fold_row(float v) {
 #pragma unroll
   for (int m = LPR >> 1; m >= 1; m >>= 1) v += __shfl_xor(v, m);
   return v;
-}
-
-// Running per-group sums over this wave's 64-entry chunks of [e0, e1): chunks e0 + 64 (wave_id + j n_waves); group g takes entries
-// g, g + G, ... of a chunk.  The index stream is read once: non-temporal.
-template <int LPR, bool XN>
-__device__ __forceinline__ float4 gather_acc(const GprArgs& a, int64_t e0, int64_t e1, int wave_id, int n_waves, int col4, bool col_ok,
-                                             int lane, float4 acc) {
-  constexpr int G = 64 / LPR;
-  constexpr int U = G >= 8 ? (64 / G < 8 ? 64 / G : 8) : 8;    // entries in flight per group (G U <= 64: one chunk)
-  const int g = lane / LPR;
-  for (int64_t base = e0 + (int64_t)wave_id * 64; base < e1; base += (int64_t)n_waves * 64) {
-    const int64_t rem = e1 - base;
-    const int cnt = rem < 64 ? (int)rem : 64;
-    const int my_idx = lane < cnt ? __builtin_nontemporal_load(a.indices + base + lane) : 0;
-    float my_cs = 0.f;
-    if (XN) my_cs = lane < cnt ? a.x_norm[my_idx] : 0.f;
-    for (int j = 0; j < cnt; j += G * U) {
-      float4 v[U];
-      float s[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int ei = j + u * G + g;
-        const int src = (G == 1) ? __builtin_amdgcn_readlane(my_idx, ei & 63) : __shfl(my_idx, ei & 63);
-        if (XN) s[u] = (G == 1) ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_cs), ei & 63))
-                                : __shfl(my_cs, ei & 63);
-        const bool ok = ei < cnt && col_ok;
-        v[u] = ok ? ld4(a.x + (int64_t)src * a.ldx + col4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc = XN ? fma4(s[u], v[u], acc) : add4(acc, v[u]);
-    }
-  }
-  return acc;
 }
 
 // The fused epilogue of one row.  EVERY lane of the wave calls it (the row_dot shuffles need all of them); `on` marks the lanes that own
@@ -156,58 +100,13 @@ __global__ __launch_bounds__(kBlock) void gpr_prop_kernel(const GprArgs a0) {
   const int col4 = (lane % LPR) * 4;
   const bool col_ok = col4 < a.d;
   const bool on = lane < LPR && col_ok;
-  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-
-  if ((int)blockIdx.x < a.n_long_blocks) {
-    // ---- long rows: scan chunk c's rows (c, c + n_chunks, ...), whole workgroup per row ----
-    __shared__ int64_t s_rows[kBlock];
-    __shared__ int s_count;
-    __shared__ float4 s_part[kWaves][64];
-    const int64_t n_chunks = (a.n + kBlock - 1) / kBlock;
-    for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += a.n_long_blocks) {
-      if (threadIdx.x == 0) s_count = 0;
-      __syncthreads();
-      const int64_t r = (int64_t)threadIdx.x * n_chunks + chunk;
-      if (r < a.n && (a.indptr[r + 1] - a.indptr[r]) > kLongRow) s_rows[atomicAdd(&s_count, 1)] = r;
-      __syncthreads();
-      const int n_found = s_count;
-      for (int i = 0; i < n_found; ++i) {               // (the order rows are taken in does not matter: each row is one workgroup's)
-        const int64_t v = s_rows[i];
-        const float4 acc = fold_groups<LPR>(gather_acc<LPR, XN>(a, a.indptr[v], a.indptr[v + 1], wave, kWaves, col4, col_ok, lane, zero));
-        if (lane < LPR) s_part[wave][lane] = acc;
-        __syncthreads();
-        if (wave == 0) {                                // (wave-uniform: all 64 lanes reach the shuffles of finish_row)
-          float4 t = zero;
-          if (lane < LPR) {
-            t = s_part[0][lane];
-#pragma unroll
-            for (int w = 1; w < kWaves; ++w) t = add4(t, s_part[w][lane]);
-          }
-          finish_row<LPR, DOT>(a, v, t, col4, on, lane, tile, tiles);
-        }
-        __syncthreads();
-      }
-    }
-    return;
-  }
-
-  __shared__ int s_ticket;
-  if (threadIdx.x == 0) s_ticket = 0;
-  __syncthreads();
-  const int64_t row_base = ((int64_t)blockIdx.x - a.n_long_blocks) * a.rows_per_block;
-#pragma unroll 1
-  while (true) {
-    int lr = 0;
-    if (lane == 0) lr = atomicAdd(&s_ticket, 1);
-    lr = __builtin_amdgcn_readfirstlane(lr);
-    if (lr >= a.rows_per_block) break;
-    const int64_t v = row_base + lr;
-    if (v >= a.n) break;
-    const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
-    if (e1 - e0 > kLongRow) continue;
-    const float4 acc = fold_groups<LPR>(gather_acc<LPR, XN>(a, e0, e1, 0, 1, col4, col_ok, lane, zero));
-    finish_row<LPR, DOT>(a, v, acc, col4, on, lane, tile, tiles);
-  }
+  NormRows<XN> ld;
+  ld.x = a.x; ld.ldx = a.ldx; ld.x_norm = a.x_norm; ld.col4 = col4; ld.col_ok = col_ok;
+  scan_rows(a.indptr, a.n, a.sg, lane, wave, [&](int64_t v, int wave_id, int n_waves) {
+    float4 sum = wave_row_sum<LPR>(a.indices, a.indptr[v], a.indptr[v + 1], wave_id, n_waves, lane, ld);
+    if (n_waves > 1) sum = sum_waves_in_order<LPR>(sum, wave_id, lane);
+    if (wave_id == 0) finish_row<LPR, DOT>(a, v, sum, col4, on, lane, tile, tiles);      // (wave-uniform: all 64 lanes reach its shuffles)
+  });
 }
 
 // K = 0 / the k = 0 entry: acc = gamma_0 x (padding zero) and row_dot[0] = <x, h0> per row and tile; one wave per row, no gather
@@ -252,28 +151,12 @@ __global__ __launch_bounds__(kBlock) void gpr_scale_kernel(const GprArgs a0) {
 
 template <bool XN, bool DOT>
 void launch_lpr(int lpr, dim3 grid, hipStream_t st, const GprArgs& a) {
-  switch (lpr) {
-    case 1: hipLaunchKernelGGL((gpr_prop_kernel<1, XN, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((gpr_prop_kernel<2, XN, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((gpr_prop_kernel<4, XN, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((gpr_prop_kernel<8, XN, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((gpr_prop_kernel<16, XN, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((gpr_prop_kernel<32, XN, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    default: hipLaunchKernelGGL((gpr_prop_kernel<64, XN, DOT>), grid, dim3(kBlock), 0, st, a); break;
-  }
+  with_lpr<1>(lpr, [&](auto L) { hipLaunchKernelGGL((gpr_prop_kernel<decltype(L)::value, XN, DOT>), grid, dim3(kBlock), 0, st, a); });
 }
 
 template <bool DOT>
 void launch_scale(int lpr, dim3 grid, hipStream_t st, const GprArgs& a) {
-  switch (lpr) {
-    case 1: hipLaunchKernelGGL((gpr_scale_kernel<1, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((gpr_scale_kernel<2, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((gpr_scale_kernel<4, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((gpr_scale_kernel<8, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((gpr_scale_kernel<16, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((gpr_scale_kernel<32, DOT>), grid, dim3(kBlock), 0, st, a); break;
-    default: hipLaunchKernelGGL((gpr_scale_kernel<64, DOT>), grid, dim3(kBlock), 0, st, a); break;
-  }
+  with_lpr<1>(lpr, [&](auto L) { hipLaunchKernelGGL((gpr_scale_kernel<decltype(L)::value, DOT>), grid, dim3(kBlock), 0, st, a); });
 }
 
 // fp64 sum of one wave's values in a fixed xor tree, then the block's waves in wave order (thread 0 holds the result)
@@ -329,9 +212,7 @@ extern "C" int glnn_gpr_prop_f32(const int64_t* indptr, const int32_t* indices, 
   GLNN_REQUIRE(k != 1 || x_norm, "%s: step 1 gathers the unscaled rows (x_norm required)", what);
   GLNN_REQUIRE(k <= 1 || !x_norm, "%s: steps k > 1 gather pre-scaled rows (x_norm must be NULL)", what);
   GLNN_REQUIRE(k == 0 || !out || out_norm, "%s: a stored row is pre-scaled for the next step (out_norm required with out)", what);
-  const int64_t d4 = (d + 3) / 4 * 4;
-  auto ld_ok = [&](const float* p, int64_t ld) { return p == nullptr || (glnn::aligned16(p) && ld % 4 == 0 && ld >= d4); };
-  GLNN_REQUIRE(ld_ok(x, ldx) && ld_ok(acc, ldacc) && ld_ok(k ? out : nullptr, ldo) && ld_ok(h0, ldh0),
+  GLNN_REQUIRE(rows_ok(x, ldx, d) && rows_ok(acc, ldacc, d) && rows_ok(k ? out : nullptr, ldo, d) && rows_ok(h0, ldh0, d),
                "%s: rows must be 16-byte aligned with a leading dimension %% 4 == 0 and >= round4(d)", what);
   GLNN_REQUIRE(acc != x && (k == 0 || !out || (out != x && out != acc)) && (!h0 || h0 != acc), "%s: acc / out must not alias an input", what);
   GprArgs a = {};
@@ -339,10 +220,7 @@ extern "C" int glnn_gpr_prop_f32(const int64_t* indptr, const int32_t* indices, 
   a.x = x; a.ldx = ldx; a.x_norm = x_norm; a.row_norm = row_norm; a.out_norm = out_norm;
   a.gamma = gamma; a.k = k; a.acc = acc; a.ldacc = ldacc; a.out = k ? out : nullptr; a.ldo = ldo;
   a.h0 = h0; a.ldh0 = ldh0; a.row_dot = row_dot;
-  const int dt = d < 256 ? d : 256;
-  const int lanes = (dt + 3) / 4;
-  int lpr = 1;
-  while (lpr < lanes) lpr <<= 1;
+  const int lpr = lpr_for(((d < 256 ? d : 256) + 3) / 4, 1);
   const unsigned tiles = (unsigned)((d + 255) / 256);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (k == 0) {
@@ -352,16 +230,9 @@ extern "C" int glnn_gpr_prop_f32(const int64_t* indptr, const int32_t* indices, 
     if (h0) launch_scale<true>(lpr, grid, st, a); else launch_scale<false>(lpr, grid, st, a);
     return glnn::check_launch(what);
   }
-  int64_t n_long = (n + kLongBlockRows - 1) / kLongBlockRows;
-  if (n_long > kLongBlockCap) n_long = kLongBlockCap;
-  a.n_long_blocks = (int)n_long;
-  int64_t rpw = n / (2048 * kWaves);
-  if (rpw < 1) rpw = 1;
-  if (rpw > kRowsPerWave) rpw = kRowsPerWave;
-  a.rows_per_block = (int)(rpw * kWaves);
-  const int64_t row_blocks = (n + a.rows_per_block - 1) / a.rows_per_block;
-  GLNN_REQUIRE(n_long + row_blocks < ((int64_t)1 << 31), "%s: n too large for one launch", what);
-  const dim3 grid((unsigned)(n_long + row_blocks), tiles);
+  const int rc = scan_grid(n, what, &a.sg);
+  if (rc != GLNN_OK) return rc;
+  const dim3 grid(a.sg.grid_x, tiles);
   const bool xn = x_norm != nullptr;
   if (h0) { if (xn) launch_lpr<true, true>(lpr, grid, st, a); else launch_lpr<false, true>(lpr, grid, st, a); }
   else { if (xn) launch_lpr<true, false>(lpr, grid, st, a); else launch_lpr<false, false>(lpr, grid, st, a); }

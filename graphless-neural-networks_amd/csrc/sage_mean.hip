@@ -6,11 +6,8 @@
 //
 //   sage_mean_fused_kernel   aggregate-first layers (d_in <= d_out <= 256), ONE launch per layer.  A workgroup of 8 waves owns a tile of 32
 //     destination rows:
-//       phase A  the waves pull the tile's rows from an LDS ticket; a wave gathers and sums one row's in-neighbours (16 bytes per lane,
-//                coalesced; the column indices read 64 at a time with the non-temporal hint and handed round with cross-lane moves), scales
-//                by 1 / max(deg, 1) and parks the row in LDS columns [0, kpad); the row's SELF row goes beside it, columns [kpad, 2 kpad).
-//                Rows of more than kLongRow in-edges are then taken by all 8 waves together, their partial sums folded through LDS in a
-//                fixed order;
+//       phase A  row_gather_dev.h's 32-row tile: a wave gathers and sums one row's in-neighbours, scales by 1 / max(deg, 1) and parks the
+//                row in LDS columns [0, kpad); the row's SELF row goes beside it, columns [kpad, 2 kpad);
 //       phase B  wave w multiplies the [32 x 2 kpad] tile with the w-th 32-column panel of W_cat = [W_neigh | W_self] on the fp32 MFMA
 //                (v_mfma_f32_32x32x2_f32) -- one product over K = 2 kpad.  W_cat arrives packed in B-fragment order (glnn_pack_weight_f32 of
 //                the concatenation), one coalesced 1 KiB load per k-group and wave from L2;
@@ -22,70 +19,19 @@
 //
 // No float atomics and no grid barrier: a row's value is a fixed-order sum over its own edges (one wave, or eight waves with a fixed split
 // and fold), so results are bit-identical run to run and do not depend on which other rows are in the launch or on the tile order.
-#include "glnn_common.h"
+#include "row_gather_dev.h"
 
 namespace {
 
-constexpr int kWaves = 8;
-constexpr int kBlock = 64 * kWaves;
-constexpr int kTileRows = 32;
-constexpr int kLongRow = 128;      // in-edges above which the whole workgroup takes a row (spmm.hip's threshold, measured there)
-constexpr int kU = 8;              // row loads in flight per lane group
 constexpr int kMaxD = 256;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-// stream-once data (column indices, output rows) with the non-temporal hint: it must not evict the re-used feature rows
+// stream-once data (output rows) with the non-temporal hint: it must not evict the re-used feature rows
 __device__ __forceinline__ void st4_stream(float* p, float4 v) {
   f32x4_t t = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(t, reinterpret_cast<f32x4_t*>(p));
-}
-__device__ __forceinline__ int ld_idx_stream(const int32_t* p) { return __builtin_nontemporal_load(p); }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
-  return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
-}
-// columns [d, ..) of a lane's four are padding: exact zeros whatever the row held there
-__device__ __forceinline__ float4 mask_cols(float4 y, int col4, int d) {
-  if (col4 + 0 >= d) y.x = 0.f;
-  if (col4 + 1 >= d) y.y = 0.f;
-  if (col4 + 2 >= d) y.z = 0.f;
-  if (col4 + 3 >= d) y.w = 0.f;
-  return y;
-}
-
-// Sum of x[indices[e], col4 .. col4 + 3] over this wave's share of the edges [e0, e1): the 64-edge chunks e0 + 64 (wave_id + k n_waves).
-// A row of d floats is covered by LPR lanes; the G = 64 / LPR lane groups take different edges of a chunk (group g: the edges with
-// position % G == g, ascending), kU loads in flight each, and are folded with cross-lane adds.  The total is in lanes < LPR.
-template <int LPR>
-__device__ __forceinline__ float4 wave_row_sum(const int32_t* __restrict__ indices, int64_t e0, int64_t e1, int wave_id, int n_waves,
-                                               const float* __restrict__ x, int64_t ldx, int col4, bool col_ok, int lane) {
-  constexpr int G = 64 / LPR;
-  const int g = lane / LPR;
-  float4 acc = zero4();
-  for (int64_t base = e0 + (int64_t)wave_id * 64; base < e1; base += (int64_t)n_waves * 64) {
-    const int64_t rem = e1 - base;
-    const int cnt = rem < 64 ? (int)rem : 64;
-    const int my_idx = lane < cnt ? ld_idx_stream(indices + base + lane) : 0;
-    for (int j = 0; j < cnt; j += G * kU) {
-      float4 v[kU];
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int ei = j + u * G + g;
-        const int src = (G == 1) ? __builtin_amdgcn_readlane(my_idx, ei & 63) : __shfl(my_idx, ei & 63);
-        v[u] = (ei < cnt && col_ok) ? ld4(x + (int64_t)src * ldx + col4) : zero4();
-      }
-#pragma unroll
-      for (int u = 0; u < kU; ++u) acc = add4(acc, v[u]);
-    }
-  }
-  if (G >= 2) acc = add4(acc, shfl_xor4(acc, 32));
-  if (G >= 4) acc = add4(acc, shfl_xor4(acc, 16));
-  return acc;
 }
 
 struct MeanArgs {
@@ -98,47 +44,15 @@ struct MeanArgs {
   const int32_t* tile_order;
 };
 
-// Phase A over one 32-row tile.  finish(lr, v, inv, sum, valid) is called by ONE whole wave per tile row lr (valid == false: the row is
-// past n_dst); `sum` is in the lanes < LPR.  s_next must be 0 and visible on entry; ends behind a barrier.
+// phase A of both kernels.  finish(lr, v, deg, sum, valid): row_gather_dev.h gather_tile
 template <int LPR, class Fin>
 __device__ __forceinline__ void aggregate_tile(const MeanArgs& a, int64_t row0, int lane, int wave, int col4, bool col_ok, int* s_next,
                                                float4* s_part, Fin&& finish) {
-#pragma unroll 1
-  while (true) {
-    int lr = 0;
-    if (lane == 0) lr = atomicAdd(s_next, 1);
-    lr = __builtin_amdgcn_readfirstlane(lr);
-    if (lr >= kTileRows) break;
-    const int64_t v = row0 + lr;
-    if (v >= a.n_dst) { finish(lr, v, 0.f, zero4(), false); continue; }
-    const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
-    const int64_t deg = e1 - e0;
-    if (deg > kLongRow) continue;
-    const float4 acc = wave_row_sum<LPR>(a.indices, e0, e1, 0, 1, a.x, a.ldx, col4, col_ok, lane);
-    finish(lr, v, 1.0f / (float)(deg > 1 ? deg : 1), acc, true);
-  }
-  __syncthreads();
-  // long rows of this tile: all 8 waves on one row at a time (uniform loop: every wave sees the same degrees)
-#pragma unroll 1
-  for (int lr = 0; lr < kTileRows; ++lr) {
-    const int64_t v = row0 + lr;
-    if (v >= a.n_dst) break;
-    const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
-    if (e1 - e0 <= kLongRow) continue;
-    const float4 acc = wave_row_sum<LPR>(a.indices, e0, e1, wave, kWaves, a.x, a.ldx, col4, col_ok, lane);
-    // fold the 8 wave partials through 4 LDS slots in a fixed order: waves 4-7 park, waves 0-3 add theirs, wave 0 sums the four
-    if (wave >= 4 && lane < LPR) s_part[(wave - 4) * 64 + lane] = acc;
-    __syncthreads();
-    if (wave < 4 && lane < LPR) s_part[wave * 64 + lane] = add4(acc, s_part[wave * 64 + lane]);
-    __syncthreads();
-    if (wave == 0) {
-      float4 t = zero4();
-      if (lane < LPR) t = add4(add4(s_part[lane], s_part[64 + lane]), add4(s_part[128 + lane], s_part[192 + lane]));
-      finish(lr, v, 1.0f / (float)(e1 - e0), t, true);
-    }
-    __syncthreads();
-  }
+  NormRows<false> ld;
+  ld.x = a.x; ld.ldx = a.ldx; ld.x_norm = nullptr; ld.col4 = col4; ld.col_ok = col_ok;
+  gather_tile<LPR>(a.indptr, a.indices, a.n_dst, row0, lane, wave, s_next, s_part, ld, finish);
 }
+__device__ __forceinline__ float inv_deg(int64_t deg) { return 1.0f / (float)(deg > 1 ? deg : 1); }
 
 // dynamic LDS (all of the kernel's LDS, so that its base stays 16-byte aligned): [tile floats][4 x 64 float4 fold slots][ticket]
 __host__ __device__ inline size_t fold_bytes() { return sizeof(float4) * 4 * 64 + 16; }
@@ -160,10 +74,11 @@ __global__ __launch_bounds__(kBlock) void sage_mean_fused_kernel(const MeanArgs 
   __syncthreads();
 
   aggregate_tile<LPR>(a, row0, lane, wave, col4, col_ok, s_next, s_part,
-                      [&](int lr, int64_t v, float inv, float4 sum, bool valid) {
+                      [&](int lr, int64_t v, int64_t deg, float4 sum, bool valid) {      // (rows past n_dst too: zeros are parked)
                         if (lane >= LPR || col4 >= kpad) return;      // (LPR * 4 >= kpad: the lanes < LPR cover the padded row)
                         float4 m = zero4(), s = zero4();
                         if (valid && col_ok) {
+                          const float inv = inv_deg(deg);
                           m = mask_cols(make_float4(sum.x * inv, sum.y * inv, sum.z * inv, sum.w * inv), col4, a.d_in);
                           const int64_t sr = a.self_rows ? a.self_rows[v] : v;
                           s = mask_cols(ld4(a.x_self + sr * a.ld_self + col4), col4, a.d_in);
@@ -242,8 +157,9 @@ __global__ __launch_bounds__(kBlock) void spmm_sage_mean_kernel(const MeanArgs a
   if (threadIdx.x == 0) *s_next = 0;
   __syncthreads();
   aggregate_tile<LPR>(a, row0, lane, wave, col4, col_ok, s_next, s_part,
-                      [&](int, int64_t v, float inv, float4 sum, bool valid) {
+                      [&](int, int64_t v, int64_t deg, float4 sum, bool valid) {
                         if (!valid || lane >= LPR || !col_ok) return;
+                        const float inv = inv_deg(deg);
                         const float4 s = ld4(a.x_self + v * a.ld_self + col4);
                         float o[4] = {sum.x * inv + s.x, sum.y * inv + s.y, sum.z * inv + s.z, sum.w * inv + s.w};
 #pragma unroll
@@ -306,10 +222,8 @@ extern "C" int glnn_sage_mean_fused_f32(const int64_t* indptr, const int32_t* in
   GLNN_REQUIRE(blocks < ((int64_t)1 << 31), "glnn_sage_mean_fused_f32: n_dst too large for one launch");
   const size_t smem = sizeof(float) * kTileRows * (2 * a.kgroups * 8 + 4) + fold_bytes();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int kv = a.kgroups * 2;      // float4 per padded half row: LPR * 4 >= kpad
-  if (kv <= 16) return launch_fused<16>(a, (unsigned)blocks, smem, st);
-  if (kv <= 32) return launch_fused<32>(a, (unsigned)blocks, smem, st);
-  return launch_fused<64>(a, (unsigned)blocks, smem, st);
+  // float4 per padded half row: LPR * 4 >= kpad
+  return with_lpr<16>(lpr_for(a.kgroups * 2, 16), [&](auto L) { return launch_fused<decltype(L)::value>(a, (unsigned)blocks, smem, st); });
 }
 
 extern "C" int glnn_spmm_sage_mean_f32(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, const float* x,
@@ -331,9 +245,8 @@ extern "C" int glnn_spmm_sage_mean_f32(const int64_t* indptr, const int32_t* ind
   GLNN_REQUIRE(blocks < ((int64_t)1 << 31), "glnn_spmm_sage_mean_f32: n_dst too large for one launch");
   const size_t smem = fold_bytes();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int dv = dpad / 4;
-  if (dv <= 16) hipLaunchKernelGGL((spmm_sage_mean_kernel<16>), dim3((unsigned)blocks), dim3(kBlock), smem, st, a);
-  else if (dv <= 32) hipLaunchKernelGGL((spmm_sage_mean_kernel<32>), dim3((unsigned)blocks), dim3(kBlock), smem, st, a);
-  else hipLaunchKernelGGL((spmm_sage_mean_kernel<64>), dim3((unsigned)blocks), dim3(kBlock), smem, st, a);
+  with_lpr<16>(lpr_for(dpad / 4, 16), [&](auto L) {
+    hipLaunchKernelGGL((spmm_sage_mean_kernel<decltype(L)::value>), dim3((unsigned)blocks), dim3(kBlock), smem, st, a);
+  });
   return glnn::check_launch("glnn_spmm_sage_mean_f32");
 }

@@ -15,12 +15,10 @@
 //   pack_pair_kernel       W_cat = [W_neigh | W_self] ([d_out, 2 round4(d_in)], zero padding) and b_neigh + b_self, re-packed every step
 //     because the parameters change every step.
 //
-// Both aggregations take the row split of csrc/sage_mean.hip: rows of more than 128 entries are summed by all eight waves of the workgroup
-// (64-entry chunks dealt round-robin, the partials folded through LDS in a fixed order), shorter rows by one wave.  No float atomics, no
-// grid barrier: bit-identical run to run.  Rows wider than 256 floats are cut into 256-column slabs (blockIdx.y).
+// Both aggregations run row_gather_dev.h's 32-row tile.  No float atomics, no grid barrier: bit-identical run to run.  Rows wider than 256
+// floats are cut into 256-column slabs (blockIdx.y).
 // The projections, weight gradients, loss, tails and Adam are the library's existing launches.
-#include <hip/hip_runtime.h>
-#include "glnn_common.h"
+#include "row_gather_dev.h"
 
 #define GLNN_TRY(expr)              \
   do {                              \
@@ -30,29 +28,7 @@
 
 namespace {
 
-constexpr int kWaves = 8;
-constexpr int kBlock = 64 * kWaves;
-constexpr int kTileRows = 32;
-constexpr int kLongRow = 128;      // entries above which the whole workgroup takes a row (csrc/sage_mean.hip)
-constexpr int kU = 8;              // row loads in flight per lane group
 constexpr int kMaxTailD = 256;     // widest hidden layer whose tail the gather evaluates (the limit of glnn::spmm_csr_tail)
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ int ld_idx_stream(const int32_t* p) { return __builtin_nontemporal_load(p); }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
-  return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
-}
-// columns [d, ..) of a lane's four are padding: exact zeros whatever the row held there
-__device__ __forceinline__ float4 mask_cols(float4 y, int col4, int d) {
-  if (col4 + 0 >= d) y.x = 0.f;
-  if (col4 + 1 >= d) y.y = 0.f;
-  if (col4 + 2 >= d) y.z = 0.f;
-  if (col4 + 3 >= d) y.w = 0.f;
-  return y;
-}
 
 // The hidden tail of the layer in front, per lane: its four columns' scale / shift (BatchNorm a_scale / a_shift, or LayerNorm gamma / beta)
 struct TailCols { float s[4], h[4]; uint32_t thr, seed; float dscale; int col; bool affine; const float* mean; const float* rstd; };
@@ -82,78 +58,6 @@ __device__ __forceinline__ float4 tail_apply(const TailCols& x, float4 v, uint32
   return make_float4(o[0], o[1], o[2], o[3]);
 }
 
-// Sum of ld.row(indices[e], ld.weight(indices[e])) over this wave's share of the entries [e0, e1): the 64-entry chunks
-// e0 + 64 (wave_id + k n_waves).  A row is covered by LPR lanes; the G = 64 / LPR lane groups take different entries of a chunk (group g:
-// positions % G == g, ascending), kU loads in flight each, and are folded with cross-lane adds.  The total is in lanes < LPR.
-template <int LPR, class Ld>
-__device__ __forceinline__ float4 wave_row_sum(const int32_t* __restrict__ indices, int64_t e0, int64_t e1, int wave_id, int n_waves, int lane,
-                                               const Ld& ld) {
-  constexpr int G = 64 / LPR;
-  const int g = lane / LPR;
-  float4 acc = zero4();
-  for (int64_t base = e0 + (int64_t)wave_id * 64; base < e1; base += (int64_t)n_waves * 64) {
-    const int64_t rem = e1 - base;
-    const int cnt = rem < 64 ? (int)rem : 64;
-    const int my_idx = lane < cnt ? ld_idx_stream(indices + base + lane) : 0;
-    const float my_w = ld.weight(my_idx, lane < cnt);
-    for (int j = 0; j < cnt; j += G * kU) {
-      float4 v[kU];
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int ei = j + u * G + g;
-        const int src = __shfl(my_idx, ei & 63);
-        const float w = __shfl(my_w, ei & 63);
-        v[u] = ei < cnt ? ld.row(src, w) : zero4();
-      }
-#pragma unroll
-      for (int u = 0; u < kU; ++u) acc = add4(acc, v[u]);
-    }
-  }
-  if (G >= 2) acc = add4(acc, shfl_xor4(acc, 32));
-  if (G >= 4) acc = add4(acc, shfl_xor4(acc, 16));
-  return acc;
-}
-
-// One 32-row tile of a CSR.  finish(v, n_entries, sum) is called by ONE whole wave per row v < n_rows; `sum` is in the lanes < LPR.
-// s_next must be 0 and visible on entry.
-template <int LPR, class Ld, class Fin>
-__device__ __forceinline__ void aggregate_tile(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows,
-                                               int64_t row0, int lane, int wave, int* s_next, float4* s_part, const Ld& ld, Fin&& finish) {
-#pragma unroll 1
-  while (true) {
-    int lr = 0;
-    if (lane == 0) lr = atomicAdd(s_next, 1);
-    lr = __builtin_amdgcn_readfirstlane(lr);
-    if (lr >= kTileRows) break;
-    const int64_t v = row0 + lr;
-    if (v >= n_rows) continue;
-    const int64_t e0 = indptr[v], e1 = indptr[v + 1];
-    if (e1 - e0 > kLongRow) continue;
-    finish(v, e1 - e0, wave_row_sum<LPR>(indices, e0, e1, 0, 1, lane, ld));
-  }
-  __syncthreads();
-  // long rows of this tile: all 8 waves on one row at a time (uniform loop: every wave sees the same row lengths)
-#pragma unroll 1
-  for (int lr = 0; lr < kTileRows; ++lr) {
-    const int64_t v = row0 + lr;
-    if (v >= n_rows) break;
-    const int64_t e0 = indptr[v], e1 = indptr[v + 1];
-    if (e1 - e0 <= kLongRow) continue;
-    const float4 acc = wave_row_sum<LPR>(indices, e0, e1, wave, kWaves, lane, ld);
-    // fold the 8 wave partials through 4 LDS slots in a fixed order: waves 4-7 park, waves 0-3 add theirs, wave 0 sums the four
-    if (wave >= 4 && lane < LPR) s_part[(wave - 4) * 64 + lane] = acc;
-    __syncthreads();
-    if (wave < 4 && lane < LPR) s_part[wave * 64 + lane] = add4(acc, s_part[wave * 64 + lane]);
-    __syncthreads();
-    if (wave == 0) {
-      float4 t = zero4();
-      if (lane < LPR) t = add4(add4(s_part[lane], s_part[64 + lane]), add4(s_part[128 + lane], s_part[192 + lane]));
-      finish(v, e1 - e0, t);
-    }
-    __syncthreads();
-  }
-}
-
 struct CatArgs {
   const int64_t* indptr; const int32_t* indices; int64_t n_dst;
   const float* x; int64_t ldx; int d;                       // the gathered rows (plain rows, or pre-activations z with `tail`)
@@ -163,11 +67,10 @@ struct CatArgs {
 };
 
 template <int XF>
-struct CatLoad {
+struct CatLoad : GatherPolicy {
   const float* x; int64_t ldx; int col4; bool col_ok; TailCols tc;
-  __device__ __forceinline__ float weight(int, bool) const { return 0.f; }
-  __device__ __forceinline__ float4 row(int src, float) const {
-    return col_ok ? tail_apply<XF>(tc, ld4(x + (int64_t)src * ldx + col4), (uint32_t)src) : zero4();
+  __device__ __forceinline__ float4 row(int src, float, bool ok) const {
+    return (ok && col_ok) ? tail_apply<XF>(tc, ld4(x + (int64_t)src * ldx + col4), (uint32_t)src) : zero4();
   }
 };
 
@@ -193,16 +96,16 @@ __global__ __launch_bounds__(kBlock) void sage_mean_cat_kernel(const CatArgs a) 
   }
   if (threadIdx.x == 0) s_next = 0;
   __syncthreads();
-  aggregate_tile<LPR>(a.indptr, a.indices, a.n_dst, (int64_t)blockIdx.x * kTileRows, lane, wave, &s_next, s_part, ld,
-                      [&](int64_t v, int64_t deg, float4 sum) {
-                        if (lane >= LPR || !col_ok) return;
-                        const float inv = 1.0f / (float)(deg > 1 ? deg : 1);      // one IEEE division per row
-                        const float4 m = mask_cols(make_float4(sum.x * inv, sum.y * inv, sum.z * inv, sum.w * inv), col4, a.d);
-                        const int64_t sr = a.self_rows ? a.self_rows[v] : v;
-                        const float4 s = mask_cols(tail_apply<XF>(tc, ld4(a.x + sr * a.ldx + col4), (uint32_t)v), col4, a.d);
-                        st4(a.cat + v * a.ld_cat + col4, m);
-                        st4(a.cat + v * a.ld_cat + dpad + col4, s);
-                      });
+  gather_tile<LPR>(a.indptr, a.indices, a.n_dst, (int64_t)blockIdx.x * kTileRows, lane, wave, &s_next, s_part, ld,
+                   [&](int, int64_t v, int64_t deg, float4 sum, bool valid) {
+                     if (!valid || lane >= LPR || !col_ok) return;
+                     const float inv = 1.0f / (float)(deg > 1 ? deg : 1);      // one IEEE division per row
+                     const float4 m = mask_cols(make_float4(sum.x * inv, sum.y * inv, sum.z * inv, sum.w * inv), col4, a.d);
+                     const int64_t sr = a.self_rows ? a.self_rows[v] : v;
+                     const float4 s = mask_cols(tail_apply<XF>(tc, ld4(a.x + sr * a.ldx + col4), (uint32_t)v), col4, a.d);
+                     st4(a.cat + v * a.ld_cat + col4, m);
+                     st4(a.cat + v * a.ld_cat + dpad + col4, s);
+                   });
 }
 
 struct BwdArgs {
@@ -212,15 +115,17 @@ struct BwdArgs {
   float* dh; int64_t ld_dh;                                              // [n_src, >= round4(d)]
 };
 
-struct BwdLoad {
+// each gathered row times inv(v): the product is rounded, then added
+struct BwdLoad : GatherPolicy {
+  static constexpr bool kWeighted = true;
   const float* dcat; int64_t ld; const int64_t* indptr; int col4; bool col_ok;
   __device__ __forceinline__ float weight(int v, bool ok) const {
     if (!ok) return 0.f;
     const int64_t deg = indptr[v + 1] - indptr[v];
     return 1.0f / (float)(deg > 1 ? deg : 1);
   }
-  __device__ __forceinline__ float4 row(int v, float w) const {
-    if (!col_ok) return zero4();
+  __device__ __forceinline__ float4 row(int v, float w, bool ok) const {
+    if (!ok || !col_ok) return zero4();
     const float4 t = ld4(dcat + (int64_t)v * ld + col4);
     return make_float4(t.x * w, t.y * w, t.z * w, t.w * w);
   }
@@ -239,12 +144,12 @@ __global__ __launch_bounds__(kBlock) void sage_mean_bwd_kernel(const BwdArgs a) 
   ld.dcat = a.dcat; ld.ld = a.ld_dcat; ld.indptr = a.indptr; ld.col4 = col4; ld.col_ok = col_ok;
   if (threadIdx.x == 0) s_next = 0;
   __syncthreads();
-  aggregate_tile<LPR>(a.t_indptr, a.t_indices, a.n_src, (int64_t)blockIdx.x * kTileRows, lane, wave, &s_next, s_part, ld,
-                      [&](int64_t u, int64_t, float4 sum) {
-                        if (lane >= LPR || !col_ok) return;
-                        if (u < a.n_dst) sum = add4(sum, ld4(a.dcat + u * a.ld_dcat + dpad + col4));
-                        st4(a.dh + u * a.ld_dh + col4, mask_cols(sum, col4, a.d));
-                      });
+  gather_tile<LPR>(a.t_indptr, a.t_indices, a.n_src, (int64_t)blockIdx.x * kTileRows, lane, wave, &s_next, s_part, ld,
+                   [&](int, int64_t u, int64_t, float4 sum, bool valid) {
+                     if (!valid || lane >= LPR || !col_ok) return;
+                     if (u < a.n_dst) sum = add4(sum, ld4(a.dcat + u * a.ld_dcat + dpad + col4));
+                     st4(a.dh + u * a.ld_dh + col4, mask_cols(sum, col4, a.d));
+                   });
 }
 
 struct PackLayer { const float* wn; const float* ws; const float* bn; const float* bs; float* wcat; float* bsum; int d_in, d_out; };
@@ -267,19 +172,15 @@ __global__ __launch_bounds__(256) void pack_pair_kernel(const PackArgs a) {
 template <int XF>
 int launch_cat(const CatArgs& a, hipStream_t st) {
   const int dv = ((a.d + 3) & ~3) / 4;
-  const unsigned tiles = (unsigned)((a.n_dst + kTileRows - 1) / kTileRows);
-  if (dv <= 16) hipLaunchKernelGGL((sage_mean_cat_kernel<16, XF>), dim3(tiles, 1), dim3(kBlock), 0, st, a);
-  else if (dv <= 32) hipLaunchKernelGGL((sage_mean_cat_kernel<32, XF>), dim3(tiles, 1), dim3(kBlock), 0, st, a);
-  else hipLaunchKernelGGL((sage_mean_cat_kernel<64, XF>), dim3(tiles, (unsigned)((dv + 63) / 64)), dim3(kBlock), 0, st, a);
+  const dim3 grid((unsigned)((a.n_dst + kTileRows - 1) / kTileRows), (unsigned)((dv + 63) / 64));
+  with_lpr<16>(lpr_for(dv, 16), [&](auto L) { hipLaunchKernelGGL((sage_mean_cat_kernel<decltype(L)::value, XF>), grid, dim3(kBlock), 0, st, a); });
   return glnn::check_launch("glnn_sage_mean_fwd_bwd_f32: forward aggregation");
 }
 
 int launch_bwd(const BwdArgs& a, hipStream_t st) {
   const int dv = ((a.d + 3) & ~3) / 4;
-  const unsigned tiles = (unsigned)((a.n_src + kTileRows - 1) / kTileRows);
-  if (dv <= 16) hipLaunchKernelGGL((sage_mean_bwd_kernel<16>), dim3(tiles, 1), dim3(kBlock), 0, st, a);
-  else if (dv <= 32) hipLaunchKernelGGL((sage_mean_bwd_kernel<32>), dim3(tiles, 1), dim3(kBlock), 0, st, a);
-  else hipLaunchKernelGGL((sage_mean_bwd_kernel<64>), dim3(tiles, (unsigned)((dv + 63) / 64)), dim3(kBlock), 0, st, a);
+  const dim3 grid((unsigned)((a.n_src + kTileRows - 1) / kTileRows), (unsigned)((dv + 63) / 64));
+  with_lpr<16>(lpr_for(dv, 16), [&](auto L) { hipLaunchKernelGGL((sage_mean_bwd_kernel<decltype(L)::value>), grid, dim3(kBlock), 0, st, a); });
   return glnn::check_launch("glnn_sage_mean_fwd_bwd_f32: backward aggregation");
 }
 
