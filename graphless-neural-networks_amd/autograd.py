@@ -485,3 +485,84 @@ def gat_conv(graph, x, w, attn_l, attn_r, heads, out_feats, slope, relu, feat_dr
         return GatConvFn.apply(graph, x, w, attn_l, attn_r, heads, out_feats, slope, relu, fp, fs, ap, as_, signed)
     with torch.no_grad():
         return gat_layer_fwd(graph, ops.as_feat(x), w, attn_l, attn_r, heads, out_feats, slope, relu, fp, fs, ap, as_, signed)[0]
+
+
+# ------------------------------------------------------------------------------------------ GATv2 layer (docs/GATV2_SEMANTICS.md)
+def gatv2_layer_fwd(g, x, w_src, b_src, w_dst, b_dst, attn, heads, out_feats, slope, relu, feat_p=0.0, feat_seed=0, attn_p=0.0, attn_seed=0,
+                    want_lse=False):
+    """One GATv2Conv forward: the dropped copy of the input (made once, read by both projections and by both weight gradients; a signed
+    input needs nothing else), zl = fc_src, zr = fc_dst, glnn_gatv2_attn_fwd_f32 (+ ReLU).  Returns (y, (xd, zl, zr, lse)); lse only when
+    the backward will follow."""
+    xd = ops.act_fwd(x, drop_p=feat_p, drop_seed=feat_seed, relu=False) if feat_p > 0 else x
+    zl = ops.gemm(xd, w_src, ep_shift=b_src)
+    zr = ops.gemm(xd, w_dst, ep_shift=b_dst)
+    y, lse = ops.gatv2_attn_fwd(g.indptr, g.indices, g.num_edges(), zl, zr, attn, heads, out_feats, slope, attn_p, attn_seed, relu=relu,
+                                want_lse=want_lse)
+    return y, (xd, zl, zr, lse)
+
+
+def gatv2_layer_bwd(g, gy, saved, w_src, w_dst, attn, heads, out_feats, slope, attn_p=0.0, attn_seed=0, need_dx=True, dw_src=None,
+                    db_src=None, dw_dst=None, db_dst=None, dattn=None):
+    """Backward of gatv2_layer_fwd.  gy = dL/dy ALREADY behind the activation mask (zero where a ReLU layer's y is 0).  Returns
+    (da = dzl W_src + dzr W_dst -- the input gradient BEFORE the feature-dropout mask, or None; dW_src; db_src; dW_dst; db_dst; dattn)."""
+    xd, zl, zr, lse = saved
+    dzl, dzr, dattn = ops.gatv2_attn_bwd(g, zl, zr, lse, attn, gy, heads, out_feats, slope, attn_p, attn_seed, dattn=dattn)
+    hf = heads * out_feats
+    if db_src is None:
+        db_src = torch.empty(hf, dtype=torch.float32, device=zl.device)
+    if db_dst is None:
+        db_dst = torch.empty(hf, dtype=torch.float32, device=zl.device)
+    dw_src = ops.gemm_tn(dzl, xd, out=dw_src, col_sum_a=db_src)
+    dw_dst = ops.gemm_tn(dzr, xd, out=dw_dst, col_sum_a=db_dst)
+    da = None
+    if need_dx:
+        da = ops.gemm(dzl, w_src, w_is_kn=True)
+        da.add_(ops.gemm(dzr, w_dst, w_is_kn=True))
+    return da, dw_src, db_src, dw_dst, db_dst, dattn
+
+
+class Gatv2ConvFn(torch.autograd.Function):
+    """GATv2Conv as a differentiable op on the HIP path; the backward replays the forward's dropout masks from their seeds."""
+
+    @staticmethod
+    def forward(ctx, graph, x, w_src, b_src, w_dst, b_dst, attn, heads, out_feats, slope, relu, feat_p, feat_seed, attn_p, attn_seed):
+        x = ops.as_feat(x.detach())
+        y, saved = gatv2_layer_fwd(graph, x, w_src.detach(), b_src.detach(), w_dst.detach(), b_dst.detach(), attn.detach(), heads, out_feats,
+                                   slope, relu, feat_p, feat_seed, attn_p, attn_seed, want_lse=True)
+        ctx.graph, ctx.cfg = graph, (heads, out_feats, slope, relu, feat_p, feat_seed, attn_p, attn_seed)
+        ctx.save_for_backward(w_src, w_dst, attn, y, *saved)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        w_src, w_dst, attn, y, xd, zl, zr, lse = ctx.saved_tensors
+        heads, out_feats, slope, relu, feat_p, feat_seed, attn_p, attn_seed = ctx.cfg
+        dy = ops.as_feat(dy.contiguous())
+        gy = ops.bn_relu_bwd(dy, y)[0] if relu else dy                     # dy * [y > 0]
+        da, dws, dbs, dwd, dbd, dat = gatv2_layer_bwd(ctx.graph, gy, (xd, zl, zr, lse), w_src.detach(), w_dst.detach(), attn.detach(), heads,
+                                                      out_feats, slope, attn_p, attn_seed, need_dx=ctx.needs_input_grad[1])
+        if da is not None and feat_p > 0:
+            da = ops.act_fwd(da, drop_p=feat_p, drop_seed=feat_seed, relu=False)      # the feature-dropout mask and 1 / (1 - p)
+        return (None, da, dws, dbs, dwd, dbd, dat.view_as(attn)) + (None,) * 8
+
+
+def gatv2_conv_seeds(count):
+    """(feature-dropout seed, attention-dropout seed) of the count-th dropout draw of this process (tests replay the masks from them)."""
+    base = int(torch.initial_seed()) * 0x85EBCA77 + count * 0x9E3779B1
+    return (base + 0x47563246) & 0xFFFFFFFF, (base + 0x47563241) & 0xFFFFFFFF
+
+
+def gatv2_conv(graph, x, w_src, b_src, w_dst, b_dst, attn, heads, out_feats, slope, relu, feat_drop, attn_drop, training):
+    """GATv2Conv forward: both dropouts only in training; their counter-based seeds are drawn like norm_act_drop's.  Differentiable in
+    training mode (appnp_propagate's rule); the eval forward keeps nothing for a backward."""
+    fp = float(feat_drop) if training else 0.0
+    ap = float(attn_drop) if training else 0.0
+    fs = as_ = 0
+    if fp > 0 or ap > 0:
+        _drop_counter[0] += 1
+        fs, as_ = gatv2_conv_seeds(_drop_counter[0])
+    params = (w_src, b_src, w_dst, b_dst, attn)
+    if training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+        return Gatv2ConvFn.apply(graph, x, w_src, b_src, w_dst, b_dst, attn, heads, out_feats, slope, relu, fp, fs, ap, as_)
+    with torch.no_grad():
+        return gatv2_layer_fwd(graph, ops.as_feat(x), w_src, b_src, w_dst, b_dst, attn, heads, out_feats, slope, relu, fp, fs, ap, as_)[0]

@@ -384,6 +384,13 @@ def _refuse_gat(encoder, who):
                                   "scores of the remote sources, an exchange the sharded forward does not have (whole-graph GAT only)")
 
 
+def _refuse_gatv2(encoder, who):
+    if type(encoder).__name__ == "GATv2":
+        raise NotImplementedError(f"{who}: the GATv2 teacher is not sharded -- its edge softmax needs every in-edge of a row and the whole "
+                                  "projected rows of the remote sources, an exchange the sharded forward does not have (whole-graph GATv2 "
+                                  "only)")
+
+
 def _refuse_gpr(encoder, who):
     if type(encoder).__name__ == "GPRGNN":
         raise NotImplementedError(f"{who}: the GPRGNN teacher is not sharded -- each of its K propagation steps needs the previous step's "
@@ -423,6 +430,7 @@ class ShardedTeacher:
         _refuse_gat(encoder, "ShardedTeacher")
         _refuse_gpr(encoder, "ShardedTeacher")
         _refuse_gcnii(encoder, "ShardedTeacher")
+        _refuse_gatv2(encoder, "ShardedTeacher")
         _refuse_mean(encoder, "ShardedTeacher")
         if widening_exchange not in ("narrow", "wide", "mixed"):
             raise ValueError("ShardedTeacher: widening_exchange must be 'narrow', 'wide' or 'mixed'")
@@ -1017,6 +1025,7 @@ class HaloShardedTeacher:
         _refuse_gat(encoder, "HaloShardedTeacher")
         _refuse_gpr(encoder, "HaloShardedTeacher")
         _refuse_gcnii(encoder, "HaloShardedTeacher")
+        _refuse_gatv2(encoder, "HaloShardedTeacher")
         _refuse_mean(encoder, "HaloShardedTeacher")
         self.enc, self.g, self.sh, self.be, self.group, self.overlap = encoder, graph_shard, shards, be, group, overlap
         if graph_shard.n_dst != shards.rows:

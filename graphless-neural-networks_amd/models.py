@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .autograd import appnp_propagate, gcnii_stack, linear_fn, norm_act_drop
-from .nn import GATConv, GCNIIConv, GPRConv, GraphConv, SAGEConv
+from .nn import GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, SAGEConv
 
 
 def _bn_eval_fold(bn, bias):
@@ -715,6 +715,47 @@ class GAT(nn.Module):
         return h_list, h
 
 
+class GATv2(nn.Module):
+    """GATv2 (Brody, Alon, Yahav, ICLR 2022; docs/GATV2_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it) in models.GAT's shape:
+    num_layers GATv2Conv layers, `num_heads` heads of hidden_dim // num_heads features on every hidden layer (ReLU inside the conv, outputs
+    flattened to [N, hidden_dim] and kept in h_list), one head of output_dim features on the last.  No norm layers and no dropout outside
+    the convs (feat_drop = dropout_ratio, attn_drop)."""
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, num_heads=8, attn_drop=0.3,
+                 negative_slope=0.2, residual=False):
+        super().__init__()
+        if num_layers <= 1:
+            raise NotImplementedError("GATv2: num_layers must be > 1 (models.GAT's shape: hidden multi-head layers and a one-head last layer)")
+        if residual:
+            raise NotImplementedError("GATv2: residual=True is not implemented (docs/GATV2_SEMANTICS.md, What is refused)")
+        hidden_dim //= num_heads
+        self.num_layers = num_layers
+        self.num_heads = num_heads
+        self.activation = activation
+        self.layers = nn.ModuleList()
+        heads = [num_heads] * num_layers + [1]
+        self.layers.append(GATv2Conv(input_dim, hidden_dim, heads[0], dropout_ratio, attn_drop, negative_slope, False, activation))
+        for l in range(1, num_layers - 1):
+            self.layers.append(GATv2Conv(hidden_dim * heads[l - 1], hidden_dim, heads[l], dropout_ratio, attn_drop, negative_slope, False,
+                                         activation))
+        self.layers.append(GATv2Conv(hidden_dim * heads[-2], output_dim, heads[-1], dropout_ratio, attn_drop, negative_slope, False, None))
+
+    def forward(self, g, feats):
+        _need_hip(feats, "GATv2.forward")
+        if isinstance(g, (list, tuple)):
+            raise NotImplementedError("GATv2: block (bipartite) inputs are not implemented: the GATv2 teacher runs on the whole graph")
+        h = feats
+        h_list = []
+        for l, layer in enumerate(self.layers):
+            h = layer(g, h)
+            if l != self.num_layers - 1:
+                h = h.flatten(1)
+                h_list.append(h)
+            else:
+                h = h[:, 0]                    # the last layer's ONE head
+        return h_list, h
+
+
 class Model(nn.Module):
     """Wrapper of different models (reference models.py:347-429).
 
@@ -741,6 +782,15 @@ class Model(nn.Module):
             self.encoder = GCN(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
         elif "APPNP" in conf["model_name"]:
             self.encoder = APPNP(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
+        elif "GATv2" in conf["model_name"]:          # (tested before "GAT", which it contains; the conf contract is GAT's)
+            missing = [k for k in ("num_heads", "attn_dropout_ratio") if k not in conf]
+            if missing:
+                raise NotImplementedError(f"{conf['model_name']}: the conf does not name {' or '.join(missing)}; GATv2 is built only from "
+                                          "confs that carry both num_heads and attn_dropout_ratio (docs/GATV2_SEMANTICS.md)")
+            heads = int(conf["num_heads"])
+            if heads < 1 or conf["hidden_dim"] < heads or conf["hidden_dim"] % heads:
+                raise ValueError(f"GATv2: hidden_dim ({conf['hidden_dim']}) must be a positive multiple of num_heads ({heads})")
+            self.encoder = GATv2(activation=F.relu, num_heads=heads, attn_drop=conf["attn_dropout_ratio"], **common).to(conf["device"])
         elif "GAT" in conf["model_name"]:
             missing = [k for k in ("num_heads", "attn_dropout_ratio") if k not in conf]
             if missing:
@@ -776,6 +826,9 @@ class Model(nn.Module):
     def inference(self, data, feats, dtype=torch.float32):
         """dtype=torch.bfloat16: bf16 activation storage, the SAGE teacher's whole-graph forward only (SAGE.inference)."""
         if dtype != torch.float32:
+            if "GATv2" in self.model_name:
+                raise NotImplementedError(f"GATv2.inference(dtype={dtype}): bf16 activation storage is not implemented for the GATv2 teacher "
+                                          "(csrc/gatv2.hip gathers and stores fp32 rows; docs/GATV2_SEMANTICS.md, What is refused)")
             if "GCNII" in self.model_name:
                 raise NotImplementedError(f"GCNII.inference(dtype={dtype}): bf16 activation storage is not implemented for the GCNII teacher "
                                           "(csrc/gcnii.hip gathers and stores fp32 rows; docs/GCNII_SEMANTICS.md, Out of scope)")

@@ -3,6 +3,7 @@
   SAGEConv(in, out, "gcn")(block, (h, h_dst))   <- dgl.nn.SAGEConv, reference models.py:84-99,112,138
   GraphConv(in, out, activation=)(g, h)          <- dgl.nn.GraphConv, reference models.py:170-187,193
   GATConv(in, out, heads, ...)(g, h)             <- dgl.nn.GATConv, reference models.py:228-267 (docs/GAT_SEMANTICS.md)
+  GATv2Conv(in, out, heads, ...)(g, h)           <- GATv2's attention layer (dgl 0.6.1 has none; docs/GATV2_SEMANTICS.md)
   GPRConv(k, alpha, init)(g, h)                  <- GPR-GNN's learned K-step propagation (no dgl counterpart; docs/GPR_SEMANTICS.md)
   GCNIIConv(hidden, layer, alpha, lamda)(g, h, h0) <- one GCNII conv layer (dgl 0.6.1 has none; docs/GCNII_SEMANTICS.md)
 
@@ -16,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import GraphConvFn, SpmmFn, gat_conv, gcnii_stack, gpr_propagate, graphconv_fwd, linear_fn
+from .autograd import GraphConvFn, SpmmFn, gat_conv, gatv2_conv, gcnii_stack, gpr_propagate, graphconv_fwd, linear_fn
 
 
 FUSED_SAGE_MAX_IN = 256   # aggregate-first layers with d_in, d_out <= 256 take the single-launch K1F kernel.  Interleaved
@@ -270,6 +271,59 @@ class GATConv(nn.Module):
             nonneg = not (self.training and self.feat_drop.p > 0) or ops.is_nonneg(feat)
         y = gat_conv(graph, feat, self.fc.weight, self.attn_l, self.attn_r, self._num_heads, self._out_feats, self.negative_slope,
                      self.relu(), self.feat_drop.p, self.attn_drop.p, self.training, signed=not nonneg)
+        return y.view(y.shape[0], self._num_heads, self._out_feats) if y.is_contiguous() else y.reshape(y.shape[0], self._num_heads,
+                                                                                                        self._out_feats)
+
+
+class GATv2Conv(nn.Module):
+    """GATv2 attention layer on a homogeneous graph (Brody, Alon, Yahav, ICLR 2022; docs/GATV2_SEMANTICS.md): fc_src / fc_dst
+    [heads * out, in] WITH bias, attn [1, heads, out]; no share_weights, no residual, no output bias.  forward returns [N, heads, out]."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2, residual=False, activation=None,
+                 allow_zero_in_degree=False):
+        super().__init__()
+        if isinstance(in_feats, (tuple, list)):
+            raise NotImplementedError("GATv2Conv: bipartite (block) inputs are not implemented: the GATv2 teacher runs on the whole graph")
+        if residual:
+            raise NotImplementedError("GATv2Conv: residual=True is not implemented (docs/GATV2_SEMANTICS.md, What is refused)")
+        if num_heads < 1 or num_heads > 64 or num_heads * out_feats > 256:
+            raise NotImplementedError("GATv2Conv: the attention kernels take num_heads <= 64 and num_heads * out_feats <= 256")
+        self._in_feats, self._out_feats, self._num_heads = in_feats, out_feats, num_heads
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self.fc_src = nn.Linear(in_feats, out_feats * num_heads, bias=True)
+        self.fc_dst = nn.Linear(in_feats, out_feats * num_heads, bias=True)
+        self.attn = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.negative_slope = float(negative_slope)
+        self.activation = activation
+        self.relu()
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        nn.init.xavier_normal_(self.fc_src.weight, gain=gain)
+        nn.init.xavier_normal_(self.fc_dst.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn, gain=gain)
+        nn.init.zeros_(self.fc_src.bias)
+        nn.init.zeros_(self.fc_dst.bias)
+
+    def relu(self):
+        act = self.activation
+        relu = act is not None and getattr(act, "__name__", "") == "relu"
+        if act is not None and not relu:
+            raise NotImplementedError("GATv2Conv: only activation=F.relu or None is implemented (the attention kernel's epilogue)")
+        return relu
+
+    def forward(self, graph, feat):
+        if (isinstance(graph, (list, tuple)) or isinstance(feat, tuple) or graph.num_dst_nodes() != graph.num_src_nodes()
+                or feat.shape[0] != graph.num_dst_nodes()):
+            raise NotImplementedError("GATv2Conv: block (bipartite) inputs are not implemented: the GATv2 teacher runs on the whole graph")
+        if not self._allow_zero_in_degree and graph.has_zero_in_degree():
+            raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
+                               "(GATv2Conv follows dgl GATConv; add self-loops or set allow_zero_in_degree).")
+        y = gatv2_conv(graph, feat, self.fc_src.weight, self.fc_src.bias, self.fc_dst.weight, self.fc_dst.bias, self.attn, self._num_heads,
+                       self._out_feats, self.negative_slope, self.relu(), self.feat_drop.p, self.attn_drop.p, self.training)
         return y.view(y.shape[0], self._num_heads, self._out_feats) if y.is_contiguous() else y.reshape(y.shape[0], self._num_heads,
                                                                                                         self._out_feats)
 

@@ -1670,6 +1670,74 @@ def gat_attn_mask(nnz, heads, attn_drop, seed, device):
     return mask
 
 
+# --------------------------------------------------------------------------------------------- GATv2 attention (csrc/gatv2.hip)
+def _gatv2_check(zl, zr, attn, heads, out_feats, name):
+    hf = heads * out_feats
+    if zl.shape[1] != hf or zr.shape != zl.shape or attn.numel() != hf or not attn.is_contiguous() or attn.dtype != torch.float32:
+        raise ValueError(f"{name}: zl and zr must be [n, heads * out_feats] and attn contiguous fp32 [1, heads, out_feats]")
+
+
+def gatv2_attn_fwd(indptr, indices, nnz, zl, zr, attn, heads, out_feats, negative_slope=0.2, attn_drop=0.0, seed=0, relu=False,
+                   want_lse=False, out=None, lse=None):
+    """glnn_gatv2_attn_fwd_f32: (out [n, heads * out_feats], lse [n, heads] or None) -- the GATv2 edge softmax and the weighted
+    aggregation of zl from ONE gather per edge (docs/GATV2_SEMANTICS.md).  lse: a buffer to take the row log-sum-exps (implies want_lse)."""
+    zl, zr = as_feat(zl), as_feat(zr)
+    n = zl.shape[0]
+    _appnp_check(indptr, indices, zl, n, "gatv2_attn_fwd")
+    _need_cuda(zr, attn, out)
+    _mat(zr, "gatv2_attn_fwd zr")
+    _gatv2_check(zl, zr, attn, heads, out_feats, "gatv2_attn_fwd")
+    if out is None:
+        out = feat_empty(n, heads * out_feats, zl.device)
+    _mat(out, "gatv2_attn_fwd out")
+    if lse is None and want_lse:
+        lse = torch.empty((n, heads), dtype=torch.float32, device=zl.device)
+    if lse is not None and (lse.shape != (n, heads) or not lse.is_contiguous() or lse.dtype != torch.float32 or not lse.is_cuda):
+        raise ValueError("gatv2_attn_fwd: lse must be a contiguous fp32 [n, heads] tensor on the GPU")
+    with _Timed("gatv2_attn_fwd", d=heads * out_feats, n_dst=n, nnz=int(nnz), attn_drop=float(attn_drop)):
+        rc = _lib.lib().glnn_gatv2_attn_fwd_f32(_p(indptr), _p(indices), n, int(nnz), _p(zl), _ld(zl), _p(zr), _ld(zr), heads, out_feats,
+                                                _p(attn), float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF,
+                                                1 if relu else 0, _p(out), _ld(out), _p(lse), _stream())
+    _lib.check(rc, "glnn_gatv2_attn_fwd_f32")
+    return out, lse
+
+
+def gatv2_attn_bwd(graph, zl, zr, lse, attn, g, heads, out_feats, negative_slope=0.2, attn_drop=0.0, seed=0, dattn=None, dzl=None,
+                   dzr=None):
+    """glnn_gatv2_attn_bwd_f32 over `graph` (CSRGraph: its in-CSR and its cached transpose with edge ids): (dzl, dzr, dattn).
+    g = dL/d out behind the activation mask.  The [E, heads] score-gradient scratch and the dattn partials live for the call."""
+    zl, zr, g = as_feat(zl), as_feat(zr), as_feat(g)
+    n = zl.shape[0]
+    _appnp_check(graph.indptr, graph.indices, zl, n, "gatv2_attn_bwd")
+    _need_cuda(zr, lse, attn, g, dattn)
+    _mat(zr, "gatv2_attn_bwd zr")
+    _mat(g, "gatv2_attn_bwd g")
+    _gatv2_check(zl, zr, attn, heads, out_feats, "gatv2_attn_bwd")
+    hf = heads * out_feats
+    if g.shape != zl.shape or lse.shape != (n, heads) or not lse.is_contiguous() or lse.dtype != torch.float32:
+        raise ValueError("gatv2_attn_bwd: g must be [n, heads * out_feats] and lse contiguous fp32 [n, heads]")
+    tg, t_eids = graph.transposed_eids()
+    nnz = graph.num_edges()
+    dev = zl.device
+    ds = torch.empty((max(nnz, 1), heads), dtype=torch.float32, device=dev)
+    dzl = feat_empty(n, hf, dev) if dzl is None else dzl
+    dzr = feat_empty(n, hf, dev) if dzr is None else dzr
+    _need_cuda(dzl, dzr)
+    _mat(dzl, "gatv2_attn_bwd dzl")
+    _mat(dzr, "gatv2_attn_bwd dzr")
+    if dattn is None:
+        dattn = torch.empty(hf, dtype=torch.float32, device=dev)
+    _vec(dattn, hf, "dattn")
+    ws = torch.empty(max(int(_lib.lib().glnn_gatv2_attn_bwd_workspace_floats(n, heads, out_feats)), 1), dtype=torch.float32, device=dev)
+    with _Timed("gatv2_attn_bwd", d=hf, n_dst=n, nnz=int(nnz), attn_drop=float(attn_drop)):
+        rc = _lib.lib().glnn_gatv2_attn_bwd_f32(_p(graph.indptr), _p(graph.indices), _p(tg.indptr), _p(tg.indices), _p(t_eids), n, int(nnz),
+                                                _p(zl), _ld(zl), _p(zr), _ld(zr), heads, out_feats, _p(lse), _p(attn), _p(g), _ld(g),
+                                                float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF, _p(ds), _p(dzl),
+                                                _ld(dzl), _p(dzr), _ld(dzr), _p(dattn), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "glnn_gatv2_attn_bwd_f32")
+    return dzl, dzr, dattn
+
+
 _NONNEG = []          # [(weakref to the tensor, key, answer)]: one entry
 
 

@@ -35,7 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .autograd import (appnp_bwd, appnp_fwd, gat_layer_bwd, gat_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd,
+from .autograd import (appnp_bwd, appnp_fwd, gat_layer_bwd, gat_layer_fwd, gatv2_layer_bwd, gatv2_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd,
                        graphconv_fwd)
 from .student import _mix32
 
@@ -45,11 +45,11 @@ def _is_relu(act):
 
 
 def check_supported(model, criterion, optimizer):
-    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GPRGNN or GCNII teacher."""
+    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GATv2, GPRGNN or GCNII teacher."""
     enc = model.encoder
     name = model.model_name
     if "MLP" in name or not ("SAGE" in name or "GCN" in name or "APPNP" in name or "GAT" in name or "GPRGNN" in name):
-        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GPRGNN or GCNII teachers only (got {name})")
+        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GATv2, GPRGNN or GCNII teachers only (got {name})")
     if not (isinstance(criterion, nn.NLLLoss) and criterion.reduction == "mean" and criterion.weight is None
             and criterion.ignore_index == -100):
         raise NotImplementedError("TeacherEngine: the criterion must be nn.NLLLoss() (reference train_teacher.py:237)")
@@ -71,6 +71,9 @@ def check_supported(model, criterion, optimizer):
     elif "GPRGNN" in name:
         if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
             raise NotImplementedError("TeacherEngine: GPRGNN with norm_type none|batch|layer and ReLU (docs/GPR_SEMANTICS.md)")
+    elif "GATv2" in name:        # (tested before "GAT", which it contains)
+        if not _is_relu(enc.activation) or any(not lay.relu() for lay in enc.layers[:-1]) or enc.layers[-1].relu():
+            raise NotImplementedError("TeacherEngine: GATv2 with ReLU hidden layers and a linear last layer (docs/GATV2_SEMANTICS.md)")
     elif "GAT" in name:
         if not _is_relu(enc.activation) or any(not lay.relu() for lay in enc.layers[:-1]) or enc.layers[-1].relu():
             raise NotImplementedError("TeacherEngine: GAT with ReLU hidden layers and a linear last layer (models.py:202-279)")
@@ -140,12 +143,12 @@ class TeacherEngine:
     def __init__(self, model, optimizer):
         self.model, self.enc, self.opt = model, model.encoder, optimizer
         name = model.model_name
-        self.kind = ("gcnii" if "GCNII" in name else "sage" if "SAGE" in name else "appnp" if "APPNP" in name else "gat" if "GAT" in name
-                     else "gpr" if "GPRGNN" in name else "gcn")
+        self.kind = ("gcnii" if "GCNII" in name else "sage" if "SAGE" in name else "appnp" if "APPNP" in name else "gatv2" if "GATv2" in name
+                     else "gat" if "GAT" in name else "gpr" if "GPRGNN" in name else "gcn")
         self.L = self.enc.num_layers
         self.bn = getattr(self.enc, "norm_type", "none") == "batch"
         self.ln = getattr(self.enc, "norm_type", "none") == "layer"
-        self.p = float(self.enc.layers[0].feat_drop.p if self.kind == "gat" else self.enc.dropout.p)
+        self.p = float(self.enc.layers[0].feat_drop.p if self.kind in ("gat", "gatv2") else self.enc.dropout.p)
         params = list(model.parameters())
         self.params = params
         dev = params[0].device
@@ -846,6 +849,46 @@ class TeacherEngine:
                                         dattn_l=self.grad(lay.attn_l).view(-1), dattn_r=self.grad(lay.attn_r).view(-1))
             if l > 0:      # the feature-dropout mask of layer l and the ReLU mask of layer l - 1 (its stored output is post-ReLU)
                 gy = ops.bn_relu_bwd(da, acts[l], dz=da, drop_p=lay.feat_drop.p, drop_seed=fs)[0]
+        ops.note_param_write()
+
+    # ------------------------------------------------------------------------------------------ full-graph GATv2
+    @torch.no_grad()
+    def step_gatv2(self, g, feats, labels, idx_train, lamb=1.0):
+        """The full-graph `train` step over GATv2 (docs/GATV2_SEMANTICS.md): per layer the dropped copy of the input, the two projections
+        and glnn_gatv2_attn_fwd_f32; NLL over idx_train; per layer glnn_gatv2_attn_bwd_f32 over the graph and its transpose, the two weight
+        gradients with their bias column sums and the input gradient; the ONE Adam launch."""
+        ops._need_cuda(feats, labels, idx_train, g.indptr)
+        if g.has_zero_in_degree():
+            raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
+                               "(GATv2Conv follows dgl GATConv; add self-loops or set allow_zero_in_degree).")
+        self.step_count += 1
+        try:
+            self._step_gatv2_body(g, feats, labels, idx_train, lamb)
+        except Exception:
+            self.step_count -= 1          # the step never happened (see step_sage)
+            raise
+        self._adam()
+
+    def _step_gatv2_body(self, g, feats, labels, idx_train, lamb):
+        enc, L = self.enc, self.L
+        n = g.num_dst_nodes()
+        a = ops.as_feat(feats)
+        saved = []
+        for l, lay in enumerate(enc.layers):
+            fs, as_ = self._seed(l), self._attn_seed(l)
+            a, sv = gatv2_layer_fwd(g, a, lay.fc_src.weight, lay.fc_src.bias, lay.fc_dst.weight, lay.fc_dst.bias, lay.attn, lay._num_heads,
+                                    lay._out_feats, lay.negative_slope, l != L - 1, lay.feat_drop.p, fs, lay.attn_drop.p, as_, want_lse=True)
+            saved.append((sv, fs, as_, a))
+        gy = self._loss_grad(a, labels, idx_train, lamb, n)
+        for l in range(L - 1, -1, -1):
+            lay = enc.layers[l]
+            sv, fs, as_, _ = saved[l]
+            da = gatv2_layer_bwd(g, gy, sv, lay.fc_src.weight, lay.fc_dst.weight, lay.attn, lay._num_heads, lay._out_feats,
+                                 lay.negative_slope, lay.attn_drop.p, as_, need_dx=l > 0, dw_src=self.grad(lay.fc_src.weight),
+                                 db_src=self.grad(lay.fc_src.bias), dw_dst=self.grad(lay.fc_dst.weight), db_dst=self.grad(lay.fc_dst.bias),
+                                 dattn=self.grad(lay.attn).view(-1))[0]
+            if l > 0:      # the feature-dropout mask of layer l and the ReLU mask of layer l - 1 (its stored output is post-ReLU)
+                gy = ops.bn_relu_bwd(da, saved[l - 1][3], dz=da, drop_p=lay.feat_drop.p, drop_seed=fs)[0]
         ops.note_param_write()
 
 

@@ -28,11 +28,11 @@ EVAL_BLOCK_ROWS = 1 << 19
 
 def train(model, data, feats, labels, criterion, optimizer, idx_train, lamb=1):
     """GNN full-batch training step (reference train_and_eval.py:12-29; `data` is the whole graph): one
-    TeacherEngine.step_gcn (GCN) / step_appnp (APPNP) / step_gat (GAT) / step_gpr (GPRGNN) / step_gcnii (GCNII) -- forward, NLL over idx_train, backward over the transposed graph, Adam -- on libglnn_hip.so.
+    TeacherEngine.step_gcn (GCN) / step_appnp (APPNP) / step_gat (GAT) / step_gatv2 (GATv2) / step_gpr (GPRGNN) / step_gcnii (GCNII) -- forward, NLL over idx_train, backward over the transposed graph, Adam -- on libglnn_hip.so.
     Returns the unscaled loss like the reference's `loss.item()`."""
     teacher.check_supported(model, criterion, optimizer)
-    if not any(k in model.model_name for k in ("GCN", "APPNP", "GAT", "GPRGNN")):          # ("GCNII" contains "GCN")
-        raise NotImplementedError("train(): the full-graph step is implemented for the GCN, APPNP, GAT, GPRGNN and GCNII teachers (SAGE trains "
+    if not any(k in model.model_name for k in ("GCN", "APPNP", "GAT", "GPRGNN")):          # ("GCNII" contains "GCN", "GATv2" contains "GAT")
+        raise NotImplementedError("train(): the full-graph step is implemented for the GCN, APPNP, GAT, GATv2, GPRGNN and GCNII teachers (SAGE trains "
                                   "with train_sage)")
     model.train()
     eng = teacher.get_engine(model, optimizer)
@@ -40,6 +40,8 @@ def train(model, data, feats, labels, criterion, optimizer, idx_train, lamb=1):
         eng.step_gcnii(data, feats, labels, idx_train, float(lamb))
     elif "APPNP" in model.model_name:
         eng.step_appnp(data, feats, labels, idx_train, float(lamb))
+    elif "GATv2" in model.model_name:        # (tested before "GAT", which it contains)
+        eng.step_gatv2(data, feats, labels, idx_train, float(lamb))
     elif "GAT" in model.model_name:
         eng.step_gat(data, feats, labels, idx_train, float(lamb))
     elif "GPRGNN" in model.model_name:

@@ -854,6 +854,35 @@ GLNN_API int glnn_gat_attn_bwd_f32(const int64_t* indptr, const int32_t* indices
 GLNN_API int glnn_gat_attn_mask_u8(int64_t nnz, int heads, float attn_drop, uint32_t seed, uint8_t* mask, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GATv2 attention (Brody, Alon, Yahav, ICLR 2022; csrc/gatv2.hip; docs/GATV2_SEMANTICS.md states the arithmetic): per-destination edge
+ * softmax whose score needs the whole projected source row.  Square graph of n nodes, indptr / indices the in-CSR (rows = destinations,
+ * edge id = CSR position); zl / zr [n, heads * out_feats] the two projections (fc_src / fc_dst), head-major columns; attn
+ * [heads * out_feats].  heads <= 64, heads * out_feats <= 256, nnz < 2^31 (GLNN_ERR_UNSUPPORTED otherwise, nothing launched); every row
+ * pointer 16-byte aligned with a leading dimension % 4 == 0 and >= round4(heads * out_feats).  Attention dropout: the mask of
+ * glnn_gat_attn_mask_u8, weight 1 / (1 - attn_drop), applied AFTER the normalisation (the denominator sums every edge).  No float
+ * atomics, no grid barrier: bit-identical run to run.  n == 0 is a no-op.
+ *
+ * out[i] = act( sum_{e = (j -> i)} a_ij w_ij zl[j] ),  a_ij = softmax over ALL in-edges of i of
+ *   s_ij[h] = sum_f attn[h, f] leaky_relu(zl[j, h, f] + zr[i, h, f], negative_slope); ONE gather of zl[j] per edge, online softmax in a
+ *   fixed edge order.  relu != 0: ReLU epilogue.  lse (optional, [n, heads]): max + log(denominator), what the backward recomputes a_ij
+ *   from.  Padding columns of out are written as zeros; a row without in-edges gives zeros. */
+GLNN_API int glnn_gatv2_attn_fwd_f32(const int64_t* indptr, const int32_t* indices, int64_t n, int64_t nnz, const float* zl, int64_t ldzl,
+                                     const float* zr, int64_t ldzr, int heads, int out_feats, const float* attn, float negative_slope,
+                                     float attn_drop, uint32_t seed, int relu, float* out, int64_t ldo, float* lse, void* stream);
+/* Backward of glnn_gatv2_attn_fwd_f32 with respect to zl, zr and attn.  g = dL/d out behind the activation mask.  Pass 1 (in-CSR, two
+ * sweeps, each gathering zl[j]): D_i = sum_k a_ik c_ik / sum_k a_ik in fp64 from the row's own c_ik = w_ik <g_i, zl_k>, then
+ * ds [nnz, heads] scratch (ds_ij = a_ij (c_ij - D_i)), dzr [n, heads * out_feats] and per-workgroup partials of dattn in `workspace`
+ * (>= glnn_gatv2_attn_bwd_workspace_floats floats); pass 2 (transposed CSR with original edge ids, glnn_csr_transpose_eids): dzl; then
+ * dattn [heads * out_feats] folded from the partials in ascending order. */
+GLNN_API int64_t glnn_gatv2_attn_bwd_workspace_floats(int64_t n, int heads, int out_feats);
+GLNN_API int glnn_gatv2_attn_bwd_f32(const int64_t* indptr, const int32_t* indices, const int64_t* t_indptr, const int32_t* t_indices,
+                                     const int32_t* t_eids, int64_t n, int64_t nnz, const float* zl, int64_t ldzl, const float* zr,
+                                     int64_t ldzr, int heads, int out_feats, const float* lse, const float* attn, const float* g,
+                                     int64_t ldg, float negative_slope, float attn_drop, uint32_t seed, float* ds, float* dzl,
+                                     int64_t lddzl, float* dzr, int64_t lddzr, float* dattn, float* workspace, int64_t workspace_floats,
+                                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * GraphSAGE "mean" aggregator (csrc/sage_mean.hip; docs/SAGE_MEAN_SEMANTICS.md states the arithmetic):
  *   h_neigh[v] = (1 / max(deg(v), 1)) * sum_{u->v} x[u]        out[v] = fc_neigh(h_neigh[v]) + fc_self(x_self[v])
  * Both entries: CSR over destination rows as glnn_spmm_csr_f32, n_src < 2^31, float4-addressable rows (leading dimensions multiples of 4
