@@ -86,6 +86,10 @@ SIGNATURES = {
     "glnn_block_build_ids": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
     "glnn_csr_transpose_workspace_bytes": [c_i64, c_i64],
     "glnn_csr_transpose": [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp],
+    "glnn_random_walk": [c_vp, c_vp, c_vp, c_i64, c_int, c_u32, c_vp, c_vp],
+    "glnn_induced_subgraph_direct": [c_i64, c_i64],
+    "glnn_induced_subgraph_workspace_bytes": [c_i64, c_i64],
+    "glnn_induced_subgraph": [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "glnn_appnp_prop_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_u32, c_int,
                             c_vp, c_i64, c_vp],
     "glnn_appnp_prop_bwd_f32": [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_f32, c_f32, c_u32, c_int, c_int,
@@ -251,6 +255,7 @@ def lib():
         h.glnn_struct_bytes.restype = c_i64
         h.glnn_block_workspace_bytes.restype = c_i64
         h.glnn_csr_transpose_workspace_bytes.restype = c_i64
+        h.glnn_induced_subgraph_workspace_bytes.restype = c_i64
         h.glnn_layernorm_bwd_workspace_floats.restype = c_i64
         h.glnn_gat_attn_bwd_workspace_floats.restype = c_i64
         h.glnn_gatv2_attn_bwd_workspace_floats.restype = c_i64

@@ -81,7 +81,21 @@ def get_teacher_args(argv=None):
     # Model; docs/GCNII_SEMANTICS.md).  Unset = the conf's value or the paper's defaults 0.1 / 0.5
     p.add_argument("--gcnii_alpha", type=float, default=None, help="alpha of the GCNII teacher's initial residual (default 0.1)")
     p.add_argument("--gcnii_lamda", type=float, default=None, help="lamda of the GCNII teacher's beta_l = log(lamda / l + 1) (default 0.5)")
+    # not reference flags: mini-batch training of the full-graph teachers (GCN, APPNP, GAT, GATv2, GPRGNN, GCNII) on random-walk induced
+    # subgraphs (conf keys `subgraph_walk_length`, `subgraph_self_loop`, read by run_transductive / run_inductive;
+    # docs/SUBGRAPH_SEMANTICS.md).  --batch_size is then the number of walk roots per batch; 0 = the full-graph step per epoch
+    p.add_argument("--subgraph_walk_length", type=int, default=0,
+                   help="Train a full-graph teacher on subgraphs induced by random walks of this many steps from --batch_size roots (0: off)")
+    p.add_argument("--subgraph_self_loop", type=str, default="keep", choices=["keep", "add"],
+                   help="Self entries of those subgraphs (add: one per row, so no row is empty; needs --subgraph_walk_length)")
     args = p.parse_args(argv)
+    if not 0 <= args.subgraph_walk_length <= 64:
+        p.error(f"--subgraph_walk_length must be in [0, 64] (got {args.subgraph_walk_length})")
+    if args.subgraph_walk_length > 0 and ("SAGE" in args.teacher or "MLP" in args.teacher):
+        p.error(f"--subgraph_walk_length applies to the full-graph teachers (GCN, APPNP, GAT, GATv2, GPRGNN, GCNII) only: SAGE trains on "
+                f"sampled blocks and MLP on feature batches (got --teacher {args.teacher})")
+    if args.subgraph_self_loop != "keep" and args.subgraph_walk_length == 0:
+        p.error(f"--subgraph_self_loop {args.subgraph_self_loop} needs --subgraph_walk_length > 0")
     for flag in ("gcnii_alpha", "gcnii_lamda"):
         if getattr(args, flag) is not None and "GCNII" not in args.teacher:
             p.error(f"--{flag} applies to the GCNII teacher only (got --teacher {args.teacher})")

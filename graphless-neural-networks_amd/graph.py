@@ -433,3 +433,60 @@ class NodeDataLoader:
                     q.get_nowait()
                 except queue.Empty:
                     th.join(0.02)
+
+
+class RandomWalkSubgraphLoader:
+    """Mini-batches for the full-graph teachers (train_and_eval.train_subgraph; docs/SUBGRAPH_SEMANTICS.md): per batch, `batch_size` training
+    nodes are the roots of one random walk of `walk_length` steps each (glnn_random_walk), and the batch is the subgraph induced by the
+    visited nodes (glnn_induced_subgraph) -- GraphSAINT's random-walk sampler without its normalisation coefficients.  An epoch visits every
+    training node once as a root; shuffling uses the same CPU permutation source as NodeDataLoader.
+    Yields (sub, nodes, idx_train_local): `sub` a CSRGraph over the visited nodes, `nodes` its local id -> global id map (walk by walk, in
+    order of first appearance), `idx_train_local` the local ids of ALL training nodes present in `sub` (not only the roots), taken from a
+    train mask built once.  self_loop: "keep" = the graph's own entries, "add" = self entries dropped and one appended to every row.
+    sub._cache["zero_in"] is pre-seeded from the builder's count of empty rows, so has_zero_in_degree() costs no host sync.
+    What a batch contains depends on (seed, epoch, batch index) only."""
+
+    def __init__(self, g, idx_train, batch_size, walk_length, self_loop="keep", shuffle=True, seed=None):
+        from . import ops
+        if not g.indptr.is_cuda:
+            raise RuntimeError("RandomWalkSubgraphLoader: walks and subgraphs are built on the GPU (move the graph with g.to(device))")
+        if not 1 <= int(walk_length) <= 64:
+            raise ValueError(f"RandomWalkSubgraphLoader: walk_length must be in [1, 64] (got {walk_length})")
+        if self_loop not in ops.SELF_LOOP_MODES:
+            raise ValueError(f"RandomWalkSubgraphLoader: self_loop must be one of {ops.SELF_LOOP_MODES} (got {self_loop!r})")
+        if int(batch_size) < 1:
+            raise ValueError(f"RandomWalkSubgraphLoader: batch_size must be >= 1 (got {batch_size})")
+        self.g = g
+        self.nids = torch.as_tensor(idx_train, dtype=torch.int64).to(g.device).contiguous()
+        self.batch_size, self.walk_length, self.self_loop, self.shuffle = int(batch_size), int(walk_length), self_loop, shuffle
+        self._epoch = 0
+        self._seed = int(torch.initial_seed() if seed is None else seed) & 0x7FFFFFFF
+        self.train_mask = torch.zeros(g.n_src, dtype=torch.bool, device=g.device)
+        self.train_mask[self.nids] = True
+
+    def __len__(self):
+        return (self.nids.numel() + self.batch_size - 1) // self.batch_size
+
+    def rng_seed(self, epoch, b):
+        """The seed of batch b (0-based) of epoch `epoch` (1-based) handed to glnn_random_walk."""
+        return (self._seed * 1000003 + epoch * 7919 + b * 31) & 0xFFFFFFFF
+
+    def _batch(self, b, idx, epoch):
+        from . import ops
+        g = self.g
+        roots = self.nids[idx.to(g.device)]
+        walks = ops.random_walk(g.indptr, g.indices, roots, self.walk_length, self.rng_seed(epoch, b))
+        nodes, indptr, indices, n_sub, nnz, zero_rows = ops.induced_subgraph(g.indptr, g.indices, walks.reshape(-1), self.self_loop)
+        sub = CSRGraph(indptr, indices, n_sub)
+        sub._nnz = nnz
+        sub._cache["zero_in"] = zero_rows > 0
+        idx_train_local = torch.nonzero(self.train_mask[nodes]).reshape(-1)
+        return sub, nodes, idx_train_local
+
+    def __iter__(self):
+        self._epoch += 1
+        from . import ops
+        n = self.nids.numel()
+        order = ops.randperm_cpu(n) if self.shuffle else torch.arange(n)
+        for b, s in enumerate(range(0, n, self.batch_size)):
+            yield self._batch(b, order[s:s + self.batch_size], self._epoch)

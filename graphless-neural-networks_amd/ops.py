@@ -1295,6 +1295,80 @@ def csr_transpose(indptr, indices, n_dst, n_src, nnz, add_self=False):
     return t_indptr, t_indices
 
 
+def _check_csr(indptr, indices, name):
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or indptr.dim() != 1 or indices.dim() != 1 \
+            or not indptr.is_contiguous() or not indices.is_contiguous() or indptr.numel() < 1:
+        raise ValueError(f"{name}: expected a CSR of contiguous int64 indptr [n + 1] and int32 indices")
+
+
+def random_walk(indptr, indices, roots, length, rng_seed):
+    """glnn_random_walk: out [n_roots, length + 1] int64, column 0 = roots; step s of walk i follows the in-edge number
+    (drop_hash(rng_seed, i, s) * deg) >> 32 of the node it stands on and stays where it is on a node without in-edges.  1 <= length <= 64.
+    Every root must be a node id of the graph (as glnn_sample_neighbors expects of its seeds)."""
+    _need_cuda(indptr, indices, roots)
+    _check_csr(indptr, indices, "random_walk")
+    if roots.dtype != torch.int64 or roots.dim() != 1 or not roots.is_contiguous():
+        raise ValueError("random_walk: roots must be a contiguous int64 vector")
+    length = int(length)
+    if not 1 <= length <= 64:
+        raise ValueError(f"random_walk: length must be in [1, 64] (got {length})")
+    n = roots.numel()
+    out = torch.empty((n, length + 1), dtype=torch.int64, device=roots.device)
+    with _Timed("random_walk", n_roots=n, length=length):
+        rc = _lib.lib().glnn_random_walk(_p(indptr), _p(indices), _p(roots), n, length, int(rng_seed) & 0xFFFFFFFF, _p(out), _stream())
+    _lib.check(rc, "glnn_random_walk")
+    return out
+
+
+SELF_LOOP_MODES = ("keep", "add")
+
+
+def induced_subgraph_direct(nc, n_nodes):
+    """True when a glnn_induced_subgraph build over nc candidates of an n_nodes graph indexes its table by the node id itself, False when
+    it probes the open-addressing table (the same results either way)."""
+    return bool(_lib.lib().glnn_induced_subgraph_direct(int(nc), int(n_nodes)))
+
+
+def induced_subgraph(indptr, indices, cand, self_loop="keep", nnz_cap=None):
+    """glnn_induced_subgraph: the subgraph of the CSR-by-destination graph induced by the distinct ids of `cand` (int64 device vector,
+    repeats allowed).  Returns (nodes [n_sub] = local id -> global id in order of first appearance, sub_indptr [n_sub + 1],
+    sub_indices [nnz] int32 local ids, n_sub, nnz, zero_rows = the number of rows without an entry).  self_loop "keep": the graph's own
+    entries (= CSRGraph.subgraph(cand) for candidates without repeats); "add": self entries dropped, one k <- k appended to every row.
+    nnz_cap: the capacity of sub_indices; None = the bound that always suffices, the sum of the candidates' in-degrees (+ nc with "add"),
+    which costs one host read before the call.  One more host read (the three counts) behind it."""
+    _need_cuda(indptr, indices, cand)
+    _check_csr(indptr, indices, "induced_subgraph")
+    if cand.dtype != torch.int64 or cand.dim() != 1 or not cand.is_contiguous():
+        raise ValueError("induced_subgraph: cand must be a contiguous int64 vector")
+    if self_loop not in SELF_LOOP_MODES:
+        raise ValueError(f"induced_subgraph: self_loop must be one of {SELF_LOOP_MODES} (got {self_loop!r})")
+    dev = cand.device
+    nc, n_nodes = cand.numel(), indptr.numel() - 1
+    add = self_loop == "add"
+    if nnz_cap is None:
+        # (ids out of range are clamped for this read only: the builder reports them)
+        c = cand.clamp(0, max(n_nodes - 1, 0))
+        nnz_cap = (int((indptr[c + 1] - indptr[c]).sum().item()) if nc and n_nodes else 0) + (nc if add else 0)
+    nnz_cap = int(nnz_cap)
+    nodes = torch.empty(nc, dtype=torch.int64, device=dev)
+    sub_indptr = torch.empty(nc + 1, dtype=torch.int64, device=dev)
+    sub_indices = _i32(nnz_cap, dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    wsb = int(_lib.lib().glnn_induced_subgraph_workspace_bytes(nc, n_nodes))
+    ws = torch.empty((wsb + 7) // 8, dtype=torch.int64, device=dev)
+    with _Timed("induced_subgraph", nc=nc, nnz_cap=nnz_cap, self_loop=self_loop):
+        rc = _lib.lib().glnn_induced_subgraph(_p(indptr), _p(indices), n_nodes, _p(cand), nc, 1 if add else 0, nnz_cap, _p(nodes),
+                                              _p(sub_indptr), _p(sub_indices) if nnz_cap else None, _p(counts), _p(ws), ws.numel() * 8,
+                                              _stream())
+    _lib.check(rc, "glnn_induced_subgraph")
+    n_sub, nnz, zero_rows = (int(v) for v in counts.tolist())
+    if n_sub < 0:
+        raise _lib.GlnnError(f"induced_subgraph: a candidate id lies outside [0, n_nodes = {n_nodes})")
+    if nnz > nnz_cap:
+        raise _lib.GlnnError(f"induced_subgraph: the subgraph has {nnz} entries, more than nnz_cap = {nnz_cap}")
+    return nodes[:n_sub], sub_indptr[:n_sub + 1], sub_indices[:nnz], n_sub, nnz, zero_rows
+
+
 def gather_rows(x, rows, out=None):
     _need_cuda(x, rows, out)
     x = as_feat(x)

@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .graph import FullNeighborLoader, MultiLayerFullNeighborSampler, MultiLayerNeighborSampler, NodeDataLoader
+from .graph import (FullNeighborLoader, MultiLayerFullNeighborSampler, MultiLayerNeighborSampler, NodeDataLoader,
+                    RandomWalkSubgraphLoader)
 from . import teacher
 from .student import get_engine, student_supported
 from .utils import set_seed
@@ -97,6 +98,47 @@ def train_sage(model, dataloader, feats, labels, criterion, optimizer, lamb=1, m
             dataloader.plain_transpose = had_plain
     eng.sync_optimizer_state()
     return eng.loss_accum.item() / max(steps, 1)
+
+
+def _full_graph_step(eng, model_name):
+    """The TeacherEngine step train() runs for a model of this name ("GCNII" contains "GCN" and "GATv2" contains "GAT": tested first)."""
+    for key, step in (("GCNII", eng.step_gcnii), ("APPNP", eng.step_appnp), ("GATv2", eng.step_gatv2), ("GAT", eng.step_gat),
+                      ("GPRGNN", eng.step_gpr), ("GCN", eng.step_gcn)):
+        if key in model_name:
+            return step
+    raise NotImplementedError(f"no full-graph step for {model_name}")
+
+
+def train_subgraph(model, loader, feats, labels, criterion, optimizer, lamb=1):
+    """Mini-batch training of a full-graph teacher (GCN, APPNP, GAT, GATv2, GPRGNN, GCNII) on random-walk induced subgraphs: per batch of
+    `loader` (glnn_amd.graph.RandomWalkSubgraphLoader: walks and subgraphs built on the device) the rows feats[nodes] / labels[nodes] are
+    gathered and the SAME TeacherEngine step train() picks for the model runs on the subgraph, its loss the plain mean over the subgraph's
+    training nodes (docs/SUBGRAPH_SEMANTICS.md: a biased, Cluster-GCN-style estimator).  The per-batch losses are summed on the device and
+    read ONCE per epoch, as in train_sage; returns their mean."""
+    if "MLP" in model.model_name:
+        raise NotImplementedError("train_subgraph(): graph teachers only -- the MLP trains with train_mini_batch")
+    if "SAGE" in model.model_name:
+        raise NotImplementedError("train_subgraph(): the full-graph teachers only -- SAGE trains on sampled blocks with train_sage")
+    teacher.check_supported(model, criterion, optimizer)
+    model.train()
+    eng = teacher.get_engine(model, optimizer)
+    step = _full_graph_step(eng, model.model_name)
+    eng.loss_accum.zero_()
+    x = ops.as_feat(feats)
+    steps = 0
+    for sub, nodes, idx_train_local in loader:
+        step(sub, ops.gather_rows(x, nodes), labels[nodes], idx_train_local, float(lamb))
+        steps += 1
+    eng.sync_optimizer_state()
+    return eng.loss_accum.item() / max(steps, 1)
+
+
+def _subgraph_loader(conf, model, g, idx_train):
+    """The RandomWalkSubgraphLoader of a run whose conf asks for one (`subgraph_walk_length` > 0, a full-graph teacher), else None."""
+    if int(conf.get("subgraph_walk_length", 0) or 0) <= 0 or "MLP" in model.model_name or "SAGE" in model.model_name:
+        return None
+    return RandomWalkSubgraphLoader(g, idx_train, conf["batch_size"], int(conf["subgraph_walk_length"]),
+                                    self_loop=conf.get("subgraph_self_loop", "keep"), shuffle=True)
 
 
 def _train_sage_autograd(model, dataloader, feats, labels, criterion, optimizer, lamb):
@@ -279,12 +321,15 @@ def run_transductive(conf, model, g, feats, labels, indices, criterion, evaluato
     else:
         g = g.to(device)
         data = data_eval = g
+    sub_loader = _subgraph_loader(conf, model, g, idx_train)          # --subgraph_walk_length > 0: mini-batches of induced subgraphs
 
     def train_epoch():
         if is_sage:
             return train_sage(model, data, feats, labels, criterion, optimizer, mean_step=conf.get("sage_mean_step", "autograd"))
         if is_mlp:
             return train_mini_batch(model, feats_train, labels_train, batch_size, criterion, optimizer)
+        if sub_loader is not None:
+            return train_subgraph(model, sub_loader, feats, labels, criterion, optimizer)
         return train(model, data, feats, labels, criterion, optimizer, idx_train)
 
     def eval_epoch():
@@ -371,12 +416,15 @@ def run_inductive(conf, model, g, feats, labels, indices, criterion, evaluator, 
         else:
             obs_data = obs_data_eval = obs_g
             data_eval = g
+    sub_loader = None if is_mlp else _subgraph_loader(conf, model, obs_g, obs_idx_train)      # over the OBSERVED graph, its own train indices
 
     def train_epoch():
         if is_sage:
             return train_sage(model, obs_data, obs_feats, obs_labels, criterion, optimizer, mean_step=conf.get("sage_mean_step", "autograd"))
         if is_mlp:
             return train_mini_batch(model, feats_train, labels_train, batch_size, criterion, optimizer)
+        if sub_loader is not None:
+            return train_subgraph(model, sub_loader, obs_feats, obs_labels, criterion, optimizer)
         return train(model, obs_data, obs_feats, obs_labels, criterion, optimizer, obs_idx_train)
 
     def eval_epoch():

@@ -726,6 +726,44 @@ GLNN_API int glnn_csr_transpose(const int64_t* indptr, const int32_t* indices, i
                                 void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mini-batches for the full-graph teachers: random-walk node sampling and the induced subgraph of the visited nodes, both sized by
+ * the batch and never by N or E (docs/SUBGRAPH_SEMANTICS.md).  GraphSAINT's random-walk sampler (Zeng et al., ICLR 2020) without its
+ * normalisation coefficients.
+ *
+ * glnn_random_walk: out [n_roots, length + 1] int64 global ids, column 0 = roots[i].  Step s (1-based) of walk i, standing on v with
+ * deg = indptr[v+1] - indptr[v]: deg == 0 -> the walk stays on v; else it moves to
+ *     indices[indptr[v] + (((uint64_t)drop_hash(rng_seed, i, s) * deg) >> 32)]
+ * (the draw of glnn_sample_neighbors; drop_hash is restated by oracle/dropout_mask.py).  The CSR is stored by destination, so a step
+ * follows an IN-edge: v has the in-edge u -> v inside the induced subgraph.  1 <= length <= 64.  Every root must be in [0, n_nodes). */
+GLNN_API int glnn_random_walk(const int64_t* indptr, const int32_t* indices, const int64_t* roots, int64_t n_roots, int length,
+                              uint32_t rng_seed, int64_t* out, void* stream);
+
+/* glnn_induced_subgraph: the subgraph of (g_indptr, g_indices) induced by the DISTINCT ids of cand [nc] (int64 global ids in
+ * [0, n_nodes), repeats allowed).  Outputs (caller-owned):
+ *   nodes   [nc]       the distinct candidates in order of first appearance = local id -> global id (first n_sub entries valid)
+ *   indptr  [nc + 1]   (first n_sub + 1 entries valid)
+ *   indices [nnz_cap]  int32 LOCAL ids: row k holds the in-edges u -> nodes[k] of the graph whose u is in the set, in the order of the
+ *                      graph's own row, multi-edges kept
+ *   counts  device int64[3] = {n_sub, nnz, rows without an entry}
+ * self_loop 0 ("keep"): exactly that -- for candidates without repeats, CSRGraph.subgraph(cand) array for array.
+ * self_loop 1 ("add"): self entries are dropped and one k <- k is appended at the end of every row, so no row is empty.
+ * SIZING: the caller supplies the capacity nnz_cap of `indices` (the sum of the candidates' in-degrees, + nc with "add", always
+ * suffices); counts[1] reports the TRUE number of entries.  counts[1] > nnz_cap: the capacity was too small -- nothing was written past
+ * it, `indices` is incomplete.  An id outside [0, n_nodes) is never used as an index: counts[0] comes back as -1 (the other outputs are
+ * then undefined, and in bounds).
+ * Work and workspace are proportional to nc plus the in-degrees of the candidates.  Integer arithmetic only; "first appearance" comes from
+ * atomicMin on list positions and the entry order from ballot ranks, so the same input gives the same bits.  One wave walks a row, 64
+ * in-edges per round, whatever its length.
+ * workspace: glnn_induced_subgraph_workspace_bytes(nc, n_nodes) bytes, 8-byte aligned.  nc < 2^30, nnz_cap < 2^31, n_nodes < 0x7F7F7F7F.
+ * glnn_induced_subgraph_direct: 1 when that build indexes its table by the node id itself (n_nodes no larger than the two arrays of
+ * the hash table, 2 x (the power of two >= 2 nc, at least 64)), 0 when it probes an open-addressing table.  Identical results. */
+GLNN_API int glnn_induced_subgraph_direct(int64_t nc, int64_t n_nodes);
+GLNN_API int64_t glnn_induced_subgraph_workspace_bytes(int64_t nc, int64_t n_nodes);
+GLNN_API int glnn_induced_subgraph(const int64_t* g_indptr, const int32_t* g_indices, int64_t n_nodes, const int64_t* cand, int64_t nc,
+                                   int self_loop, int64_t nnz_cap, int64_t* nodes, int64_t* indptr, int32_t* indices,
+                                   int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * APPNP propagation (dgl APPNPConv(k, alpha, edge_drop) of the reference APPNP teacher, models.py:282-344): K launches of ONE power
  * iteration each, forward and backward, ping-ponging two buffers.  docs/APPNP_SEMANTICS.md states the arithmetic.  Square graph of n nodes,
  * indptr / indices the in-CSR (rows = destinations); dst_norm / src_norm = in_deg.clamp(1)^-1/2 / out_deg.clamp(1)^-1/2 (glnn_degrees_f32,
