@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void block_relabel_kernel(const BlockArgs a, c
     a.counts[0] = (a.direct && *a.bad == 0) ? -1 : a.indptr[a.ns];
     a.counts[1] = a.ns + *n_new;
   }
-  if (e >= a.indptr[a.ns]) return;
+  if (e >= a.indptr[a.ns] || e >= a.nnz_cap) return;      // (a capacity below the true count: the grid's last workgroup reaches past it)
   a.indices[e] = a.pos[a.slot_of_edge[e]] & (kLocalBit - 1);
 }
 

@@ -687,7 +687,10 @@ GLNN_API int glnn_sample_neighbors(const int64_t* indptr, const int32_t* indices
  *   seeds [ns]        the block's destination nodes (global ids)
  *   sampled mode      smp_src [ns, fanout] / smp_cnt [ns] from glnn_sample_neighbors, nnz_cap >= ns * fanout
  *   full mode         smp_src = smp_cnt = NULL: every in-edge of every seed from (g_indptr, g_indices);
- *                     nnz_cap >= the block's edge count (the caller's bound; counts[0] reports the true number)
+ *                     nnz_cap >= the block's edge count (the caller's bound; counts[0] reports the true number: when it
+ *                     exceeds nnz_cap the capacity was too small -- nothing was written at or past it, call again with more)
+ *   nnz_cap == 0      the caller asserts an EMPTY block: no row is read, whatever in-edges the seeds have -- indptr is all
+ *                     zeros, input_nodes = seeds, counts = {0, ns}
  * Outputs (caller-owned): indptr [ns+1]; indices [nnz_cap] LOCAL source ids (block CSR over its destinations, edges in
  * the order of smp_src / of the graph's rows); gindices [nnz_cap] the same edges' GLOBAL source ids (optional);
  * input_nodes [ns + nnz_cap]: the block's source nodes = its destinations first (models.py:109), then every other

@@ -11,6 +11,7 @@ import torch
 from golden_inputs import sub_dict, teacher_training
 from graphgen import random_graph
 from oracle import teacher_train_oracle as tt
+from sampling_oracle import first_appearance_block as _first_appearance_block      # (the numpy restatement of glnn_block_build)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -59,22 +60,6 @@ def test_csr_transpose_of_a_block_and_empty_inputs():
     assert t_ix.tolist() == [0, 2, 0, 1, 2, 0, 2, 2]
     t_ip, t_ix = ops.csr_transpose(torch.zeros(5, dtype=torch.int64, device=DEV), torch.zeros(0, dtype=torch.int32, device=DEV), 4, 4, 0, False)
     assert t_ip.tolist() == [0] * 5 and t_ix.numel() == 0
-
-
-def _first_appearance_block(seeds, rows):
-    """numpy restatement of glnn_block_build: rows[i] = global source ids of destination i, in order."""
-    pos = {int(v): i for i, v in enumerate(seeds)}
-    input_nodes = [int(v) for v in seeds]
-    indptr, local = [0], []
-    for r in rows:
-        for u in r:
-            u = int(u)
-            if u not in pos:
-                pos[u] = len(input_nodes)
-                input_nodes.append(u)
-            local.append(pos[u])
-        indptr.append(len(local))
-    return np.asarray(indptr, np.int64), np.asarray(local, np.int32), np.asarray(input_nodes, np.int64)
 
 
 @pytest.mark.parametrize("known_ids", [False, True])
