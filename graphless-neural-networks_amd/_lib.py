@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GLNN_LIB_PATH") or os.path.join(_HERE, "libglnn_hip.so")   # override: A/B of kernel variants
 
 c_i64, c_int, c_f32, c_vp, c_u32 = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32
+c_f64 = ctypes.c_double
 
 # name -> argtypes, exactly the prototypes of include/glnn_hip.h (pointers as void*)
 SIGNATURES = {
@@ -96,6 +97,10 @@ SIGNATURES = {
                                 c_vp, c_i64, c_vp, c_i64, c_vp],
     "glnn_csr_transpose_eids": [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "glnn_edge_drop_mask_u8": [c_i64, c_int, c_f32, c_u32, c_vp, c_vp],
+    "glnn_deepwalk_pairs": [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "glnn_deepwalk_score_f32": [c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "glnn_deepwalk_apply_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64,
+                                c_f64, c_f64, c_f64, c_i64, c_vp, c_vp, c_vp],
     "glnn_gpr_prop_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp,
                           c_i64, c_vp, c_vp],
     "glnn_gpr_fold_f32": [c_vp, c_int, c_i64, c_vp, c_vp, c_i64, c_vp],

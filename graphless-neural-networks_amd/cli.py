@@ -117,7 +117,27 @@ def get_student_args(argv=None):
     # bfloat16 = weights and hidden activations stored as bf16, bf16 MFMA products, fp32 accumulation and saved log-probs (glnn_amd.serve)
     p.add_argument("--serve_dtype", type=str, default="float32", choices=["float32", "bfloat16"],
                    help="Storage of the MLP student's evaluation passes (bfloat16: norm_type none / batch)")
-    return p.parse_args(argv)
+    # not reference flags: DeepWalk position features concatenated to the student's input (glnn_amd.position; docs/POSITION_SEMANTICS.md).
+    # --position_dim 0 (the default) is off: nothing changes.  The YAML section is still the plain student's
+    p.add_argument("--position_dim", type=int, default=0,
+                   help="Width of the DeepWalk position embedding appended to the student's features (0: off; a multiple of 4, <= 256)")
+    p.add_argument("--position_walk_length", type=int, default=20, help="Steps per random walk of the position embedding")
+    p.add_argument("--position_context", type=int, default=10, help="Skip-gram window (nodes per window) of the position embedding")
+    p.add_argument("--position_negatives", type=int, default=1, help="Uniform negatives per positive pair of the position embedding")
+    p.add_argument("--position_epochs", type=int, default=5, help="Passes over the nodes (each a walk root once) of the position embedding")
+    p.add_argument("--position_batch_size", type=int, default=4096, help="Walk roots per step of the position embedding")
+    p.add_argument("--position_lr", type=float, default=0.01, help="Learning rate of the position embedding's lazy Adam")
+    args = p.parse_args(argv)
+    if args.position_dim < 0 or args.position_dim % 4 or args.position_dim > 256:
+        p.error(f"--position_dim must be 0 (off) or a multiple of 4 up to 256 (got {args.position_dim})")
+    if args.position_dim > 0:
+        if not 1 <= args.position_walk_length <= 64:
+            p.error(f"--position_walk_length must be in [1, 64] (got {args.position_walk_length})")
+        if not 2 <= args.position_context <= args.position_walk_length + 1:
+            p.error(f"--position_context must be in [2, --position_walk_length + 1] (got {args.position_context})")
+        if args.position_negatives < 1 or args.position_epochs < 1 or args.position_batch_size < 1:
+            p.error("--position_negatives, --position_epochs and --position_batch_size must be >= 1")
+    return args
 
 
 def _device(args):
@@ -166,6 +186,27 @@ def _save(args, output_dir, out, loss_and_score, model, g):
 
 def _prop(feats, g, k, device):
     return feature_prop(feats.to(device), g.to(device), k).cpu() if k > 0 else feats
+
+
+def _with_position(args, feats, g, idx_obs, device, logger):
+    """--position_dim D > 0: feats with a DeepWalk embedding of D columns appended (run_student widens conf["feat_dim"] by D).  idx_obs None
+    (transductive): fitted on g.  Inductive: fitted on g.subgraph(idx_obs) only, the rows of the hidden test nodes filled with the mean
+    over their observed in-neighbours (position.fill_unseen) -- NOSMOG's recipe."""
+    if args.position_dim <= 0:
+        return feats
+    from .position import DeepWalk, fill_unseen
+    gd = g.to(device)
+    sub = gd if idx_obs is None else g.subgraph(idx_obs).to(device)
+    dw = DeepWalk(sub, args.position_dim, args.position_walk_length, args.position_context, args.position_negatives,
+                  lr=args.position_lr, seed=args.seed)
+    losses = dw.fit(args.position_epochs, args.position_batch_size)
+    logger.info(f"position embedding: {sub.num_nodes()} nodes x {args.position_dim}, loss per epoch " + " ".join(f"{x:.4f}" for x in losses))
+    z = dw.embedding
+    if idx_obs is not None:
+        full = torch.zeros((g.num_nodes(), args.position_dim), dtype=torch.float32, device=device)
+        full[torch.as_tensor(idx_obs, dtype=torch.int64, device=device)] = z
+        z = fill_unseen(gd, full, idx_obs)
+    return torch.cat([feats, z.to(feats.device)], dim=1)
 
 
 def run_teacher(args):
@@ -219,7 +260,8 @@ def run_student(args):
     if args.feature_aug_k > 0 and args.seed == 0:
         args.output_path = Path.cwd().joinpath(args.output_path, "aug_features", f"aug_hop_{args.feature_aug_k}")
         args.student = f"GA{args.feature_aug_k}{args.student}"
-    output_dir = _setting_dir(args, args.output_path, f"{args.teacher}_{args.student}")
+    pe = f"PE{args.position_dim}" if args.position_dim > 0 else ""          # runs with position features get a leaf of their own
+    output_dir = _setting_dir(args, args.output_path, f"{args.teacher}_{pe}{args.student}")
     out_t_dir = _setting_dir(args, args.out_t_path, args.teacher)
     args.output_dir = output_dir
     check_writable(output_dir, overwrite=False)
@@ -229,6 +271,7 @@ def run_student(args):
     logger.info(f"out_t_dir: {out_t_dir}")
     g, feats, labels, (idx_train, idx_val, idx_test), conf = _load(args, logger, args.student)     # student section of the YAML
     conf["device"] = device
+    conf["feat_dim"] += args.position_dim        # the first layer also takes the position columns (_with_position appends them below)
     logger.info(f"conf: {conf}")
     model = Model(conf)
     optimizer = optim.Adam(model.parameters(), lr=conf["learning_rate"], weight_decay=conf["weight_decay"])
@@ -242,6 +285,7 @@ def run_student(args):
     if args.exp_setting == "tran":
         distill_indices = (idx_train, torch.cat([idx_train, idx_val, idx_test]), idx_val, idx_test)
         feats = _prop(feats, g, args.feature_aug_k, device)
+        feats = _with_position(args, feats, g, None, device, logger)
         out, score_val, score_test = distill_run_transductive(conf, model, feats, labels, out_t, distill_indices, criterion_l,
                                                               criterion_t, evaluator, optimizer, logger, loss_and_score)
         score_lst = [score_test]
@@ -253,6 +297,7 @@ def run_student(args):
             obs_feats = _prop(feats[idx_obs], g.subgraph(idx_obs), args.feature_aug_k, device)
             feats = _prop(feats, g, args.feature_aug_k, device)
             feats[idx_obs] = obs_feats
+        feats = _with_position(args, feats, g, idx_obs, device, logger)
         out, score_val, score_tt, score_ti = distill_run_inductive(conf, model, feats, labels, out_t, distill_indices, criterion_l,
                                                                    criterion_t, evaluator, optimizer, logger, loss_and_score)
         score_lst = [score_tt, score_ti]

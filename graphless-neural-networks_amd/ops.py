@@ -1615,6 +1615,116 @@ def csr_transpose_eids(indptr, indices, n_dst, n_src, nnz):
     return t_indptr, t_indices, t_eids
 
 
+# --------------------------------------------------------------------------------------------- DeepWalk position embeddings (csrc/deepwalk.hip)
+DEEPWALK_MAX_DIM = 256          # kDwMaxD of csrc/deepwalk.hip
+
+
+def _dw_check(rc, what):
+    """A refused argument of the DeepWalk entries is the caller's ValueError, with the C message; anything else is a GlnnError."""
+    if rc == -1:
+        raise ValueError(_lib.lib().glnn_last_error().decode(errors="replace"))
+    _lib.check(rc, what)
+
+
+def _dw_table(t, name, rows=None):
+    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or (rows is not None and t.shape[0] != rows):
+        raise ValueError(f"{name}: expected a contiguous float32 matrix" + ("" if rows is None else f" of {rows} rows"))
+    return t
+
+
+def deepwalk_windows(n_roots, length, context, negatives):
+    """(Q, R) of a DeepWalk step: Q = n_roots * (length + 2 - context) windows of R = (1 + negatives) * (context - 1) entries."""
+    return int(n_roots) * (int(length) + 2 - int(context)), (1 + int(negatives)) * (int(context) - 1)
+
+
+def deepwalk_pairs(indptr, indices, roots, length, context, negatives, walk_seed, neg_seed):
+    """glnn_deepwalk_pairs (docs/POSITION_SEMANTICS.md): walks = random_walk(roots, length, walk_seed), then per window q = i * nwin + j its
+    start walks[i, j] and its pair row: the context - 1 positives walks[i, j + 1 ..], then negatives * (context - 1) uniform negatives
+    (drop_hash(neg_seed, q, t') * N) >> 32.  `roots`: int64 vector on the CPU (checked against the graph there, then copied to the device:
+    no device read) or on the device (one copy back for the check).  Returns (walks [B, length + 1] int64, start [Q] int32, rest [Q, R] int32,
+    pair_indptr [Q + 1], win_indptr [Q + 1]) -- the two indptr arrays are q * R and q, what the transposes of the pair list and of the
+    start list read."""
+    _need_cuda(indptr, indices)
+    _check_csr(indptr, indices, "deepwalk_pairs")
+    if roots.dtype != torch.int64 or roots.dim() != 1:
+        raise ValueError("deepwalk_pairs: roots must be an int64 vector")
+    dev = indptr.device
+    roots_host = roots.contiguous() if not roots.is_cuda else roots.cpu().contiguous()
+    roots = roots.contiguous() if roots.is_cuda else roots_host.to(dev)
+    n, b = indptr.numel() - 1, roots.numel()
+    length, context, negatives = int(length), int(context), int(negatives)
+    q, r = deepwalk_windows(b, length, context, negatives)
+    ok = 1 <= length <= 64 and 2 <= context <= length + 1 and negatives >= 1 and q * r < 2 ** 31      # (else: refused below, nothing allocated)
+    q, r = (q, r) if ok else (0, 0)
+    walks = torch.empty((b, length + 1) if ok else (0, 1), dtype=torch.int64, device=dev)
+    start, rest = _i32(q, dev), _i32(q * r, dev)
+    pair_indptr = torch.empty(q + 1, dtype=torch.int64, device=dev)
+    win_indptr = torch.empty(q + 1, dtype=torch.int64, device=dev)
+    with _Timed("deepwalk_pairs", n_roots=b, length=length, context=context, negatives=negatives):
+        rc = _lib.lib().glnn_deepwalk_pairs(_p(indptr), _p(indices), n, _p(roots), _p(roots_host), b, length, context, negatives,
+                                            int(walk_seed) & 0xFFFFFFFF, int(neg_seed) & 0xFFFFFFFF, _p(walks), _p(start), _p(rest),
+                                            _p(pair_indptr), _p(win_indptr), _stream())
+    _dw_check(rc, "glnn_deepwalk_pairs")
+    return walks, start, rest.view(q, r), pair_indptr, win_indptr
+
+
+def deepwalk_score(z, start, rest, context, negatives):
+    """glnn_deepwalk_score_f32 at frozen z [N, d]: g [Q * R] = dLoss/ds of every pair, gs [Q, d] = sum_t g z[rest] (the start-side gradient of
+    window q), zs [Q, d] = z[start] (the snapshot the entry side reads), loss_parts [2, Q] = the windows' softplus sums over positives /
+    negatives.  Returns (g, gs, zs, loss_parts)."""
+    _need_cuda(z, start, rest)
+    _dw_table(z, "deepwalk_score z")
+    if start.dtype != torch.int32 or rest.dtype != torch.int32 or rest.dim() != 2 or not rest.is_contiguous() or not start.is_contiguous() \
+            or rest.shape[0] != start.numel():
+        raise ValueError("deepwalk_score: start [Q] and rest [Q, R] must be contiguous int32 (ops.deepwalk_pairs)")
+    n, d = z.shape
+    q, r = rest.shape
+    if r != (1 + int(negatives)) * (int(context) - 1):
+        raise ValueError(f"deepwalk_score: rest has {r} entries per window, (1 + negatives) * (context - 1) = {(1 + int(negatives)) * (int(context) - 1)}")
+    g = torch.empty(max(q * r, 1), dtype=torch.float32, device=z.device)[:q * r]
+    gs = torch.empty((q, d), dtype=torch.float32, device=z.device)
+    zs = torch.empty((q, d), dtype=torch.float32, device=z.device)
+    loss_parts = torch.empty((2, q), dtype=torch.float32, device=z.device)
+    with _Timed("deepwalk_score", d=d, n_windows=q, row=r):
+        rc = _lib.lib().glnn_deepwalk_score_f32(_p(z), n, d, _p(start), _p(rest), q, int(context), int(negatives), _p(g), _p(gs), _p(zs),
+                                                _p(loss_parts), _stream())
+    _dw_check(rc, "glnn_deepwalk_score_f32")
+    return g, gs, zs, loss_parts
+
+
+def deepwalk_apply(z, m, v, tw, tp, g, gs, zs, loss_parts, context, negatives, lr, betas, eps, step, loss_out=None):
+    """glnn_deepwalk_apply_f32: the lazy-Adam update of the rows of z, m, v [N, d] (in place) that are the start or an entry of some pair.
+    tw = (t_indptr, t_indices) of csr_transpose over the start list, tp = (t_indptr, t_eids) of csr_transpose_eids over the pair list.
+    dz[n] = sum of gs over n's windows + sum of g[e] * zs[e // R] over n's pair-list positions; rows in no pair are not written.
+    `step` is the global step count (>= 1).  Returns the loss as a device scalar (loss_out, a float32 tensor of one element, if given)."""
+    _need_cuda(z, m, v, g, gs, zs, loss_parts, loss_out, *tw, *tp)
+    n, d = _dw_table(z, "deepwalk_apply z").shape
+    for name, t in (("m", m), ("v", v)):
+        if tuple(_dw_table(t, f"deepwalk_apply {name}").shape) != (n, d):
+            raise ValueError(f"deepwalk_apply: {name} must have z's shape")
+    q = gs.shape[0]
+    if tuple(_dw_table(zs, "deepwalk_apply zs").shape) != (q, d) or _dw_table(gs, "deepwalk_apply gs").shape[1] != d \
+            or loss_parts.numel() != 2 * q or not loss_parts.is_contiguous() or loss_parts.dtype != torch.float32 \
+            or g.dtype != torch.float32 or not g.is_contiguous():
+        raise ValueError("deepwalk_apply: g, gs, zs and loss_parts must be those of ops.deepwalk_score")
+    r = (1 + int(negatives)) * (int(context) - 1)
+    (tw_indptr, tw_indices), (tp_indptr, tp_eids) = tw, tp
+    if tw_indptr.dtype != torch.int64 or tp_indptr.dtype != torch.int64 or tw_indptr.numel() != n + 1 or tp_indptr.numel() != n + 1 \
+            or tw_indices.dtype != torch.int32 or tp_eids.dtype != torch.int32 or tw_indices.numel() != q or tp_eids.numel() != q * r \
+            or g.numel() != q * r:
+        raise ValueError("deepwalk_apply: tw / tp must be the transposes of the start list (Q entries) and of the pair list (Q * R entries) over N nodes")
+    if loss_out is None:
+        loss_out = torch.empty((), dtype=torch.float32, device=z.device)
+    elif loss_out.dtype != torch.float32 or loss_out.numel() != 1:
+        raise ValueError("deepwalk_apply: loss_out must be a float32 tensor of one element")
+    with _Timed("deepwalk_apply", d=d, n_nodes=n, n_windows=q, row=r):
+        rc = _lib.lib().glnn_deepwalk_apply_f32(_p(tw_indptr), _p(tw_indices), _p(tp_indptr), _p(tp_eids), n, d, q, int(context),
+                                                int(negatives), _p(g), _p(gs), _p(zs), _p(z), _p(m), _p(v), float(lr), float(betas[0]),
+                                                float(betas[1]), float(eps), int(step), _p(loss_parts), _p(loss_out), _stream())
+    _dw_check(rc, "glnn_deepwalk_apply_f32")
+    return loss_out
+
+
 def edge_drop_mask(nnz, t, edge_drop, seed, device):
     """glnn_edge_drop_mask_u8: uint8 [nnz], 1 = edge kept in iteration t (1-based) -- the mask the propagation kernels evaluate."""
     mask = torch.empty(max(int(nnz), 1), dtype=torch.uint8, device=device)[:int(nnz)]

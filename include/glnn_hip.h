@@ -801,6 +801,49 @@ GLNN_API int glnn_csr_transpose_eids(const int64_t* indptr, const int32_t* indic
 GLNN_API int glnn_edge_drop_mask_u8(int64_t nnz, int t, float edge_drop, uint32_t seed, uint8_t* mask, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DeepWalk position embeddings for the MLP student (Perozzi et al., KDD 2014; used as in NOSMOG, Tian et al., ICLR 2023): one skip-gram
+ * step with negative sampling over ONE table z [n_nodes, d] and batch-synchronous lazy Adam.  docs/POSITION_SEMANTICS.md states the
+ * arithmetic.  fp32, contiguous rows (leading dimension d), d % 4 == 0, 4 <= d <= 256, 16-byte aligned.  L = length in [1, 64], c = context
+ * in [2, L + 1], k = negatives >= 1; nwin = L + 2 - c windows per walk, Q = n_roots nwin windows, R = (1 + k)(c - 1) entries per window;
+ * Q R < 2^31 and n_nodes < 2^31.  Any of these violated: GLNN_ERR_INVALID_ARG with nothing launched.  No float atomics; the same input
+ * gives the same bits.  A step is glnn_deepwalk_pairs, glnn_deepwalk_score_f32, glnn_csr_transpose(win_indptr, start, Q, n_nodes, Q),
+ * glnn_csr_transpose_eids(pair_indptr, rest, Q, n_nodes, Q R), glnn_deepwalk_apply_f32.
+ *
+ * glnn_deepwalk_pairs: walks [n_roots, L + 1] = glnn_random_walk(roots, L, walk_seed) (called from here), then for window q = i nwin + j:
+ *   start[q] = walks[i, j];  rest[q R + t] = walks[i, j + 1 + t] for t < c - 1 (the positives), else the uniform negative
+ *   ((uint64_t)drop_hash(neg_seed, q, t - (c - 1)) * n_nodes) >> 32 (kept even where it equals the start or a positive);
+ *   pair_indptr[q] = q R and win_indptr[q] = q for q <= Q: the indptr arrays of the two CSRs the transposes read.
+ *   roots_host (optional): a host copy of roots; every entry is checked against [0, n_nodes) before anything is launched.  NULL: every
+ *   root must be a node id, as glnn_random_walk expects. */
+GLNN_API int glnn_deepwalk_pairs(const int64_t* indptr, const int32_t* indices, int64_t n_nodes, const int64_t* roots,
+                                 const int64_t* roots_host, int64_t n_roots, int length, int context, int negatives,
+                                 uint32_t walk_seed, uint32_t neg_seed, int64_t* walks, int32_t* start, int32_t* rest,
+                                 int64_t* pair_indptr, int64_t* win_indptr, void* stream);
+/* glnn_deepwalk_score_f32, at frozen z, with s = <z[start[q]], z[rest[q R + t]]>, n_pos = Q (c - 1), n_neg = k n_pos:
+ *   g[q R + t] = (sigmoid(s) - 1) / n_pos for a positive, sigmoid(s) / n_neg for a negative;
+ *   gs[q] = sum_t g[q R + t] z[rest[q R + t]] (t ascending per lane group, the groups folded by an xor tree);  zs[q] = z[start[q]];
+ *   loss_parts[q] = sum over the positives of softplus(-s), loss_parts[Q + q] = sum over the negatives of softplus(s).
+ * g [Q R], gs / zs [Q, d], loss_parts [2 Q].  An id outside [0, n_nodes) in start / rest is never used as an index (g = 0 there). */
+GLNN_API int glnn_deepwalk_score_f32(const float* z, int64_t n_nodes, int d, const int32_t* start, const int32_t* rest,
+                                     int64_t n_windows, int context, int negatives, float* g, float* gs, float* zs,
+                                     float* loss_parts, void* stream);
+/* glnn_deepwalk_apply_f32: (tw_indptr, tw_indices) = glnn_csr_transpose of (win_indptr, start): per node its windows;
+ * (tp_indptr, tp_eids) = t_indptr and t_eids of glnn_csr_transpose_eids of (pair_indptr, rest): per node the pair-list positions at which
+ * it is the entry, ascending.  For every node n with a window or an entry:
+ *   dz = sum over its windows of gs[q]  +  sum over its positions e of g[e] zs[e / R]      (each list in its stored order, then the two)
+ *   m <- beta1 m + (1 - beta1) dz;  v <- beta2 v + (1 - beta2) dz^2;  z <- z - lr sqrt(1 - beta2^step) / (1 - beta1^step) m / (sqrt(v) + eps)
+ * in place (torch.optim.SparseAdam's arithmetic, no weight decay; step >= 1 is the global step count; the hyper-parameters are doubles, as
+ * there: the bias corrections are formed in double and the step size, beta, 1 - beta and eps rounded to fp32 once).  Every other row of z, m, v is
+ * not written.  A node of more than 128 entries is summed by a whole workgroup, the wave partials added in wave order.
+ * loss_out (device float) = sum(loss_parts[0 .. Q)) / n_pos + sum(loss_parts[Q .. 2 Q)) / n_neg, summed in fp64 in a fixed order by one
+ * more workgroup of the same launch. */
+GLNN_API int glnn_deepwalk_apply_f32(const int64_t* tw_indptr, const int32_t* tw_indices, const int64_t* tp_indptr,
+                                     const int32_t* tp_eids, int64_t n_nodes, int d, int64_t n_windows, int context, int negatives,
+                                     const float* g, const float* gs, const float* zs, float* z, float* m, float* v, double lr,
+                                     double beta1, double beta2, double eps, int64_t step, const float* loss_parts, float* loss_out,
+                                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * GPR-GNN propagation (Chien et al., ICLR 2021): result = sum_{k = 0..K} gamma[k] P^k x0 with K + 1 learned coefficients and APPNP's
  * operator P = D_in^-1/2 A D_out^-1/2.  docs/GPR_SEMANTICS.md states the arithmetic.  ONE entry serves both directions, one call per
  * step k = 1..K (k = 0 alone when K = 0); square graph of n nodes, nnz = indptr[n] < 2^31 (GLNN_ERR_UNSUPPORTED otherwise), no edge
