@@ -76,6 +76,12 @@ inline bool rows_ok(const float* p, int64_t ld, int d) { return p == nullptr || 
   do {                                                              \
     if (!(cond)) return ::glnn::fail(GLNN_ERR_INVALID_ARG, __VA_ARGS__); \
   } while (0)
+// pass a callee's failure on (its error text is already set)
+#define GLNN_TRY(expr)              \
+  do {                              \
+    const int rc_ = (expr);         \
+    if (rc_ != GLNN_OK) return rc_; \
+  } while (0)
 
 constexpr int kWave = 64;  // CDNA wavefront
 

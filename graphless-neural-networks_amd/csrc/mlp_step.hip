@@ -7,13 +7,7 @@
 // the tiled GEMM + separate reduction kernels follow).
 #include <cstdlib>
 
-#include "glnn_common.h"
-
-#define GLNN_TRY(expr)          \
-  do {                          \
-    const int rc_ = (expr);     \
-    if (rc_ != GLNN_OK) return rc_; \
-  } while (0)
+#include "step_common.h"
 
 // pf != NULL (glnn_mlp_train_step_f32): the fused Adam launch follows immediately and is the only consumer of the gradients, so the
 // final sums of gradient partials (split-K slabs of the weight gradients, ...) are left to it: they are registered in *pf instead of
@@ -557,12 +551,7 @@ extern "C" int glnn_mlp_train_step_f32(const glnn_mlp_step_desc* d, const float*
                                        int64_t m, int kind, const int64_t* labels, const float* target_logp, int64_t ldt,
                                        const int64_t* target_rows, float lamb, const uint32_t* drop_seeds, const glnn_adam_desc* adam,
                                        void* stream) {
-  GLNN_REQUIRE(adam && adam->params && adam->grads && adam->exp_avg && adam->exp_avg_sq && adam->sizes && adam->grads_host,
-               "glnn_mlp_train_step_f32: the Adam descriptor is incomplete");
-  glnn::PendingFolds pf = {};
-  const bool folds = glnn::opts().adam_folds && adam->num_tensors <= 32;
-  GLNN_TRY(mlp_fwd_bwd_impl(d, feats, ldx, idx, m, kind, labels, target_logp, ldt, target_rows, lamb, drop_seeds, stream, folds ? &pf : nullptr));
-  return glnn::adam_step(adam->params, adam->grads, adam->exp_avg, adam->exp_avg_sq, adam->sizes, adam->num_tensors, adam->max_size,
-                         adam->lr, adam->beta1, adam->beta2, adam->eps, adam->weight_decay, adam->step, adam->grads_host,
-                         folds ? &pf : nullptr, stream);
+  return glnn::step_then_adam(adam, "glnn_mlp_train_step_f32", true, stream, [&](glnn::PendingFolds* pf) {
+    return mlp_fwd_bwd_impl(d, feats, ldx, idx, m, kind, labels, target_logp, ldt, target_rows, lamb, drop_seeds, stream, pf);
+  });
 }

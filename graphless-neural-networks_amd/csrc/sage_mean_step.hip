@@ -8,7 +8,7 @@
 //     2 round4(d_in) (second half at the float4-aligned column round4(d_in); padding columns written as zeros).  Sources: plain local rows,
 //     the global feature matrix through global ids + self_rows (outermost block), or pre-activations z of the hidden layer in front with
 //     its tail (BatchNorm affine / LayerNorm -> ReLU -> dropout, the counter-based mask keyed by the ACTIVATION's row and column) applied
-//     to every gathered row and to the self row -- xf_apply of csrc/spmm.hip, so the step is bit-identical to the materialised-h form.
+//     to every gathered row and to the self row -- tail_apply of source_tail_dev.h, so the step is bit-identical to the materialised-h form.
 //   sage_mean_bwd_kernel   backward aggregation over the PLAIN transposed block (glnn_csr_transpose, add_self = 0):
 //     dh[u] = sum_{v: u->v} inv(v) dcat[v, :d] + (u < n_dst ? dcat[u, off : off + d] : 0),  inv(v) from the forward block's indptr.
 //     Every source row is written -- a row no edge references gets exact zeros (+ its self term).
@@ -19,44 +19,12 @@
 // floats are cut into 256-column slabs (blockIdx.y).
 // The projections, weight gradients, loss, tails and Adam are the library's existing launches.
 #include "row_gather_dev.h"
-
-#define GLNN_TRY(expr)              \
-  do {                              \
-    const int rc_ = (expr);         \
-    if (rc_ != GLNN_OK) return rc_; \
-  } while (0)
+#include "source_tail_dev.h"
+#include "step_common.h"
 
 namespace {
 
 constexpr int kMaxTailD = 256;     // widest hidden layer whose tail the gather evaluates (the limit of glnn::spmm_csr_tail)
-
-// The hidden tail of the layer in front, per lane: its four columns' scale / shift (BatchNorm a_scale / a_shift, or LayerNorm gamma / beta)
-struct TailCols { float s[4], h[4]; uint32_t thr, seed; float dscale; int col; bool affine; const float* mean; const float* rstd; };
-// XF == 1: drop(relu(z * s + h)) (BatchNorm affine / none);  XF == 2: drop(relu(((z - mean_r) * rstd_r) * s + h)) (LayerNorm) -- the
-// arithmetic of glnn_act_fwd_f32 / glnn_layernorm_fwd_f32 per element, roundings pinned as csrc/spmm.hip's xf_apply pins them
-template <int XF>
-__device__ __forceinline__ float4 tail_apply(const TailCols& x, float4 v, uint32_t row) {
-  if (XF == 0) return v;
-  float o[4] = {v.x, v.y, v.z, v.w};
-  float mu = 0.f, rs = 1.f;
-  if (XF == 2) { mu = x.mean[row]; rs = x.rstd[row]; }
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    float y;
-    if (XF == 2) {
-      y = (o[t] - mu) * rs;
-      asm volatile("" : "+v"(y));
-      y = fmaf(y, x.s[t], x.h[t]);
-    } else {
-      y = x.affine ? fmaf(o[t], x.s[t], x.h[t]) : o[t];
-    }
-    y = fmaxf(y, 0.f);
-    if (x.thr) y = glnn::drop_keep(x.seed, x.thr, row, (uint32_t)(x.col + t)) ? y * x.dscale : 0.f;
-    asm volatile("" : "+v"(y));        // the ROUNDED tail value is what gets summed (the materialised form stored it)
-    o[t] = y;
-  }
-  return make_float4(o[0], o[1], o[2], o[3]);
-}
 
 struct CatArgs {
   const int64_t* indptr; const int32_t* indices; int64_t n_dst;
@@ -86,14 +54,7 @@ __global__ __launch_bounds__(kBlock) void sage_mean_cat_kernel(const CatArgs a) 
   CatLoad<XF> ld;
   ld.x = a.x; ld.ldx = a.ldx; ld.col4 = col4; ld.col_ok = col_ok;
   TailCols& tc = ld.tc;
-  tc.thr = a.t_thr; tc.seed = a.t_seed; tc.dscale = a.t_dscale; tc.col = col4; tc.affine = a.t_scale != nullptr;
-  tc.mean = a.t_mean; tc.rstd = a.t_rstd;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const bool ok = XF != 0 && tc.affine && col4 + t < a.d;
-    tc.s[t] = ok ? a.t_scale[col4 + t] : (XF == 2 ? 0.f : 1.f);
-    tc.h[t] = ok ? a.t_shift[col4 + t] : 0.f;
-  }
+  if (XF) tc = load_tail_cols(a.t_scale, a.t_shift, a.t_mean, a.t_rstd, a.t_thr, a.t_seed, a.t_dscale, a.d, col4, XF);
   if (threadIdx.x == 0) s_next = 0;
   __syncthreads();
   gather_tile<LPR>(a.indptr, a.indices, a.n_dst, (int64_t)blockIdx.x * kTileRows, lane, wave, &s_next, s_part, ld,
@@ -195,13 +156,7 @@ int check_desc(const glnn_sage_step_desc* d, const glnn_sage_mean_desc* m, const
   GLNN_REQUIRE(m->num_layers == L, "glnn_sage_mean_fwd_bwd_f32: the mean descriptor has %d layers, the step descriptor %d", m->num_layers, L);
   for (int l = 0; l <= L; ++l) GLNN_REQUIRE(d->dims[l] >= 1, "glnn_sage_mean_fwd_bwd_f32: dims[%d] must be positive", l);
   GLNN_REQUIRE(d->dropout_p >= 0.f && d->dropout_p < 1.f, "glnn_sage_mean_fwd_bwd_f32: dropout_p outside [0, 1)");
-  if (ln) {
-    GLNN_REQUIRE(!d->batchnorm && ln->eps > 0.f, "glnn_sage_mean_fwd_bwd_f32: LayerNorm tails need batchnorm == 0 and eps > 0");
-    for (int l = 0; l < L - 1; ++l) {
-      const glnn_sage_ln_layer& q = ln->layer[l];
-      GLNN_REQUIRE(q.gamma && q.beta && q.ggamma && q.gbeta && q.mean && q.rstd, "glnn_sage_mean_fwd_bwd_f32: LayerNorm of hidden layer %d: null pointer", l);
-    }
-  }
+  if (ln) GLNN_TRY(glnn::check_sage_ln_desc(d, ln, "glnn_sage_mean_fwd_bwd_f32"));
   GLNN_REQUIRE(d->ldx % 4 == 0 && d->ldx >= r4(d->dims[0]) && glnn::aligned16(d->x),
                "glnn_sage_mean_fwd_bwd_f32: x needs float4 rows (ldx a multiple of 4, >= %d; 16-byte aligned)", r4(d->dims[0]));
   GLNN_REQUIRE(d->ld_dlogits >= d->dims[L], "glnn_sage_mean_fwd_bwd_f32: ld_dlogits < dims[%d]", L);
@@ -302,19 +257,7 @@ int sage_mean_fwd_bwd_impl(const glnn_sage_step_desc* d, const glnn_sage_mean_de
     else
       GLNN_TRY(glnn_gemm_f32(q.cat, q.ld_cat, nullptr, nullptr, nullptr, 0.f, 0u, y.n_dst, k, q.wcat, q.ld_cat, 0, d_out, nullptr, nullptr, q.bsum, 0,
                              y.z, y.ldz, d->ws_gemm, d->ws_gemm_floats, stream));
-    if (l == L - 1) break;
-    if (ln) {
-      const glnn_sage_ln_layer& g = ln->layer[l];
-      GLNN_TRY(glnn_layernorm_fwd_f32(y.z, y.ldz, y.n_dst, d_out, g.gamma, g.beta, ln->eps, 1, p, y.drop_seed, y.h, y.ldh, g.mean, g.rstd, stream));
-      continue;
-    }
-    if (d->batchnorm)
-      GLNN_TRY(glnn::bn_stats(y.z, y.ldz, y.n_dst, d_out, y.gamma, y.beta, d->bn_eps, d->bn_momentum, y.running_mean, y.running_var, y.nbt,
-                              y.mean, y.rstd, y.a_scale, y.a_shift, d->ws_bn, d->ws_bn_floats, stream, nullptr, nullptr, nullptr, 0, nullptr,
-                              cs.done ? &cs : nullptr));
-    if (y.h)
-      GLNN_TRY(glnn_act_fwd_f32(y.z, y.ldz, y.n_dst, d_out, d->batchnorm ? y.a_scale : nullptr, d->batchnorm ? y.a_shift : nullptr, p,
-                                y.drop_seed, y.h, y.ldh, stream));
+    if (l < L - 1) GLNN_TRY(glnn::sage_hidden_tail_fwd(d, ln, l, cs, stream));
   }
   // ---- loss + dlogits (labels indexed by the batch's output nodes) -------------------------------------------------------------------------
   const glnn_sage_layer& top = d->layer[L - 1];
@@ -374,9 +317,6 @@ extern "C" int glnn_sage_mean_fwd_bwd_f32(const glnn_sage_step_desc* d, const gl
 // folded by launches of their own (nothing is left pending for Adam), so the two-call form gives the same bits trivially.
 extern "C" int glnn_sage_mean_train_step_f32(const glnn_sage_step_desc* d, const glnn_sage_mean_desc* m, const glnn_sage_ln_desc* ln,
                                              const glnn_adam_desc* adam, void* stream) {
-  GLNN_REQUIRE(adam && adam->params && adam->grads && adam->exp_avg && adam->exp_avg_sq && adam->sizes && adam->grads_host,
-               "glnn_sage_mean_train_step_f32: the Adam descriptor is incomplete");
-  GLNN_TRY(sage_mean_fwd_bwd_impl(d, m, ln, stream));
-  return glnn::adam_step(adam->params, adam->grads, adam->exp_avg, adam->exp_avg_sq, adam->sizes, adam->num_tensors, adam->max_size, adam->lr,
-                         adam->beta1, adam->beta2, adam->eps, adam->weight_decay, adam->step, adam->grads_host, nullptr, stream);
+  return glnn::step_then_adam(adam, "glnn_sage_mean_train_step_f32", false, stream,
+                              [&](glnn::PendingFolds*) { return sage_mean_fwd_bwd_impl(d, m, ln, stream); });
 }

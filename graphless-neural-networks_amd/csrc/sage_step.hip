@@ -4,13 +4,7 @@
 // (issued from Python they took ~0.7 ms of host time per step -- more than the 0.55 ms the GPU needs on the ogbn-arxiv config).
 // Every buffer is caller-owned (glnn_sage_step_desc); the optimiser step is NOT included: call glnn_adam_step_f32 next.
 #include <hip/hip_runtime.h>
-#include "glnn_common.h"
-
-#define GLNN_TRY(expr)              \
-  do {                              \
-    const int rc_ = (expr);         \
-    if (rc_ != GLNN_OK) return rc_; \
-  } while (0)
+#include "step_common.h"
 
 // pf != NULL (glnn_sage_train_step_f32, round 6): the fused Adam launch follows immediately and is the only consumer of the gradients, so the
 // last sums of gradient partials -- the split slabs of every weight gradient, the column-sum partials behind the last layer's bias gradient,
@@ -21,13 +15,7 @@ static int sage_fwd_bwd_impl(const glnn_sage_step_desc* d, void* stream, glnn::P
   GLNN_REQUIRE(d && d->x && d->labels && d->dlogits && d->loss_out, "glnn_sage_fwd_bwd_f32: null pointer");
   const int L = d->num_layers;
   GLNN_REQUIRE(L >= 1 && L <= GLNN_SAGE_MAX_LAYERS, "glnn_sage_fwd_bwd_f32: num_layers=%d outside [1,%d]", L, GLNN_SAGE_MAX_LAYERS);
-  if (ln) {
-    GLNN_REQUIRE(!d->batchnorm && ln->eps > 0.f, "glnn_sage_fwd_bwd_ln_f32: batchnorm must be 0 and eps > 0");
-    for (int l = 0; l < L - 1; ++l) {
-      const glnn_sage_ln_layer& q = ln->layer[l];
-      GLNN_REQUIRE(q.gamma && q.beta && q.ggamma && q.gbeta && q.mean && q.rstd, "glnn_sage_fwd_bwd_ln_f32: hidden layer %d: null pointer", l);
-    }
-  }
+  if (ln) GLNN_TRY(glnn::check_sage_ln_desc(d, ln, "glnn_sage_fwd_bwd_ln_f32"));
   const float p = d->dropout_p;
   for (int l = 0; l < L; ++l) {
     const glnn_sage_layer& y = d->layer[l];
@@ -76,19 +64,7 @@ static int sage_fwd_bwd_impl(const glnn_sage_step_desc* d, void* stream, glnn::P
     else
       GLNN_TRY(glnn_gemm_f32(y.agg, y.ld_agg, nullptr, nullptr, nullptr, 0.f, 0u, y.n_dst, d_in, y.w, d_in, 0, d_out, nullptr, nullptr, y.b, 0,
                              y.z, y.ldz, d->ws_gemm, d->ws_gemm_floats, stream));
-    if (l == L - 1) break;
-    if (ln) {          // the row statistics of z (h = tail(z) too when it is materialised)
-      const glnn_sage_ln_layer& q = ln->layer[l];
-      GLNN_TRY(glnn_layernorm_fwd_f32(y.z, y.ldz, y.n_dst, d_out, q.gamma, q.beta, ln->eps, 1, p, y.drop_seed, y.h, y.ldh, q.mean, q.rstd, stream));
-      continue;
-    }
-    if (d->batchnorm)
-      GLNN_TRY(glnn::bn_stats(y.z, y.ldz, y.n_dst, d_out, y.gamma, y.beta, d->bn_eps, d->bn_momentum, y.running_mean, y.running_var, y.nbt,
-                              y.mean, y.rstd, y.a_scale, y.a_shift, d->ws_bn, d->ws_bn_floats, stream, nullptr, nullptr, nullptr, 0, nullptr,
-                              cs.done ? &cs : nullptr));
-    if (y.h)          // h = tail(z) materialised (optional: with h == NULL the next layer's gather evaluates the tail itself)
-      GLNN_TRY(glnn_act_fwd_f32(y.z, y.ldz, y.n_dst, d_out, d->batchnorm ? y.a_scale : nullptr, d->batchnorm ? y.a_shift : nullptr, p,
-                                y.drop_seed, y.h, y.ldh, stream));
+    if (l < L - 1) GLNN_TRY(glnn::sage_hidden_tail_fwd(d, ln, l, cs, stream));
   }
   // ---- loss + dlogits (labels indexed by the batch's output nodes) ----------------------------------------------------
   const glnn_sage_layer& top = d->layer[L - 1];
@@ -210,14 +186,15 @@ extern "C" int glnn_sage_fwd_bwd_f32(const glnn_sage_step_desc* d, void* stream)
 // optimizer.step()) -- in ONE call (ABI 11): glnn_sage_fwd_bwd_f32 followed by glnn_adam_step_f32 on the same stream, for hosts that have
 // nothing to put between them (no gradient exchange), with the backward's last partial sums left to the Adam launch.  Same partials, same
 // fold order: the same parameters, moments and loss as the two calls, bit for bit.
+// (want_ln: the entry that takes a LayerNorm descriptor; ln == NULL otherwise)
+static int sage_train_step(const glnn_sage_step_desc* d, const glnn_sage_ln_desc* ln, bool want_ln, const glnn_adam_desc* adam, void* stream,
+                           const char* who) {
+  GLNN_REQUIRE(ln || !want_ln, "%s: null LayerNorm descriptor", who);
+  return glnn::step_then_adam(adam, who, true, stream, [&](glnn::PendingFolds* pf) { return sage_fwd_bwd_impl(d, stream, pf, ln); });
+}
+
 extern "C" int glnn_sage_train_step_f32(const glnn_sage_step_desc* d, const glnn_adam_desc* adam, void* stream) {
-  GLNN_REQUIRE(adam && adam->params && adam->grads && adam->exp_avg && adam->exp_avg_sq && adam->sizes && adam->grads_host,
-               "glnn_sage_train_step_f32: the Adam descriptor is incomplete");
-  glnn::PendingFolds pf = {};
-  const bool folds = glnn::opts().adam_folds && adam->num_tensors <= 32;
-  GLNN_TRY(sage_fwd_bwd_impl(d, stream, folds ? &pf : nullptr));
-  return glnn::adam_step(adam->params, adam->grads, adam->exp_avg, adam->exp_avg_sq, adam->sizes, adam->num_tensors, adam->max_size, adam->lr,
-                         adam->beta1, adam->beta2, adam->eps, adam->weight_decay, adam->step, adam->grads_host, folds ? &pf : nullptr, stream);
+  return sage_train_step(d, nullptr, false, adam, stream, "glnn_sage_train_step_f32");
 }
 
 // The LayerNorm form of the two calls above (norm_type "layer"): same launch sequence, LayerNorm tails (see include/glnn_hip.h)
@@ -227,12 +204,5 @@ extern "C" int glnn_sage_fwd_bwd_ln_f32(const glnn_sage_step_desc* d, const glnn
 }
 
 extern "C" int glnn_sage_train_step_ln_f32(const glnn_sage_step_desc* d, const glnn_sage_ln_desc* ln, const glnn_adam_desc* adam, void* stream) {
-  GLNN_REQUIRE(ln, "glnn_sage_train_step_ln_f32: null LayerNorm descriptor");
-  GLNN_REQUIRE(adam && adam->params && adam->grads && adam->exp_avg && adam->exp_avg_sq && adam->sizes && adam->grads_host,
-               "glnn_sage_train_step_ln_f32: the Adam descriptor is incomplete");
-  glnn::PendingFolds pf = {};
-  const bool folds = glnn::opts().adam_folds && adam->num_tensors <= 32;
-  GLNN_TRY(sage_fwd_bwd_impl(d, stream, folds ? &pf : nullptr, ln));
-  return glnn::adam_step(adam->params, adam->grads, adam->exp_avg, adam->exp_avg_sq, adam->sizes, adam->num_tensors, adam->max_size, adam->lr,
-                         adam->beta1, adam->beta2, adam->eps, adam->weight_decay, adam->step, adam->grads_host, folds ? &pf : nullptr, stream);
+  return sage_train_step(d, ln, true, adam, stream, "glnn_sage_train_step_ln_f32");
 }

@@ -18,6 +18,7 @@
 //   * epilogue fused: +self, /(deg+1) (SAGE "gcn") or *row_scale (GraphConv / feature_prop), then
 //     optional per-column scale/shift (+ReLU) for the project-first form.
 #include "glnn_common.h"
+#include "source_tail_dev.h"
 
 namespace {
 
@@ -142,44 +143,6 @@ struct SpmmArgs {
   ChunkMap cm;                  // n == 0: off (glnn_spmm_csr_chunks_f32: the chunks of a row range in ONE launch, a completion signal per chunk)
 };
 
-// per-lane constants of the source transform: the lane's four columns (XF == 2: gamma / beta, and the row-statistics arrays)
-struct XfCols { float s[4], h[4]; uint32_t thr, seed; float dscale; int col; bool affine; const float* mean; const float* rstd; };
-__device__ __forceinline__ XfCols load_xf_cols(const SpmmArgs& a, int col4) {
-  XfCols x;
-  x.thr = a.xf_thr; x.seed = a.xf_seed; x.dscale = a.xf_dscale; x.col = col4; x.affine = a.xf_scale != nullptr;
-  x.mean = a.xf_mean; x.rstd = a.xf_rstd;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const bool ok = x.affine && col4 + t < a.d;
-    x.s[t] = ok ? a.xf_scale[col4 + t] : (a.xf_on == 2 ? 0.f : 1.f);      // (LayerNorm: padding columns come out as 0)
-    x.h[t] = ok ? a.xf_shift[col4 + t] : 0.f;
-  }
-  return x;
-}
-// XF == 1: drop(relu(z * s + h)) (BatchNorm affine / none);  XF == 2: drop(relu(((z - mean_u) * rstd_u) * s + h)) (LayerNorm)
-template <int XF>
-__device__ __forceinline__ float4 xf_apply(const XfCols& x, float4 v, uint32_t row) {
-  float o[4] = {v.x, v.y, v.z, v.w};
-  float mu = 0.f, rs = 1.f;
-  if (XF == 2) { mu = x.mean[row]; rs = x.rstd[row]; }
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    float y;
-    if (XF == 2) {
-      y = (o[t] - mu) * rs;
-      asm volatile("" : "+v"(y));      // xhat rounded as glnn_layernorm_fwd_f32 rounds it, then ONE fma with gamma / beta
-      y = fmaf(y, x.s[t], x.h[t]);
-    } else {
-      y = x.affine ? fmaf(o[t], x.s[t], x.h[t]) : o[t];
-    }
-    y = fmaxf(y, 0.f);
-    if (x.thr) y = glnn::drop_keep(x.seed, x.thr, row, (uint32_t)(x.col + t)) ? y * x.dscale : 0.f;
-    asm volatile("" : "+v"(y));        // the ROUNDED tail value is what gets summed (act_fwd stored it): no fma of y * dscale into the row sum
-    o[t] = y;
-  }
-  return make_float4(o[0], o[1], o[2], o[3]);
-}
-
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 // stream-once data (column indices, the output rows) moved with the non-temporal hint so that it does not evict the
@@ -253,7 +216,7 @@ template <int LPR, int U, bool CS, int XF = 0>
 __device__ __forceinline__ float4 wave_gather_acc(const int32_t* __restrict__ indices, int64_t e0, int64_t e1,
                                                   int wave_id, int n_waves, const float* __restrict__ x,
                                                   int64_t ldx, int col4, bool col_ok,
-                                                  const float* __restrict__ col_scale, int lane, const XfCols& xf, float4 acc) {
+                                                  const float* __restrict__ col_scale, int lane, const TailCols& xf, float4 acc) {
   constexpr int G = 64 / LPR;
   const int g = lane / LPR;
   for (int64_t base = e0 + (int64_t)wave_id * 64; base < e1; base += (int64_t)n_waves * 64) {
@@ -284,7 +247,7 @@ __device__ __forceinline__ float4 wave_gather_acc(const int32_t* __restrict__ in
       if (XF) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
-          if (srcs[u] >= 0) v[u] = xf_apply<XF>(xf, v[u], (uint32_t)srcs[u]);      // (absent edges stay exact zeros)
+          if (srcs[u] >= 0) v[u] = tail_apply<XF>(xf, v[u], (uint32_t)srcs[u]);      // (absent edges stay exact zeros)
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) acc = CS ? fma4(s[u], v[u], acc) : add4(acc, v[u]);
@@ -296,7 +259,7 @@ template <int LPR, int U, bool CS, int XF = 0>
 __device__ __forceinline__ float4 wave_gather_sum(const int32_t* __restrict__ indices, int64_t e0, int64_t e1,
                                                   int wave_id, int n_waves, const float* __restrict__ x,
                                                   int64_t ldx, int col4, bool col_ok,
-                                                  const float* __restrict__ col_scale, int lane, const XfCols& xf) {
+                                                  const float* __restrict__ col_scale, int lane, const TailCols& xf) {
   return fold_groups<LPR>(wave_gather_acc<LPR, U, CS, XF>(indices, e0, e1, wave_id, n_waves, x, ldx, col4, col_ok, col_scale, lane, xf,
                                                            make_float4(0.f, 0.f, 0.f, 0.f)));
 }
@@ -343,12 +306,12 @@ __device__ __forceinline__ void finish_row_s(const SpmmArgs& a, int64_t v, int64
 }
 template <int MODE, int XF = 0>
 __device__ __forceinline__ void finish_row(const SpmmArgs& a, int64_t v, int64_t deg, float4 acc, int col4, const EpCols& ep,
-                                           const XfCols& xf, int64_t out_shift = 0, int64_t self_shift = 0) {
+                                           const TailCols& xf, int64_t out_shift = 0, int64_t self_shift = 0) {
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   if (MODE == GLNN_AGG_SAGE_GCN) {
     const int64_t sr = a.self_rows ? a.self_rows[v] : v + self_shift;
     s = ld4(a.x_self + sr * a.ld_self + col4);
-    if (XF) s = xf_apply<XF>(xf, s, (uint32_t)sr);
+    if (XF) s = tail_apply<XF>(xf, s, (uint32_t)sr);
   }
   finish_row_s<MODE>(a, v, deg, acc, s, col4, ep, out_shift);
 }
@@ -371,7 +334,7 @@ __device__ __forceinline__ int hub_find(const HubPlan& h, int64_t v) {
 template <int LPR, int U, bool CS, int XF>
 __device__ __forceinline__ float4 hub_wave_share(const HubPlan& h, const int32_t* __restrict__ indices, int64_t v, int64_t e0, int64_t e1,
                                                  const float* __restrict__ x, int64_t ldx, int col4, bool col_ok, const float* __restrict__ col_scale,
-                                                 int wave, int lane, const XfCols& xf) {
+                                                 int wave, int lane, const TailCols& xf) {
   float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
   const int hi = h.n_hub > 0 ? hub_find(h, v) : -1;
   if (hi >= 0) {
@@ -395,8 +358,8 @@ __global__ __launch_bounds__(kBlock) void hub_gather_kernel(const SpmmArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int col4 = (lane % LPR) * 4;
   const bool col_ok = col4 < a.d;
-  XfCols xf = {};
-  if (XF) xf = load_xf_cols(a, col_ok ? col4 : 0);
+  TailCols xf = {};
+  if (XF) xf = load_tail_cols(a.xf_scale, a.xf_shift, a.xf_mean, a.xf_rstd, a.xf_thr, a.xf_seed, a.xf_dscale, a.d, col_ok ? col4 : 0, a.xf_on);
   const int sg = (int)blockIdx.x;
   int lo = 0, hi = a.hub.n_hub - 1;                      // the hub row whose segment range holds sg: last h with seg_ptr[h] <= sg
   while (lo < hi) {
@@ -414,7 +377,7 @@ __global__ __launch_bounds__(kBlock) void hub_gather_kernel(const SpmmArgs a) {
 // ---- long-row role: scan a strided share of the rows, whole workgroup per long row (deterministic LDS fold) ----
 template <int LPR, int U, int MODE, bool CS, int XF = 0>
 __device__ __forceinline__ void long_rows_role(const SpmmArgs& a, int lane, int wave, int col4, bool col_ok, const EpCols& ep,
-                                               const XfCols& xf) {
+                                               const TailCols& xf) {
   __shared__ int64_t s_rows[kBlock];
   __shared__ int s_count;
   __shared__ float4 s_part[kWavesPerBlock][64];
@@ -459,7 +422,7 @@ __device__ __forceinline__ void long_rows_role(const SpmmArgs& a, int lane, int 
 // chunk: expected = row workgroups of the chunk + n_long_blocks).
 template <int LPR, int U, int MODE, bool CS, int XF>
 __device__ __forceinline__ void long_rows_role_chunks(const SpmmArgs& a, const ChunkMap& cm, int lane, int wave, int col4, bool col_ok,
-                                                      const EpCols& ep, const XfCols& xf) {
+                                                      const EpCols& ep, const TailCols& xf) {
   __shared__ int64_t s_rows[kBlock];
   __shared__ int s_count;
   __shared__ float4 s_part[kWavesPerBlock][64];
@@ -535,8 +498,8 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_kernel(const SpmmArgs a0) {
   const int col4 = c * 4;
   const bool col_ok = col4 < a.d;
   const EpCols ep = load_ep_cols(a, col_ok ? col4 : 0);
-  XfCols xf = {};                                     // (registers; dead code when !XF)
-  if (XF) xf = load_xf_cols(a, col_ok ? col4 : 0);
+  TailCols xf = {};                                     // (registers; dead code when !XF)
+  if (XF) xf = load_tail_cols(a.xf_scale, a.xf_shift, a.xf_mean, a.xf_rstd, a.xf_thr, a.xf_seed, a.xf_dscale, a.d, col_ok ? col4 : 0, a.xf_on);
 
   if ((int)blockIdx.x < a.n_long_blocks) {
     if constexpr (CM) long_rows_role_chunks<LPR, U, MODE, CS, XF>(a, a0.cm, lane, wave, col4, col_ok, ep, xf);
@@ -612,8 +575,8 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_short_kernel(const SpmmArgs a
   const int col4 = c * 4;
   const bool col_ok = col4 < a.d;
   const EpCols ep = load_ep_cols(a, col_ok ? col4 : 0);
-  XfCols xf = {};
-  if (XF) xf = load_xf_cols(a, col_ok ? col4 : 0);
+  TailCols xf = {};
+  if (XF) xf = load_tail_cols(a.xf_scale, a.xf_shift, a.xf_mean, a.xf_rstd, a.xf_thr, a.xf_seed, a.xf_dscale, a.d, col_ok ? col4 : 0, a.xf_on);
   if ((int)blockIdx.x < a.n_long_blocks) {
     long_rows_role<LPR, U, MODE, CS, XF>(a, lane, wave, col4, col_ok, ep, xf);
     return;
@@ -679,7 +642,7 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_short_kernel(const SpmmArgs a
         const int64_t sr = readlane64(my_self, r < nr ? r : 0);
         if (live[r] && col_ok) {
           selfv[r] = ld4(a.x_self + sr * a.ld_self + col4);
-          if (XF) selfv[r] = xf_apply<XF>(xf, selfv[r], (uint32_t)sr);
+          if (XF) selfv[r] = tail_apply<XF>(xf, selfv[r], (uint32_t)sr);
         }
       }
     }
@@ -689,7 +652,7 @@ __global__ __launch_bounds__(kBlock) void spmm_csr_short_kernel(const SpmmArgs a
 #pragma unroll
       for (int k = 0; k < UB; ++k) {
         if (XF) {
-          if (srcs[r][k] >= 0) v[r][k] = xf_apply<XF>(xf, v[r][k], (uint32_t)srcs[r][k]);
+          if (srcs[r][k] >= 0) v[r][k] = tail_apply<XF>(xf, v[r][k], (uint32_t)srcs[r][k]);
         }
         acc = CS ? fma4(sc[r][k], v[r][k], acc) : add4(acc, v[r][k]);
       }
@@ -755,7 +718,7 @@ __global__ __launch_bounds__(kBlock) void spmm_bn_dy_kernel(const SpmmArgs a, co
   const int col4 = (lane % LPR) * 4;
   const bool col_ok = col4 < a.d;                        // d % 4 == 0: a lane's four columns are all inside or all outside
   const DyCols c = load_dy_cols(t, col_ok ? col4 : 0);
-  const XfCols xf = {};
+  const TailCols xf = {};
   float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
   __shared__ float4 s_part[kWavesPerBlock][64], s_part2[kWavesPerBlock][64];
   if ((int)blockIdx.x < a.n_long_blocks) {
@@ -973,7 +936,7 @@ __global__ __launch_bounds__(kBlock) void spmm_ln_dz_kernel(const SpmmArgs a, co
     g[k] = ok ? t.gamma[col4 + k] : 0.f;
     b[k] = ok ? t.beta[col4 + k] : 0.f;
   }
-  const XfCols xf = {};
+  const TailCols xf = {};
   float pg[4] = {0.f, 0.f, 0.f, 0.f}, pb[4] = {0.f, 0.f, 0.f, 0.f}, pz[4] = {0.f, 0.f, 0.f, 0.f};
   __shared__ float4 s_part[kWavesPerBlock][64];
   if ((int)blockIdx.x < a.n_long_blocks) {
@@ -1184,7 +1147,7 @@ __global__ __launch_bounds__(kFusedBlock) void sage_fused_kernel(const FusedArgs
       const int64_t deg = e1 - e0;
       deferred = deg > kLongRow;
       if (!deferred) {
-        const float4 acc = wave_gather_sum<LPR, U, false>(a.indices, e0, e1, 0, 1, a.x, a.ldx, col4, col_ok, nullptr, lane, XfCols{});
+        const float4 acc = wave_gather_sum<LPR, U, false>(a.indices, e0, e1, 0, 1, a.x, a.ldx, col4, col_ok, nullptr, lane, TailCols{});
         if (lane < LPR && col_ok) {
           const float4 sf = ld4(a.x_self + (v + self_shift) * a.ld_self + col4);
           const float dp1 = (float)deg + 1.0f;
@@ -1210,8 +1173,8 @@ __global__ __launch_bounds__(kFusedBlock) void sage_fused_kernel(const FusedArgs
     const int64_t e0 = a.indptr[v], e1 = a.indptr[v + 1];
     if (e1 - e0 <= kLongRow) continue;
     const float4 acc = e1 - e0 > kHubRow
-        ? hub_wave_share<LPR, U, false, false>(a.hub, a.indices, v, e0, e1, a.x, a.ldx, col4, col_ok, nullptr, wave, lane, XfCols{})
-        : wave_gather_sum<LPR, U, false>(a.indices, e0, e1, wave, kFusedWaves, a.x, a.ldx, col4, col_ok, nullptr, lane, XfCols{});
+        ? hub_wave_share<LPR, U, false, false>(a.hub, a.indices, v, e0, e1, a.x, a.ldx, col4, col_ok, nullptr, wave, lane, TailCols{})
+        : wave_gather_sum<LPR, U, false>(a.indices, e0, e1, wave, kFusedWaves, a.x, a.ldx, col4, col_ok, nullptr, lane, TailCols{});
     // fold 8 wave partials through 4 LDS slots, fixed order: waves 4-7 park, waves 0-3 add theirs, wave 0 sums
     if (wave >= 4 && lane < LPR) s_part[wave - 4][lane] = acc;
     __syncthreads();

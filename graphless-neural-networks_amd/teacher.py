@@ -44,18 +44,36 @@ def _is_relu(act):
     return act is F.relu or getattr(act, "__name__", "") == "relu"
 
 
+def _check_criterion_and_optimizer(who, criterion, optimizer):
+    """What reference train_teacher.py:234-237 builds: nn.NLLLoss() and a plain single-group torch.optim.Adam."""
+    if not (isinstance(criterion, nn.NLLLoss) and criterion.reduction == "mean" and criterion.weight is None
+            and criterion.ignore_index == -100):
+        raise NotImplementedError(f"{who}: the criterion must be nn.NLLLoss() (reference train_teacher.py:237)")
+    grp = optimizer.param_groups
+    if type(optimizer) is not torch.optim.Adam or len(grp) != 1 or grp[0].get("amsgrad") or grp[0].get("maximize"):
+        raise NotImplementedError(f"{who}: torch.optim.Adam, one param group, no amsgrad/maximize (train_teacher.py:234-236)")
+
+
+def _check_norms_and_device(who, model):
+    """The norm modules with the reference's defaults, and the model on the GPU (the last check: everything else is accepted by then)."""
+    for bn in getattr(model.encoder, "norms", ()):
+        if isinstance(bn, nn.LayerNorm):
+            if not bn.elementwise_affine or len(bn.normalized_shape) != 1:
+                raise NotImplementedError(f"{who}: nn.LayerNorm(hidden_dim) with the reference's defaults")
+        elif bn.momentum is None or not bn.affine or not bn.track_running_stats:
+            raise NotImplementedError(f"{who}: BatchNorm1d with the reference's defaults")
+    if next(model.parameters()).device.type != "cuda":
+        raise RuntimeError(f"{who} needs the model on the GPU (HIP path only; the reference's --device -1 default selects the CPU: "
+                           "pass --device 0)")
+
+
 def check_supported(model, criterion, optimizer):
     """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GATv2, GPRGNN or GCNII teacher."""
     enc = model.encoder
     name = model.model_name
     if "MLP" in name or not ("SAGE" in name or "GCN" in name or "APPNP" in name or "GAT" in name or "GPRGNN" in name):
         raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GATv2, GPRGNN or GCNII teachers only (got {name})")
-    if not (isinstance(criterion, nn.NLLLoss) and criterion.reduction == "mean" and criterion.weight is None
-            and criterion.ignore_index == -100):
-        raise NotImplementedError("TeacherEngine: the criterion must be nn.NLLLoss() (reference train_teacher.py:237)")
-    grp = optimizer.param_groups
-    if type(optimizer) is not torch.optim.Adam or len(grp) != 1 or grp[0].get("amsgrad") or grp[0].get("maximize"):
-        raise NotImplementedError("TeacherEngine: torch.optim.Adam, one param group, no amsgrad/maximize (train_teacher.py:234-236)")
+    _check_criterion_and_optimizer("TeacherEngine", criterion, optimizer)
     if "GCNII" in name:          # (tested before "GCN", which it contains; the encoder's constructor refused everything else)
         if enc.norm_type != "none" or not _is_relu(enc.activation):
             raise NotImplementedError("TeacherEngine: GCNII with norm_type none and ReLU (docs/GCNII_SEMANTICS.md)")
@@ -83,15 +101,7 @@ def check_supported(model, criterion, optimizer):
         for lay in enc.layers[:-1]:
             if not _is_relu(lay._activation):
                 raise NotImplementedError("TeacherEngine: GraphConv(activation=F.relu) on hidden layers (models.py:170-187)")
-    for bn in getattr(enc, "norms", ()):
-        if isinstance(bn, nn.LayerNorm):
-            if not bn.elementwise_affine or len(bn.normalized_shape) != 1:
-                raise NotImplementedError("TeacherEngine: nn.LayerNorm(hidden_dim) with the reference's defaults")
-        elif bn.momentum is None or not bn.affine or not bn.track_running_stats:
-            raise NotImplementedError("TeacherEngine: BatchNorm1d with the reference's defaults")
-    if next(model.parameters()).device.type != "cuda":
-        raise RuntimeError("TeacherEngine needs the model on the GPU (HIP path only; the reference's --device -1 default "
-                           "selects the CPU: pass --device 0)")
+    _check_norms_and_device("TeacherEngine", model)
 
 
 def check_supported_mean(model, criterion, optimizer):
@@ -111,20 +121,8 @@ def check_supported_mean(model, criterion, optimizer):
         raise NotImplementedError("TeacherEngine.step_sage_mean: the hidden activation must be ReLU")
     if any(lay.fc_self.bias is None or lay.fc_neigh.bias is None for lay in enc.layers):
         raise NotImplementedError("TeacherEngine.step_sage_mean: SAGEConv(bias=True) layers only")
-    if not (isinstance(criterion, nn.NLLLoss) and criterion.reduction == "mean" and criterion.weight is None
-            and criterion.ignore_index == -100):
-        raise NotImplementedError("TeacherEngine.step_sage_mean: the criterion must be nn.NLLLoss()")
-    grp = optimizer.param_groups
-    if type(optimizer) is not torch.optim.Adam or len(grp) != 1 or grp[0].get("amsgrad") or grp[0].get("maximize"):
-        raise NotImplementedError("TeacherEngine.step_sage_mean: torch.optim.Adam, one param group, no amsgrad/maximize")
-    for bn in getattr(enc, "norms", ()):
-        if isinstance(bn, nn.LayerNorm):
-            if not bn.elementwise_affine or len(bn.normalized_shape) != 1:
-                raise NotImplementedError("TeacherEngine.step_sage_mean: nn.LayerNorm(hidden_dim) with the reference's defaults")
-        elif bn.momentum is None or not bn.affine or not bn.track_running_stats:
-            raise NotImplementedError("TeacherEngine.step_sage_mean: BatchNorm1d with the reference's defaults")
-    if next(model.parameters()).device.type != "cuda":
-        raise RuntimeError("TeacherEngine.step_sage_mean needs the model on the GPU (HIP path only; pass --device 0)")
+    _check_criterion_and_optimizer("TeacherEngine.step_sage_mean", criterion, optimizer)
+    _check_norms_and_device("TeacherEngine.step_sage_mean", model)
 
 
 class _Arena:
@@ -137,6 +135,112 @@ class _Arena:
         p = None if self.base is None else self.base + self.off
         self.off += (int(nbytes) + 255) // 256 * 256
         return p
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _r4(c):
+    return (c + 3) // 4 * 4
+
+
+class _GcnBlocks:
+    """What TeacherEngine._block_step does for the "gcn" aggregator only (csrc/sage_step.hip): agg_l is the projection's operand, the
+    backward reads the transposed block WITH the self entries and 1 / (deg + 1), and one dagg buffer serves every layer."""
+    name = "step_sage"
+
+    def static(self, eng):                              # no side descriptor
+        return None
+
+    def operands(self, A, y, md, l, n_dst, dims):
+        y.agg, y.ld_agg = A.take(4 * n_dst * _r4(dims[l])), _r4(dims[l])
+
+    def transpose(self, A, y, blk):
+        # transposed by the loader (NodeDataLoader.global_first_block) -- with the self entries, not the "mean" step's plain form
+        if getattr(blk, "t_indptr", None) is not None and getattr(blk, "t_add_self", True) is not False:
+            y.t_indptr, y.t_indices, y.inv_deg = _ptr(blk.t_indptr), _ptr(blk.t_indices), _ptr(blk.inv_deg)
+            y.tr_ws, y.tr_ws_bytes = None, 0
+        else:
+            n_dst, n_src = blk.num_dst_nodes(), blk.num_src_nodes()
+            nnz_t = blk.num_edges() + n_dst
+            wsb = int(_lib.lib().glnn_csr_transpose_workspace_bytes(n_src, nnz_t))
+            y.t_indptr, y.t_indices, y.inv_deg = A.take(8 * (n_src + 1)), A.take(4 * max(nnz_t, 1)), A.take(4 * n_dst)
+            y.tr_ws, y.tr_ws_bytes = A.take(wsb), (wsb + 7) // 8 * 8
+
+    def input_grad(self, A, d, md, blocks, dims, wd):
+        d.dagg, d.ld_dagg = A.take(4 * max(b.num_dst_nodes() for b in blocks[1:]) * wd), wd
+
+    def workspaces(self, eng, d, blocks, dims):
+        L, lib = eng.L, _lib.lib()
+        if L > 1 and eng.bn:     # room for the outermost layer's BatchNorm backward without passes of its own (round 5)
+            d.ws_bn_floats = max(d.ws_bn_floats, int(lib.glnn_sage_step_ws_bn_floats(blocks[0].num_dst_nodes(), dims[1])))
+        if eng.ln:               # the LayerNorm backward's column partials (fused into the transposed aggregation, or its own launch)
+            for l in range(L - 1):
+                d.ws_bn_floats = max(d.ws_bn_floats, int(lib.glnn_sage_step_ws_ln_floats(blocks[l].num_dst_nodes(), dims[l + 1])))
+        # (x L: in the one-call step every layer's split slabs wait in ws_tn for the Adam launch to fold them -- csrc/sage_step.hip)
+        d.ws_tn_floats = L * (64 * max(dims) + 256 * 128 * 128 + 2 * max(dims) * max(dims))
+
+    def call(self, d, md, lnd, ad, stream):
+        entry = ("glnn_sage_train_step" if ad is not None else "glnn_sage_fwd_bwd") + ("_ln_f32" if lnd is not None else "_f32")
+        args = [ctypes.byref(a) for a in (d, lnd, ad) if a is not None]
+        return getattr(_lib.lib(), entry)(*args, stream), entry
+
+
+class _MeanBlocks:
+    """... and for the "mean" aggregator (csrc/sage_mean_step.hip): the [mean | self] operand pair against the packed [W_neigh | W_self]
+    (re-packed in the call), the PLAIN transposed block, and one dcat buffer, layer by layer."""
+    name = "step_sage_mean"
+
+    def static(self, eng):                              # the fc_self half of every layer
+        md = _lib.SageMeanDesc()
+        md.num_layers = eng.L
+        for l, layer in enumerate(eng.enc.layers):
+            q, w, b = md.layer[l], layer.fc_self.weight, layer.fc_self.bias
+            q.w_self, q.b_self, q.gw_self, q.gb_self = _ptr(w), _ptr(b), _ptr(eng.grad(w)), _ptr(eng.grad(b))
+        return md
+
+    def operands(self, A, y, md, l, n_dst, dims):
+        q = md.layer[l]
+        q.ld_cat = 2 * _r4(dims[l])
+        q.cat = A.take(4 * n_dst * q.ld_cat)
+        q.wcat, q.bsum = A.take(4 * dims[l + 1] * q.ld_cat), A.take(4 * dims[l + 1])
+
+    def transpose(self, A, y, blk):
+        # the PLAIN transpose: the loader's when it built that one (t_add_self False), else built inside the C call -- never one that
+        # carries the "gcn" step's self entries
+        if getattr(blk, "t_indptr", None) is not None and getattr(blk, "t_add_self", None) is False:
+            y.t_indptr, y.t_indices = _ptr(blk.t_indptr), _ptr(blk.t_indices)
+            y.tr_ws, y.tr_ws_bytes = None, 0
+        else:
+            n_src, nnz = blk.num_src_nodes(), blk.num_edges()
+            wsb = int(_lib.lib().glnn_csr_transpose_workspace_bytes(n_src, nnz))
+            y.t_indptr, y.t_indices = A.take(8 * (n_src + 1)), A.take(4 * max(nnz, 1))
+            y.tr_ws, y.tr_ws_bytes = A.take(wsb + 8), (wsb + 7) // 8 * 8
+
+    def input_grad(self, A, d, md, blocks, dims, wd):
+        dcat = A.take(4 * max(blocks[l].num_dst_nodes() * 2 * _r4(dims[l]) for l in range(1, len(blocks))))
+        for l in range(1, len(blocks)):
+            md.layer[l].dcat, md.layer[l].ld_dcat = dcat, 2 * _r4(dims[l])
+
+    def workspaces(self, eng, d, blocks, dims):
+        lib = _lib.lib()
+        if eng.ln:
+            for l in range(eng.L - 1):
+                n_l = blocks[l].num_dst_nodes()
+                d.ws_bn_floats = max(d.ws_bn_floats, int(lib.glnn_sage_step_ws_ln_floats(n_l, dims[l + 1])),
+                                     int(lib.glnn_layernorm_bwd_workspace_floats(n_l, dims[l + 1])))
+        d.ws_tn_floats = 64 * max(dims) + 256 * 128 * 128 + 2 * max(dims) * max(dims)
+
+    def call(self, d, md, lnd, ad, stream):
+        lnp = ctypes.byref(lnd) if lnd is not None else None
+        if ad is not None:
+            return (_lib.lib().glnn_sage_mean_train_step_f32(ctypes.byref(d), ctypes.byref(md), lnp, ctypes.byref(ad), stream),
+                    "glnn_sage_mean_train_step_f32")
+        return _lib.lib().glnn_sage_mean_fwd_bwd_f32(ctypes.byref(d), ctypes.byref(md), lnp, stream), "glnn_sage_mean_fwd_bwd_f32"
+
+
+_GCN_BLOCKS, _MEAN_BLOCKS = _GcnBlocks(), _MeanBlocks()
 
 
 class TeacherEngine:
@@ -235,7 +339,7 @@ class TeacherEngine:
         """Everything the persistent glnn_sage_step_desc captured once: the data pointers of every parameter, gradient buffer and BatchNorm
         buffer, and the scalars baked into it.  A step whose signature differs rebuilds the descriptor (only the weight / bias
         pointers used to be compared, so a replaced norm module or a changed dropout left the C call on stale or freed pointers)."""
-        ptr = lambda t: None if t is None else t.data_ptr()
+        ptr = _ptr
         sig = [float(enc.dropout.p), len(enc.layers)]
         for l, layer in enumerate(enc.layers):
             w, b = layer.fc_neigh.weight, layer.fc_neigh.bias
@@ -256,71 +360,85 @@ class TeacherEngine:
         """One optimisation step on a batch of sampled blocks (blocks[0] outermost).  `feats` is the GLOBAL feature matrix:
         when blocks[0] carries global source ids (glnn_amd.graph.NodeDataLoader) its aggregation gathers from it directly,
         otherwise feats[input_nodes] is gathered once (blocks that came from elsewhere).  The whole forward + loss + backward
-        is ONE C call (glnn_sage_fwd_bwd_f32, csrc/sage_step.hip) over buffers allocated here; Adam follows."""
-        enc, L = self.enc, self.L
+        is ONE C call (glnn_sage_fwd_bwd_f32, csrc/sage_step.hip) over buffers allocated here; Adam follows -- inside the same call
+        (glnn_sage_train_step_f32) when nothing sits between the backward and Adam."""
         if self.mean:      # (this step has no fc_self term: it would silently train another model)
             raise NotImplementedError("TeacherEngine.step_sage implements the 'gcn' aggregator; a SAGE 'mean' teacher steps through "
                                       "TeacherEngine.step_sage_mean")
+        self._block_step(_GCN_BLOCKS, blocks, feats, labels, output_nodes, lamb, input_nodes)
+
+    def step_sage_mean(self, blocks, feats, labels, output_nodes, lamb=1.0, input_nodes=None):
+        """step_sage for a SAGE "mean" teacher (docs/SAGE_MEAN_SEMANTICS.md): the same contract -- in place on the parameters, the BatchNorm
+        buffers and the optimiser's moments; `feats` global, gathered through blocks[0]'s global ids when it carries them -- as ONE C call,
+        glnn_sage_mean_train_step_f32 (csrc/sage_mean_step.hip): per layer the [mean | self] operand pair and one projection against the
+        packed [W_neigh | W_self]; backward over the PLAIN transposed blocks.  grad_sync set (or GLNN_TEACHER_ONE_CALL=0):
+        glnn_sage_mean_fwd_bwd_f32, then Adam."""
+        if not self.mean:
+            raise NotImplementedError("TeacherEngine.step_sage_mean: SAGE 'mean' teachers only; a 'gcn' teacher steps through step_sage")
+        self._block_step(_MEAN_BLOCKS, blocks, feats, labels, output_nodes, lamb, input_nodes)
+
+    def _block_descriptors(self, v):
+        """Everything of a sampled-block step that does not depend on the batch, written ONCE: sizes, parameter / gradient / BatchNorm
+        pointers, the LayerNorm side descriptor, and what variant `v` adds.  (Building the ~150 ctypes fields from nothing was 0.1 ms of the
+        0.25 ms of host time per step of a loop that is host-bound.)  _sage_signature() is what they captured."""
+        enc, L, ptr = self.enc, self.L, _ptr
+        d = _lib.SageStepDesc()
+        self._sage_dims = [enc.layers[0].fc_neigh.weight.shape[1]] + [lay.fc_neigh.weight.shape[0] for lay in enc.layers]
+        self.p = float(enc.dropout.p)
+        d.num_layers, d.batchnorm, d.dropout_p = L, 1 if self.bn else 0, self.p
+        for i, n in enumerate(self._sage_dims):
+            d.dims[i] = n
+        for l, layer in enumerate(enc.layers):
+            y = d.layer[l]
+            w, b = layer.fc_neigh.weight, layer.fc_neigh.bias
+            y.w, y.b, y.gw, y.gb = ptr(w), ptr(b), ptr(self.grad(w)), ptr(self.grad(b))
+            if l != L - 1 and self.bn:
+                bn = enc.norms[l]
+                d.bn_eps, d.bn_momentum = bn.eps, bn.momentum
+                y.gamma, y.beta, y.ggamma, y.gbeta = ptr(bn.weight), ptr(bn.bias), ptr(self.grad(bn.weight)), ptr(self.grad(bn.bias))
+                y.running_mean, y.running_var, y.nbt = ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked)
+        lnd = None
+        if self.ln and L > 1:          # nn.LayerNorm tails: parameters and gradients in the side descriptor (the row statistics are scratch);
+            lnd = _lib.SageLnDesc()    # a one-layer encoder has no hidden tail and no norm module
+            lnd.eps = enc.norms[0].eps
+            for l in range(L - 1):
+                ln, q = enc.norms[l], lnd.layer[l]
+                if ctypes.c_float(ln.eps).value != lnd.eps:
+                    raise NotImplementedError("TeacherEngine: the hidden LayerNorms of a SAGE teacher must share one eps")
+                q.gamma, q.beta, q.ggamma, q.gbeta = ptr(ln.weight), ptr(ln.bias), ptr(self.grad(ln.weight)), ptr(self.grad(ln.bias))
+        self._sage_desc, self._sage_mean, self._sage_ln = d, v.static(self), lnd
+        self._sage_static = self._sage_signature(enc)
+
+    def _block_step(self, v, blocks, feats, labels, output_nodes, lamb, input_nodes):
+        """The sampled-block step behind step_sage / step_sage_mean; `v` (_GcnBlocks / _MeanBlocks) holds what the two aggregators do
+        differently: operand buffers, the transpose the backward reads, two workspace sizes and the C entry."""
+        enc, L, who, ptr, r4 = self.enc, self.L, "TeacherEngine." + v.name, _ptr, _r4
         ops._need_cuda(feats, labels, output_nodes, input_nodes)
         if len(blocks) != L:
-            raise ValueError(f"TeacherEngine.step_sage: {len(blocks)} blocks for {L} layers")
+            raise ValueError(f"{who}: {len(blocks)} blocks for {L} layers")
         if L > _lib.SAGE_MAX_LAYERS:
             raise NotImplementedError(f"TeacherEngine: at most {_lib.SAGE_MAX_LAYERS} layers")
         if labels.dtype != torch.int64 or output_nodes.dtype != torch.int64 or not output_nodes.is_contiguous():
-            raise ValueError("TeacherEngine.step_sage: labels / output_nodes must be int64 (output_nodes contiguous)")
+            raise ValueError(f"{who}: labels / output_nodes must be int64 (output_nodes contiguous)")
         x = ops.as_feat(feats)
         dev = self.dev
         if blocks[0].gindices is None:
             if input_nodes is None:
-                raise ValueError("TeacherEngine.step_sage: blocks without global ids need input_nodes")
+                raise ValueError(f"{who}: blocks without global ids need input_nodes")
             x = ops.gather_rows(x, input_nodes)
         for l in range(1, L):
             if blocks[l].num_src_nodes() != blocks[l - 1].num_dst_nodes():
-                raise ValueError(f"TeacherEngine.step_sage: block {l} has {blocks[l].num_src_nodes()} sources, block {l - 1} "
+                raise ValueError(f"{who}: block {l} has {blocks[l].num_src_nodes()} sources, block {l - 1} "
                                  f"{blocks[l - 1].num_dst_nodes()} destinations")
         if x.shape[0] < (blocks[0].num_src_nodes() if blocks[0].gindices is None else 1):
-            raise ValueError("TeacherEngine.step_sage: the layer-0 source matrix is smaller than the outermost block")
+            raise ValueError(f"{who}: the layer-0 source matrix is smaller than the outermost block")
+        # The descriptors live across steps; a step only fills in the blocks, the dropout seeds and the scratch pointers.  They are rebuilt
+        # when something they captured was replaced (load_state_dict keeps the tensors; .to(), a new norm module, a changed dropout / eps /
+        # momentum do not).
+        if self._sage_desc is None or self._sage_static != self._sage_signature(enc):
+            self._block_descriptors(v)
+        d, md, lnd, dims = self._sage_desc, self._sage_mean, self._sage_ln, self._sage_dims
         self.step_count += 1
-        # The descriptor lives across steps: everything that does not depend on the batch (parameter / gradient / BatchNorm pointers, sizes,
-        # loss buffers) is written once; a step only fills in the blocks, the dropout seeds and the scratch pointers.  (Building the
-        # ~150 ctypes fields from nothing was 0.1 ms of the 0.25 ms of host time per step of a loop that is host-bound.)
-        r4 = lambda c: (c + 3) // 4 * 4
-        ptr = lambda t: None if t is None else t.data_ptr()
-        d = self._sage_desc
-        if d is None:
-            d = self._sage_desc = _lib.SageStepDesc()
-            self._sage_dims = [enc.layers[0].fc_neigh.weight.shape[1]] + [lay.fc_neigh.weight.shape[0] for lay in enc.layers]
-            self.p = float(enc.dropout.p)
-            d.num_layers, d.batchnorm, d.dropout_p = L, 1 if self.bn else 0, self.p
-            for i, v in enumerate(self._sage_dims):
-                d.dims[i] = v
-            for l, layer in enumerate(enc.layers):
-                y = d.layer[l]
-                w, b = layer.fc_neigh.weight, layer.fc_neigh.bias
-                y.w, y.b, y.gw, y.gb = ptr(w), ptr(b), ptr(self.grad(w)), ptr(self.grad(b))
-                if l != L - 1 and self.bn:
-                    bn = enc.norms[l]
-                    d.bn_eps, d.bn_momentum = bn.eps, bn.momentum
-                    y.gamma, y.beta, y.ggamma, y.gbeta = ptr(bn.weight), ptr(bn.bias), ptr(self.grad(bn.weight)), ptr(self.grad(bn.bias))
-                    y.running_mean, y.running_var, y.nbt = ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked)
-            self._sage_ln = None
-            if self.ln:          # nn.LayerNorm tails: parameters and gradients in the side descriptor (the row statistics are scratch)
-                lnd = self._sage_ln = _lib.SageLnDesc()
-                lnd.eps = enc.norms[0].eps
-                for l in range(L - 1):
-                    ln, q = enc.norms[l], lnd.layer[l]
-                    if ctypes.c_float(ln.eps).value != lnd.eps:
-                        raise NotImplementedError("TeacherEngine: the hidden LayerNorms of a SAGE teacher must share one eps")
-                    q.gamma, q.beta, q.ggamma, q.gbeta = ptr(ln.weight), ptr(ln.bias), ptr(self.grad(ln.weight)), ptr(self.grad(ln.bias))
-            d.ws_loss, d.ws_loss_floats = ptr(self.ws_loss), self.ws_loss.numel()
-            d.loss_out, d.loss_accum = ptr(self.loss_out), ptr(self.loss_accum)
-            self._sage_static = self._sage_signature(enc)
-        elif self._sage_static != self._sage_signature(enc):
-            self._sage_desc = None                          # something the descriptor captured was replaced (load_state_dict keeps the
-                                                            # tensors; .to(), a new norm module, a changed dropout / eps / momentum do not)
-            self.step_count -= 1
-            return self.step_sage(blocks, feats, labels, output_nodes, lamb, input_nodes)
-        dims = self._sage_dims
         d.lamb = float(lamb)
         # Every buffer of the step is scratch that only the C call touches, so they are carved as raw pointers out of ONE arena that
         # persists across steps (same-stream reuse is ordered; it grows when a batch needs more).  ONE pass hands out the pointers.
@@ -329,44 +447,30 @@ class TeacherEngine:
             max_rows, max_hidden = 1, 4
             for l, blk in enumerate(blocks):
                 y = d.layer[l]
-                n_dst, n_src, nnz = blk.num_dst_nodes(), blk.num_src_nodes(), blk.num_edges()
-                y.agg, y.ld_agg = A.take(4 * n_dst * r4(dims[l])), r4(dims[l])
+                n_dst = blk.num_dst_nodes()
+                v.operands(A, y, md, l, n_dst, dims)
                 y.z, y.ldz = A.take(4 * n_dst * r4(dims[l + 1])), r4(dims[l + 1])
                 if l != L - 1:
-                    if self.gather_tail and dims[l + 1] <= 256:      # (the tail-in-gather kernel holds a row in registers: d <= 256)
+                    if self.gather_tail and dims[l + 1] <= 256:      # (the tail-in-gather kernels hold a row in registers: d <= 256)
                         y.h, y.ldh = None, 0
                     else:
                         y.h, y.ldh = A.take(4 * n_dst * r4(dims[l + 1])), r4(dims[l + 1])
                     max_rows, max_hidden = max(max_rows, n_dst), max(max_hidden, dims[l + 1])
                     if self.bn:
                         y.mean, y.rstd, y.a_scale, y.a_shift = (A.take(4 * dims[l + 1]) for _ in range(4))
-                    if self.ln:          # per-ROW statistics of z_l (written by the forward, read by the backward)
-                        q = self._sage_ln.layer[l]
+                    if lnd is not None:          # per-ROW statistics of z_l (written by the forward, read by the backward)
+                        q = lnd.layer[l]
                         q.mean, q.rstd = A.take(4 * n_dst), A.take(4 * n_dst)
-                # transposed by the loader (NodeDataLoader.global_first_block) -- with the self entries, not the "mean" step's plain form
-                if l >= 1 and getattr(blk, "t_indptr", None) is not None and getattr(blk, "t_add_self", True) is not False:
-                    y.t_indptr, y.t_indices, y.inv_deg = ptr(blk.t_indptr), ptr(blk.t_indices), ptr(blk.inv_deg)
-                    y.tr_ws, y.tr_ws_bytes = None, 0
-                elif l >= 1:
-                    nnz_t = nnz + n_dst
-                    wsb = int(_lib.lib().glnn_csr_transpose_workspace_bytes(n_src, nnz_t))
-                    y.t_indptr, y.t_indices, y.inv_deg = A.take(8 * (n_src + 1)), A.take(4 * max(nnz_t, 1)), A.take(4 * n_dst)
-                    y.tr_ws, y.tr_ws_bytes = A.take(wsb), (wsb + 7) // 8 * 8
-            n_out = blocks[-1].num_dst_nodes()
-            d.dlogits, d.ld_dlogits = A.take(4 * n_out * r4(dims[-1])), r4(dims[-1])
-            if L > 1:
-                wd = r4(max(dims[1:L]))
-                d.dagg, d.ld_dagg = A.take(4 * max(b.num_dst_nodes() for b in blocks[1:]) * wd), wd
-                d.dh, d.ld_dh = A.take(4 * max(b.num_src_nodes() for b in blocks[1:]) * wd), wd
+                if l >= 1:
+                    v.transpose(A, y, blk)
+            d.dlogits, d.ld_dlogits = A.take(4 * blocks[-1].num_dst_nodes() * r4(dims[-1])), r4(dims[-1])
             nchunks = (max_rows + 127) // 128
             d.ws_bn_floats = (3 * nchunks + 2 + 3 * ((nchunks + 63) // 64)) * max_hidden + 1024
-            if L > 1 and self.bn:     # room for the outermost layer's BatchNorm backward without passes of its own (round 5)
-                d.ws_bn_floats = max(d.ws_bn_floats, int(_lib.lib().glnn_sage_step_ws_bn_floats(blocks[0].num_dst_nodes(), dims[1])))
-            if self.ln:          # the LayerNorm backward's column partials (fused into the transposed aggregation, or its own launch)
-                for l in range(L - 1):
-                    d.ws_bn_floats = max(d.ws_bn_floats, int(_lib.lib().glnn_sage_step_ws_ln_floats(blocks[l].num_dst_nodes(), dims[l + 1])))
-            # (x L: in the one-call step every layer's split slabs wait in ws_tn for the Adam launch to fold them -- csrc/sage_step.hip)
-            d.ws_tn_floats = L * (64 * max(dims) + 256 * 128 * 128 + 2 * max(dims) * max(dims))
+            if L > 1:
+                wd = r4(max(dims[1:L]))
+                v.input_grad(A, d, md, blocks, dims, wd)
+                d.dh, d.ld_dh = A.take(4 * max(b.num_src_nodes() for b in blocks[1:]) * wd), wd
+            v.workspaces(self, d, blocks, dims)
             # split-K slabs, sized as StudentEngine does; the GEMM only splits outputs of < 256 tiles, i.e. <= 512 slabs of 128 x 128
             d.ws_gemm_floats = min(max(16 * max(b.num_dst_nodes() for b in blocks) * min(dims[1:]), 1 << 20), 512 * 128 * 128)
             d.ws_bn, d.ws_tn, d.ws_gemm = A.take(4 * d.ws_bn_floats), A.take(4 * d.ws_tn_floats), A.take(4 * d.ws_gemm_floats)
@@ -390,209 +494,48 @@ class TeacherEngine:
         if arena is None or total + 256 > arena.numel():    # first step / a bigger batch: (re)allocate with headroom, lay out again
             arena = self._arena = torch.empty(int(total * 1.25) + 256, dtype=torch.uint8, device=dev)
             layout(_Arena((arena.data_ptr() + 255) // 256 * 256))
-        d.x, d.ldx, d.x_rows = ptr(x), x.stride(0), x.shape[0]
+        d.x, d.ldx, d.x_rows = ptr(x), x.stride(0), x.shape[0]      # (x stays alive until the call below is queued: same-stream reuse is ordered)
         d.labels, d.label_rows = ptr(labels), ptr(output_nodes)
         d.ws_loss, d.ws_loss_floats = ptr(self.ws_loss), self.ws_loss.numel()
         d.loss_out, d.loss_accum = ptr(self.loss_out), ptr(self.loss_accum)
-        keep = [x]                                              # alive until the call below is queued (same-stream reuse is ordered)
         ops.note_param_write()      # (running statistics are written through raw pointers; Adam follows)
-        # nothing sits between the backward and Adam (no gradient exchange): the whole step is ONE C call and Adam folds the backward's
-        # last partial sums itself (glnn_sage_train_step_f32, round 6; GLNN_TEACHER_ONE_CALL=0 keeps the two calls)
-        one_call = self.grad_sync is None and self._one_call
-        if one_call:
+        # nothing sits between the backward and Adam (no gradient exchange): the whole step is ONE C call (and in the "gcn" step Adam folds
+        # the backward's last partial sums itself); GLNN_TEACHER_ONE_CALL=0 keeps the two calls
+        ad = None
+        if self.grad_sync is None and self._one_call:
             g_ = self.opt.param_groups[0]
             ad = self.table.desc
             ad.lr, ad.beta1, ad.beta2, ad.eps, ad.weight_decay, ad.step = g_["lr"], g_["betas"][0], g_["betas"][1], g_["eps"], g_["weight_decay"], self.step_count
-            if self.ln:
-                rc = _lib.lib().glnn_sage_train_step_ln_f32(ctypes.byref(d), ctypes.byref(self._sage_ln), ctypes.byref(ad), ops._stream())
-            else:
-                rc = _lib.lib().glnn_sage_train_step_f32(ctypes.byref(d), ctypes.byref(ad), ops._stream())
-        elif self.ln:
-            rc = _lib.lib().glnn_sage_fwd_bwd_ln_f32(ctypes.byref(d), ctypes.byref(self._sage_ln), ops._stream())
-        else:
-            rc = _lib.lib().glnn_sage_fwd_bwd_f32(ctypes.byref(d), ops._stream())
+        rc, entry = v.call(d, md, lnd, ad, ops._stream())
         if rc != 0:
             self.step_count -= 1          # the step never happened: Adam's bias correction and the dropout seeds stay where they were
-        _lib.check(rc, ("glnn_sage_train_step" if one_call else "glnn_sage_fwd_bwd") + ("_ln_f32" if self.ln else "_f32"))
-        if not one_call:
+        _lib.check(rc, entry)
+        if ad is None:
             self._adam()
 
-    def step_sage_mean(self, blocks, feats, labels, output_nodes, lamb=1.0, input_nodes=None):
-        """step_sage for a SAGE "mean" teacher (docs/SAGE_MEAN_SEMANTICS.md): the same contract -- in place on the parameters, the BatchNorm
-        buffers and the optimiser's moments; `feats` global, gathered through blocks[0]'s global ids when it carries them -- as ONE C call,
-        glnn_sage_mean_train_step_f32 (csrc/sage_mean_step.hip): per layer the [mean | self] operand pair and one projection against the
-        packed [W_neigh | W_self]; backward over the PLAIN transposed blocks.  grad_sync set (or GLNN_TEACHER_ONE_CALL=0):
-        glnn_sage_mean_fwd_bwd_f32, then Adam."""
-        enc, L = self.enc, self.L
-        if not self.mean:
-            raise NotImplementedError("TeacherEngine.step_sage_mean: SAGE 'mean' teachers only; a 'gcn' teacher steps through step_sage")
-        ops._need_cuda(feats, labels, output_nodes, input_nodes)
-        if len(blocks) != L:
-            raise ValueError(f"TeacherEngine.step_sage_mean: {len(blocks)} blocks for {L} layers")
-        if L > _lib.SAGE_MAX_LAYERS:
-            raise NotImplementedError(f"TeacherEngine: at most {_lib.SAGE_MAX_LAYERS} layers")
-        if labels.dtype != torch.int64 or output_nodes.dtype != torch.int64 or not output_nodes.is_contiguous():
-            raise ValueError("TeacherEngine.step_sage_mean: labels / output_nodes must be int64 (output_nodes contiguous)")
-        x = ops.as_feat(feats)
-        dev = self.dev
-        if blocks[0].gindices is None:
-            if input_nodes is None:
-                raise ValueError("TeacherEngine.step_sage_mean: blocks without global ids need input_nodes")
-            x = ops.gather_rows(x, input_nodes)
-        for l in range(1, L):
-            if blocks[l].num_src_nodes() != blocks[l - 1].num_dst_nodes():
-                raise ValueError(f"TeacherEngine.step_sage_mean: block {l} has {blocks[l].num_src_nodes()} sources, block {l - 1} "
-                                 f"{blocks[l - 1].num_dst_nodes()} destinations")
-        if x.shape[0] < (blocks[0].num_src_nodes() if blocks[0].gindices is None else 1):
-            raise ValueError("TeacherEngine.step_sage_mean: the layer-0 source matrix is smaller than the outermost block")
+    # ------------------------------------------------------------------------------------------ full-graph steps
+    def _run_full_graph(self, body, g, feats, labels, idx_train, lamb):
+        """One full-graph optimisation step: body(g, feats, labels, idx_train, lamb) is forward + loss + backward into the gradient
+        buffers, Adam follows.  A body that raises leaves step_count -- Adam's bias correction and the dropout seeds -- where it was: the
+        step never happened (see _block_step)."""
+        ops._need_cuda(feats, labels, idx_train, g.indptr)
         self.step_count += 1
-        r4 = lambda c: (c + 3) // 4 * 4
-        ptr = lambda t: None if t is None else t.data_ptr()
-        d, md = self._sage_desc, self._sage_mean
-        if d is None:       # everything that does not depend on the batch, written once (see step_sage)
-            d, md = _lib.SageStepDesc(), _lib.SageMeanDesc()
-            self._sage_desc, self._sage_mean = d, md
-            self._sage_dims = [enc.layers[0].fc_neigh.weight.shape[1]] + [lay.fc_neigh.weight.shape[0] for lay in enc.layers]
-            self.p = float(enc.dropout.p)
-            d.num_layers, d.batchnorm, d.dropout_p = L, 1 if self.bn else 0, self.p
-            md.num_layers = L
-            for i, v in enumerate(self._sage_dims):
-                d.dims[i] = v
-            for l, layer in enumerate(enc.layers):
-                y, q = d.layer[l], md.layer[l]
-                w, b = layer.fc_neigh.weight, layer.fc_neigh.bias
-                y.w, y.b, y.gw, y.gb = ptr(w), ptr(b), ptr(self.grad(w)), ptr(self.grad(b))
-                w, b = layer.fc_self.weight, layer.fc_self.bias
-                q.w_self, q.b_self, q.gw_self, q.gb_self = ptr(w), ptr(b), ptr(self.grad(w)), ptr(self.grad(b))
-                if l != L - 1 and self.bn:
-                    bn = enc.norms[l]
-                    d.bn_eps, d.bn_momentum = bn.eps, bn.momentum
-                    y.gamma, y.beta, y.ggamma, y.gbeta = ptr(bn.weight), ptr(bn.bias), ptr(self.grad(bn.weight)), ptr(self.grad(bn.bias))
-                    y.running_mean, y.running_var, y.nbt = ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked)
-            self._sage_ln = None
-            if self.ln and L > 1:          # (a one-layer encoder has no hidden tail and no norm module)
-                lnd = self._sage_ln = _lib.SageLnDesc()
-                lnd.eps = enc.norms[0].eps
-                for l in range(L - 1):
-                    ln, q = enc.norms[l], lnd.layer[l]
-                    if ctypes.c_float(ln.eps).value != lnd.eps:
-                        raise NotImplementedError("TeacherEngine: the hidden LayerNorms of a SAGE teacher must share one eps")
-                    q.gamma, q.beta, q.ggamma, q.gbeta = ptr(ln.weight), ptr(ln.bias), ptr(self.grad(ln.weight)), ptr(self.grad(ln.bias))
-            self._sage_static = self._sage_signature(enc)
-        elif self._sage_static != self._sage_signature(enc):
-            self._sage_desc = self._sage_mean = None        # something the descriptors captured was replaced: rebuild them
+        try:
+            body(g, feats, labels, idx_train, lamb)
+        except Exception:
             self.step_count -= 1
-            return self.step_sage_mean(blocks, feats, labels, output_nodes, lamb, input_nodes)
-        dims = self._sage_dims
-        d.lamb = float(lamb)
-
-        def layout(A):      # ONE pass hands out the step's scratch from the arena (see step_sage)
-            max_rows, max_hidden = 1, 4
-            for l, blk in enumerate(blocks):
-                y, q = d.layer[l], md.layer[l]
-                n_dst, n_src, nnz = blk.num_dst_nodes(), blk.num_src_nodes(), blk.num_edges()
-                q.ld_cat = 2 * r4(dims[l])
-                q.cat = A.take(4 * n_dst * q.ld_cat)
-                q.wcat, q.bsum = A.take(4 * dims[l + 1] * q.ld_cat), A.take(4 * dims[l + 1])
-                y.z, y.ldz = A.take(4 * n_dst * r4(dims[l + 1])), r4(dims[l + 1])
-                if l != L - 1:
-                    if self.gather_tail and dims[l + 1] <= 256:      # (the tail-in-gather form: hidden width <= 256, as in step_sage)
-                        y.h, y.ldh = None, 0
-                    else:
-                        y.h, y.ldh = A.take(4 * n_dst * r4(dims[l + 1])), r4(dims[l + 1])
-                    max_rows, max_hidden = max(max_rows, n_dst), max(max_hidden, dims[l + 1])
-                    if self.bn:
-                        y.mean, y.rstd, y.a_scale, y.a_shift = (A.take(4 * dims[l + 1]) for _ in range(4))
-                    if self.ln:
-                        g = self._sage_ln.layer[l]
-                        g.mean, g.rstd = A.take(4 * n_dst), A.take(4 * n_dst)
-                # the PLAIN transpose: the loader's when it built that one (t_add_self False), else built inside the C call -- never one
-                # that carries the "gcn" step's self entries
-                if l >= 1 and getattr(blk, "t_indptr", None) is not None and getattr(blk, "t_add_self", None) is False:
-                    y.t_indptr, y.t_indices = ptr(blk.t_indptr), ptr(blk.t_indices)
-                    y.tr_ws, y.tr_ws_bytes = None, 0
-                elif l >= 1:
-                    wsb = int(_lib.lib().glnn_csr_transpose_workspace_bytes(n_src, nnz))
-                    y.t_indptr, y.t_indices = A.take(8 * (n_src + 1)), A.take(4 * max(nnz, 1))
-                    y.tr_ws, y.tr_ws_bytes = A.take(wsb + 8), (wsb + 7) // 8 * 8
-            n_out = blocks[-1].num_dst_nodes()
-            d.dlogits, d.ld_dlogits = A.take(4 * n_out * r4(dims[-1])), r4(dims[-1])
-            if L > 1:
-                wd = r4(max(dims[1:L]))
-                dcat = A.take(4 * max(blocks[l].num_dst_nodes() * 2 * r4(dims[l]) for l in range(1, L)))      # one buffer, layer by layer
-                for l in range(1, L):
-                    md.layer[l].dcat, md.layer[l].ld_dcat = dcat, 2 * r4(dims[l])
-                d.dh, d.ld_dh = A.take(4 * max(b.num_src_nodes() for b in blocks[1:]) * wd), wd
-            nchunks = (max_rows + 127) // 128
-            d.ws_bn_floats = (3 * nchunks + 2 + 3 * ((nchunks + 63) // 64)) * max_hidden + 1024
-            if self.ln:
-                for l in range(L - 1):
-                    n_l = blocks[l].num_dst_nodes()
-                    d.ws_bn_floats = max(d.ws_bn_floats, int(_lib.lib().glnn_sage_step_ws_ln_floats(n_l, dims[l + 1])),
-                                         int(_lib.lib().glnn_layernorm_bwd_workspace_floats(n_l, dims[l + 1])))
-            d.ws_tn_floats = 64 * max(dims) + 256 * 128 * 128 + 2 * max(dims) * max(dims)
-            d.ws_gemm_floats = min(max(16 * max(b.num_dst_nodes() for b in blocks) * min(dims[1:]), 1 << 20), 512 * 128 * 128)
-            d.ws_bn, d.ws_tn, d.ws_gemm = A.take(4 * d.ws_bn_floats), A.take(4 * d.ws_tn_floats), A.take(4 * d.ws_gemm_floats)
-            return A.off
-
-        for l, blk in enumerate(blocks):       # the batch: blocks and dropout seeds
-            y = d.layer[l]
-            glob = l == 0 and blk.gindices is not None
-            y.indptr, y.indices = ptr(blk.indptr), ptr(blk.gindices if glob else blk.indices)
-            y.n_dst, y.n_src, y.nnz = blk.num_dst_nodes(), blk.num_src_nodes(), blk.num_edges()
-            y.self_rows = ptr(blk.dst_nodes) if glob else None
-            if l != L - 1:
-                y.drop_seed = self._seed(l)
-        cur = torch.cuda.current_stream(dev)
-        if self._arena_stream is not None and self._arena_stream != cur:
-            cur.wait_stream(self._arena_stream)            # the previous step used the arena on another stream
-        self._arena_stream = cur
-        arena = self._arena
-        base = 0 if arena is None else (arena.data_ptr() + 255) // 256 * 256
-        total = layout(_Arena(base))
-        if arena is None or total + 256 > arena.numel():    # first step / a bigger batch: (re)allocate with headroom, lay out again
-            arena = self._arena = torch.empty(int(total * 1.25) + 256, dtype=torch.uint8, device=dev)
-            layout(_Arena((arena.data_ptr() + 255) // 256 * 256))
-        d.x, d.ldx, d.x_rows = ptr(x), x.stride(0), x.shape[0]
-        d.labels, d.label_rows = ptr(labels), ptr(output_nodes)
-        d.ws_loss, d.ws_loss_floats = ptr(self.ws_loss), self.ws_loss.numel()
-        d.loss_out, d.loss_accum = ptr(self.loss_out), ptr(self.loss_accum)
-        keep = [x]                                              # alive until the call below is queued (same-stream reuse is ordered)
-        ops.note_param_write()      # (running statistics are written through raw pointers; Adam follows)
-        one_call = self.grad_sync is None and self._one_call
-        lnp = ctypes.byref(self._sage_ln) if self._sage_ln is not None else None
-        if one_call:
-            g_ = self.opt.param_groups[0]
-            ad = self.table.desc
-            ad.lr, ad.beta1, ad.beta2, ad.eps, ad.weight_decay, ad.step = g_["lr"], g_["betas"][0], g_["betas"][1], g_["eps"], g_["weight_decay"], self.step_count
-            rc = _lib.lib().glnn_sage_mean_train_step_f32(ctypes.byref(d), ctypes.byref(md), lnp, ctypes.byref(ad), ops._stream())
-        else:
-            rc = _lib.lib().glnn_sage_mean_fwd_bwd_f32(ctypes.byref(d), ctypes.byref(md), lnp, ops._stream())
-        del keep
-        if rc != 0:
-            self.step_count -= 1          # the step never happened: Adam's bias correction and the dropout seeds stay where they were
-        _lib.check(rc, "glnn_sage_mean_train_step_f32" if one_call else "glnn_sage_mean_fwd_bwd_f32")
-        if not one_call:
-            self._adam()
+            raise
+        self._adam()
 
     # ------------------------------------------------------------------------------------------ full-graph GCN
     @torch.no_grad()
     def step_gcn(self, g, feats, labels, idx_train, lamb=1.0):
-        enc, L, p = self.enc, self.L, self.p
-        ops._need_cuda(feats, labels, idx_train, g.indptr)
-        if g.has_zero_in_degree() and not all(lay._allow_zero_in_degree for lay in enc.layers):
+        if g.has_zero_in_degree() and not all(lay._allow_zero_in_degree for lay in self.enc.layers):
             raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
                                "(dgl GraphConv semantics; add self-loops or set allow_zero_in_degree).")
-        n = g.num_dst_nodes()
-        self.step_count += 1
-        try:
-            self._step_gcn_body(g, feats, labels, idx_train, lamb, n)
-        except Exception:
-            self.step_count -= 1          # the step never happened (see step_sage)
-            raise
-        self._adam()
+        self._run_full_graph(self._step_gcn_body, g, feats, labels, idx_train, lamb)
 
-    def _step_gcn_body(self, g, feats, labels, idx_train, lamb, n):
+    def _step_gcn_body(self, g, feats, labels, idx_train, lamb):
         enc, L, p = self.enc, self.L, self.p
         a = ops.as_feat(feats)
         saved = []
@@ -615,12 +558,7 @@ class TeacherEngine:
                 else:
                     a = ops.act_fwd(y, drop_p=p, drop_seed=seed) if p > 0 else y       # y >= 0 already (ReLU inside the conv)
             saved.append((mid, first, y, seed, stats))
-        logits = saved[-1][2]
-        logits_tr = ops.gather_rows(logits, idx_train)                            # out[idx_train] (train_and_eval.py:22)
-        _, dl = ops.softmax_loss(logits_tr, ops.LOSS_NLL, float(lamb), labels=labels, label_rows=idx_train, loss_out=self.loss_out,
-                                 loss_accum=self.loss_accum, workspace=self.ws_loss)
-        dz = ops.feat_empty(n, logits.shape[1], self.dev, zero=True)
-        ops.scatter_rows(dl, idx_train, dz)
+        dz = self._loss_grad(saved[-1][2], labels, idx_train, lamb, g.num_dst_nodes())
         ops.col_sum(dz, out=self.grad(enc.layers[-1].bias))
         for l in range(L - 1, -1, -1):
             layer = enc.layers[l]
@@ -657,14 +595,7 @@ class TeacherEngine:
         """The reference's full-graph `train` (train_and_eval.py:12-29) over APPNP (models.py:326-344): the MLP trunk (glnn_gemm_f32 +
         norm / ReLU / dropout tails), K launches of glnn_appnp_prop_f32, NLL over idx_train, K launches of glnn_appnp_prop_bwd_f32 over
         the transposed graph, the trunk backward, Adam."""
-        ops._need_cuda(feats, labels, idx_train, g.indptr)
-        self.step_count += 1
-        try:
-            self._step_appnp_body(g, feats, labels, idx_train, lamb)
-        except Exception:
-            self.step_count -= 1          # the step never happened (see step_sage)
-            raise
-        self._adam()
+        self._run_full_graph(self._step_appnp_body, g, feats, labels, idx_train, lamb)
 
     def _appnp_tail_fwd(self, l, z):
         """norms[l] -> relu -> dropout of hidden layer l (models.py:334-338)."""
@@ -737,22 +668,18 @@ class TeacherEngine:
         """The full-graph `train` step over GPRGNN (docs/GPR_SEMANTICS.md): the MLP trunk with its norm / ReLU / dropout tails, K launches
         of glnn_gpr_prop_f32, NLL over idx_train, K launches over the transposed graph whose epilogues leave the per-row <G_k, h0>,
         glnn_gpr_fold_f32 into grad(gamma), the trunk backward, and the ONE Adam launch (gamma is one more tensor of its table)."""
-        ops._need_cuda(feats, labels, idx_train, g.indptr)
-        self.step_count += 1
-        try:
-            enc = self.enc
-            gamma = enc.propagate.gamma
-            h0, acts, saved = self._trunk_fwd(feats)
-            logits = gpr_fwd(g, h0, gamma, enc.k)
-            dlog = self._loss_grad(logits, labels, idx_train, lamb, g.num_dst_nodes())
-            dz, dgamma = gpr_bwd(g, dlog, h0, gamma, enc.k)
-            self.grad(gamma).copy_(dgamma)
-            self._trunk_bwd(dz, acts, saved)
-            ops.note_param_write()
-        except Exception:
-            self.step_count -= 1          # the step never happened (see step_sage)
-            raise
-        self._adam()
+        self._run_full_graph(self._step_gpr_body, g, feats, labels, idx_train, lamb)
+
+    def _step_gpr_body(self, g, feats, labels, idx_train, lamb):
+        enc = self.enc
+        gamma = enc.propagate.gamma
+        h0, acts, saved = self._trunk_fwd(feats)
+        logits = gpr_fwd(g, h0, gamma, enc.k)
+        dlog = self._loss_grad(logits, labels, idx_train, lamb, g.num_dst_nodes())
+        dz, dgamma = gpr_bwd(g, dlog, h0, gamma, enc.k)
+        self.grad(gamma).copy_(dgamma)
+        self._trunk_bwd(dz, acts, saved)
+        ops.note_param_write()
 
     # ------------------------------------------------------------------------------------------ full-graph GCNII
     def _gcnii_seed(self, site, step=None):
@@ -768,14 +695,7 @@ class TeacherEngine:
         glnn_gcnii_layer_f32 that keep S_l and H_l, fc_out, NLL over idx_train, fc_out's backward, L launches of
         glnn_gcnii_layer_bwd_f32 over the transposed graph with one glnn_gemm_tn_f32 each (beta_l folded into its stored operand), the
         launch for dH_0, H_0's ReLU backward, fc_in's backward, and the ONE Adam launch."""
-        ops._need_cuda(feats, labels, idx_train, g.indptr)
-        self.step_count += 1
-        try:
-            self._step_gcnii_body(g, feats, labels, idx_train, lamb)
-        except Exception:
-            self.step_count -= 1          # the step never happened (see step_sage)
-            raise
-        self._adam()
+        self._run_full_graph(self._step_gcnii_body, g, feats, labels, idx_train, lamb)
 
     def _step_gcnii_body(self, g, feats, labels, idx_train, lamb):
         enc, L, p = self.enc, self.L, self.p
@@ -810,17 +730,10 @@ class TeacherEngine:
         """The reference's full-graph `train` (train_and_eval.py:12-29) over GAT (models.py:202-279): per layer the projection with the
         feature dropout in its operand load, glnn_gat_scores_f32 and glnn_gat_attn_fwd_f32; NLL over idx_train; per layer
         glnn_gat_attn_bwd_f32 over the graph and its transpose, the weight gradient and the input gradient; Adam."""
-        ops._need_cuda(feats, labels, idx_train, g.indptr)
         if g.has_zero_in_degree():
             raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
                                "(dgl GATConv semantics; add self-loops or set allow_zero_in_degree).")
-        self.step_count += 1
-        try:
-            self._step_gat_body(g, feats, labels, idx_train, lamb)
-        except Exception:
-            self.step_count -= 1          # the step never happened (see step_sage)
-            raise
-        self._adam()
+        self._run_full_graph(self._step_gat_body, g, feats, labels, idx_train, lamb)
 
     def _step_gat_body(self, g, feats, labels, idx_train, lamb):
         enc, L = self.enc, self.L
@@ -834,12 +747,7 @@ class TeacherEngine:
                                   l != L - 1, lay.feat_drop.p, fs, lay.attn_drop.p, as_, signed0 if l == 0 else False, want_lse=True)
             saved.append((sv, fs, as_))
             acts.append(y)
-        logits = acts[L]
-        logits_tr = ops.gather_rows(logits, idx_train)                            # out[idx_train] (train_and_eval.py:22)
-        _, dl = ops.softmax_loss(logits_tr, ops.LOSS_NLL, float(lamb), labels=labels, label_rows=idx_train, loss_out=self.loss_out,
-                                 loss_accum=self.loss_accum, workspace=self.ws_loss)
-        gy = ops.feat_empty(n, logits.shape[1], self.dev, zero=True)
-        ops.scatter_rows(dl, idx_train, gy)
+        gy = self._loss_grad(acts[L], labels, idx_train, lamb, n)
         for l in range(L - 1, -1, -1):
             lay = enc.layers[l]
             sv, fs, as_ = saved[l]
@@ -857,17 +765,10 @@ class TeacherEngine:
         """The full-graph `train` step over GATv2 (docs/GATV2_SEMANTICS.md): per layer the dropped copy of the input, the two projections
         and glnn_gatv2_attn_fwd_f32; NLL over idx_train; per layer glnn_gatv2_attn_bwd_f32 over the graph and its transpose, the two weight
         gradients with their bias column sums and the input gradient; the ONE Adam launch."""
-        ops._need_cuda(feats, labels, idx_train, g.indptr)
         if g.has_zero_in_degree():
             raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
                                "(GATv2Conv follows dgl GATConv; add self-loops or set allow_zero_in_degree).")
-        self.step_count += 1
-        try:
-            self._step_gatv2_body(g, feats, labels, idx_train, lamb)
-        except Exception:
-            self.step_count -= 1          # the step never happened (see step_sage)
-            raise
-        self._adam()
+        self._run_full_graph(self._step_gatv2_body, g, feats, labels, idx_train, lamb)
 
     def _step_gatv2_body(self, g, feats, labels, idx_train, lamb):
         enc, L = self.enc, self.L

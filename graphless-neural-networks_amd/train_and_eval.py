@@ -37,18 +37,7 @@ def train(model, data, feats, labels, criterion, optimizer, idx_train, lamb=1):
                                   "with train_sage)")
     model.train()
     eng = teacher.get_engine(model, optimizer)
-    if "GCNII" in model.model_name:          # (tested before the GCN fall-through below: "GCNII" contains "GCN")
-        eng.step_gcnii(data, feats, labels, idx_train, float(lamb))
-    elif "APPNP" in model.model_name:
-        eng.step_appnp(data, feats, labels, idx_train, float(lamb))
-    elif "GATv2" in model.model_name:        # (tested before "GAT", which it contains)
-        eng.step_gatv2(data, feats, labels, idx_train, float(lamb))
-    elif "GAT" in model.model_name:
-        eng.step_gat(data, feats, labels, idx_train, float(lamb))
-    elif "GPRGNN" in model.model_name:
-        eng.step_gpr(data, feats, labels, idx_train, float(lamb))
-    else:
-        eng.step_gcn(data, feats, labels, idx_train, float(lamb))
+    _full_graph_step(eng, model.model_name)(data, feats, labels, idx_train, float(lamb))
     eng.sync_optimizer_state()
     return eng.loss_out.item()
 

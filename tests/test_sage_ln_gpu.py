@@ -267,6 +267,31 @@ def test_descriptor_rebuild_after_load_state_dict_a_changed_eps_and_a_replaced_l
     check(eng2, 0, 1e-3)
 
 
+def test_one_layer_layernorm_teacher_steps_through_the_plain_entry():
+    """A one-layer encoder has no hidden tail and no norm module: with norm_type "layer" the engine builds no LayerNorm side descriptor and
+    the step is the plain entry's -- the bits of the same model built with norm_type "none"."""
+    from glnn_amd import teacher
+    from glnn_amd.models import Model
+    n_src, n_dst, d, c = 70, 23, 19, 7
+    rs = np.random.RandomState(5)
+    indptr = np.concatenate([[0], np.cumsum(rs.randint(0, 6, n_dst))])
+    blocks = [_graph(indptr, rs.randint(0, n_src, indptr[-1]), n_src)]
+    feats, labels = torch.from_numpy(rs.standard_normal((n_src, d)).astype(np.float32)).to(DEV), torch.from_numpy(rs.randint(0, c, n_dst)).to(DEV)
+    rows, inp = torch.arange(n_dst, device=DEV), torch.arange(n_src, device=DEV)
+    out = {}
+    for norm in ("layer", "none"):
+        torch.manual_seed(3)
+        model = Model(dict(model_name="SAGE", num_layers=1, feat_dim=d, hidden_dim=8, label_dim=c, dropout_ratio=0.5, norm_type=norm,
+                           device=DEV)).train()
+        eng = teacher.get_engine(model, torch.optim.Adam(model.parameters(), lr=0.01))
+        for _ in range(2):
+            eng.step_sage(blocks, feats, labels, rows, 1.0, input_nodes=inp)
+        assert eng._sage_ln is None and eng.step_count == 2 and np.isfinite(eng.loss_out.item())
+        out[norm] = (eng.loss_out.clone(), [p.detach().clone() for p in model.parameters()])
+    assert torch.equal(out["layer"][0], out["none"][0])
+    _assert_equal(out["layer"][1], out["none"][1])
+
+
 def _run_cli(script, args, cwd):
     env = dict(os.environ, PYTHONPATH=ROOT)
     r = subprocess.run([sys.executable, os.path.join(ROOT, script)] + args, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)

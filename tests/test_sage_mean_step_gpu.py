@@ -413,6 +413,90 @@ def test_step_sage_refuses_a_mean_model_and_names_the_mean_step():
     assert eng.step_count == 0
 
 
+@pytest.mark.parametrize("norm", ["batch", "layer"])
+def test_mean_descriptor_rebuilds_when_captured_state_changes(norm):
+    """tests/test_sage_ln_gpu.py::test_descriptor_rebuild_after_load_state_dict_a_changed_eps_and_a_replaced_layernorm for step_sage_mean, on
+    the hand-built blocks: load_state_dict keeps the tensors (same descriptors, new values); a changed dropout and, for LayerNorm, a changed
+    eps are part of the descriptors' signature (both rebuilt).  Each time the next step's loss and gradients are the oracle's for the state
+    the model then holds (the bounds of test_dropout_step_matches_the_oracle_given_the_masks)."""
+    from oracle.dropout_mask import keep_mask
+    blocks, x, y = _hand_blocks()
+    dev, xd, yd = _hand_dev()
+    rows, inp = torch.arange(HB_N2, device=DEV), torch.arange(HB_N0, device=DEV)
+    model = _model(norm, HB_DIMS)
+    eng, _ = _engine(model)
+
+    def check(what, p, eps):
+        sd = _state(model)
+        eng.step_sage_mean(dev, xd, yd, rows, 1.0, input_nodes=inp)
+        masks = [keep_mask(HB_N1, HB_DIMS[1], p, eng._seed(0))] if p > 0 else None      # (the step's own seed: step_count stays put)
+        st64, st32 = mo.State(sd, 2, norm, eps=eps), mo.State(sd, 2, norm, eps=eps, dtype=np.float32)
+        want, g64, _ = so.step(st64, blocks, x.astype(np.float64), y, LR, masks, p)
+        _, g32, _ = so.step(st32, blocks, x, y, LR, masks, p)
+        loss = eng.loss_out.item()
+        print(f"rebuild {norm} {what}: loss {loss:.6f} oracle {want:.6f}")
+        assert abs(loss - want) < TOL + TOL * abs(want)
+        _check_grads(model, norm, 2, g64, g32, f"rebuild {norm} {what}")
+
+    check("first step", 0.0, 1e-5)
+    d, md = eng._sage_desc, eng._sage_mean
+    assert d is not None and md is not None
+    model.load_state_dict(_model(norm, HB_DIMS, seed=9).state_dict())
+    check("after load_state_dict", 0.0, 1e-5)
+    assert eng._sage_desc is d and eng._sage_mean is md
+    model.encoder.dropout.p = 0.5
+    check("after dropout 0.5", 0.5, 1e-5)
+    assert eng._sage_desc is not d and eng._sage_mean is not md and eng.p == 0.5
+    if norm == "layer":
+        d, md = eng._sage_desc, eng._sage_mean
+        for nm in model.encoder.norms:
+            nm.eps = 1e-3
+        check("after eps 1e-3", 0.5, 1e-3)
+        assert eng._sage_desc is not d and eng._sage_mean is not md
+    assert eng.step_count == (4 if norm == "layer" else 3)
+
+
+@pytest.mark.parametrize("entry", ["step_sage", "step_sage_mean"])
+def test_failed_step_leaves_the_counter_and_seeds_where_they_were(entry):
+    """A refused step never happened: step_count -- Adam's bias correction and the dropout seeds -- stays, and the next good step gives the
+    bits of the same step on a fresh engine seeded alike (dropout 0.5, so the seeds matter).  Two refusals, both argument checks in front
+    of every launch of the step: block 1 with one source more than block 0 has destinations (ValueError, raised in Python), and block 0
+    with fewer sources than destinations, which reaches the C entry and is refused by its first loop of checks (GlnnError: the rc != 0
+    rollback).  A descriptor with dropout_p = 1 is NOT used: csrc/sage_step.hip does not check dropout_p before its first launch."""
+    from glnn_amd._lib import GlnnError
+    from glnn_amd.graph import CSRGraph
+    from glnn_amd.models import Model
+    dev, xd, yd = _hand_dev()
+    rows, inp = torch.arange(HB_N2, device=DEV), torch.arange(HB_N0, device=DEV)
+
+    def fresh():
+        torch.manual_seed(4)
+        model = Model(dict(model_name="SAGE", num_layers=2, feat_dim=HB_DIMS[0], hidden_dim=HB_DIMS[1], label_dim=HB_DIMS[2], dropout_ratio=0.5,
+                           norm_type="batch", device=DEV, sage_aggregator="mean" if entry == "step_sage_mean" else "gcn")).train()
+        return model, _engine(model)[0]
+
+    def step(eng, blocks):
+        getattr(eng, entry)(blocks, xd, yd, rows, 1.0, input_nodes=inp)
+
+    model, eng = fresh()
+    step(eng, dev)
+    assert eng.step_count == 1
+    wide = CSRGraph(dev[1].indptr, dev[1].indices, HB_N2, HB_N1 + 1)
+    with pytest.raises(ValueError, match=f"TeacherEngine.{entry}: block 1 has {HB_N1 + 1} sources"):
+        step(eng, [dev[0], wide])
+    assert eng.step_count == 1
+    short = CSRGraph(dev[0].indptr, dev[0].indices, HB_N1, HB_N1 - 1)
+    with pytest.raises(GlnnError, match="n_src=329|bad block sizes"):
+        step(eng, [short, dev[1]])
+    assert eng.step_count == 1
+    step(eng, dev)
+    assert eng.step_count == 2
+    model_b, eng_b = fresh()
+    step(eng_b, dev)
+    step(eng_b, dev)
+    _params_equal(model, model_b)
+
+
 def test_loader_transposes_with_self_entries_are_not_read():
     """An engine-mode loader in its default ("gcn") form tags its inner transposes add_self=True: step_sage_mean builds its own."""
     dims = [20, 32, 6]
