@@ -3,6 +3,7 @@
 keep working on HIP for callers that differentiate `Model.forward` themselves: the dense projections, the neighbour
 aggregation and the norm/ReLU/dropout tails run on libglnn_hip.so in both directions.  The training loops of this package
 do not go through autograd at all -- see student.py (StudentEngine) and teacher.py (TeacherEngine)."""
+import functools
 import math
 
 import torch
@@ -417,6 +418,41 @@ def gcnii_stack(graph, h0, weights, alpha, betas, drop_p, training):
         return gcnii_fwd(graph, h0, list(weights), float(alpha), betas, p, seeds)[0]
 
 
+# ------------------------------------------------------------------------------------------ what the two attention layers share
+def _attn_seeds(count, tag_feat, tag_attn):
+    """(feature-dropout seed, attention-dropout seed) of the count-th dropout draw of this process (tests replay the masks from them)."""
+    base = int(torch.initial_seed()) * 0x85EBCA77 + count * 0x9E3779B1
+    return (base + tag_feat) & 0xFFFFFFFF, (base + tag_attn) & 0xFFFFFFFF
+
+
+gat_conv_seeds = functools.partial(_attn_seeds, tag_feat=0x47415446, tag_attn=0x47415441)
+gatv2_conv_seeds = functools.partial(_attn_seeds, tag_feat=0x47563246, tag_attn=0x47563241)
+
+
+def _attn_conv(fn, layer_fwd, seeds, graph, x, params, shape, feat_drop, attn_drop, training, *extra):
+    """Both attention convs: the dropouts only in training, their counter-based seeds drawn like norm_act_drop's; differentiable in
+    training mode (appnp_propagate's rule), else the eval forward, which keeps nothing.  shape = (heads, out_feats, slope, relu)."""
+    fp, ap = (float(feat_drop), float(attn_drop)) if training else (0.0, 0.0)
+    fs = as_ = 0
+    if fp > 0 or ap > 0:
+        _drop_counter[0] += 1
+        fs, as_ = seeds(_drop_counter[0])
+    args = (*params, *shape, fp, fs, ap, as_, *extra)
+    if training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+        return fn.apply(graph, x, *args)
+    with torch.no_grad():
+        return layer_fwd(graph, ops.as_feat(x), *args)[0]
+
+
+def _attn_backward(dy, y, relu, feat_p, feat_seed, layer_bwd):
+    """layer_bwd(gy = dy * [y > 0] for a ReLU layer) with the feature-dropout mask and 1 / (1 - p) on the input gradient it returns first."""
+    dy = ops.as_feat(dy.contiguous())
+    da, *grads = layer_bwd(ops.bn_relu_bwd(dy, y)[0] if relu else dy)
+    if da is not None and feat_p > 0:
+        da = ops.act_fwd(da, drop_p=feat_p, drop_seed=feat_seed, relu=False)
+    return (da, *grads)
+
+
 # ------------------------------------------------------------------------------------------ GAT layer (dgl 0.6.1 GATConv)
 def gat_layer_fwd(g, x, w, attn_l, attn_r, heads, out_feats, slope, relu, feat_p=0.0, feat_seed=0, attn_p=0.0, attn_seed=0, signed=True,
                   want_lse=False):
@@ -457,34 +493,16 @@ class GatConvFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w, attn_l, attn_r, y, z, el, er, lse = ctx.saved_tensors
         heads, out_feats, slope, relu, feat_p, feat_seed, attn_p, attn_seed, signed = ctx.cfg
-        dy = ops.as_feat(dy.contiguous())
-        gy = ops.bn_relu_bwd(dy, y)[0] if relu else dy                     # dy * [y > 0]
-        da, dw, dal, dar = gat_layer_bwd(ctx.graph, gy, y, (z, el, er, lse), x, w.detach(), attn_l.detach(), attn_r.detach(), heads,
-                                         out_feats, slope, feat_p, feat_seed, attn_p, attn_seed, signed, need_dx=ctx.needs_input_grad[1])
-        if da is not None and feat_p > 0:
-            da = ops.act_fwd(da, drop_p=feat_p, drop_seed=feat_seed, relu=False)      # the feature-dropout mask and 1 / (1 - p)
+        da, dw, dal, dar = _attn_backward(dy, y, relu, feat_p, feat_seed, lambda gy: gat_layer_bwd(
+            ctx.graph, gy, y, (z, el, er, lse), x, w.detach(), attn_l.detach(), attn_r.detach(), heads, out_feats, slope, feat_p, feat_seed,
+            attn_p, attn_seed, signed, need_dx=ctx.needs_input_grad[1]))
         return (None, da, dw, dal.view_as(attn_l), dar.view_as(attn_r)) + (None,) * 9
 
 
-def gat_conv_seeds(count):
-    """(feature-dropout seed, attention-dropout seed) of the count-th dropout draw of this process (tests replay the masks from them)."""
-    base = int(torch.initial_seed()) * 0x85EBCA77 + count * 0x9E3779B1
-    return (base + 0x47415446) & 0xFFFFFFFF, (base + 0x47415441) & 0xFFFFFFFF
-
-
 def gat_conv(graph, x, w, attn_l, attn_r, heads, out_feats, slope, relu, feat_drop, attn_drop, training, signed=True):
-    """GATConv forward: both dropouts only in training; their counter-based seeds are drawn like norm_act_drop's.  Differentiable in
-    training mode (appnp_propagate's rule); the eval forward keeps nothing for a backward."""
-    fp = float(feat_drop) if training else 0.0
-    ap = float(attn_drop) if training else 0.0
-    fs = as_ = 0
-    if fp > 0 or ap > 0:
-        _drop_counter[0] += 1
-        fs, as_ = gat_conv_seeds(_drop_counter[0])
-    if training and torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or attn_l.requires_grad or attn_r.requires_grad):
-        return GatConvFn.apply(graph, x, w, attn_l, attn_r, heads, out_feats, slope, relu, fp, fs, ap, as_, signed)
-    with torch.no_grad():
-        return gat_layer_fwd(graph, ops.as_feat(x), w, attn_l, attn_r, heads, out_feats, slope, relu, fp, fs, ap, as_, signed)[0]
+    """GATConv forward (_attn_conv's rule)."""
+    return _attn_conv(GatConvFn, gat_layer_fwd, gat_conv_seeds, graph, x, (w, attn_l, attn_r), (heads, out_feats, slope, relu), feat_drop,
+                      attn_drop, training, signed)
 
 
 # ------------------------------------------------------------------------------------------ GATv2 layer (docs/GATV2_SEMANTICS.md)
@@ -537,32 +555,13 @@ class Gatv2ConvFn(torch.autograd.Function):
     def backward(ctx, dy):
         w_src, w_dst, attn, y, xd, zl, zr, lse = ctx.saved_tensors
         heads, out_feats, slope, relu, feat_p, feat_seed, attn_p, attn_seed = ctx.cfg
-        dy = ops.as_feat(dy.contiguous())
-        gy = ops.bn_relu_bwd(dy, y)[0] if relu else dy                     # dy * [y > 0]
-        da, dws, dbs, dwd, dbd, dat = gatv2_layer_bwd(ctx.graph, gy, (xd, zl, zr, lse), w_src.detach(), w_dst.detach(), attn.detach(), heads,
-                                                      out_feats, slope, attn_p, attn_seed, need_dx=ctx.needs_input_grad[1])
-        if da is not None and feat_p > 0:
-            da = ops.act_fwd(da, drop_p=feat_p, drop_seed=feat_seed, relu=False)      # the feature-dropout mask and 1 / (1 - p)
+        da, dws, dbs, dwd, dbd, dat = _attn_backward(dy, y, relu, feat_p, feat_seed, lambda gy: gatv2_layer_bwd(
+            ctx.graph, gy, (xd, zl, zr, lse), w_src.detach(), w_dst.detach(), attn.detach(), heads, out_feats, slope, attn_p, attn_seed,
+            need_dx=ctx.needs_input_grad[1]))
         return (None, da, dws, dbs, dwd, dbd, dat.view_as(attn)) + (None,) * 8
 
 
-def gatv2_conv_seeds(count):
-    """(feature-dropout seed, attention-dropout seed) of the count-th dropout draw of this process (tests replay the masks from them)."""
-    base = int(torch.initial_seed()) * 0x85EBCA77 + count * 0x9E3779B1
-    return (base + 0x47563246) & 0xFFFFFFFF, (base + 0x47563241) & 0xFFFFFFFF
-
-
 def gatv2_conv(graph, x, w_src, b_src, w_dst, b_dst, attn, heads, out_feats, slope, relu, feat_drop, attn_drop, training):
-    """GATv2Conv forward: both dropouts only in training; their counter-based seeds are drawn like norm_act_drop's.  Differentiable in
-    training mode (appnp_propagate's rule); the eval forward keeps nothing for a backward."""
-    fp = float(feat_drop) if training else 0.0
-    ap = float(attn_drop) if training else 0.0
-    fs = as_ = 0
-    if fp > 0 or ap > 0:
-        _drop_counter[0] += 1
-        fs, as_ = gatv2_conv_seeds(_drop_counter[0])
-    params = (w_src, b_src, w_dst, b_dst, attn)
-    if training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-        return Gatv2ConvFn.apply(graph, x, w_src, b_src, w_dst, b_dst, attn, heads, out_feats, slope, relu, fp, fs, ap, as_)
-    with torch.no_grad():
-        return gatv2_layer_fwd(graph, ops.as_feat(x), w_src, b_src, w_dst, b_dst, attn, heads, out_feats, slope, relu, fp, fs, ap, as_)[0]
+    """GATv2Conv forward (_attn_conv's rule)."""
+    return _attn_conv(Gatv2ConvFn, gatv2_layer_fwd, gatv2_conv_seeds, graph, x, (w_src, b_src, w_dst, b_dst, attn),
+                      (heads, out_feats, slope, relu), feat_drop, attn_drop, training)

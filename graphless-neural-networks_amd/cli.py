@@ -13,7 +13,7 @@ import torch
 from torch import optim
 
 from .dataloader import load_data, load_out_t
-from .models import Model
+from .models import Model, teacher_kind
 from .train_and_eval import distill_run_inductive, distill_run_transductive, run_inductive, run_transductive
 from .utils import (check_readable, check_writable, compute_min_cut_loss, feature_prop, get_evaluator, get_logger,
                     get_training_config, graph_split, set_seed)
@@ -91,7 +91,7 @@ def get_teacher_args(argv=None):
     args = p.parse_args(argv)
     if not 0 <= args.subgraph_walk_length <= 64:
         p.error(f"--subgraph_walk_length must be in [0, 64] (got {args.subgraph_walk_length})")
-    if args.subgraph_walk_length > 0 and ("SAGE" in args.teacher or "MLP" in args.teacher):
+    if args.subgraph_walk_length > 0 and teacher_kind(args.teacher) in ("sage", "mlp"):
         p.error(f"--subgraph_walk_length applies to the full-graph teachers (GCN, APPNP, GAT, GATv2, GPRGNN, GCNII) only: SAGE trains on "
                 f"sampled blocks and MLP on feature batches (got --teacher {args.teacher})")
     if args.subgraph_self_loop != "keep" and args.subgraph_walk_length == 0:

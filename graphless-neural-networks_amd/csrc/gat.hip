@@ -17,12 +17,9 @@
 // lane groups take different edges and are folded with cross-lane adds (row_gather_dev.h's mapping); each lane recomputes the weight of its
 // own head from el[j] (4 bytes, the same 32-byte segment for the whole group).  Rows go to waves by that header's two-role scan with the
 // static assignment of short rows; a long row's eight partials are folded through LDS in wave order.  No float atomics.
-#include "row_gather_dev.h"
+#include "attn_dev.h"
 
 namespace {
-
-constexpr int kU = 4;                      // edges in flight per lane group
-constexpr float kNegBig = -3.0e38f;
 
 struct GatArgs {
   const int64_t* indptr; const int32_t* indices; const int32_t* eids;   // eids NULL: the edge id is the CSR position
@@ -40,11 +37,6 @@ struct GatArgs {
   const float* attn_l; const float* attn_r;
   ScanGrid sg;
 };
-
-__device__ __forceinline__ float lrelu(float s, float slope) { return s > 0.f ? s : s * slope; }
-__device__ __forceinline__ bool attn_keep(uint32_t seed, uint32_t thr, uint32_t eid, uint32_t head) {
-  return (glnn::drop_hash(seed, eid, head) & 0xFFFFu) >= thr;
-}
 
 struct Smem {
   double red[kWaves][64];                   // holds a float exactly; the backward's per-head sums are doubles
@@ -319,8 +311,10 @@ __global__ __launch_bounds__(kBlock) void gat_rows_kernel(const GatArgs a) {
   __shared__ Smem sm;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // row_gather_dev.h's two roles with the loops written out: behind scan_rows' callback the KIND 2 kernels take 107..120 VGPRs for
-  // 84..96 and drop from 5 waves per SIMD to 4.  Short rows are assigned statically.
+  // row_gather_dev.h's two roles with the loops WRITTEN OUT, short rows assigned statically.  Behind a callback -- scan_rows', or a
+  // scan_rows_static shared with gatv2_rows_kernel, whose loops are these -- the KIND 2 kernels go from 71 / 71 / 77 / 90 VGPRs (LPR 32 /
+  // 16 / 8 / 4, UNI) to 107 / 109 / 112 / 120 and from 84 - 102 to 113 - 126 (non-UNI): a wave per SIMD less.  Measured with the build's
+  // flags, three forms of the shared function, the same figures each time (row_gather_dev.h, "the two-role scan"): leave them here.
   if ((int)blockIdx.x < a.sg.n_long_blocks) {
     const int64_t n_chunks = (a.n + kBlock - 1) / kBlock;
     for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += a.sg.n_long_blocks) {
@@ -342,11 +336,6 @@ __global__ __launch_bounds__(kBlock) void gat_rows_kernel(const GatArgs a) {
   }
 }
 
-template <int KIND, bool UNI>
-void launch_lpr(int lpr, dim3 grid, hipStream_t st, const GatArgs& a) {
-  with_lpr<4>(lpr, [&](auto L) { hipLaunchKernelGGL((gat_rows_kernel<KIND, decltype(L)::value, UNI>), grid, dim3(kBlock), 0, st, a); });
-}
-
 int set_shape(GatArgs& a, int64_t n, int64_t nnz, int heads, int f, float p, const char* what) {
   GLNN_REQUIRE(n >= 0 && nnz >= 0 && heads >= 1 && f >= 1, "%s: bad size", what);
   GLNN_REQUIRE(nnz < ((int64_t)1 << 31), "%s: nnz >= 2^31 (edge ids are 32-bit)", what);
@@ -361,15 +350,12 @@ int set_shape(GatArgs& a, int64_t n, int64_t nnz, int heads, int f, float p, con
 }
 
 int rows_launch(GatArgs& a, int kind, const char* what, void* stream) {
-  const int lpr = lpr_for((a.HF + 3) / 4, 4);
   const int rc = scan_grid(a.n, what, &a.sg);
   if (rc != GLNN_OK) return rc;
-  const dim3 grid(a.sg.grid_x);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool uni = a.F % 4 == 0;
-  if (kind == 0) { if (uni) launch_lpr<0, true>(lpr, grid, st, a); else launch_lpr<0, false>(lpr, grid, st, a); }
-  else if (kind == 1) { if (uni) launch_lpr<1, true>(lpr, grid, st, a); else launch_lpr<1, false>(lpr, grid, st, a); }
-  else { if (uni) launch_lpr<2, true>(lpr, grid, st, a); else launch_lpr<2, false>(lpr, grid, st, a); }
+  with_attn_variant(kind, a.F % 4 == 0, lpr_for((a.HF + 3) / 4, 4), [&](auto K, auto U, auto L) {
+    hipLaunchKernelGGL((gat_rows_kernel<decltype(K)::value, decltype(L)::value, decltype(U)::value>), dim3(a.sg.grid_x), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), a);
+  });
   return glnn::check_launch(what);
 }
 

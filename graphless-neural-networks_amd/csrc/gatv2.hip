@@ -18,14 +18,12 @@
 // a head (UNI, F % 4 == 0), the slot picked per column otherwise.  Each group keeps a running (max, denominator, accumulator) per column
 // and updates it online, edge by edge in ascending order; the groups are merged with xor moves, a long row's eight waves through LDS in wave
 // order.  Rows go to waves by the two-role scan with the static assignment of short rows (as gat.hip).  No float atomics, no grid barrier.
-#include "row_gather_dev.h"
+#include "attn_dev.h"
 
 namespace {
 
-constexpr int kU = 4;                      // edges in flight per lane group (forward, destination pass)
-constexpr int kU2 = 2;                     // source pass: two rows are gathered per edge
+constexpr int kU2 = 2;                     // edges in flight per lane group in the source pass (two rows are gathered per edge; else kU)
 constexpr int kFoldPer = 128;              // dattn partials summed per workgroup of the first fold
-constexpr float kNegBig = -3.0e38f;
 
 struct V2Args {
   const int64_t* indptr; const int32_t* indices; const int32_t* eids;   // eids NULL: the edge id is the CSR position
@@ -42,11 +40,6 @@ struct V2Args {
   float* part;                             // destination pass: [grid_x, H F] partials of dattn
   ScanGrid sg;
 };
-
-__device__ __forceinline__ float lrelu(float s, float slope) { return s > 0.f ? s : s * slope; }
-__device__ __forceinline__ bool attn_keep(uint32_t seed, uint32_t thr, uint32_t eid, uint32_t head) {
-  return (glnn::drop_hash(seed, eid, head) & 0xFFFFu) >= thr;
-}
 
 // what a lane knows about its four columns; fixed for the launch
 template <bool UNI>
@@ -459,7 +452,9 @@ __global__ __launch_bounds__(kBlock) void gatv2_rows_kernel(const V2Args a) {
     else if (KIND == 1) bwd_dst_row<LPR, UNI>(a, L, v, wave_id, n_waves, lane, sm, datt);
     else bwd_src_row<LPR, UNI>(a, L, v, wave_id, n_waves, lane, sm);
   };
-  if ((int)blockIdx.x < a.sg.n_long_blocks) {                     // row_gather_dev.h's two roles, short rows assigned statically
+  // row_gather_dev.h's two roles, short rows assigned statically: gat_rows_kernel's loops plus the ascending order of KIND 1, written
+  // out in both.  THIS kernel keeps every register figure behind a shared scan_rows_static; gat.hip's KIND 2 does not (see there).
+  if ((int)blockIdx.x < a.sg.n_long_blocks) {
     const int64_t n_chunks = (a.n + kBlock - 1) / kBlock;
     for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += a.sg.n_long_blocks) {
       const int64_t* rows;
@@ -515,11 +510,6 @@ __global__ __launch_bounds__(256) void gatv2_fold_kernel(const float* __restrict
   out[(int64_t)blockIdx.x * HF + c] = s;
 }
 
-template <int KIND, bool UNI>
-void launch_lpr(int lpr, dim3 grid, hipStream_t st, const V2Args& a) {
-  with_lpr<4>(lpr, [&](auto L) { hipLaunchKernelGGL((gatv2_rows_kernel<KIND, decltype(L)::value, UNI>), grid, dim3(kBlock), 0, st, a); });
-}
-
 // GLNN_ERR_UNSUPPORTED: a shape the kernels do not take; GLNN_ERR_INVALID_ARG: arguments that make no sense
 int set_shape(V2Args& a, int64_t n, int64_t nnz, int heads, int f, float p, const char* what) {
   GLNN_REQUIRE(n >= 0 && nnz >= 0 && heads >= 1 && f >= 1, "%s: bad size", what);
@@ -535,13 +525,10 @@ int set_shape(V2Args& a, int64_t n, int64_t nnz, int heads, int f, float p, cons
 }
 
 int rows_launch(V2Args& a, int kind, const char* what, void* stream) {
-  const int lpr = lpr_for((a.HF + 3) / 4, 4);
-  const dim3 grid(a.sg.grid_x);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool uni = a.F % 4 == 0;
-  if (kind == 0) { if (uni) launch_lpr<0, true>(lpr, grid, st, a); else launch_lpr<0, false>(lpr, grid, st, a); }
-  else if (kind == 1) { if (uni) launch_lpr<1, true>(lpr, grid, st, a); else launch_lpr<1, false>(lpr, grid, st, a); }
-  else { if (uni) launch_lpr<2, true>(lpr, grid, st, a); else launch_lpr<2, false>(lpr, grid, st, a); }
+  with_attn_variant(kind, a.F % 4 == 0, lpr_for((a.HF + 3) / 4, 4), [&](auto K, auto U, auto L) {
+    hipLaunchKernelGGL((gatv2_rows_kernel<decltype(K)::value, decltype(L)::value, decltype(U)::value>), dim3(a.sg.grid_x), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), a);
+  });
   return glnn::check_launch(what);
 }
 

@@ -20,6 +20,23 @@ from .autograd import appnp_propagate, gcnii_stack, linear_fn, norm_act_drop
 from .nn import GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, SAGEConv
 
 
+_KINDS = (("MLP", "mlp"), ("SAGE", "sage"), ("GCNII", "gcnii"), ("GCN", "gcn"), ("APPNP", "appnp"), ("GATv2", "gatv2"), ("GAT", "gat"),
+          ("GPRGNN", "gpr"))
+
+
+def teacher_kind(model_name):
+    """The model family a `model_name` selects: the first of _KINDS whose key the name contains (the reference's substring dispatch,
+    models.py:355,409).  The order is the rule and is written down here alone: "MLP" first ("MLP3w4" is an MLP), "GCNII" before "GCN"
+    and "GATv2" before "GAT", which they contain.  Every caller switches on the kind it returns."""
+    for key, kind in _KINDS:
+        if key in model_name:
+            return kind
+    raise ValueError(f"Unknown model_name {model_name}")
+
+
+FULL_GRAPH_KINDS = ("gcn", "gcnii", "appnp", "gat", "gatv2", "gpr")      # the teachers whose training step takes the whole graph
+
+
 def _bn_eval_fold(bn, bias):
     """Per-column (scale, shift) of  BN_eval(x + bias):  y = x*s + ((bias - rm)*s + beta), s = gamma/sqrt(rv+eps)."""
     s = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
@@ -675,85 +692,66 @@ class GCNII(nn.Module):
         return hs, linear_fn(h, self.fc_out.weight, self.fc_out.bias)
 
 
-class GAT(nn.Module):
-    """reference models.py:202-279: num_layers GATConv layers, `num_heads` heads of hidden_dim // num_heads features on every hidden layer
-    (ReLU inside the conv, outputs flattened to [N, hidden_dim] and kept in h_list), one head of output_dim features on the last (its
-    mean over one head is a reshape).  No norm layers and no dropout outside the convs (feat_drop = dropout_ratio, attn_drop)."""
+class _AttnStack(nn.Module):
+    """The layer stack GAT and GATv2 share (reference models.py:202-279): num_layers convs of class CONV, `num_heads` heads of
+    hidden_dim // num_heads features on every hidden layer (ReLU inside the conv, outputs flattened to [N, hidden_dim] and kept in
+    h_list), one head of output_dim features on the last.  No norm layers and no dropout outside the convs (feat_drop = dropout_ratio,
+    attn_drop).  A subclass names its conv, the tails of its messages and where its conf contract is written (Model.__init__)."""
+    CONV = NUM_LAYERS = CONF_DOC = None
 
     def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, num_heads=8, attn_drop=0.3,
                  negative_slope=0.2, residual=False):
         super().__init__()
+        who, conv = type(self).__name__, self.CONV
         if num_layers <= 1:
-            raise NotImplementedError("GAT: num_layers must be > 1 (the reference asserts it, models.py:218)")
+            raise NotImplementedError(f"{who}: num_layers must be > 1 ({self.NUM_LAYERS})")
         if residual:
-            raise NotImplementedError("GAT: residual=True is not implemented (the reference's Model never sets it)")
+            raise NotImplementedError(f"{who}: residual=True is not implemented ({conv.RESIDUAL})")
         hidden_dim //= num_heads
         self.num_layers = num_layers
         self.num_heads = num_heads
         self.activation = activation
-        self.layers = nn.ModuleList()
-        heads = [num_heads] * num_layers + [1]
-        self.layers.append(GATConv(input_dim, hidden_dim, heads[0], dropout_ratio, attn_drop, negative_slope, False, activation))
-        for l in range(1, num_layers - 1):
-            self.layers.append(GATConv(hidden_dim * heads[l - 1], hidden_dim, heads[l], dropout_ratio, attn_drop, negative_slope, residual,
-                                       activation))
-        self.layers.append(GATConv(hidden_dim * heads[-2], output_dim, heads[-1], dropout_ratio, attn_drop, negative_slope, residual, None))
+        dims = [input_dim] + [hidden_dim * num_heads] * (num_layers - 1)
+        self.layers = nn.ModuleList(conv(d, hidden_dim, num_heads, dropout_ratio, attn_drop, negative_slope, False, activation)
+                                    for d in dims[:-1])
+        self.layers.append(conv(dims[-1], output_dim, 1, dropout_ratio, attn_drop, negative_slope, False, None))
+
+    def conv_forward(self, l, g, h):
+        return self.layers[l](g, h)
 
     def forward(self, g, feats):
-        _need_hip(feats, "GAT.forward")
+        who = type(self).__name__
+        _need_hip(feats, f"{who}.forward")
         if isinstance(g, (list, tuple)):
-            raise NotImplementedError("GAT: block (bipartite) inputs are not implemented: the reference's GAT runs on the whole graph")
+            raise NotImplementedError(f"{who}: block (bipartite) inputs are not implemented: {self.CONV.WHOLE_GRAPH}")
         h = feats
         h_list = []
-        for l, layer in enumerate(self.layers):
-            h = layer(g, h, nonneg=True if l > 0 and self.layers[l - 1].relu() else None)   # a ReLU layer's output is >= 0
+        for l in range(self.num_layers):
+            h = self.conv_forward(l, g, h)
             if l != self.num_layers - 1:
                 h = h.flatten(1)
                 h_list.append(h)
             else:
-                h = h[:, 0]                    # mean(1) over the last layer's ONE head (heads[-1] = 1, models.py:225)
+                h = h[:, 0]                    # mean(1) over the last layer's ONE head (models.py:225)
         return h_list, h
 
 
-class GATv2(nn.Module):
-    """GATv2 (Brody, Alon, Yahav, ICLR 2022; docs/GATV2_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it) in models.GAT's shape:
-    num_layers GATv2Conv layers, `num_heads` heads of hidden_dim // num_heads features on every hidden layer (ReLU inside the conv, outputs
-    flattened to [N, hidden_dim] and kept in h_list), one head of output_dim features on the last.  No norm layers and no dropout outside
-    the convs (feat_drop = dropout_ratio, attn_drop)."""
+class GAT(_AttnStack):
+    """reference models.py:202-279 over GATConv (the last layer's mean over one head is a reshape)."""
+    CONV = GATConv
+    NUM_LAYERS = "the reference asserts it, models.py:218"
+    CONF_DOC = "no implicit 8 heads, docs/GAT_SEMANTICS.md"
 
-    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, num_heads=8, attn_drop=0.3,
-                 negative_slope=0.2, residual=False):
-        super().__init__()
-        if num_layers <= 1:
-            raise NotImplementedError("GATv2: num_layers must be > 1 (models.GAT's shape: hidden multi-head layers and a one-head last layer)")
-        if residual:
-            raise NotImplementedError("GATv2: residual=True is not implemented (docs/GATV2_SEMANTICS.md, What is refused)")
-        hidden_dim //= num_heads
-        self.num_layers = num_layers
-        self.num_heads = num_heads
-        self.activation = activation
-        self.layers = nn.ModuleList()
-        heads = [num_heads] * num_layers + [1]
-        self.layers.append(GATv2Conv(input_dim, hidden_dim, heads[0], dropout_ratio, attn_drop, negative_slope, False, activation))
-        for l in range(1, num_layers - 1):
-            self.layers.append(GATv2Conv(hidden_dim * heads[l - 1], hidden_dim, heads[l], dropout_ratio, attn_drop, negative_slope, False,
-                                         activation))
-        self.layers.append(GATv2Conv(hidden_dim * heads[-2], output_dim, heads[-1], dropout_ratio, attn_drop, negative_slope, False, None))
+    def conv_forward(self, l, g, h):
+        return self.layers[l](g, h, nonneg=True if l > 0 and self.layers[l - 1].relu() else None)   # a ReLU layer's output is >= 0
 
-    def forward(self, g, feats):
-        _need_hip(feats, "GATv2.forward")
-        if isinstance(g, (list, tuple)):
-            raise NotImplementedError("GATv2: block (bipartite) inputs are not implemented: the GATv2 teacher runs on the whole graph")
-        h = feats
-        h_list = []
-        for l, layer in enumerate(self.layers):
-            h = layer(g, h)
-            if l != self.num_layers - 1:
-                h = h.flatten(1)
-                h_list.append(h)
-            else:
-                h = h[:, 0]                    # the last layer's ONE head
-        return h_list, h
+
+class GATv2(_AttnStack):
+    """GATv2 (Brody, Alon, Yahav, ICLR 2022; docs/GATV2_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it) in models.GAT's shape,
+    over GATv2Conv."""
+    CONV = GATv2Conv
+    NUM_LAYERS = "models.GAT's shape: hidden multi-head layers and a one-head last layer"
+    CONF_DOC = "docs/GATV2_SEMANTICS.md"
 
 
 class Model(nn.Module):
@@ -767,49 +765,42 @@ class Model(nn.Module):
     def __init__(self, conf):
         super().__init__()
         self.model_name = conf["model_name"]
+        kind = self.kind
         common = dict(num_layers=conf["num_layers"], input_dim=conf["feat_dim"], hidden_dim=conf["hidden_dim"],
                       output_dim=conf["label_dim"], dropout_ratio=conf["dropout_ratio"])
-        if "MLP" in conf["model_name"]:
-            self.encoder = MLP(norm_type=conf["norm_type"], **common).to(conf["device"])
-        elif "SAGE" in conf["model_name"]:
-            self.encoder = SAGE(activation=F.relu, norm_type=conf["norm_type"], aggregator_type=conf.get("sage_aggregator", "gcn"),
-                                **common).to(conf["device"])
-        elif "GCNII" in conf["model_name"]:          # (tested before "GCN", which it contains)
+        if kind == "mlp":
+            enc = MLP(norm_type=conf["norm_type"], **common)
+        elif kind == "sage":
+            enc = SAGE(activation=F.relu, norm_type=conf["norm_type"], aggregator_type=conf.get("sage_aggregator", "gcn"), **common)
+        elif kind == "gcnii":
             alpha, lamda = conf.get("gcnii_alpha"), conf.get("gcnii_lamda")          # (absent or None: the paper's defaults)
-            self.encoder = GCNII(activation=F.relu, norm_type=conf["norm_type"], alpha=0.1 if alpha is None else alpha,
-                                 lamda=0.5 if lamda is None else lamda, **common).to(conf["device"])
-        elif "GCN" in conf["model_name"]:
-            self.encoder = GCN(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
-        elif "APPNP" in conf["model_name"]:
-            self.encoder = APPNP(activation=F.relu, norm_type=conf["norm_type"], **common).to(conf["device"])
-        elif "GATv2" in conf["model_name"]:          # (tested before "GAT", which it contains; the conf contract is GAT's)
+            enc = GCNII(activation=F.relu, norm_type=conf["norm_type"], alpha=0.1 if alpha is None else alpha,
+                        lamda=0.5 if lamda is None else lamda, **common)
+        elif kind == "gcn":
+            enc = GCN(activation=F.relu, norm_type=conf["norm_type"], **common)
+        elif kind == "appnp":
+            enc = APPNP(activation=F.relu, norm_type=conf["norm_type"], **common)
+        elif kind in ("gatv2", "gat"):               # (the conf contract of GATv2 is GAT's)
+            cls = GATv2 if kind == "gatv2" else GAT
+            who = cls.__name__
             missing = [k for k in ("num_heads", "attn_dropout_ratio") if k not in conf]
             if missing:
-                raise NotImplementedError(f"{conf['model_name']}: the conf does not name {' or '.join(missing)}; GATv2 is built only from "
-                                          "confs that carry both num_heads and attn_dropout_ratio (docs/GATV2_SEMANTICS.md)")
+                raise NotImplementedError(f"{conf['model_name']}: the conf does not name {' or '.join(missing)}; {who} is built only from "
+                                          f"confs that carry both num_heads and attn_dropout_ratio ({cls.CONF_DOC})")
             heads = int(conf["num_heads"])
             if heads < 1 or conf["hidden_dim"] < heads or conf["hidden_dim"] % heads:
-                raise ValueError(f"GATv2: hidden_dim ({conf['hidden_dim']}) must be a positive multiple of num_heads ({heads})")
-            self.encoder = GATv2(activation=F.relu, num_heads=heads, attn_drop=conf["attn_dropout_ratio"], **common).to(conf["device"])
-        elif "GAT" in conf["model_name"]:
-            missing = [k for k in ("num_heads", "attn_dropout_ratio") if k not in conf]
-            if missing:
-                raise NotImplementedError(f"{conf['model_name']}: the conf does not name {' or '.join(missing)}; GAT is built only from "
-                                          "confs that carry both num_heads and attn_dropout_ratio (no implicit 8 heads, "
-                                          "docs/GAT_SEMANTICS.md)")
-            heads = int(conf["num_heads"])
-            if heads < 1 or conf["hidden_dim"] < heads or conf["hidden_dim"] % heads:
-                raise ValueError(f"GAT: hidden_dim ({conf['hidden_dim']}) must be a positive multiple of num_heads ({heads})")
-            self.encoder = GAT(activation=F.relu, num_heads=heads, attn_drop=conf["attn_dropout_ratio"], **common).to(conf["device"])
-        elif "GPRGNN" in conf["model_name"]:
-            self.encoder = GPRGNN(activation=F.relu, norm_type=conf["norm_type"], k=conf.get("gpr_k", 10), alpha=conf.get("gpr_alpha", 0.1),
-                                  init=conf.get("gpr_init", "PPR"), **common).to(conf["device"])
+                raise ValueError(f"{who}: hidden_dim ({conf['hidden_dim']}) must be a positive multiple of num_heads ({heads})")
+            enc = cls(activation=F.relu, num_heads=heads, attn_drop=conf["attn_dropout_ratio"], **common)
         else:
-            raise ValueError(f"Unknown model_name {conf['model_name']}")
+            enc = GPRGNN(activation=F.relu, norm_type=conf["norm_type"], k=conf.get("gpr_k", 10), alpha=conf.get("gpr_alpha", 0.1),
+                         init=conf.get("gpr_init", "PPR"), **common)
+        self.encoder = enc.to(conf["device"])
+
+    kind = property(lambda self: teacher_kind(self.model_name))
 
     def forward(self, data, feats):
         """data: a graph `g`, a list of blocks, or None for MLPs."""
-        if "MLP" in self.model_name:
+        if self.kind == "mlp":
             if not self.encoder.training:           # logits only: the hidden Linear outputs need not be kept raw
                 _need_hip(feats, "MLP.forward")
                 _check_tail(self.encoder)
@@ -819,23 +810,24 @@ class Model(nn.Module):
         return self.encoder(data, feats)[1]
 
     def forward_fitnet(self, data, feats):
-        if "MLP" in self.model_name:
+        if self.kind == "mlp":
             return self.encoder(feats)
         return self.encoder(data, feats)
 
     def inference(self, data, feats, dtype=torch.float32):
         """dtype=torch.bfloat16: bf16 activation storage, the SAGE teacher's whole-graph forward only (SAGE.inference)."""
+        kind = self.kind
         if dtype != torch.float32:
-            if "GATv2" in self.model_name:
+            if kind == "gatv2":
                 raise NotImplementedError(f"GATv2.inference(dtype={dtype}): bf16 activation storage is not implemented for the GATv2 teacher "
                                           "(csrc/gatv2.hip gathers and stores fp32 rows; docs/GATV2_SEMANTICS.md, What is refused)")
-            if "GCNII" in self.model_name:
+            if kind == "gcnii":
                 raise NotImplementedError(f"GCNII.inference(dtype={dtype}): bf16 activation storage is not implemented for the GCNII teacher "
                                           "(csrc/gcnii.hip gathers and stores fp32 rows; docs/GCNII_SEMANTICS.md, Out of scope)")
-            if "SAGE" not in self.model_name:
+            if kind != "sage":
                 raise NotImplementedError(f"{self.model_name}.inference(dtype={dtype}): bf16 activation storage is implemented for the SAGE "
                                           "teacher's whole-graph forward only")
             return self.encoder.inference(data, feats, dtype=dtype)
-        if "SAGE" in self.model_name:
+        if kind == "sage":
             return self.encoder.inference(data, feats)
         return self.forward(data, feats)

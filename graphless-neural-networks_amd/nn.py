@@ -221,30 +221,63 @@ class GraphConv(nn.Module):
         return graphconv_fwd(graph, ops.as_feat(feat), self.weight, self.bias, relu)[0]
 
 
-class GATConv(nn.Module):
-    """dgl 0.6.1 GATConv on a homogeneous graph (docs/GAT_SEMANTICS.md): fc [heads * out, in] without bias, attn_l / attn_r [1, heads, out],
-    no bias parameter, res_fc a None buffer (residual=False only).  forward returns [N, heads, out]."""
+class _AttnConv(nn.Module):
+    """What GATConv and GATv2Conv share: the constructor's refusals, relu(), forward's guards and the [N, heads, out] view.  A subclass
+    registers its parameters in make_parameters() and draws them in reset_parameters() (its own RNG stream) and ends the messages."""
+    WHOLE_GRAPH = RESIDUAL = ACTIVATION = ZERO_IN_DEGREE = None
 
     def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2, residual=False, activation=None,
                  allow_zero_in_degree=False):
         super().__init__()
+        who = type(self).__name__
         if isinstance(in_feats, (tuple, list)):
-            raise NotImplementedError("GATConv: bipartite (block) inputs are not implemented: the reference's GAT runs on the whole graph")
+            raise NotImplementedError(f"{who}: bipartite (block) inputs are not implemented: {self.WHOLE_GRAPH}")
         if residual:
-            raise NotImplementedError("GATConv: residual=True is not implemented (the reference's Model never sets it)")
+            raise NotImplementedError(f"{who}: residual=True is not implemented ({self.RESIDUAL})")
         if num_heads < 1 or num_heads > 64 or num_heads * out_feats > 256:
-            raise NotImplementedError("GATConv: the attention kernels take num_heads <= 64 and num_heads * out_feats <= 256")
+            raise NotImplementedError(f"{who}: the attention kernels take num_heads <= 64 and num_heads * out_feats <= 256")
         self._in_feats, self._out_feats, self._num_heads = in_feats, out_feats, num_heads
         self._allow_zero_in_degree = allow_zero_in_degree
-        self.fc = nn.Linear(in_feats, out_feats * num_heads, bias=False)
-        self.attn_l = nn.Parameter(torch.empty(1, num_heads, out_feats))
-        self.attn_r = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.activation = activation
+        self.make_parameters(in_feats, out_feats, num_heads)
         self.feat_drop = nn.Dropout(feat_drop)
         self.attn_drop = nn.Dropout(attn_drop)
         self.negative_slope = float(negative_slope)
-        self.register_buffer("res_fc", None)
-        self.activation = activation
         self.reset_parameters()
+
+    def relu(self):
+        act = self.activation
+        relu = act is not None and getattr(act, "__name__", "") == "relu"
+        if act is not None and not relu:
+            raise NotImplementedError(f"{type(self).__name__}: only activation=F.relu or None is {self.ACTIVATION}")
+        return relu
+
+    def check_inputs(self, graph, feat):
+        if (isinstance(graph, (list, tuple)) or isinstance(feat, tuple) or graph.num_dst_nodes() != graph.num_src_nodes()
+                or feat.shape[0] != graph.num_dst_nodes()):
+            raise NotImplementedError(f"{type(self).__name__}: block (bipartite) inputs are not implemented: {self.WHOLE_GRAPH}")
+        if not self._allow_zero_in_degree and graph.has_zero_in_degree():
+            raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
+                               f"({self.ZERO_IN_DEGREE}; add self-loops or set allow_zero_in_degree).")
+
+    def by_head(self, y):
+        shape = (y.shape[0], self._num_heads, self._out_feats)
+        return y.view(shape) if y.is_contiguous() else y.reshape(shape)
+
+
+class GATConv(_AttnConv):
+    """dgl 0.6.1 GATConv on a homogeneous graph (docs/GAT_SEMANTICS.md): fc [heads * out, in] without bias, attn_l / attn_r [1, heads, out],
+    no bias parameter, res_fc a None buffer (residual=False only).  forward returns [N, heads, out]."""
+    WHOLE_GRAPH = "the reference's GAT runs on the whole graph"
+    RESIDUAL = "the reference's Model never sets it"
+    ACTIVATION = "used by the reference"
+    ZERO_IN_DEGREE = "dgl GATConv semantics"
+
+    def make_parameters(self, in_feats, out_feats, num_heads):
+        self.fc = nn.Linear(in_feats, out_feats * num_heads, bias=False)
+        self.attn_l = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.attn_r = nn.Parameter(torch.empty(1, num_heads, out_feats))
+        self.register_buffer("res_fc", None)
 
     def reset_parameters(self):
         gain = nn.init.calculate_gain("relu")
@@ -252,53 +285,29 @@ class GATConv(nn.Module):
         nn.init.xavier_normal_(self.attn_l, gain=gain)
         nn.init.xavier_normal_(self.attn_r, gain=gain)
 
-    def relu(self):
-        act = self.activation
-        relu = act is not None and getattr(act, "__name__", "") == "relu"
-        if act is not None and not relu:
-            raise NotImplementedError("GATConv: only activation=F.relu or None is used by the reference")
-        return relu
-
     def forward(self, graph, feat, nonneg=None):
         """nonneg: the caller knows feat >= 0 (a ReLU layer's output), so the feature dropout needs one product (ops.gat_project);
         None: looked at here when the dropout is active."""
-        if isinstance(feat, tuple) or graph.num_dst_nodes() != graph.num_src_nodes() or feat.shape[0] != graph.num_dst_nodes():
-            raise NotImplementedError("GATConv: block (bipartite) inputs are not implemented: the reference's GAT runs on the whole graph")
-        if not self._allow_zero_in_degree and graph.has_zero_in_degree():
-            raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
-                               "(dgl GATConv semantics; add self-loops or set allow_zero_in_degree).")
+        self.check_inputs(graph, feat)
         if nonneg is None:
             nonneg = not (self.training and self.feat_drop.p > 0) or ops.is_nonneg(feat)
-        y = gat_conv(graph, feat, self.fc.weight, self.attn_l, self.attn_r, self._num_heads, self._out_feats, self.negative_slope,
-                     self.relu(), self.feat_drop.p, self.attn_drop.p, self.training, signed=not nonneg)
-        return y.view(y.shape[0], self._num_heads, self._out_feats) if y.is_contiguous() else y.reshape(y.shape[0], self._num_heads,
-                                                                                                        self._out_feats)
+        return self.by_head(gat_conv(graph, feat, self.fc.weight, self.attn_l, self.attn_r, self._num_heads, self._out_feats,
+                                     self.negative_slope, self.relu(), self.feat_drop.p, self.attn_drop.p, self.training, signed=not nonneg))
 
 
-class GATv2Conv(nn.Module):
+class GATv2Conv(_AttnConv):
     """GATv2 attention layer on a homogeneous graph (Brody, Alon, Yahav, ICLR 2022; docs/GATV2_SEMANTICS.md): fc_src / fc_dst
     [heads * out, in] WITH bias, attn [1, heads, out]; no share_weights, no residual, no output bias.  forward returns [N, heads, out]."""
+    WHOLE_GRAPH = "the GATv2 teacher runs on the whole graph"
+    RESIDUAL = "docs/GATV2_SEMANTICS.md, What is refused"
+    ACTIVATION = "implemented (the attention kernel's epilogue)"
+    ZERO_IN_DEGREE = "GATv2Conv follows dgl GATConv"
 
-    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2, residual=False, activation=None,
-                 allow_zero_in_degree=False):
-        super().__init__()
-        if isinstance(in_feats, (tuple, list)):
-            raise NotImplementedError("GATv2Conv: bipartite (block) inputs are not implemented: the GATv2 teacher runs on the whole graph")
-        if residual:
-            raise NotImplementedError("GATv2Conv: residual=True is not implemented (docs/GATV2_SEMANTICS.md, What is refused)")
-        if num_heads < 1 or num_heads > 64 or num_heads * out_feats > 256:
-            raise NotImplementedError("GATv2Conv: the attention kernels take num_heads <= 64 and num_heads * out_feats <= 256")
-        self._in_feats, self._out_feats, self._num_heads = in_feats, out_feats, num_heads
-        self._allow_zero_in_degree = allow_zero_in_degree
+    def make_parameters(self, in_feats, out_feats, num_heads):
         self.fc_src = nn.Linear(in_feats, out_feats * num_heads, bias=True)
         self.fc_dst = nn.Linear(in_feats, out_feats * num_heads, bias=True)
         self.attn = nn.Parameter(torch.empty(1, num_heads, out_feats))
-        self.feat_drop = nn.Dropout(feat_drop)
-        self.attn_drop = nn.Dropout(attn_drop)
-        self.negative_slope = float(negative_slope)
-        self.activation = activation
-        self.relu()
-        self.reset_parameters()
+        self.relu()                                # an activation the kernel's epilogue lacks is refused by the constructor
 
     def reset_parameters(self):
         gain = nn.init.calculate_gain("relu")
@@ -308,24 +317,11 @@ class GATv2Conv(nn.Module):
         nn.init.zeros_(self.fc_src.bias)
         nn.init.zeros_(self.fc_dst.bias)
 
-    def relu(self):
-        act = self.activation
-        relu = act is not None and getattr(act, "__name__", "") == "relu"
-        if act is not None and not relu:
-            raise NotImplementedError("GATv2Conv: only activation=F.relu or None is implemented (the attention kernel's epilogue)")
-        return relu
-
     def forward(self, graph, feat):
-        if (isinstance(graph, (list, tuple)) or isinstance(feat, tuple) or graph.num_dst_nodes() != graph.num_src_nodes()
-                or feat.shape[0] != graph.num_dst_nodes()):
-            raise NotImplementedError("GATv2Conv: block (bipartite) inputs are not implemented: the GATv2 teacher runs on the whole graph")
-        if not self._allow_zero_in_degree and graph.has_zero_in_degree():
-            raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
-                               "(GATv2Conv follows dgl GATConv; add self-loops or set allow_zero_in_degree).")
-        y = gatv2_conv(graph, feat, self.fc_src.weight, self.fc_src.bias, self.fc_dst.weight, self.fc_dst.bias, self.attn, self._num_heads,
-                       self._out_feats, self.negative_slope, self.relu(), self.feat_drop.p, self.attn_drop.p, self.training)
-        return y.view(y.shape[0], self._num_heads, self._out_feats) if y.is_contiguous() else y.reshape(y.shape[0], self._num_heads,
-                                                                                                        self._out_feats)
+        self.check_inputs(graph, feat)
+        return self.by_head(gatv2_conv(graph, feat, self.fc_src.weight, self.fc_src.bias, self.fc_dst.weight, self.fc_dst.bias, self.attn,
+                                       self._num_heads, self._out_feats, self.negative_slope, self.relu(), self.feat_drop.p,
+                                       self.attn_drop.p, self.training))
 
 
 GPR_INITS = ("PPR", "NPPR", "Random")

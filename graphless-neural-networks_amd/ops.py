@@ -1795,6 +1795,42 @@ def gat_scores(z, attn_l, attn_r, heads, out_feats, z2=None):
     return el, er
 
 
+def _attn_out(name, n, heads, out_feats, device, out, lse, want_lse):
+    """(out, lse) of an attention forward `name`: allocated where None (lse only when wanted), checked either way."""
+    if out is None:
+        out = feat_empty(n, heads * out_feats, device)
+    _mat(out, f"{name} out")
+    if lse is None and want_lse:
+        lse = torch.empty((n, heads), dtype=torch.float32, device=device)
+    if lse is not None and (lse.shape != (n, heads) or not lse.is_contiguous() or lse.dtype != torch.float32 or not lse.is_cuda):
+        raise ValueError(f"{name}: lse must be a contiguous fp32 [n, heads] tensor on the GPU")
+    return out, lse
+
+
+def _attn_bwd_bufs(name, graph, n, heads, out_feats, device, dz, dattn):
+    """The common part of an attention backward `name`: (the C call's leading arguments -- in-CSR, cached transpose with edge ids, n, nnz --,
+    nnz, the [E, heads] score-gradient scratch, the row buffers dz {name: tensor or None}, the dattn vectors), allocated where None."""
+    hf = heads * out_feats
+    tg, t_eids = graph.transposed_eids()
+    nnz = graph.num_edges()
+    csr = (_p(graph.indptr), _p(graph.indices), _p(tg.indptr), _p(tg.indices), _p(t_eids), n, int(nnz))
+    ds = torch.empty((max(nnz, 1), heads), dtype=torch.float32, device=device)
+    dz = {k: feat_empty(n, hf, device) if t is None else t for k, t in dz.items()}
+    _need_cuda(*dz.values())
+    for k, t in dz.items():
+        _mat(t, f"{name} {k}")
+    dattn = [torch.empty(hf, dtype=torch.float32, device=device) if t is None else t for t in dattn]
+    return csr, nnz, ds, list(dz.values()), dattn
+
+
+def _attn_call(name, heads, out_feats, n, nnz, attn_drop, *args):
+    """glnn_<name>_f32(*args, stream) under the optional launch timing, its status checked."""
+    entry = f"glnn_{name}_f32"
+    with _Timed(name, d=heads * out_feats, n_dst=n, nnz=int(nnz), attn_drop=float(attn_drop)):
+        rc = getattr(_lib.lib(), entry)(*args, _stream())
+    _lib.check(rc, entry)
+
+
 def gat_attn_fwd(indptr, indices, nnz, z, el, er, heads, out_feats, negative_slope=0.2, attn_drop=0.0, seed=0, relu=False, want_lse=False,
                  out=None):
     """glnn_gat_attn_fwd_f32: (out [n, heads * out_feats], lse [n, heads] or None) -- edge softmax + weighted aggregation of z."""
@@ -1802,16 +1838,10 @@ def gat_attn_fwd(indptr, indices, nnz, z, el, er, heads, out_feats, negative_slo
     n = z.shape[0]
     _appnp_check(indptr, indices, z, n, "gat_attn_fwd")
     _need_cuda(el, er, out)
-    if out is None:
-        out = feat_empty(n, heads * out_feats, z.device)
-    _mat(out, "gat_attn_fwd out")
-    lse = torch.empty((n, heads), dtype=torch.float32, device=z.device) if want_lse else None
-    with _Timed("gat_attn_fwd", d=heads * out_feats, n_dst=n, nnz=int(nnz), attn_drop=float(attn_drop)):
-        rc = _lib.lib().glnn_gat_attn_fwd_f32(_p(indptr), _p(indices), n, int(nnz), _p(z), _ld(z), heads, out_feats,
-                                              _p(_vec(el.view(-1), n * heads, "el")), _p(_vec(er.view(-1), n * heads, "er")),
-                                              float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF, 1 if relu else 0, _p(out),
-                                              _ld(out), _p(lse), _stream())
-    _lib.check(rc, "glnn_gat_attn_fwd_f32")
+    out, lse = _attn_out("gat_attn_fwd", n, heads, out_feats, z.device, out, None, want_lse)
+    _attn_call("gat_attn_fwd", heads, out_feats, n, nnz, attn_drop, _p(indptr), _p(indices), n, int(nnz), _p(z), _ld(z), heads, out_feats,
+               _p(_vec(el.view(-1), n * heads, "el")), _p(_vec(er.view(-1), n * heads, "er")), float(negative_slope), float(attn_drop),
+               int(seed) & 0xFFFFFFFF, 1 if relu else 0, _p(out), _ld(out), _p(lse))
     return out, lse
 
 
@@ -1824,25 +1854,14 @@ def gat_attn_bwd(graph, z, el, er, lse, attn_l, attn_r, g, y, heads, out_feats, 
     n = z.shape[0]
     _appnp_check(graph.indptr, graph.indices, z, n, "gat_attn_bwd")
     _need_cuda(el, er, lse, attn_l, attn_r, g, y)
-    tg, t_eids = graph.transposed_eids()
-    nnz = graph.num_edges()
     dev = z.device
-    hf = heads * out_feats
-    ds = torch.empty((max(nnz, 1), heads), dtype=torch.float32, device=dev)
+    csr, nnz, ds, (dz,), (dattn_l, dattn_r) = _attn_bwd_bufs("gat_attn_bwd", graph, n, heads, out_feats, dev, {"dz": None}, (dattn_l, dattn_r))
     der = torch.empty((n, heads), dtype=torch.float32, device=dev)
     dl = torch.empty((n, heads), dtype=torch.float32, device=dev)
-    dz = feat_empty(n, hf, dev)
-    if dattn_l is None:
-        dattn_l = torch.empty(hf, dtype=torch.float32, device=dev)
-    if dattn_r is None:
-        dattn_r = torch.empty(hf, dtype=torch.float32, device=dev)
     ws = torch.empty(int(_lib.lib().glnn_gat_attn_bwd_workspace_floats(n, heads, out_feats)), dtype=torch.float32, device=dev)
-    with _Timed("gat_attn_bwd", d=hf, n_dst=n, nnz=int(nnz), attn_drop=float(attn_drop)):
-        rc = _lib.lib().glnn_gat_attn_bwd_f32(_p(graph.indptr), _p(graph.indices), _p(tg.indptr), _p(tg.indices), _p(t_eids), n, int(nnz),
-                                              _p(z), _ld(z), heads, out_feats, _p(el), _p(er), _p(lse), _p(attn_l), _p(attn_r), _p(g), _ld(g),
-                                              _p(y), _ld(y), float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF, _p(ds), _p(der),
-                                              _p(dl), _p(dz), _ld(dz), _p(dattn_l), _p(dattn_r), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "glnn_gat_attn_bwd_f32")
+    _attn_call("gat_attn_bwd", heads, out_feats, n, nnz, attn_drop, *csr, _p(z), _ld(z), heads, out_feats, _p(el), _p(er), _p(lse), _p(attn_l),
+               _p(attn_r), _p(g), _ld(g), _p(y), _ld(y), float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF, _p(ds), _p(der),
+               _p(dl), _p(dz), _ld(dz), _p(dattn_l), _p(dattn_r), _p(ws), ws.numel())
     return dz, dattn_l, dattn_r
 
 
@@ -1871,18 +1890,10 @@ def gatv2_attn_fwd(indptr, indices, nnz, zl, zr, attn, heads, out_feats, negativ
     _need_cuda(zr, attn, out)
     _mat(zr, "gatv2_attn_fwd zr")
     _gatv2_check(zl, zr, attn, heads, out_feats, "gatv2_attn_fwd")
-    if out is None:
-        out = feat_empty(n, heads * out_feats, zl.device)
-    _mat(out, "gatv2_attn_fwd out")
-    if lse is None and want_lse:
-        lse = torch.empty((n, heads), dtype=torch.float32, device=zl.device)
-    if lse is not None and (lse.shape != (n, heads) or not lse.is_contiguous() or lse.dtype != torch.float32 or not lse.is_cuda):
-        raise ValueError("gatv2_attn_fwd: lse must be a contiguous fp32 [n, heads] tensor on the GPU")
-    with _Timed("gatv2_attn_fwd", d=heads * out_feats, n_dst=n, nnz=int(nnz), attn_drop=float(attn_drop)):
-        rc = _lib.lib().glnn_gatv2_attn_fwd_f32(_p(indptr), _p(indices), n, int(nnz), _p(zl), _ld(zl), _p(zr), _ld(zr), heads, out_feats,
-                                                _p(attn), float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF,
-                                                1 if relu else 0, _p(out), _ld(out), _p(lse), _stream())
-    _lib.check(rc, "glnn_gatv2_attn_fwd_f32")
+    out, lse = _attn_out("gatv2_attn_fwd", n, heads, out_feats, zl.device, out, lse, want_lse)
+    _attn_call("gatv2_attn_fwd", heads, out_feats, n, nnz, attn_drop, _p(indptr), _p(indices), n, int(nnz), _p(zl), _ld(zl), _p(zr), _ld(zr),
+               heads, out_feats, _p(attn), float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF, 1 if relu else 0, _p(out),
+               _ld(out), _p(lse))
     return out, lse
 
 
@@ -1900,25 +1911,13 @@ def gatv2_attn_bwd(graph, zl, zr, lse, attn, g, heads, out_feats, negative_slope
     hf = heads * out_feats
     if g.shape != zl.shape or lse.shape != (n, heads) or not lse.is_contiguous() or lse.dtype != torch.float32:
         raise ValueError("gatv2_attn_bwd: g must be [n, heads * out_feats] and lse contiguous fp32 [n, heads]")
-    tg, t_eids = graph.transposed_eids()
-    nnz = graph.num_edges()
     dev = zl.device
-    ds = torch.empty((max(nnz, 1), heads), dtype=torch.float32, device=dev)
-    dzl = feat_empty(n, hf, dev) if dzl is None else dzl
-    dzr = feat_empty(n, hf, dev) if dzr is None else dzr
-    _need_cuda(dzl, dzr)
-    _mat(dzl, "gatv2_attn_bwd dzl")
-    _mat(dzr, "gatv2_attn_bwd dzr")
-    if dattn is None:
-        dattn = torch.empty(hf, dtype=torch.float32, device=dev)
+    csr, nnz, ds, (dzl, dzr), (dattn,) = _attn_bwd_bufs("gatv2_attn_bwd", graph, n, heads, out_feats, dev, {"dzl": dzl, "dzr": dzr}, (dattn,))
     _vec(dattn, hf, "dattn")
     ws = torch.empty(max(int(_lib.lib().glnn_gatv2_attn_bwd_workspace_floats(n, heads, out_feats)), 1), dtype=torch.float32, device=dev)
-    with _Timed("gatv2_attn_bwd", d=hf, n_dst=n, nnz=int(nnz), attn_drop=float(attn_drop)):
-        rc = _lib.lib().glnn_gatv2_attn_bwd_f32(_p(graph.indptr), _p(graph.indices), _p(tg.indptr), _p(tg.indices), _p(t_eids), n, int(nnz),
-                                                _p(zl), _ld(zl), _p(zr), _ld(zr), heads, out_feats, _p(lse), _p(attn), _p(g), _ld(g),
-                                                float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF, _p(ds), _p(dzl),
-                                                _ld(dzl), _p(dzr), _ld(dzr), _p(dattn), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "glnn_gatv2_attn_bwd_f32")
+    _attn_call("gatv2_attn_bwd", heads, out_feats, n, nnz, attn_drop, *csr, _p(zl), _ld(zl), _p(zr), _ld(zr), heads, out_feats, _p(lse),
+               _p(attn), _p(g), _ld(g), float(negative_slope), float(attn_drop), int(seed) & 0xFFFFFFFF, _p(ds), _p(dzl), _ld(dzl), _p(dzr),
+               _ld(dzr), _p(dattn), _p(ws), ws.numel())
     return dzl, dzr, dattn
 
 

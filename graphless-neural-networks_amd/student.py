@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from .models import teacher_kind
 
 
 def _mix32(x):
@@ -44,7 +45,7 @@ class StudentEngine:
         `self.flat_grads`, see glnn_amd.dist.make_grad_sync).  loss_scale_rows: the GLOBAL batch size when
         the batch is split over ranks (the loss mean and dlogits are taken over it)."""
         enc = model.encoder
-        if "MLP" not in model.model_name or enc.norm_type not in ("none", "batch", "layer"):
+        if teacher_kind(model.model_name) != "mlp" or enc.norm_type not in ("none", "batch", "layer"):
             raise NotImplementedError("StudentEngine: MLP students with norm_type none|batch|layer (reference models.py:28-31)")
         if type(optimizer) is not torch.optim.Adam:
             raise NotImplementedError("StudentEngine: the reference uses torch.optim.Adam (train_student.py:275)")
@@ -358,7 +359,7 @@ def student_supported(model, criterion, optimizer, feats=None, labels=None):
         raise NotImplementedError("student step: the criterion must be nn.NLLLoss() or nn.KLDivLoss(reduction='batchmean', "
                                   "log_target=True) (reference train_student.py:278-279)")
     enc = model.encoder
-    if "MLP" not in model.model_name or enc.norm_type not in ("none", "batch", "layer"):
+    if teacher_kind(model.model_name) != "mlp" or enc.norm_type not in ("none", "batch", "layer"):
         raise NotImplementedError("student step: MLP students with norm_type none|batch|layer (reference models.py:28-31)")
     if enc.num_layers > _lib.MLP_MAX_LAYERS:
         raise NotImplementedError(f"student step: at most {_lib.MLP_MAX_LAYERS} layers")

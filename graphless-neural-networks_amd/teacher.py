@@ -28,6 +28,7 @@ synchronisation:
 The engine works IN PLACE on the Model's parameters / BatchNorm buffers and on the torch optimizer's state tensors, exactly
 like glnn_amd.student.StudentEngine, so state_dict(), early-stopping snapshots and optimizer.state_dict() keep working."""
 import ctypes
+import functools
 import os
 
 import torch
@@ -35,6 +36,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
+from .models import teacher_kind
 from .autograd import (appnp_bwd, appnp_fwd, gat_layer_bwd, gat_layer_fwd, gatv2_layer_bwd, gatv2_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd,
                        graphconv_fwd)
 from .student import _mix32
@@ -67,34 +69,36 @@ def _check_norms_and_device(who, model):
                            "pass --device 0)")
 
 
+_NORM_RELU = {"sage": "SAGE with norm_type none|batch|layer and ReLU (the reference's configs)",
+              "appnp": "APPNP with norm_type none|batch|layer and ReLU (models.py:282-344)",
+              "gpr": "GPRGNN with norm_type none|batch|layer and ReLU (docs/GPR_SEMANTICS.md)"}
+_ATTN_RELU = {"gatv2": "GATv2 with ReLU hidden layers and a linear last layer (docs/GATV2_SEMANTICS.md)",
+              "gat": "GAT with ReLU hidden layers and a linear last layer (models.py:202-279)"}
+
+
 def check_supported(model, criterion, optimizer):
     """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GATv2, GPRGNN or GCNII teacher."""
     enc = model.encoder
     name = model.model_name
-    if "MLP" in name or not ("SAGE" in name or "GCN" in name or "APPNP" in name or "GAT" in name or "GPRGNN" in name):
+    try:
+        kind = teacher_kind(name)
+    except ValueError:           # (a name no family claims: refused like the MLP)
+        kind = "mlp"
+    if kind == "mlp":
         raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GATv2, GPRGNN or GCNII teachers only (got {name})")
     _check_criterion_and_optimizer("TeacherEngine", criterion, optimizer)
-    if "GCNII" in name:          # (tested before "GCN", which it contains; the encoder's constructor refused everything else)
+    if kind == "gcnii":          # (the encoder's constructor refused everything else)
         if enc.norm_type != "none" or not _is_relu(enc.activation):
             raise NotImplementedError("TeacherEngine: GCNII with norm_type none and ReLU (docs/GCNII_SEMANTICS.md)")
-    elif "SAGE" in name:
-        if getattr(enc, "aggregator_type", "gcn") != "gcn":
+    elif kind in _NORM_RELU:
+        if kind == "sage" and getattr(enc, "aggregator_type", "gcn") != "gcn":
             raise NotImplementedError(f"TeacherEngine: the one-call SAGE step implements the 'gcn' aggregator only; a SAGE "
                                       f"{enc.aggregator_type!r} teacher trains through SAGE.forward's differentiable ops (train_sage)")
         if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
-            raise NotImplementedError("TeacherEngine: SAGE with norm_type none|batch|layer and ReLU (the reference's configs)")
-    elif "APPNP" in name:
-        if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
-            raise NotImplementedError("TeacherEngine: APPNP with norm_type none|batch|layer and ReLU (models.py:282-344)")
-    elif "GPRGNN" in name:
-        if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
-            raise NotImplementedError("TeacherEngine: GPRGNN with norm_type none|batch|layer and ReLU (docs/GPR_SEMANTICS.md)")
-    elif "GATv2" in name:        # (tested before "GAT", which it contains)
+            raise NotImplementedError("TeacherEngine: " + _NORM_RELU[kind])
+    elif kind in _ATTN_RELU:
         if not _is_relu(enc.activation) or any(not lay.relu() for lay in enc.layers[:-1]) or enc.layers[-1].relu():
-            raise NotImplementedError("TeacherEngine: GATv2 with ReLU hidden layers and a linear last layer (docs/GATV2_SEMANTICS.md)")
-    elif "GAT" in name:
-        if not _is_relu(enc.activation) or any(not lay.relu() for lay in enc.layers[:-1]) or enc.layers[-1].relu():
-            raise NotImplementedError("TeacherEngine: GAT with ReLU hidden layers and a linear last layer (models.py:202-279)")
+            raise NotImplementedError("TeacherEngine: " + _ATTN_RELU[kind])
     else:
         if enc.norm_type not in ("none", "batch", "layer"):      # train.conf.yaml: cora-style GCN none, pokec / penn94 GCN batch
             raise NotImplementedError("TeacherEngine: GCN with norm_type none|batch|layer")
@@ -246,9 +250,7 @@ _GCN_BLOCKS, _MEAN_BLOCKS = _GcnBlocks(), _MeanBlocks()
 class TeacherEngine:
     def __init__(self, model, optimizer):
         self.model, self.enc, self.opt = model, model.encoder, optimizer
-        name = model.model_name
-        self.kind = ("gcnii" if "GCNII" in name else "sage" if "SAGE" in name else "appnp" if "APPNP" in name else "gatv2" if "GATv2" in name
-                     else "gat" if "GAT" in name else "gpr" if "GPRGNN" in name else "gcn")
+        self.kind = teacher_kind(model.model_name)
         self.L = self.enc.num_layers
         self.bn = getattr(self.enc, "norm_type", "none") == "batch"
         self.ln = getattr(self.enc, "norm_type", "none") == "layer"
@@ -730,67 +732,61 @@ class TeacherEngine:
         """The reference's full-graph `train` (train_and_eval.py:12-29) over GAT (models.py:202-279): per layer the projection with the
         feature dropout in its operand load, glnn_gat_scores_f32 and glnn_gat_attn_fwd_f32; NLL over idx_train; per layer
         glnn_gat_attn_bwd_f32 over the graph and its transpose, the weight gradient and the input gradient; Adam."""
-        if g.has_zero_in_degree():
-            raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
-                               "(dgl GATConv semantics; add self-loops or set allow_zero_in_degree).")
-        self._run_full_graph(self._step_gat_body, g, feats, labels, idx_train, lamb)
+        self._step_attn(self._step_gat_body, "dgl GATConv semantics", g, feats, labels, idx_train, lamb)
 
-    def _step_gat_body(self, g, feats, labels, idx_train, lamb):
-        enc, L = self.enc, self.L
-        n = g.num_dst_nodes()
-        x = ops.as_feat(feats)
-        signed0 = self.p > 0 and not ops.is_nonneg(feats)
-        acts, saved = [x], []
-        for l, lay in enumerate(enc.layers):
-            fs, as_ = self._seed(l), self._attn_seed(l)
-            y, sv = gat_layer_fwd(g, acts[l], lay.fc.weight, lay.attn_l, lay.attn_r, lay._num_heads, lay._out_feats, lay.negative_slope,
-                                  l != L - 1, lay.feat_drop.p, fs, lay.attn_drop.p, as_, signed0 if l == 0 else False, want_lse=True)
-            saved.append((sv, fs, as_))
-            acts.append(y)
-        gy = self._loss_grad(acts[L], labels, idx_train, lamb, n)
-        for l in range(L - 1, -1, -1):
-            lay = enc.layers[l]
-            sv, fs, as_ = saved[l]
-            da, _, _, _ = gat_layer_bwd(g, gy, acts[l + 1], sv, acts[l], lay.fc.weight, lay.attn_l, lay.attn_r, lay._num_heads,
-                                        lay._out_feats, lay.negative_slope, lay.feat_drop.p, fs, lay.attn_drop.p, as_,
-                                        signed0 if l == 0 else False, need_dx=l > 0, dw=self.grad(lay.fc.weight),
-                                        dattn_l=self.grad(lay.attn_l).view(-1), dattn_r=self.grad(lay.attn_r).view(-1))
-            if l > 0:      # the feature-dropout mask of layer l and the ReLU mask of layer l - 1 (its stored output is post-ReLU)
-                gy = ops.bn_relu_bwd(da, acts[l], dz=da, drop_p=lay.feat_drop.p, drop_seed=fs)[0]
-        ops.note_param_write()
-
-    # ------------------------------------------------------------------------------------------ full-graph GATv2
     @torch.no_grad()
     def step_gatv2(self, g, feats, labels, idx_train, lamb=1.0):
         """The full-graph `train` step over GATv2 (docs/GATV2_SEMANTICS.md): per layer the dropped copy of the input, the two projections
         and glnn_gatv2_attn_fwd_f32; NLL over idx_train; per layer glnn_gatv2_attn_bwd_f32 over the graph and its transpose, the two weight
         gradients with their bias column sums and the input gradient; the ONE Adam launch."""
+        self._step_attn(self._step_gatv2_body, "GATv2Conv follows dgl GATConv", g, feats, labels, idx_train, lamb)
+
+    def _step_attn(self, body, semantics, g, feats, labels, idx_train, lamb):
         if g.has_zero_in_degree():
             raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
-                               "(GATv2Conv follows dgl GATConv; add self-loops or set allow_zero_in_degree).")
-        self._run_full_graph(self._step_gatv2_body, g, feats, labels, idx_train, lamb)
+                               f"({semantics}; add self-loops or set allow_zero_in_degree).")
+        self._run_full_graph(body, g, feats, labels, idx_train, lamb)
 
-    def _step_gatv2_body(self, g, feats, labels, idx_train, lamb):
+    def _step_attn_body(self, fwd, bwd, signed_input, g, feats, labels, idx_train, lamb):
+        """Forward, loss and backward of an attention teacher through its per-kind pair (fwd, bwd).  acts[l] is the input of layer l: the
+        features, then the stored (post-ReLU) output of layer l - 1.  signed_input: GAT's, whose feature dropout rides in the projection."""
         enc, L = self.enc, self.L
-        n = g.num_dst_nodes()
-        a = ops.as_feat(feats)
-        saved = []
+        acts, saved = [ops.as_feat(feats)], []
+        signed0 = signed_input and self.p > 0 and not ops.is_nonneg(feats)
         for l, lay in enumerate(enc.layers):
             fs, as_ = self._seed(l), self._attn_seed(l)
-            a, sv = gatv2_layer_fwd(g, a, lay.fc_src.weight, lay.fc_src.bias, lay.fc_dst.weight, lay.fc_dst.bias, lay.attn, lay._num_heads,
-                                    lay._out_feats, lay.negative_slope, l != L - 1, lay.feat_drop.p, fs, lay.attn_drop.p, as_, want_lse=True)
-            saved.append((sv, fs, as_, a))
-        gy = self._loss_grad(a, labels, idx_train, lamb, n)
+            y, sv = fwd(self, g, lay, acts[l], l != L - 1, fs, as_, signed0 and l == 0)
+            saved.append((sv, fs, as_))
+            acts.append(y)
+        gy = self._loss_grad(acts[L], labels, idx_train, lamb, g.num_dst_nodes())
         for l in range(L - 1, -1, -1):
             lay = enc.layers[l]
-            sv, fs, as_, _ = saved[l]
-            da = gatv2_layer_bwd(g, gy, sv, lay.fc_src.weight, lay.fc_dst.weight, lay.attn, lay._num_heads, lay._out_feats,
-                                 lay.negative_slope, lay.attn_drop.p, as_, need_dx=l > 0, dw_src=self.grad(lay.fc_src.weight),
-                                 db_src=self.grad(lay.fc_src.bias), dw_dst=self.grad(lay.fc_dst.weight), db_dst=self.grad(lay.fc_dst.bias),
-                                 dattn=self.grad(lay.attn).view(-1))[0]
+            sv, fs, as_ = saved[l]
+            da = bwd(self, g, lay, gy, acts[l], acts[l + 1], sv, fs, as_, signed0 and l == 0, l > 0)
             if l > 0:      # the feature-dropout mask of layer l and the ReLU mask of layer l - 1 (its stored output is post-ReLU)
-                gy = ops.bn_relu_bwd(da, saved[l - 1][3], dz=da, drop_p=lay.feat_drop.p, drop_seed=fs)[0]
+                gy = ops.bn_relu_bwd(da, acts[l], dz=da, drop_p=lay.feat_drop.p, drop_seed=fs)[0]
         ops.note_param_write()
+
+    def _gat_fwd(self, g, lay, x, relu, fs, as_, signed):
+        return gat_layer_fwd(g, x, lay.fc.weight, lay.attn_l, lay.attn_r, lay._num_heads, lay._out_feats, lay.negative_slope, relu,
+                             lay.feat_drop.p, fs, lay.attn_drop.p, as_, signed, want_lse=True)
+
+    def _gat_bwd(self, g, lay, gy, x, y, sv, fs, as_, signed, need_dx):
+        return gat_layer_bwd(g, gy, y, sv, x, lay.fc.weight, lay.attn_l, lay.attn_r, lay._num_heads, lay._out_feats, lay.negative_slope,
+                             lay.feat_drop.p, fs, lay.attn_drop.p, as_, signed, need_dx=need_dx, dw=self.grad(lay.fc.weight),
+                             dattn_l=self.grad(lay.attn_l).view(-1), dattn_r=self.grad(lay.attn_r).view(-1))[0]
+
+    def _gatv2_fwd(self, g, lay, x, relu, fs, as_, signed):
+        return gatv2_layer_fwd(g, x, lay.fc_src.weight, lay.fc_src.bias, lay.fc_dst.weight, lay.fc_dst.bias, lay.attn, lay._num_heads,
+                               lay._out_feats, lay.negative_slope, relu, lay.feat_drop.p, fs, lay.attn_drop.p, as_, want_lse=True)
+
+    def _gatv2_bwd(self, g, lay, gy, x, y, sv, fs, as_, signed, need_dx):      # (the dropped input copy is among what the forward saved)
+        return gatv2_layer_bwd(g, gy, sv, lay.fc_src.weight, lay.fc_dst.weight, lay.attn, lay._num_heads, lay._out_feats, lay.negative_slope,
+                               lay.attn_drop.p, as_, need_dx=need_dx, dw_src=self.grad(lay.fc_src.weight), db_src=self.grad(lay.fc_src.bias),
+                               dw_dst=self.grad(lay.fc_dst.weight), db_dst=self.grad(lay.fc_dst.bias), dattn=self.grad(lay.attn).view(-1))[0]
+
+    _step_gat_body = functools.partialmethod(_step_attn_body, _gat_fwd, _gat_bwd, True)
+    _step_gatv2_body = functools.partialmethod(_step_attn_body, _gatv2_fwd, _gatv2_bwd, False)
 
 
 def get_engine(model, optimizer):

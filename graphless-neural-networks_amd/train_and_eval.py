@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .models import FULL_GRAPH_KINDS, teacher_kind
 from .graph import (FullNeighborLoader, MultiLayerFullNeighborSampler, MultiLayerNeighborSampler, NodeDataLoader,
                     RandomWalkSubgraphLoader)
 from . import teacher
@@ -32,7 +33,7 @@ def train(model, data, feats, labels, criterion, optimizer, idx_train, lamb=1):
     TeacherEngine.step_gcn (GCN) / step_appnp (APPNP) / step_gat (GAT) / step_gatv2 (GATv2) / step_gpr (GPRGNN) / step_gcnii (GCNII) -- forward, NLL over idx_train, backward over the transposed graph, Adam -- on libglnn_hip.so.
     Returns the unscaled loss like the reference's `loss.item()`."""
     teacher.check_supported(model, criterion, optimizer)
-    if not any(k in model.model_name for k in ("GCN", "APPNP", "GAT", "GPRGNN")):          # ("GCNII" contains "GCN", "GATv2" contains "GAT")
+    if teacher_kind(model.model_name) not in FULL_GRAPH_KINDS:
         raise NotImplementedError("train(): the full-graph step is implemented for the GCN, APPNP, GAT, GATv2, GPRGNN and GCNII teachers (SAGE trains "
                                   "with train_sage)")
     model.train()
@@ -54,14 +55,14 @@ def train_sage(model, dataloader, feats, labels, criterion, optimizer, lamb=1, m
     _train_sage_autograd, "native" = one TeacherEngine.step_sage_mean per batch, the loader in engine mode with plain transposes."""
     if mean_step not in SAGE_MEAN_STEPS:
         raise ValueError(f"train_sage: mean_step must be one of {SAGE_MEAN_STEPS} (got {mean_step!r})")
-    is_mean = "SAGE" in model.model_name and getattr(model.encoder, "aggregator_type", "gcn") == "mean"
+    is_mean = teacher_kind(model.model_name) == "sage" and getattr(model.encoder, "aggregator_type", "gcn") == "mean"
     if is_mean and mean_step == "autograd":
         return _train_sage_autograd(model, dataloader, feats, labels, criterion, optimizer, lamb)
     if is_mean:
         teacher.check_supported_mean(model, criterion, optimizer)
     else:
         teacher.check_supported(model, criterion, optimizer)
-    if "SAGE" not in model.model_name:
+    if teacher_kind(model.model_name) != "sage":
         raise NotImplementedError("train_sage(): GraphSAGE teachers only")
     model.train()
     eng = teacher.get_engine(model, optimizer)
@@ -90,12 +91,11 @@ def train_sage(model, dataloader, feats, labels, criterion, optimizer, lamb=1, m
 
 
 def _full_graph_step(eng, model_name):
-    """The TeacherEngine step train() runs for a model of this name ("GCNII" contains "GCN" and "GATv2" contains "GAT": tested first)."""
-    for key, step in (("GCNII", eng.step_gcnii), ("APPNP", eng.step_appnp), ("GATv2", eng.step_gatv2), ("GAT", eng.step_gat),
-                      ("GPRGNN", eng.step_gpr), ("GCN", eng.step_gcn)):
-        if key in model_name:
-            return step
-    raise NotImplementedError(f"no full-graph step for {model_name}")
+    """The TeacherEngine step train() runs for a model of this name: step_<kind> of the full-graph kinds."""
+    kind = teacher_kind(model_name)
+    if kind not in FULL_GRAPH_KINDS:
+        raise NotImplementedError(f"no full-graph step for {model_name}")
+    return getattr(eng, "step_" + kind)
 
 
 def train_subgraph(model, loader, feats, labels, criterion, optimizer, lamb=1):
@@ -104,9 +104,10 @@ def train_subgraph(model, loader, feats, labels, criterion, optimizer, lamb=1):
     gathered and the SAME TeacherEngine step train() picks for the model runs on the subgraph, its loss the plain mean over the subgraph's
     training nodes (docs/SUBGRAPH_SEMANTICS.md: a biased, Cluster-GCN-style estimator).  The per-batch losses are summed on the device and
     read ONCE per epoch, as in train_sage; returns their mean."""
-    if "MLP" in model.model_name:
+    kind = teacher_kind(model.model_name)
+    if kind == "mlp":
         raise NotImplementedError("train_subgraph(): graph teachers only -- the MLP trains with train_mini_batch")
-    if "SAGE" in model.model_name:
+    if kind == "sage":
         raise NotImplementedError("train_subgraph(): the full-graph teachers only -- SAGE trains on sampled blocks with train_sage")
     teacher.check_supported(model, criterion, optimizer)
     model.train()
@@ -124,7 +125,7 @@ def train_subgraph(model, loader, feats, labels, criterion, optimizer, lamb=1):
 
 def _subgraph_loader(conf, model, g, idx_train):
     """The RandomWalkSubgraphLoader of a run whose conf asks for one (`subgraph_walk_length` > 0, a full-graph teacher), else None."""
-    if int(conf.get("subgraph_walk_length", 0) or 0) <= 0 or "MLP" in model.model_name or "SAGE" in model.model_name:
+    if int(conf.get("subgraph_walk_length", 0) or 0) <= 0 or teacher_kind(model.model_name) not in FULL_GRAPH_KINDS:
         return None
     return RandomWalkSubgraphLoader(g, idx_train, conf["batch_size"], int(conf["subgraph_walk_length"]),
                                     self_loop=conf.get("subgraph_self_loop", "keep"), shuffle=True)
@@ -295,7 +296,7 @@ def run_transductive(conf, model, g, feats, labels, indices, criterion, evaluato
     idx_train, idx_val, idx_test = indices
     feats, labels = feats.to(device), labels.to(device)
     idx_train, idx_val, idx_test = idx_train.to(device), idx_val.to(device), idx_test.to(device)
-    is_mlp, is_sage = "MLP" in model.model_name, "SAGE" in model.model_name
+    is_mlp, is_sage = model.kind == "mlp", model.kind == "sage"
     if is_sage:
         # the reference's two loaders (train_and_eval.py:176-205), sampling on the GPU-resident CSR
         g = g.to(device)
@@ -387,7 +388,7 @@ def run_inductive(conf, model, g, feats, labels, indices, criterion, evaluator, 
     obs_idx_train, obs_idx_val, obs_idx_test, idx_obs, idx_test_ind = [i.to(device) for i in indices]
     feats, labels = feats.to(device), labels.to(device)
     obs_feats, obs_labels = feats[idx_obs], labels[idx_obs]
-    is_mlp, is_sage = "MLP" in model.model_name, "SAGE" in model.model_name
+    is_mlp, is_sage = model.kind == "mlp", model.kind == "sage"
     if is_mlp:
         feats_train, labels_train = obs_feats[obs_idx_train], obs_labels[obs_idx_train]
         feats_val, labels_val = obs_feats[obs_idx_val], obs_labels[obs_idx_val]

@@ -245,6 +245,38 @@ def test_engine_and_train_recognise_the_name_before_gat():
     assert hasattr(teacher.TeacherEngine, "step_gatv2")
 
 
+def test_one_resolver_routes_every_configured_name(monkeypatch):
+    """models.teacher_kind over every model name of train.conf.yaml (read from the file) plus the names a substring rule can mis-route:
+    the kind, Model's encoder class, TeacherEngine.kind and train()'s step all follow it.  The expectation is derived apart from the
+    resolver: a configured name is a family name with an optional "GA1" prefix and width suffix ("3w4")."""
+    import yaml
+    from glnn_amd import models, ops, teacher
+    from glnn_amd.train_and_eval import _full_graph_step
+    family = {"MLP": ("mlp", models.MLP), "SAGE": ("sage", models.SAGE), "GCNII": ("gcnii", models.GCNII), "GCN": ("gcn", models.GCN),
+              "APPNP": ("appnp", models.APPNP), "GATv2": ("gatv2", models.GATv2), "GAT": ("gat", models.GAT),
+              "GPRGNN": ("gpr", models.GPRGNN)}
+    conf = yaml.safe_load(open(os.path.join(ROOT, "train.conf.yaml")))
+    names = {name for ds, section in conf.items() if ds != "global" for name in section}
+    assert {"MLP", "SAGE", "GCN", "GAT", "GATv2", "MLP3w4"} <= names
+    names |= {"GCNII", "GATv2", "GAT", "GCN", "GPRGNN", "MLP3w4"}
+    monkeypatch.setattr(ops, "TensorTable", lambda *a: None)               # the engine's only GPU-bound member
+    for name in sorted(names):
+        kind, cls = family[re.sub(r"\d+w\d+$", "", re.sub(r"^GA1", "", name))]
+        assert models.teacher_kind(name) == kind, name
+        m = models.Model(_conf(model_name=name))
+        assert type(m.encoder) is cls and m.kind == kind, name
+        eng = teacher.TeacherEngine(m, torch.optim.Adam(m.parameters(), lr=0.01))
+        assert eng.kind == kind, name
+        if kind in ("mlp", "sage"):
+            with pytest.raises(NotImplementedError, match="no full-graph step"):
+                _full_graph_step(eng, name)
+        else:
+            assert _full_graph_step(eng, name) == getattr(eng, "step_" + kind), name
+    for name in ("GCII", "GPR", "gat", ""):
+        with pytest.raises(ValueError, match="Unknown model_name"):
+            models.teacher_kind(name)
+
+
 def test_cli_and_training_config():
     from glnn_amd.cli import get_student_args, get_teacher_args
     from glnn_amd.utils import get_training_config
