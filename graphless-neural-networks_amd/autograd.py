@@ -174,11 +174,33 @@ class _NormActDropFn(torch.autograd.Function):
 _drop_counter = [0]
 
 
+def _draw_base(count=None):
+    """The base of the count-th per-process dropout draw of a graph teacher's op (a site's seed: (base + its tag) & 0xFFFFFFFF).  None: a
+    NEW draw, the one place the call counter advances for APPNP, GCNII and the attention layers; tests replay masks from a recorded count."""
+    if count is None:
+        _drop_counter[0] += 1
+        count = _drop_counter[0]
+    return int(torch.initial_seed()) * 0x85EBCA77 + count * 0x9E3779B1
+
+
+def _differentiable(training, *tensors):
+    """The rule of every graph teacher's op: through its autograd.Function only in training mode with something to differentiate;
+    otherwise the forward runs under no_grad and keeps nothing for a backward."""
+    return training and torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def _pingpong(n, d, device, count):
+    """buf(t) for step t of a chain of `count` launches that each read the one before: two [n, d] buffers in turn (or one, or none)."""
+    bufs = [ops.feat_empty(n, d, device) for _ in range(min(count, 2))]
+    return lambda t: bufs[t % len(bufs)]
+
+
 def norm_act_drop(z, bn, p, relu=True):
     """Training-mode tail of a hidden layer: norm -> ReLU -> dropout (MLP / SAGE, reference models.py:48-52, 113-117) or, with
     relu=False, norm -> dropout (GCN, models.py:195-198: the ReLU sits inside the GraphConv).  bn: nn.BatchNorm1d (reference
     defaults), nn.LayerNorm, or None; p: dropout probability.
-    The dropout stream is counter-based: seed = hash(torch.initial_seed(), call counter)."""
+    The dropout stream is counter-based: seed = hash(torch.initial_seed(), call counter) -- _draw_base's multipliers the other way
+    round, and the counter advances for p = 0 too, so it keeps its own line."""
     _drop_counter[0] += 1
     seed = (int(torch.initial_seed()) * 0x9E3779B1 + _drop_counter[0] * 0x85EBCA77) & 0xFFFFFFFF if p > 0 else 0
     if bn is not None:
@@ -198,11 +220,11 @@ def appnp_fwd(g, h0, k, alpha, edge_drop=0.0, seed=0):
         return out
     in_norm, out_norm = g.degree_norms()
     nnz = g.num_edges()
-    bufs = [ops.feat_empty(n, d, h0.device) for _ in range(min(k, 2))]
+    buf = _pingpong(n, d, h0.device, k)
     x = h0
     for t in range(1, k + 1):
         x = ops.appnp_propagate(g.indptr, g.indices, x, nnz, t, in_norm, out_norm, h0, alpha, edge_drop, seed, x_scaled=t > 1,
-                                last=t == k, out=bufs[t % len(bufs)])
+                                last=t == k, out=buf(t))
     return x
 
 
@@ -218,11 +240,11 @@ def appnp_bwd(g, dy, k, alpha, edge_drop=0.0, seed=0):
     tg, t_eids = g.transposed_eids()
     nnz = g.num_edges()
     acc = ops.feat_empty(n, d, dy.device) if k > 1 else None
-    bufs = [ops.feat_empty(n, d, dy.device) for _ in range(min(k, 2))]
+    buf = _pingpong(n, d, dy.device, k)
     x = dy
     for t in range(k, 0, -1):
         x = ops.appnp_propagate_bwd(tg.indptr, tg.indices, t_eids, x, nnz, t, t == k, in_norm, out_norm, alpha, edge_drop, seed, acc=acc,
-                                    out=bufs[t % len(bufs)])
+                                    out=buf(t))
     return x
 
 
@@ -242,15 +264,16 @@ class AppnpPropFn(torch.autograd.Function):
         return None, dh0, None, None, None, None
 
 
+def appnp_edge_seed(count):
+    """The edge-dropout seed of the count-th dropout draw of this process (tests replay the masks from it; None: a new draw)."""
+    return (_draw_base(count) + 0x41505050) & 0xFFFFFFFF
+
+
 def appnp_propagate(graph, h0, k, alpha, edge_drop, training):
-    """APPNPConv forward of the reference's APPNP (models.py:342): edge dropout only in training; its counter-based seed is drawn like
-    norm_act_drop's (torch.initial_seed() and a call counter)."""
+    """APPNPConv forward of the reference's APPNP (models.py:342): edge dropout only in training (one _draw_base draw)."""
     p = float(edge_drop) if training else 0.0
-    seed = 0
-    if p > 0:
-        _drop_counter[0] += 1
-        seed = (int(torch.initial_seed()) * 0x85EBCA77 + _drop_counter[0] * 0x9E3779B1 + 0x41505050) & 0xFFFFFFFF
-    if training and torch.is_grad_enabled() and h0.requires_grad:
+    seed = appnp_edge_seed(None) if p > 0 else 0
+    if _differentiable(training, h0):
         return AppnpPropFn.apply(graph, h0, int(k), float(alpha), p, seed)
     with torch.no_grad():
         return appnp_fwd(graph, h0, int(k), float(alpha), p, seed)
@@ -268,11 +291,11 @@ def _gpr_run(csr, nnz, x0, gamma, k, first_norm, row_norm, h0=None):
     if k == 0:
         ops.gpr_prop(None, None, 0, x0, 0, None, None, None, gamma, acc, h0=h0, row_dot=row_dot)
         return acc, row_dot
-    bufs = [ops.feat_empty(n, d, x0.device) for _ in range(min(k - 1, 2))]
+    buf = _pingpong(n, d, x0.device, k - 1)
     x = x0
     for j in range(1, k + 1):
         x = ops.gpr_prop(csr.indptr, csr.indices, nnz, x, j, first_norm if j == 1 else None, row_norm, first_norm, gamma, acc,
-                         out=None if j == k else bufs[j % len(bufs)], h0=h0, row_dot=row_dot)
+                         out=None if j == k else buf(j), h0=h0, row_dot=row_dot)
     return acc, row_dot
 
 
@@ -315,8 +338,8 @@ class GprPropFn(torch.autograd.Function):
 
 
 def gpr_propagate(graph, h0, gamma, k, training):
-    """GPRConv forward: differentiable in training mode (appnp_propagate's rule); the eval forward keeps nothing for a backward."""
-    if training and torch.is_grad_enabled() and (h0.requires_grad or gamma.requires_grad):
+    """GPRConv forward, differentiable by _differentiable's rule."""
+    if _differentiable(training, h0, gamma):
         return GprPropFn.apply(graph, h0, gamma, int(k))
     with torch.no_grad():
         return gpr_fwd(graph, h0, gamma, int(k))
@@ -360,14 +383,14 @@ def gcnii_bwd(g, da, hs, ss, weights, alpha, betas, dws, drop_p=0.0, seeds=None,
     tg = g.transposed(False)
     nnz = g.num_edges()
     dz, acc = ops.feat_empty(n, d, da.device), ops.feat_empty(n, d, da.device)
-    bufs = [ops.feat_empty(n, d, da.device) for _ in range(min(L, 2))]
+    buf = _pingpong(n, d, da.device, L)
     seed = lambda s: seeds[s] if drop_p > 0 else 0
     x = da
     for l in range(L, 0, -1):
         p_l = drop_p if (l < L or drop_last) else 0.0
         x = ops.gcnii_layer_bwd(tg.indptr, tg.indices, nnz, x, hs[l - 1], weights[l - 1].t().contiguous(), alpha, betas[l - 1], dz, acc,
                                 first=l == L, row_norm=out_norm, out_norm=in_norm, plain=l == L, drop_p=p_l, drop_seed=seed(l + 1),
-                                dz_scale=betas[l - 1], ds_out=bufs[l % len(bufs)])
+                                dz_scale=betas[l - 1], ds_out=buf(l))
         ops.gemm_tn(dz, ss[l - 1], out=dws[l - 1])
     return ops.gcnii_layer_bwd(tg.indptr, tg.indices, nnz, x, None, None, alpha, 0.0, dz, acc, first=False, row_norm=out_norm,
                                drop_p=drop_p, drop_seed=seed(1))
@@ -399,20 +422,16 @@ class GcniiStackFn(torch.autograd.Function):
 
 
 def gcnii_stack_seeds(count, sites):
-    """The seeds of the dropout sites 0..sites-1 of the count-th dropout draw of this process (tests replay the masks from them)."""
-    base = int(torch.initial_seed()) * 0x85EBCA77 + count * 0x9E3779B1 + 0x47434E32
+    """The seeds of the dropout sites 0..sites-1 of the count-th dropout draw of this process (tests replay the masks; None: a new draw)."""
+    base = _draw_base(count) + 0x47434E32
     return [(base + s * 0x632BE5AB) & 0xFFFFFFFF for s in range(sites)]
 
 
 def gcnii_stack(graph, h0, weights, alpha, betas, drop_p, training):
-    """[H_1..H_L] of the conv stack: differentiable in training mode (appnp_propagate's rule; the per-layer dropout only then, its
-    counter-based seeds drawn like norm_act_drop's); the eval forward keeps nothing for a backward."""
+    """[H_1..H_L] of the conv stack: the per-layer dropout only in training (one _draw_base draw for all its sites)."""
     p = float(drop_p) if training else 0.0
-    seeds = None
-    if p > 0:
-        _drop_counter[0] += 1
-        seeds = gcnii_stack_seeds(_drop_counter[0], len(weights) + 2)
-    if training and torch.is_grad_enabled() and (h0.requires_grad or any(w.requires_grad for w in weights)):
+    seeds = gcnii_stack_seeds(None, len(weights) + 2) if p > 0 else None
+    if _differentiable(training, h0, *weights):
         return list(GcniiStackFn.apply(graph, h0, float(alpha), tuple(betas), p, seeds, *weights))
     with torch.no_grad():
         return gcnii_fwd(graph, h0, list(weights), float(alpha), betas, p, seeds)[0]
@@ -420,8 +439,8 @@ def gcnii_stack(graph, h0, weights, alpha, betas, drop_p, training):
 
 # ------------------------------------------------------------------------------------------ what the two attention layers share
 def _attn_seeds(count, tag_feat, tag_attn):
-    """(feature-dropout seed, attention-dropout seed) of the count-th dropout draw of this process (tests replay the masks from them)."""
-    base = int(torch.initial_seed()) * 0x85EBCA77 + count * 0x9E3779B1
+    """(feature-dropout seed, attention-dropout seed) of the count-th dropout draw of this process (tests replay them; None: a new draw)."""
+    base = _draw_base(count)
     return (base + tag_feat) & 0xFFFFFFFF, (base + tag_attn) & 0xFFFFFFFF
 
 
@@ -430,15 +449,11 @@ gatv2_conv_seeds = functools.partial(_attn_seeds, tag_feat=0x47563246, tag_attn=
 
 
 def _attn_conv(fn, layer_fwd, seeds, graph, x, params, shape, feat_drop, attn_drop, training, *extra):
-    """Both attention convs: the dropouts only in training, their counter-based seeds drawn like norm_act_drop's; differentiable in
-    training mode (appnp_propagate's rule), else the eval forward, which keeps nothing.  shape = (heads, out_feats, slope, relu)."""
+    """Both attention convs: the dropouts only in training (one _draw_base draw).  shape = (heads, out_feats, slope, relu)."""
     fp, ap = (float(feat_drop), float(attn_drop)) if training else (0.0, 0.0)
-    fs = as_ = 0
-    if fp > 0 or ap > 0:
-        _drop_counter[0] += 1
-        fs, as_ = seeds(_drop_counter[0])
+    fs, as_ = seeds(None) if fp > 0 or ap > 0 else (0, 0)
     args = (*params, *shape, fp, fs, ap, as_, *extra)
-    if training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+    if _differentiable(training, x, *params):
         return fn.apply(graph, x, *args)
     with torch.no_grad():
         return layer_fwd(graph, ops.as_feat(x), *args)[0]

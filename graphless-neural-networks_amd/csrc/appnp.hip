@@ -13,8 +13,9 @@
 // dropped edge's feature row is never loaded -- the kept entries of a 64-edge index chunk are compacted with ds_permute before the loads.
 // Every kept edge carries the same weight 1 / (1 - p), so the sum runs over the plain rows and dscale goes into the row's coefficient.
 //
-// Mapping: row_gather_dev.h's wave gather under the two-role scan, rows pulled from an LDS ticket.  Wider rows: blockIdx.y = the 256-column tile.
-#include "row_gather_dev.h"
+// Mapping: row_gather_dev.h's wave gather under the two-role scan, rows pulled from an LDS ticket.  Wider rows: blockIdx.y = the
+// 256-column tile (prop_dev.h's to_col_tile).
+#include "prop_dev.h"
 
 namespace {
 
@@ -98,12 +99,7 @@ __device__ __forceinline__ void finish_row(const PropArgs& a, int64_t v, float4 
 template <int LPR, bool BWD, bool XN>
 __global__ __launch_bounds__(kBlock) void appnp_prop_kernel(const PropArgs a0) {
   PropArgs a = a0;
-  if (gridDim.y > 1) {                                  // the 256-column tile of this workgroup
-    const int off = 256 * (int)blockIdx.y;
-    a.x += off; a.out += off; a.d = a0.d - off < 256 ? a0.d - off : 256;
-    if (a.h0) a.h0 += off;
-    if (a.acc) a.acc += off;
-  }
+  to_col_tile<2>(gridDim.y, a.d, a.x, a.out, a.h0, a.acc);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int col4 = (lane % LPR) * 4;
@@ -112,25 +108,19 @@ __global__ __launch_bounds__(kBlock) void appnp_prop_kernel(const PropArgs a0) {
   ld.x = a.x; ld.ldx = a.ldx; ld.x_norm = a.x_norm; ld.col4 = col4; ld.col_ok = col_ok;
   ld.eids = a.eids; ld.thr = a.thr; ld.seed = a.seed; ld.t = a.t;
   scan_rows(a.indptr, a.n, a.sg, lane, wave, [&](int64_t v, int wave_id, int n_waves) {
-    float4 sum = wave_row_sum<LPR>(a.indices, a.indptr[v], a.indptr[v + 1], wave_id, n_waves, lane, ld);
-    if (n_waves > 1) sum = sum_waves_in_order<LPR>(sum, wave_id, lane);
+    const float4 sum = row_sum<LPR>(a.indptr, a.indices, v, wave_id, n_waves, lane, ld);
     if (wave_id == 0 && lane < LPR && col_ok) finish_row<BWD>(a, v, sum, col4);
   });
 }
 
-template <bool BWD, bool XN>
-void launch_lpr(int lpr, dim3 grid, hipStream_t st, const PropArgs& a) {
-  with_lpr<1>(lpr, [&](auto L) { hipLaunchKernelGGL((appnp_prop_kernel<decltype(L)::value, BWD, XN>), grid, dim3(kBlock), 0, st, a); });
-}
-
 int prop_launch(PropArgs& a, int64_t nnz, int bwd, const char* what, void* stream) {
-  GLNN_REQUIRE(a.n >= 0 && a.d >= 1 && nnz >= 0, "%s: bad size", what);
-  GLNN_REQUIRE(nnz < ((int64_t)1 << 31), "%s: nnz >= 2^31 (edge ids are 32-bit)", what);
+  GLNN_TRY(prop_sizes_ok(what, a.n, a.d, nnz));
+  GLNN_TRY(prop_nnz_ok(what, nnz, GLNN_ERR_INVALID_ARG, "edge ids"));
   if (a.n == 0) return GLNN_OK;
   GLNN_REQUIRE(a.indptr && (a.indices || nnz == 0) && a.x && a.out && a.row_norm, "%s: null pointer", what);
   GLNN_REQUIRE(bwd ? (a.acc != nullptr || (a.first && a.last)) : a.h0 != nullptr, "%s: null pointer", what);
   GLNN_REQUIRE(rows_ok(a.x, a.ldx, a.d) && rows_ok(a.out, a.ldo, a.d) && rows_ok(a.h0, a.ldh0, a.d) &&
-               rows_ok(a.acc, a.ldacc, a.d), "%s: rows must be 16-byte aligned with a leading dimension %% 4 == 0 and >= round4(d)", what);
+               rows_ok(a.acc, a.ldacc, a.d), kRowsText, what);
   GLNN_REQUIRE(a.out != a.x && (!a.h0 || a.out != a.h0) && (!a.acc || (a.acc != a.out && a.acc != a.x)),
                "%s: out must not alias the input, h0 or acc", what);
   const int lpr = lpr_for(((a.d < 256 ? a.d : 256) + 3) / 4, 1);
@@ -138,9 +128,9 @@ int prop_launch(PropArgs& a, int64_t nnz, int bwd, const char* what, void* strea
   if (rc != GLNN_OK) return rc;
   const dim3 grid(a.sg.grid_x, (unsigned)((a.d + 255) / 256));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool xn = a.x_norm != nullptr;
-  if (bwd) { if (xn) launch_lpr<true, true>(lpr, grid, st, a); else launch_lpr<true, false>(lpr, grid, st, a); }
-  else { if (xn) launch_lpr<false, true>(lpr, grid, st, a); else launch_lpr<false, false>(lpr, grid, st, a); }
+  with_prop_variant<1>(bwd != 0, a.x_norm != nullptr, lpr, [&](auto BWD, auto XN, auto L) {
+    hipLaunchKernelGGL((appnp_prop_kernel<decltype(L)::value, decltype(BWD)::value, decltype(XN)::value>), grid, dim3(kBlock), 0, st, a);
+  });
   return glnn::check_launch(what);
 }
 

@@ -1,5 +1,5 @@
 // GCNII (Chen et al., "Simple and Deep Graph Convolutional Networks", ICML 2020; docs/GCNII_SEMANTICS.md) for gfx950 (MI355X): one launch
-// per conv layer and direction over P = D_in^-1/2 A D_out^-1/2, the operator of appnp.hip / gpr.hip.
+// per conv layer and direction over P = D_in^-1/2 A D_out^-1/2 (prop_dev.h: what the three files over P share).
 //
 //   forward   S = (1 - alpha) P drop(H_{l-1}) + alpha H_0          (eq. 5: initial residual)
 //             H_l = relu((1 - beta) S + beta S W^T)                 (eq. 5: identity mapping)
@@ -20,7 +20,7 @@
 //
 // No float atomics and no grid barrier: a row's value is a fixed-order sum over its own edges (one wave, or eight waves with a fixed split
 // and fold), so results are bit-identical run to run and do not depend on which other rows are in the launch or on the tile order.
-#include "row_gather_dev.h"
+#include "prop_dev.h"
 
 namespace {
 
@@ -167,14 +167,6 @@ __global__ __launch_bounds__(kBlock) void gcnii_layer_kernel(const GcniiArgs a) 
   }
 }
 
-template <bool XN, bool DROP>
-void launch_lpr(const GcniiArgs& a, unsigned blocks, size_t smem, hipStream_t st) {
-  // float4 per padded row: LPR * 4 >= kpad
-  with_lpr<16>(lpr_for(a.kgroups * 2, 16), [&](auto L) {
-    hipLaunchKernelGGL((gcnii_layer_kernel<decltype(L)::value, XN, DROP>), dim3(blocks), dim3(kBlock), smem, st, a);
-  });
-}
-
 // the geometry depends on d alone (LPR, the LDS tile) and on ceil(n / 32): no branch on n
 int launch(GcniiArgs& a, const char* what, void* stream) {
   a.kgroups = (a.d + 7) / 8;
@@ -182,12 +174,21 @@ int launch(GcniiArgs& a, const char* what, void* stream) {
   GLNN_REQUIRE(blocks < ((int64_t)1 << 31), "%s: n too large for one launch", what);
   const size_t smem = sizeof(float) * kTileRows * (a.kgroups * 8 + 4) + fold_bytes();      // <= 37392 bytes at d = 256
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a.src_thr) {                             // the training forward: the source-keyed mask on every gathered element
-    if (a.x_norm) launch_lpr<true, true>(a, (unsigned)blocks, smem, st); else launch_lpr<false, true>(a, (unsigned)blocks, smem, st);
-  } else {
-    if (a.x_norm) launch_lpr<true, false>(a, (unsigned)blocks, smem, st); else launch_lpr<false, false>(a, (unsigned)blocks, smem, st);
-  }
+  // DROP: the training forward, the source-keyed mask on every gathered element.  float4 per padded row: LPR * 4 >= kpad
+  with_prop_variant<16>(a.x_norm != nullptr, a.src_thr != 0, lpr_for(a.kgroups * 2, 16), [&](auto XN, auto DROP, auto L) {
+    hipLaunchKernelGGL((gcnii_layer_kernel<decltype(L)::value, decltype(XN)::value, decltype(DROP)::value>), dim3((unsigned)blocks),
+                       dim3(kBlock), smem, st, a);
+  });
   return glnn::check_launch(what);
+}
+
+// the first checks of both entries, in their order
+int entry_checks(const char* what, int64_t n, int d, int64_t nnz, float drop_p) {
+  GLNN_TRY(prop_sizes_ok(what, n, d, nnz));
+  GLNN_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p must be in [0, 1)", what);
+  GLNN_TRY(prop_nnz_ok(what, nnz, GLNN_ERR_UNSUPPORTED, "CSR positions"));
+  if (d > kMaxD) return glnn::fail(GLNN_ERR_UNSUPPORTED, "%s: hidden widths of at most %d (got %d)", what, kMaxD, d);
+  return GLNN_OK;
 }
 
 }  // namespace
@@ -197,14 +198,11 @@ extern "C" int glnn_gcnii_layer_f32(const int64_t* indptr, const int32_t* indice
                                     int64_t ldh0, float alpha, float beta, const float* w_packed, float drop_p, uint32_t drop_seed,
                                     float* s_out, int64_t lds, float* out, int64_t ldo, const int32_t* tile_order, void* stream) {
   const char* what = "glnn_gcnii_layer_f32";
-  GLNN_REQUIRE(n >= 0 && d >= 1 && nnz >= 0, "%s: bad size", what);
-  GLNN_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p must be in [0, 1)", what);
-  if (nnz >= ((int64_t)1 << 31)) return glnn::fail(GLNN_ERR_UNSUPPORTED, "%s: nnz >= 2^31 (CSR positions are 32-bit)", what);
-  if (d > kMaxD) return glnn::fail(GLNN_ERR_UNSUPPORTED, "%s: hidden widths of at most %d (got %d)", what, kMaxD, d);
+  GLNN_TRY(entry_checks(what, n, d, nnz, drop_p));
   if (n == 0) return GLNN_OK;
   GLNN_REQUIRE(indptr && (indices || nnz == 0) && x && row_norm && h0 && w_packed && out, "%s: null pointer", what);
   GLNN_REQUIRE(rows_ok(x, ldx, d) && rows_ok(h0, ldh0, d) && rows_ok(s_out, lds, d) && rows_ok(out, ldo, d) && glnn::aligned16(w_packed),
-               "%s: rows must be 16-byte aligned with a leading dimension %% 4 == 0 and >= round4(d)", what);
+               kRowsText, what);
   GLNN_REQUIRE(out != x && out != h0 && (!s_out || (s_out != x && s_out != h0 && s_out != out)), "%s: out / s_out must not alias an input",
                what);
   GcniiArgs a = {};
@@ -221,17 +219,14 @@ extern "C" int glnn_gcnii_layer_bwd_f32(const int64_t* t_indptr, const int32_t* 
                                         const float* wt_packed, float dz_scale, float* dz_out, int64_t lddz, float* ds_out, int64_t ldds,
                                         float* dh0_acc, int64_t ldacc, int first, const int32_t* tile_order, void* stream) {
   const char* what = "glnn_gcnii_layer_bwd_f32";
-  GLNN_REQUIRE(n >= 0 && d >= 1 && nnz >= 0, "%s: bad size", what);
-  GLNN_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p must be in [0, 1)", what);
-  if (nnz >= ((int64_t)1 << 31)) return glnn::fail(GLNN_ERR_UNSUPPORTED, "%s: nnz >= 2^31 (CSR positions are 32-bit)", what);
-  if (d > kMaxD) return glnn::fail(GLNN_ERR_UNSUPPORTED, "%s: hidden widths of at most %d (got %d)", what, kMaxD, d);
+  GLNN_TRY(entry_checks(what, n, d, nnz, drop_p));
   if (n == 0) return GLNN_OK;
   GLNN_REQUIRE(g && dz_out && dh0_acc && (h || !wt_packed), "%s: null pointer", what);
   GLNN_REQUIRE(plain || (t_indptr && (t_indices || nnz == 0) && row_norm), "%s: null pointer (the gather form needs the transposed CSR)", what);
   GLNN_REQUIRE((wt_packed == nullptr) == (ds_out == nullptr), "%s: wt_packed and ds_out go together (both NULL: the dH_0 launch)", what);
   GLNN_REQUIRE(wt_packed || (!plain && !first), "%s: the dH_0 launch is a gather behind at least one layer launch", what);
   GLNN_REQUIRE(rows_ok(g, ldg, d) && rows_ok(h, ldh, d) && rows_ok(dz_out, lddz, d) && rows_ok(ds_out, ldds, d) && rows_ok(dh0_acc, ldacc, d) &&
-               glnn::aligned16(wt_packed), "%s: rows must be 16-byte aligned with a leading dimension %% 4 == 0 and >= round4(d)", what);
+               glnn::aligned16(wt_packed), kRowsText, what);
   GLNN_REQUIRE(dz_out != g && ds_out != g && dh0_acc != g && dz_out != ds_out && dz_out != dh0_acc && (!ds_out || ds_out != dh0_acc) &&
                (!h || (h != dz_out && h != ds_out && h != dh0_acc)), "%s: outputs must not alias an input or each other", what);
   GcniiArgs a = {};

@@ -1,7 +1,7 @@
 // GPR-GNN propagation (Chien et al., ICLR 2021; docs/GPR_SEMANTICS.md) for gfx950 (MI355X): out = sum_{k = 0..K} gamma_k P^k h0 with
-// K + 1 LEARNED coefficients, P = D_in^-1/2 A D_out^-1/2 -- the operator of appnp.hip.  One launch per step k = 1..K serves both
-// directions: the forward over the in-CSR with (x_norm, row_norm, out_norm) = (src_norm, dst_norm, src_norm), the backward over the
-// transposed CSR with the norms swapped (G_k = P^T G_{k-1}; no edge ids: there is no edge dropout).
+// K + 1 LEARNED coefficients, P = D_in^-1/2 A D_out^-1/2 (prop_dev.h: what the three files over P share).  One launch per step
+// k = 1..K serves both directions: the forward over the in-CSR with (x_norm, row_norm, out_norm) = (src_norm, dst_norm, src_norm), the
+// backward over the transposed CSR with the norms swapped (G_k = P^T G_{k-1}; no edge ids: there is no edge dropout).
 //
 //   step k:  row[i] = row_norm[i] * sum_{e = (j -> i)} xs[j],   xs = x_norm * x at k = 1 (x = h0 or g, unscaled), else the previous step's
 //            stored rows, which are PRE-SCALED by out_norm (no per-edge multiply after step 1)
@@ -13,8 +13,8 @@
 //   gamma is read from device memory (the parameter tensor Adam updates in place): no host read.
 //
 // Mapping: row_gather_dev.h's wave gather under the two-role scan, rows pulled from an LDS ticket.  Wider rows: blockIdx.y = the
-// 256-column tile (row_dot then holds one scalar per tile and row).  No float atomics, no grid barrier.
-#include "row_gather_dev.h"
+// 256-column tile (prop_dev.h's to_col_tile; row_dot then holds one scalar per tile and row).  No float atomics, no grid barrier.
+#include "prop_dev.h"
 
 namespace {
 
@@ -89,12 +89,7 @@ template <int LPR, bool XN, bool DOT>
 __global__ __launch_bounds__(kBlock) void gpr_prop_kernel(const GprArgs a0) {
   GprArgs a = a0;
   const int tile = (int)blockIdx.y, tiles = (int)gridDim.y;
-  if (tiles > 1) {                                      // the 256-column tile of this workgroup
-    const int off = 256 * tile;
-    a.x += off; a.acc += off; a.d = a0.d - off < 256 ? a0.d - off : 256;
-    if (a.out) a.out += off;
-    if (a.h0) a.h0 += off;
-  }
+  to_col_tile<2>(tiles, a.d, a.x, a.acc, a.out, a.h0);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int col4 = (lane % LPR) * 4;
@@ -103,8 +98,7 @@ __global__ __launch_bounds__(kBlock) void gpr_prop_kernel(const GprArgs a0) {
   NormRows<XN> ld;
   ld.x = a.x; ld.ldx = a.ldx; ld.x_norm = a.x_norm; ld.col4 = col4; ld.col_ok = col_ok;
   scan_rows(a.indptr, a.n, a.sg, lane, wave, [&](int64_t v, int wave_id, int n_waves) {
-    float4 sum = wave_row_sum<LPR>(a.indices, a.indptr[v], a.indptr[v + 1], wave_id, n_waves, lane, ld);
-    if (n_waves > 1) sum = sum_waves_in_order<LPR>(sum, wave_id, lane);
+    float4 sum = row_sum<LPR>(a.indptr, a.indices, v, wave_id, n_waves, lane, ld);
     if (wave_id == 0) finish_row<LPR, DOT>(a, v, sum, col4, on, lane, tile, tiles);      // (wave-uniform: all 64 lanes reach its shuffles)
   });
 }
@@ -114,6 +108,8 @@ template <int LPR, bool DOT>
 __global__ __launch_bounds__(kBlock) void gpr_scale_kernel(const GprArgs a0) {
   GprArgs a = a0;
   const int tile = (int)blockIdx.y, tiles = (int)gridDim.y;
+  // to_col_tile written out: behind the function this kernel alone comes out with another prologue (a branch where the two selects
+  // are now) and 30 SGPRs for 34, every LPR; appnp_prop_kernel and gpr_prop_kernel come out the same instruction for instruction
   if (tiles > 1) {
     const int off = 256 * tile;
     a.x += off; a.acc += off; a.d = a0.d - off < 256 ? a0.d - off : 256;
@@ -147,11 +143,6 @@ __global__ __launch_bounds__(kBlock) void gpr_scale_kernel(const GprArgs a0) {
       if (on && lane == 0) a.row_dot[(int64_t)tile * a.n + v] = d0;
     }
   }
-}
-
-template <bool XN, bool DOT>
-void launch_lpr(int lpr, dim3 grid, hipStream_t st, const GprArgs& a) {
-  with_lpr<1>(lpr, [&](auto L) { hipLaunchKernelGGL((gpr_prop_kernel<decltype(L)::value, XN, DOT>), grid, dim3(kBlock), 0, st, a); });
 }
 
 template <bool DOT>
@@ -203,8 +194,8 @@ extern "C" int glnn_gpr_prop_f32(const int64_t* indptr, const int32_t* indices, 
                                  const float* x_norm, const float* row_norm, const float* out_norm, const float* gamma, int k, float* acc,
                                  int64_t ldacc, float* out, int64_t ldo, const float* h0, int64_t ldh0, float* row_dot, void* stream) {
   const char* what = "glnn_gpr_prop_f32";
-  GLNN_REQUIRE(n >= 0 && d >= 1 && nnz >= 0 && k >= 0, "%s: bad size", what);
-  if (nnz >= ((int64_t)1 << 31)) return glnn::fail(GLNN_ERR_UNSUPPORTED, "%s: nnz >= 2^31 (CSR positions are 32-bit)", what);
+  GLNN_TRY(prop_sizes_ok(what, n, d, nnz, k >= 0));
+  GLNN_TRY(prop_nnz_ok(what, nnz, GLNN_ERR_UNSUPPORTED, "CSR positions"));
   if (n == 0) return GLNN_OK;
   GLNN_REQUIRE(x && acc && gamma, "%s: null pointer", what);
   GLNN_REQUIRE(k == 0 || (indptr && (indices || nnz == 0) && row_norm), "%s: null pointer", what);
@@ -213,7 +204,7 @@ extern "C" int glnn_gpr_prop_f32(const int64_t* indptr, const int32_t* indices, 
   GLNN_REQUIRE(k <= 1 || !x_norm, "%s: steps k > 1 gather pre-scaled rows (x_norm must be NULL)", what);
   GLNN_REQUIRE(k == 0 || !out || out_norm, "%s: a stored row is pre-scaled for the next step (out_norm required with out)", what);
   GLNN_REQUIRE(rows_ok(x, ldx, d) && rows_ok(acc, ldacc, d) && rows_ok(k ? out : nullptr, ldo, d) && rows_ok(h0, ldh0, d),
-               "%s: rows must be 16-byte aligned with a leading dimension %% 4 == 0 and >= round4(d)", what);
+               kRowsText, what);
   GLNN_REQUIRE(acc != x && (k == 0 || !out || (out != x && out != acc)) && (!h0 || h0 != acc), "%s: acc / out must not alias an input", what);
   GprArgs a = {};
   a.indptr = indptr; a.indices = indices; a.n = n; a.d = d;
@@ -233,9 +224,9 @@ extern "C" int glnn_gpr_prop_f32(const int64_t* indptr, const int32_t* indices, 
   const int rc = scan_grid(n, what, &a.sg);
   if (rc != GLNN_OK) return rc;
   const dim3 grid(a.sg.grid_x, tiles);
-  const bool xn = x_norm != nullptr;
-  if (h0) { if (xn) launch_lpr<true, true>(lpr, grid, st, a); else launch_lpr<false, true>(lpr, grid, st, a); }
-  else { if (xn) launch_lpr<true, false>(lpr, grid, st, a); else launch_lpr<false, false>(lpr, grid, st, a); }
+  with_prop_variant<1>(x_norm != nullptr, h0 != nullptr, lpr, [&](auto XN, auto DOT, auto L) {
+    hipLaunchKernelGGL((gpr_prop_kernel<decltype(L)::value, decltype(XN)::value, decltype(DOT)::value>), grid, dim3(kBlock), 0, st, a);
+  });
   return glnn::check_launch(what);
 }
 

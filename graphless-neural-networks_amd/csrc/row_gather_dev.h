@@ -1,4 +1,5 @@
-// The CSR row gather shared by the graph-teacher kernels (appnp.hip, gpr.hip, gcnii.hip, gat.hip, gatv2.hip, sage_mean.hip, sage_mean_step.hip):
+// The CSR row gather shared by the graph-teacher kernels (appnp.hip, gpr.hip and gcnii.hip through prop_dev.h, gat.hip and gatv2.hip
+// through attn_dev.h, sage_mean.hip, sage_mean_step.hip; deepwalk.hip borrows the lane layout):
 // the ideas of spmm.hip for narrow rows, tuned there and kept in ONE place here.  Included inside each translation unit; everything is
 // static to the including file.
 //
@@ -13,7 +14,7 @@
 //                                   ones together, the eight partials folded through four LDS slots (fold_waves_tree);
 //   the two-role scan (scan_rows)   the first n_long_blocks workgroups search the row lengths (find_long_rows) and take every long row of
 //                                   the graph, the partials summed in wave order; the others take the short rows of their block.
-// gat.hip and gatv2.hip (through attn_dev.h) write the two loops out around find_long_rows, with the short rows assigned statically, and
+// gat.hip and gatv2.hip write the two loops out around find_long_rows, with the short rows assigned statically, and
 // do NOT share them as a function.  A scan_rows_static<ASCENDING>(indptr, n, sg, wave, row) here, tried with the build's flags, left every
 // gatv2_rows_kernel figure alone but took gat_rows_kernel<2, ..> from 71 / 71 / 77 / 90 VGPRs (LPR 32 / 16 / 8 / 4, UNI) to 107 / 109 /
 // 112 / 120 and its non-UNI forms from 84 - 102 to 113 - 126: a wave per SIMD less.  Taking sg and the callable by reference, by value, or

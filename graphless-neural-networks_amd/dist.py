@@ -378,32 +378,21 @@ def _fp32_only(dtype, who):
                                   "SAGE.inference(..., dtype=torch.bfloat16) on one device)")
 
 
-def _refuse_gat(encoder, who):
-    if type(encoder).__name__ == "GAT":
-        raise NotImplementedError(f"{who}: the GAT teacher is not sharded -- its edge softmax needs every in-edge of a row and the per-head "
-                                  "scores of the remote sources, an exchange the sharded forward does not have (whole-graph GAT only)")
+# teachers whose forward needs remote rows through an exchange the sharded forward does not have: class name -> what it needs
+UNSHARDED_TEACHERS = {
+    "GAT": "its edge softmax needs every in-edge of a row and the per-head scores of the remote sources",
+    "GATv2": "its edge softmax needs every in-edge of a row and the whole projected rows of the remote sources",
+    "GPRGNN": "each of its K propagation steps needs the previous step's rows of the remote sources",
+    "GCNII": "each of its conv layers needs the previous layer's hidden rows of the remote sources",
+}
 
 
-def _refuse_gatv2(encoder, who):
-    if type(encoder).__name__ == "GATv2":
-        raise NotImplementedError(f"{who}: the GATv2 teacher is not sharded -- its edge softmax needs every in-edge of a row and the whole "
-                                  "projected rows of the remote sources, an exchange the sharded forward does not have (whole-graph GATv2 "
-                                  "only)")
-
-
-def _refuse_gpr(encoder, who):
-    if type(encoder).__name__ == "GPRGNN":
-        raise NotImplementedError(f"{who}: the GPRGNN teacher is not sharded -- each of its K propagation steps needs the previous step's "
-                                  "rows of the remote sources, an exchange the sharded forward does not have (whole-graph GPRGNN only)")
-
-
-def _refuse_gcnii(encoder, who):
-    if type(encoder).__name__ == "GCNII":
-        raise NotImplementedError(f"{who}: the GCNII teacher is not sharded -- each of its conv layers needs the previous layer's hidden "
-                                  "rows of the remote sources, an exchange the sharded forward does not have (whole-graph GCNII only)")
-
-
-def _refuse_mean(encoder, who):
+def _refuse_unsharded(encoder, who):
+    """The encoders neither sharded teacher runs: the kinds of UNSHARDED_TEACHERS, then a SAGE with another aggregator than 'gcn'."""
+    kind = type(encoder).__name__
+    if kind in UNSHARDED_TEACHERS:
+        raise NotImplementedError(f"{who}: the {kind} teacher is not sharded -- {UNSHARDED_TEACHERS[kind]}, an exchange the sharded "
+                                  f"forward does not have (whole-graph {kind} only)")
     if getattr(encoder, "aggregator_type", "gcn") != "gcn":
         raise NotImplementedError(f"{who}: the sharded teacher forward implements the SAGE 'gcn' aggregator only -- a SAGE "
                                   f"{encoder.aggregator_type!r} teacher (separate fc_self) runs on one device (SAGE.inference)")
@@ -427,11 +416,7 @@ class ShardedTeacher:
         "mixed":  (round 6) a fraction `mixed_fraction` of every chunk's rows travels wide, the rest narrow -- the continuous form between
                   the two: `shards` is replaced by shards.mixed(mixed_fraction) (whole chunks of either kind).
         All are chunked and overlapped when shards.chunks > 1; results are identical."""
-        _refuse_gat(encoder, "ShardedTeacher")
-        _refuse_gpr(encoder, "ShardedTeacher")
-        _refuse_gcnii(encoder, "ShardedTeacher")
-        _refuse_gatv2(encoder, "ShardedTeacher")
-        _refuse_mean(encoder, "ShardedTeacher")
+        _refuse_unsharded(encoder, "ShardedTeacher")
         if widening_exchange not in ("narrow", "wide", "mixed"):
             raise ValueError("ShardedTeacher: widening_exchange must be 'narrow', 'wide' or 'mixed'")
         if widening_exchange == "mixed":
@@ -1022,11 +1007,7 @@ class HaloShardedTeacher:
         a widening layer projects its own rows while the halo rows of its aggregate travel, and an aggregation whose input is
         being exchanged runs in two passes over the split CSR of HaloPlan.split_csr (local-source edges + self first, then the
         remote-source edges once the halo has landed).  Same sums, local edges before remote ones (results equal to rounding)."""
-        _refuse_gat(encoder, "HaloShardedTeacher")
-        _refuse_gpr(encoder, "HaloShardedTeacher")
-        _refuse_gcnii(encoder, "HaloShardedTeacher")
-        _refuse_gatv2(encoder, "HaloShardedTeacher")
-        _refuse_mean(encoder, "HaloShardedTeacher")
+        _refuse_unsharded(encoder, "HaloShardedTeacher")
         self.enc, self.g, self.sh, self.be, self.group, self.overlap = encoder, graph_shard, shards, be, group, overlap
         if graph_shard.n_dst != shards.rows:
             raise ValueError(f"HaloShardedTeacher: the graph shard has {graph_shard.n_dst} rows, the shard range {shards.rows}")

@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .autograd import appnp_propagate, gcnii_stack, linear_fn, norm_act_drop
-from .nn import GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, SAGEConv
+from .nn import GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, SAGEConv, _whole_graph_only
 
 
 _KINDS = (("MLP", "mlp"), ("SAGE", "sage"), ("GCNII", "gcnii"), ("GCN", "gcn"), ("APPNP", "appnp"), ("GATv2", "gatv2"), ("GAT", "gat"),
@@ -606,43 +606,47 @@ class GCN(nn.Module):
         return h_list, h
 
 
-class APPNP(MLP):
-    """reference models.py:282-344: the MLP trunk (same layers, norms and state_dict keys) followed by dgl APPNPConv(k, alpha, edge_drop)
-    -- K power iterations of personalised-PageRank propagation with a fresh edge-dropout mask per iteration in training."""
+class _TrunkProp(MLP):
+    """What APPNP and GPRGNN share: the MLP trunk (same layers, norms and state_dict keys), its Linears initialised once more (the
+    reference's APPNP does so, models.py:282-344: the RNG stream is kept in step), and forward = self.propagate(g, trunk logits)."""
 
-    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", edge_drop=0.5,
-                 alpha=0.1, k=10):
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none"):
         super().__init__(num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, norm_type)
         self.activation = activation
-        self.k, self.alpha, self.edge_drop = int(k), float(alpha), float(edge_drop)
         self.reset_parameters()
 
     def reset_parameters(self):
-        for layer in self.layers:          # (the reference re-initialises its Linears once more: the RNG stream is kept in step)
+        for layer in self.layers:
             layer.reset_parameters()
-
-    def forward(self, g, feats):
-        h_list, h = super().forward(feats)
-        return h_list, appnp_propagate(g, h, self.k, self.alpha, self.edge_drop, self.training)
-
-
-class GPRGNN(MLP):
-    """GPR-GNN (Chien et al., ICLR 2021; docs/GPR_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it): APPNP's MLP trunk (same
-    layers, norms and state_dict keys) followed by GPRConv(k, alpha, init) -- K propagation steps over APPNP's operator whose K + 1
-    mixing coefficients `propagate.gamma` are learned.  No edge dropout and no dropout in front of the propagation."""
-
-    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", k=10, alpha=0.1,
-                 init="PPR"):
-        super().__init__(num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, norm_type)
-        self.activation = activation
-        for layer in self.layers:          # (APPNP's trunk, draw for draw: its Linears are initialised once more)
-            layer.reset_parameters()
-        self.propagate = GPRConv(k, alpha, init)      # "Random" draws from torch's generator here, after the trunk's layers
-        self.k, self.alpha = self.propagate.k, self.propagate.alpha
 
     def forward(self, g, feats):
         h_list, h = super().forward(feats)
         return h_list, self.propagate(g, h)
+
+
+class APPNP(_TrunkProp):
+    """reference models.py:282-344: the trunk followed by dgl APPNPConv(k, alpha, edge_drop) -- K power iterations of personalised-PageRank
+    propagation with a fresh edge-dropout mask per iteration in training."""
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", edge_drop=0.5,
+                 alpha=0.1, k=10):
+        super().__init__(num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type)
+        self.k, self.alpha, self.edge_drop = int(k), float(alpha), float(edge_drop)
+
+    def propagate(self, g, h):
+        return appnp_propagate(g, h, self.k, self.alpha, self.edge_drop, self.training)
+
+
+class GPRGNN(_TrunkProp):
+    """GPR-GNN (Chien et al., ICLR 2021; docs/GPR_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it): the trunk followed by
+    GPRConv(k, alpha, init) -- K propagation steps over APPNP's operator whose K + 1 mixing coefficients `propagate.gamma` are learned.
+    No edge dropout and no dropout in front of the propagation."""
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", k=10, alpha=0.1,
+                 init="PPR"):
+        super().__init__(num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type)
+        self.propagate = GPRConv(k, alpha, init)      # "Random" draws from torch's generator here, after the trunk's layers
+        self.k, self.alpha = self.propagate.k, self.propagate.alpha
 
 
 GCNII_MAX_LAYERS = 64
@@ -675,9 +679,7 @@ class GCNII(nn.Module):
 
     def forward(self, g, feats):
         _need_hip(feats, "GCNII.forward")
-        if (isinstance(g, (list, tuple)) or isinstance(feats, tuple) or g.num_dst_nodes() != g.num_src_nodes()
-                or feats.shape[0] != g.num_dst_nodes()):
-            raise NotImplementedError("GCNII: block (bipartite) inputs are not implemented: GCNII runs on the whole graph")
+        _whole_graph_only(g, feats, "GCNII", "GCNII runs on the whole graph")
         weights = [layer.weight for layer in self.layers]
         if not self.training:
             with torch.no_grad():

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import GraphConvFn, SpmmFn, gat_conv, gatv2_conv, gcnii_stack, gpr_propagate, graphconv_fwd, linear_fn
+from .autograd import GraphConvFn, SpmmFn, _differentiable, gat_conv, gatv2_conv, gcnii_stack, gpr_propagate, graphconv_fwd, linear_fn
 
 
 FUSED_SAGE_MAX_IN = 256   # aggregate-first layers with d_in, d_out <= 256 take the single-launch K1F kernel.  Interleaved
@@ -324,6 +324,13 @@ class GATv2Conv(_AttnConv):
                                        self.attn_drop.p, self.training))
 
 
+def _whole_graph_only(graph, feat, who, why):
+    """Refuses a block (bipartite) input: a list of blocks, a (src, dst) feature pair, other source than destination rows, other rows."""
+    if (isinstance(graph, (list, tuple)) or isinstance(feat, tuple) or graph.num_dst_nodes() != graph.num_src_nodes()
+            or feat.shape[0] != graph.num_dst_nodes()):
+        raise NotImplementedError(f"{who}: block (bipartite) inputs are not implemented: {why}")
+
+
 GPR_INITS = ("PPR", "NPPR", "Random")
 
 
@@ -359,9 +366,7 @@ class GPRConv(nn.Module):
             self.gamma.copy_(g.to(torch.float32))
 
     def forward(self, graph, feat):
-        if (isinstance(graph, (list, tuple)) or isinstance(feat, tuple) or graph.num_dst_nodes() != graph.num_src_nodes()
-                or feat.shape[0] != graph.num_dst_nodes()):
-            raise NotImplementedError("GPRConv: block (bipartite) inputs are not implemented: GPR-GNN propagates over the whole graph")
+        _whole_graph_only(graph, feat, "GPRConv", "GPR-GNN propagates over the whole graph")
         return gpr_propagate(graph, feat, self.gamma, self.k, self.training)
 
 
@@ -392,12 +397,10 @@ class GCNIIConv(nn.Module):
     def forward(self, graph, feat, h0):
         """feat = H_{l-1}, h0 = H_0 (both [n, hidden]).  Differentiable in training mode when feat IS h0 (a one-layer stack); deeper
         stacks differentiate as a whole (models.GCNII -> autograd.gcnii_stack), so a layer in the middle runs without a graph."""
-        if (isinstance(graph, (list, tuple)) or isinstance(feat, tuple) or graph.num_dst_nodes() != graph.num_src_nodes()
-                or feat.shape[0] != graph.num_dst_nodes()):
-            raise NotImplementedError("GCNIIConv: block (bipartite) inputs are not implemented: GCNII runs on the whole graph")
+        _whole_graph_only(graph, feat, "GCNIIConv", "GCNII runs on the whole graph")
         if feat is h0:
             return gcnii_stack(graph, h0, [self.weight], self.alpha, [self.beta], 0.0, self.training)[0]
-        if self.training and torch.is_grad_enabled() and (feat.requires_grad or h0.requires_grad or self.weight.requires_grad):
+        if _differentiable(self.training, feat, h0, self.weight):
             raise NotImplementedError("GCNIIConv: a GCNII layer behind another one is differentiated by the whole stack "
                                       "(glnn_amd.autograd.gcnii_stack); call it under torch.no_grad()")
         in_norm, out_norm = graph.degree_norms()

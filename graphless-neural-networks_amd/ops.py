@@ -1391,15 +1391,35 @@ def scatter_rows(x, rows, out):
     return out
 
 
-# --------------------------------------------------------------------------------------------- APPNP propagation
-def _appnp_check(indptr, indices, x, n, name):
+# --------------------------------------------------------------------------------------------- what the graph teachers' wrappers check
+_GCNII_ENTRIES = ("gcnii_layer", "gcnii_layer_bwd")      # they word the two rules below their own way, and ask for a little more
+
+
+def _csr_check(name, indptr, indices, n, x=None):
+    """indptr int64, indices int32 (None: a launch without a graph); the GCNII entries also ask for indptr's n + 1 entries, and say so.
+    x: the gathered rows, which must hold the graph's n rows."""
+    if indptr is None:
+        return
     _need_cuda(indptr, indices, x)
-    if indptr.dtype != torch.int64 or indices.dtype != torch.int32:
-        raise ValueError(f"{name}: indptr must be int64 and indices int32")
-    if x.shape[0] < n:
+    with_len = name in _GCNII_ENTRIES
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or (with_len and indptr.numel() < n + 1):
+        raise ValueError(f"{name}: indptr must be int64{' with n + 1 entries' if with_len else ''} and indices int32")
+    if x is not None and x.shape[0] < n:
         raise ValueError(f"{name}: x must hold the graph's {n} rows")
 
 
+def _rows_like(name, what, t, n, d):
+    """t (None: no such buffer) is a row-major float32 [n, d]; the GCNII entries also ask for float4-addressable rows, and say so."""
+    if t is None:
+        return None
+    _mat(t, f"{name} {what}")
+    rows4 = name in _GCNII_ENTRIES
+    if tuple(t.shape) != (n, d) or (rows4 and (_ld(t) % 4 or t.data_ptr() % 16)):
+        raise ValueError(f"{name}: {what} must " + ("be [n, d] float32 with float4-addressable rows (ops.feat_empty)" if rows4 else "have x's shape"))
+    return t
+
+
+# --------------------------------------------------------------------------------------------- APPNP propagation
 def appnp_propagate(indptr, indices, x, nnz, t, dst_norm, src_norm, h0, alpha, edge_drop=0.0, seed=0, x_scaled=True, last=False, out=None):
     """ONE forward iteration t (1-based) of APPNP propagation, glnn_appnp_prop_f32 (square graph, n = x.shape[0]):
     h_t = (1 - alpha) D_in^-1/2 M_t A D_out^-1/2 h_{t-1} + alpha h0.  x is the previous iteration's stored output -- already scaled by
@@ -1408,7 +1428,7 @@ def appnp_propagate(indptr, indices, x, nnz, t, dst_norm, src_norm, h0, alpha, e
     x = as_feat(x)
     h0 = as_feat(h0)
     n, d = h0.shape
-    _appnp_check(indptr, indices, x, n, "appnp_propagate")
+    _csr_check("appnp_propagate", indptr, indices, n, x)
     _need_cuda(dst_norm, src_norm, h0, out)
     if x.shape[1] != d:
         raise ValueError("appnp_propagate: x and h0 must have the same width")
@@ -1431,7 +1451,7 @@ def appnp_propagate_bwd(t_indptr, t_indices, t_eids, x, nnz, t, first, dst_norm,
     call's output dst_norm * g_t and `acc` the running sum (updated in place).  Returns out: dst_norm * g_{t-1} for t > 1, dL/dh0 at t = 1."""
     x = as_feat(x)
     n, d = x.shape
-    _appnp_check(t_indptr, t_indices, x, n, "appnp_propagate_bwd")
+    _csr_check("appnp_propagate_bwd", t_indptr, t_indices, n, x)
     _need_cuda(t_eids, dst_norm, src_norm, acc, out)
     if out is None:
         out = feat_empty(n, d, x.device)
@@ -1464,24 +1484,17 @@ def gpr_prop(indptr, indices, nnz, x, k, x_norm, row_norm, out_norm, gamma, acc,
     x = as_feat(x)
     n, d = x.shape
     k = int(k)
-    _mat(acc, "gpr_prop acc")
-    if tuple(acc.shape) != (n, d):
-        raise ValueError("gpr_prop: acc must have x's shape")
+    _rows_like("gpr_prop", "acc", acc, n, d)
     if gamma.dtype != torch.float32 or gamma.dim() != 1 or gamma.numel() < k + 1 or not gamma.is_contiguous():
         raise ValueError(f"gpr_prop: gamma must be a contiguous float32 vector of >= {k + 1} coefficients")
     if k > 0:
-        _appnp_check(indptr, indices, x, n, "gpr_prop")
+        _csr_check("gpr_prop", indptr, indices, n, x)
         _vec(row_norm, n, "row_norm")
-    if out is not None:
-        _mat(out, "gpr_prop out")
-        if tuple(out.shape) != (n, d):
-            raise ValueError("gpr_prop: out must have x's shape")
+    _rows_like("gpr_prop", "out", out, n, d)
     if (h0 is None) != (row_dot is None):
         raise ValueError("gpr_prop: h0 and row_dot go together")
     if h0 is not None:
-        h0 = as_feat(h0)
-        if tuple(h0.shape) != (n, d):
-            raise ValueError("gpr_prop: h0 must have x's shape")
+        h0 = _rows_like("gpr_prop", "h0", as_feat(h0), n, d)
         if row_dot.dtype != torch.float32 or not row_dot.is_contiguous() or row_dot.numel() < (k + 1) * gpr_col_tiles(d) * n:
             raise ValueError("gpr_prop: row_dot must be contiguous float32 with >= (k + 1) * ceil(d / 256) * n elements")
     with _Timed("gpr_prop", d=d, n_dst=n, nnz=int(nnz), k=k):
@@ -1516,19 +1529,9 @@ GCNII_MAX_HIDDEN = 256          # kMaxD of csrc/gcnii.hip: the kernel's tile wid
 def _gcnii_check(name, indptr, indices, n, d, tile_order):
     if d > GCNII_MAX_HIDDEN:
         raise NotImplementedError(f"{name}: GCNII hidden widths of at most {GCNII_MAX_HIDDEN} (the fused kernel's tile; got {d})")
-    if indptr is not None and (indptr.dtype != torch.int64 or indices.dtype != torch.int32 or indptr.numel() < n + 1):
-        raise ValueError(f"{name}: indptr must be int64 with n + 1 entries and indices int32")
+    _csr_check(name, indptr, indices, n)
     if tile_order is not None and (tile_order.dtype != torch.int32 or not tile_order.is_contiguous() or tile_order.numel() != (n + 31) // 32):
         raise ValueError(f"{name}: tile_order must be a contiguous int32 permutation of the ceil(n / 32) tile ids")
-
-
-def _gcnii_rows(name, what, t, n, d):
-    if t is None:
-        return None
-    _mat(t, f"{name} {what}")
-    if tuple(t.shape) != (n, d) or _ld(t) % 4 or t.data_ptr() % 16:
-        raise ValueError(f"{name}: {what} must be [n, d] float32 with float4-addressable rows (ops.feat_empty)")
-    return t
 
 
 def gcnii_layer(indptr, indices, nnz, x, h0, w, alpha, beta, row_norm, x_norm=None, out_norm=None, drop_p=0.0, drop_seed=0, s_out=None,
@@ -1548,8 +1551,8 @@ def gcnii_layer(indptr, indices, nnz, x, h0, w, alpha, beta, row_norm, x_norm=No
         w_packed = pack_weight(w)
     if out is None:
         out = feat_empty(n, d, x.device)
-    _gcnii_rows("gcnii_layer", "out", out, n, d)
-    _gcnii_rows("gcnii_layer", "s_out", s_out, n, d)
+    _rows_like("gcnii_layer", "out", out, n, d)
+    _rows_like("gcnii_layer", "s_out", s_out, n, d)
     with _Timed("gcnii_layer", d=d, n_dst=n, nnz=int(nnz), train=s_out is not None):
         rc = _lib.lib().glnn_gcnii_layer_f32(
             _p(indptr), _p(indices), n, int(nnz), _p(x), _ld(x), d, _p(_vec(x_norm, n, "x_norm")), _p(_vec(row_norm, n, "row_norm")),
@@ -1588,7 +1591,7 @@ def gcnii_layer_bwd(t_indptr, t_indices, nnz, g, h, wt, alpha, beta, dz_out, dh0
     if h is not None and tuple(h.shape) != (n, d):
         raise ValueError("gcnii_layer_bwd: h must have g's shape")
     for what, t in (("dz_out", dz_out), ("ds_out", ds_out), ("dh0_acc", dh0_acc)):
-        _gcnii_rows("gcnii_layer_bwd", what, t, n, d)
+        _rows_like("gcnii_layer_bwd", what, t, n, d)
     with _Timed("gcnii_layer_bwd", d=d, n_dst=n, nnz=int(nnz), plain=bool(plain)):
         rc = _lib.lib().glnn_gcnii_layer_bwd_f32(
             _p(t_indptr), _p(t_indices), n, int(nnz), _p(g), _ld(g), d, _p(_vec(x_norm, n, "x_norm")), _p(_vec(row_norm, n, "row_norm")),
@@ -1836,7 +1839,7 @@ def gat_attn_fwd(indptr, indices, nnz, z, el, er, heads, out_feats, negative_slo
     """glnn_gat_attn_fwd_f32: (out [n, heads * out_feats], lse [n, heads] or None) -- edge softmax + weighted aggregation of z."""
     z = as_feat(z)
     n = z.shape[0]
-    _appnp_check(indptr, indices, z, n, "gat_attn_fwd")
+    _csr_check("gat_attn_fwd", indptr, indices, n, z)
     _need_cuda(el, er, out)
     out, lse = _attn_out("gat_attn_fwd", n, heads, out_feats, z.device, out, None, want_lse)
     _attn_call("gat_attn_fwd", heads, out_feats, n, nnz, attn_drop, _p(indptr), _p(indices), n, int(nnz), _p(z), _ld(z), heads, out_feats,
@@ -1852,7 +1855,7 @@ def gat_attn_bwd(graph, z, el, er, lse, attn_l, attn_r, g, y, heads, out_feats, 
     own edges).  The [E, heads] score-gradient scratch lives for the call."""
     z, g, y = as_feat(z), as_feat(g), as_feat(y)
     n = z.shape[0]
-    _appnp_check(graph.indptr, graph.indices, z, n, "gat_attn_bwd")
+    _csr_check("gat_attn_bwd", graph.indptr, graph.indices, n, z)
     _need_cuda(el, er, lse, attn_l, attn_r, g, y)
     dev = z.device
     csr, nnz, ds, (dz,), (dattn_l, dattn_r) = _attn_bwd_bufs("gat_attn_bwd", graph, n, heads, out_feats, dev, {"dz": None}, (dattn_l, dattn_r))
@@ -1886,7 +1889,7 @@ def gatv2_attn_fwd(indptr, indices, nnz, zl, zr, attn, heads, out_feats, negativ
     aggregation of zl from ONE gather per edge (docs/GATV2_SEMANTICS.md).  lse: a buffer to take the row log-sum-exps (implies want_lse)."""
     zl, zr = as_feat(zl), as_feat(zr)
     n = zl.shape[0]
-    _appnp_check(indptr, indices, zl, n, "gatv2_attn_fwd")
+    _csr_check("gatv2_attn_fwd", indptr, indices, n, zl)
     _need_cuda(zr, attn, out)
     _mat(zr, "gatv2_attn_fwd zr")
     _gatv2_check(zl, zr, attn, heads, out_feats, "gatv2_attn_fwd")
@@ -1903,7 +1906,7 @@ def gatv2_attn_bwd(graph, zl, zr, lse, attn, g, heads, out_feats, negative_slope
     g = dL/d out behind the activation mask.  The [E, heads] score-gradient scratch and the dattn partials live for the call."""
     zl, zr, g = as_feat(zl), as_feat(zr), as_feat(g)
     n = zl.shape[0]
-    _appnp_check(graph.indptr, graph.indices, zl, n, "gatv2_attn_bwd")
+    _csr_check("gatv2_attn_bwd", graph.indptr, graph.indices, n, zl)
     _need_cuda(zr, lse, attn, g, dattn)
     _mat(zr, "gatv2_attn_bwd zr")
     _mat(g, "gatv2_attn_bwd g")

@@ -300,7 +300,7 @@ class TeacherEngine:
         return self._g[id(p)]
 
     def _seed(self, layer):
-        return _mix32(self.base_seed ^ _mix32(self.step_count * 131 + layer + 1)) if self.p > 0 else 0
+        return _stream_seed(self, 0, 1, layer, self.p > 0)
 
     def _adam(self):
         g = self.opt.param_groups[0]
@@ -587,10 +587,8 @@ class TeacherEngine:
 
     # ------------------------------------------------------------------------------------------ full-graph APPNP
     def _edge_seed(self, step=None):
-        """The edge-dropout seed of step `step` (default: the current one): a stream of its own, apart from the hidden-layer dropout seeds
-        _seed(layer) (layer < 8)."""
-        step = self.step_count if step is None else step
-        return _mix32(self.base_seed ^ 0x41505050 ^ _mix32(step * 131 + 0x7F)) if self.enc.edge_drop > 0 else 0
+        """The edge-dropout seed of step `step` (default: the current one): a stream apart from the hidden-layer seeds _seed(layer < 8)."""
+        return _stream_seed(self, 0x41505050, 0x7F, 0, self.enc.edge_drop > 0, step)
 
     @torch.no_grad()
     def step_appnp(self, g, feats, labels, idx_train, lamb=1.0):
@@ -599,7 +597,7 @@ class TeacherEngine:
         the transposed graph, the trunk backward, Adam."""
         self._run_full_graph(self._step_appnp_body, g, feats, labels, idx_train, lamb)
 
-    def _appnp_tail_fwd(self, l, z):
+    def _trunk_tail_fwd(self, l, z):
         """norms[l] -> relu -> dropout of hidden layer l (models.py:334-338)."""
         if self.enc.norm_type == "layer":
             seed = self._seed(l)
@@ -608,7 +606,7 @@ class TeacherEngine:
             return a, (mu, rs), seed
         return self._tail_fwd(l, z)
 
-    def _appnp_tail_bwd(self, l, dh, z, stats, seed, bias_grad):
+    def _trunk_tail_bwd(self, l, dh, z, stats, seed, bias_grad):
         if self.enc.norm_type == "layer":
             ln = self.enc.norms[l]
             _, dg, db = ops.layernorm_bwd(dh, z, ln.weight, ln.bias, stats[0], stats[1], relu=True, drop_p=self.p, drop_seed=seed, dz=dh,
@@ -626,7 +624,7 @@ class TeacherEngine:
         for l, layer in enumerate(enc.layers):
             z = ops.gemm(a, layer.weight, ep_shift=layer.bias)
             if l != L - 1:
-                a, stats, seed = self._appnp_tail_fwd(l, z)
+                a, stats, seed = self._trunk_tail_fwd(l, z)
                 saved.append((z, stats, seed))
                 acts.append(a)
             else:
@@ -643,7 +641,7 @@ class TeacherEngine:
                 break
             da = ops.gemm(dz, layer.weight, w_is_kn=True)                        # dz W
             z, stats, seed = saved[l - 1]
-            dz = self._appnp_tail_bwd(l - 1, da, z, stats, seed, None)
+            dz = self._trunk_tail_bwd(l - 1, da, z, stats, seed, None)
 
     def _loss_grad(self, logits, labels, idx_train, lamb, n):
         """NLL over out[idx_train] (train_and_eval.py:22) and its gradient scattered back to [n, C]."""
@@ -654,15 +652,23 @@ class TeacherEngine:
         ops.scatter_rows(dl, idx_train, dlog)
         return dlog
 
-    def _step_appnp_body(self, g, feats, labels, idx_train, lamb):
-        enc = self.enc
-        a, acts, saved = self._trunk_fwd(feats)
-        seed_e = self._edge_seed()
-        logits = appnp_fwd(g, a, enc.k, enc.alpha, enc.edge_drop, seed_e)
+    def _step_prop_body(self, fwd, bwd, g, feats, labels, idx_train, lamb):
+        """A trunk-and-propagate teacher through its per-kind pair: fwd(self, g, h0) -> (logits, kept), bwd(self, g, dlog, h0, kept) ->
+        d/d(trunk logits), which also leaves the gradients of the propagation's own parameters."""
+        h0, acts, saved = self._trunk_fwd(feats)
+        logits, kept = fwd(self, g, h0)
         dlog = self._loss_grad(logits, labels, idx_train, lamb, g.num_dst_nodes())
-        dz = appnp_bwd(g, dlog, enc.k, enc.alpha, enc.edge_drop, seed_e)         # d/d(trunk logits)
-        self._trunk_bwd(dz, acts, saved)
+        self._trunk_bwd(bwd(self, g, dlog, h0, kept), acts, saved)
         ops.note_param_write()
+
+    def _appnp_fwd(self, g, h0):
+        enc, seed_e = self.enc, self._edge_seed()
+        return appnp_fwd(g, h0, enc.k, enc.alpha, enc.edge_drop, seed_e), seed_e
+
+    def _appnp_bwd(self, g, dlog, h0, seed_e):
+        return appnp_bwd(g, dlog, self.enc.k, self.enc.alpha, self.enc.edge_drop, seed_e)
+
+    _step_appnp_body = functools.partialmethod(_step_prop_body, _appnp_fwd, _appnp_bwd)
 
     # ------------------------------------------------------------------------------------------ full-graph GPR-GNN
     @torch.no_grad()
@@ -672,24 +678,23 @@ class TeacherEngine:
         glnn_gpr_fold_f32 into grad(gamma), the trunk backward, and the ONE Adam launch (gamma is one more tensor of its table)."""
         self._run_full_graph(self._step_gpr_body, g, feats, labels, idx_train, lamb)
 
-    def _step_gpr_body(self, g, feats, labels, idx_train, lamb):
-        enc = self.enc
-        gamma = enc.propagate.gamma
-        h0, acts, saved = self._trunk_fwd(feats)
-        logits = gpr_fwd(g, h0, gamma, enc.k)
-        dlog = self._loss_grad(logits, labels, idx_train, lamb, g.num_dst_nodes())
-        dz, dgamma = gpr_bwd(g, dlog, h0, gamma, enc.k)
+    def _gpr_fwd(self, g, h0):
+        return gpr_fwd(g, h0, self.enc.propagate.gamma, self.enc.k), None
+
+    def _gpr_bwd(self, g, dlog, h0, _):
+        gamma = self.enc.propagate.gamma
+        dz, dgamma = gpr_bwd(g, dlog, h0, gamma, self.enc.k)
         self.grad(gamma).copy_(dgamma)
-        self._trunk_bwd(dz, acts, saved)
-        ops.note_param_write()
+        return dz
+
+    _step_gpr_body = functools.partialmethod(_step_prop_body, _gpr_fwd, _gpr_bwd)
 
     # ------------------------------------------------------------------------------------------ full-graph GCNII
     def _gcnii_seed(self, site, step=None):
         """The seed of dropout site `site` (0: the input, l = 1..L: in front of conv layer l, L + 1: in front of fc_out) in step `step`
         (default: the current one): a stream of its own, apart from _seed, _edge_seed and _attn_seed.  site < 131, so no two (step, site)
         pairs share a counter."""
-        step = self.step_count if step is None else step
-        return _mix32(self.base_seed ^ 0x47434E32 ^ _mix32(step * 131 + site + 0x51)) if self.p > 0 else 0
+        return _stream_seed(self, 0x47434E32, 0x51, site, self.p > 0, step)
 
     @torch.no_grad()
     def step_gcnii(self, g, feats, labels, idx_train, lamb=1.0):
@@ -724,8 +729,7 @@ class TeacherEngine:
     # ------------------------------------------------------------------------------------------ full-graph GAT
     def _attn_seed(self, layer):
         """The attention-dropout seed of `layer` in the current step: a stream of its own, apart from the feature dropout seeds _seed(layer)."""
-        p = float(self.enc.layers[layer].attn_drop.p)
-        return _mix32(self.base_seed ^ 0x47415441 ^ _mix32(self.step_count * 131 + layer + 0x3D)) if p > 0 else 0
+        return _stream_seed(self, 0x47415441, 0x3D, layer, float(self.enc.layers[layer].attn_drop.p) > 0)
 
     @torch.no_grad()
     def step_gat(self, g, feats, labels, idx_train, lamb=1.0):
@@ -787,6 +791,13 @@ class TeacherEngine:
 
     _step_gat_body = functools.partialmethod(_step_attn_body, _gat_fwd, _gat_bwd, True)
     _step_gatv2_body = functools.partialmethod(_step_attn_body, _gatv2_fwd, _gatv2_bwd, False)
+
+
+def _stream_seed(eng, tag, offset, site, on, step=None):
+    """The seed of dropout site `site` in step `step` (default: the engine's current one) of TeacherEngine's stream (tag, offset); 0 when
+    the stream's probability is 0 (`on` False)."""
+    step = eng.step_count if step is None else step
+    return _mix32(eng.base_seed ^ tag ^ _mix32(step * 131 + site + offset)) if on else 0
 
 
 def get_engine(model, optimizer):

@@ -1,15 +1,22 @@
-"""Do the GAT and GATv2 teachers still compute the same bits?  Fixed seeds, one process: per teacher (2 layers, 8 heads, hidden 64, both
-dropouts on) three train() steps and one train_subgraph epoch on a 600-row graph with a 200-edge hub row and self-loop-only rows, then
-the parameter gradients of one autograd step (model(g, feats) in training mode, loss.backward()).  Prints one sha256 per line; run it
-on two builds and compare the lines.
-python scripts/attn_bits_probe.py"""
-import hashlib, os, sys
+"""Do the full-graph teachers still compute the same bits?  Fixed seeds, one process: per teacher kind (hidden 64, every dropout on:
+GAT / GATv2 2 layers, 8 heads, feature and attention dropout; APPNP 2 trunk layers, trunk and edge dropout; GPRGNN 2 trunk layers; GCNII
+3 conv layers, dropout 0.5) three train() steps and one train_subgraph epoch on a 600-row graph with a 200-edge hub row and
+self-loop-only rows, then the parameter gradients of one autograd step (model(g, feats) in training mode, loss.backward()).  Prints one
+sha256 per line; run it on two builds and compare the lines.  Public entry points only: it runs next to any build of the package.
+python scripts/teacher_bits_probe.py [--kinds GAT,GATv2,APPNP,GPRGNN,GCNII]"""
+import argparse, hashlib, os, sys
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from glnn_amd.graph import CSRGraph, RandomWalkSubgraphLoader
 from glnn_amd.models import Model
 from glnn_amd.train_and_eval import train, train_subgraph
+
+KINDS = dict(GAT=dict(num_layers=2, num_heads=8, attn_dropout_ratio=0.3), GATv2=dict(num_layers=2, num_heads=8, attn_dropout_ratio=0.3),
+             APPNP=dict(num_layers=2), GPRGNN=dict(num_layers=2), GCNII=dict(num_layers=3))      # (APPNP's edge_drop is 0.5 by default)
+ap = argparse.ArgumentParser()
+ap.add_argument("--kinds", default=",".join(KINDS))
+kinds = ap.parse_args().kinds.split(",")
 
 dev, N, D_IN, C = "cuda:0", 600, 24, 5
 rs = np.random.RandomState(3)
@@ -33,9 +40,8 @@ def sha(tensors):
     return h.hexdigest()[:16]
 
 
-for name in ("GAT", "GATv2"):
-    conf = dict(model_name=name, num_layers=2, feat_dim=D_IN, hidden_dim=64, label_dim=C, dropout_ratio=0.5, norm_type="none", device=dev,
-                num_heads=8, attn_dropout_ratio=0.3)
+for name in kinds:
+    conf = dict(model_name=name, feat_dim=D_IN, hidden_dim=64, label_dim=C, dropout_ratio=0.5, norm_type="none", device=dev, **KINDS[name])
     torch.manual_seed(11)
     m = Model(conf)
     opt = torch.optim.Adam(m.parameters(), lr=0.01, weight_decay=5e-4)

@@ -113,19 +113,19 @@ def _check_propagation(ip, ix, g, d, k, alpha, p):
 
 
 # ---------------------------------------------------------------------------------------------------------------- launch geometry
-# The numbers prop_launch and appnp_prop_kernel derive the grid from, mirrored by name (csrc/appnp.hip; gat.hip has the same values, so
-# test_gat_gpu.py plants the same rows):
-K_BLOCK = 512                 # appnp.hip:24  kBlock: the rows one trip of the long-row scan looks at (n_chunks = ceil(n / kBlock), appnp.hip:170)
-K_WAVES = K_BLOCK // 64       # appnp.hip:25  kWaves
-K_ROWS_PER_WAVE = 8           # appnp.hip:26  kRowsPerWave
-K_LONG_ROW = 128              # appnp.hip:27  kLongRow: a row above it is a whole workgroup's
-K_LONG_BLOCK_ROWS = 512       # appnp.hip:28  kLongBlockRows
-K_LONG_BLOCK_CAP = 512        # appnp.hip:29  kLongBlockCap
+# The numbers prop_launch and appnp_prop_kernel derive the grid from, mirrored by name (csrc/row_gather_dev.h, shared by every scan kernel;
+# gat.hip reads the same header, so test_gat_gpu.py plants the same rows):
+K_BLOCK = 512                 # row_gather_dev.h  kBlock: the rows one trip of the long-row scan looks at (n_chunks = ceil(n / kBlock), scan_rows)
+K_WAVES = K_BLOCK // 64       # row_gather_dev.h  kWaves
+K_ROWS_PER_WAVE = 8           # row_gather_dev.h  kRowsPerWave
+K_LONG_ROW = 128              # row_gather_dev.h  kLongRow: a row above it is a whole workgroup's
+K_LONG_BLOCK_ROWS = 512       # row_gather_dev.h  kLongBlockRows
+K_LONG_BLOCK_CAP = 512        # row_gather_dev.h  kLongBlockCap
 BIG_N = K_LONG_BLOCK_ROWS * K_LONG_BLOCK_CAP + 656      # 262 800: just above the size at which every scan chunk has a workgroup of its own
 
 
 def _geometry(n):
-    """(n_chunks, n_long_blocks, rows_per_block) of prop_launch (appnp.hip:243-249) and the scan loop (appnp.hip:170-171)."""
+    """(n_chunks, n_long_blocks, rows_per_block) of scan_grid and the scan loop scan_rows (both in csrc/row_gather_dev.h)."""
     return scan_geometry(n, K_BLOCK, K_WAVES, K_ROWS_PER_WAVE, K_LONG_BLOCK_ROWS, K_LONG_BLOCK_CAP)
 
 
@@ -272,8 +272,10 @@ def test_autograd_path_matches_the_engine_gradients(gold):
     g = _gold_graph(gold)
     x = torch.from_numpy(gold["feats"]).to(DEV)
     idx = torch.from_numpy(gold["idx_train"]).to(DEV)
+    from glnn_amd import autograd
+    c0 = autograd._drop_counter[0]
     logits = m(g, x)
-    assert logits.requires_grad
+    assert logits.requires_grad and autograd._drop_counter[0] == c0 + 1      # the trunk's one hidden tail; edge_drop 0 draws nothing
     params = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in m.state_dict().items()}
     _, h0, cache = ao.trunk_forward(params, gold["feats"], 2, "none", training=True)
     ref_logits = ao.propagate(gold["indptr"], gold["indices"], h0, 10, 0.1)

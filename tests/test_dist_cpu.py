@@ -535,3 +535,32 @@ def test_emulated_rank_halo_equals_unsharded_rows(world, dims, overlap):
         for p, (shp, plp) in enumerate(plans):
             assert pl.send_counts[p] == plp.recv_counts[sh.rank]
         assert pl.n_send == sum(plp.recv_counts[sh.rank] for _, plp in plans)
+
+
+# ---------------------------------------------------------------------------------------------------------------- refusals
+_REFUSAL_PHRASES = {"GAT": "per-head scores of the remote sources", "GATv2": "whole projected rows of the remote sources",
+                    "GPRGNN": "each of its K propagation steps needs the previous step's rows",
+                    "GCNII": "each of its conv layers needs the previous layer's hidden rows"}
+
+
+@pytest.mark.parametrize("teacher", ["ShardedTeacher", "HaloShardedTeacher"])
+@pytest.mark.parametrize("kind", sorted(_REFUSAL_PHRASES))
+def test_both_sharded_teachers_refuse_the_unsharded_kinds(teacher, kind):
+    """Every kind of dist.UNSHARDED_TEACHERS is refused by both constructors before they look at anything else, with its own reason; a
+    'mean' aggregator does not change that text (the kinds come first)."""
+    import glnn_amd.dist as gdist
+    assert set(gdist.UNSHARDED_TEACHERS) == set(_REFUSAL_PHRASES)
+    enc = type(kind, (), {"aggregator_type": "mean"})()
+    with pytest.raises(NotImplementedError) as e:
+        getattr(gdist, teacher)(enc, None, None, None)
+    msg = str(e.value)
+    assert msg.startswith(f"{teacher}: the {kind} teacher is not sharded -- ") and _REFUSAL_PHRASES[kind] in msg
+    assert msg.endswith(f"an exchange the sharded forward does not have (whole-graph {kind} only)")
+
+
+@pytest.mark.parametrize("teacher", ["ShardedTeacher", "HaloShardedTeacher"])
+def test_both_sharded_teachers_still_refuse_a_mean_sage(teacher):
+    import glnn_amd.dist as gdist
+    enc = type("SAGE", (), {"aggregator_type": "mean"})()
+    with pytest.raises(NotImplementedError, match="implements the SAGE 'gcn' aggregator only -- a SAGE 'mean' teacher"):
+        getattr(gdist, teacher)(enc, None, None, None)

@@ -259,6 +259,36 @@ def test_seed_stream_is_distinct_within_a_step_and_between_steps():
     assert [TeacherEngine._gcnii_seed(eng, s) for s in range(3)] == [0, 0, 0]
 
 
+def test_seed_streams_are_frozen():
+    """The four per-step streams of the engine at base_seed 1234567, step 7 (and step=3 where a stream takes one): the values the methods
+    returned before they became calls of teacher._stream_seed.  A stream whose probability is 0 returns 0."""
+    from glnn_amd.teacher import TeacherEngine as T
+    eng = types.SimpleNamespace(base_seed=1234567, step_count=7, p=0.6)
+    eng.enc = types.SimpleNamespace(edge_drop=0.5, layers=[types.SimpleNamespace(attn_drop=types.SimpleNamespace(p=0.3))] * 3)
+    assert [T._seed(eng, l) for l in range(3)] == [3955525820, 1064812690, 3377682224]
+    assert (T._edge_seed(eng), T._edge_seed(eng, step=3)) == (18478059, 1909480548)
+    assert [T._gcnii_seed(eng, s) for s in range(4)] == [689725636, 1727155465, 1644716809, 1755993479]
+    assert [T._gcnii_seed(eng, s, step=3) for s in range(4)] == [543932833, 2033871902, 1256181285, 1450154528]
+    assert [T._attn_seed(eng, l) for l in range(3)] == [4294299793, 1597889159, 1524044609]
+    eng.p, eng.enc.edge_drop, eng.enc.layers[0].attn_drop.p = 0.0, 0.0, 0.0
+    assert (T._seed(eng, 0), T._edge_seed(eng), T._gcnii_seed(eng, 1), T._gcnii_seed(eng, 1, step=3), T._attn_seed(eng, 0)) == (0,) * 5
+
+
+def test_process_draws_are_frozen():
+    """The per-process dropout draws at torch.manual_seed(11), count 5: the values before autograd._draw_base (APPNP's: its former inline
+    expression, (initial_seed * 0x85EBCA77 + 5 * 0x9E3779B1 + 0x41505050) mod 2^32, worked out by hand).  Replaying a count leaves the
+    call counter alone; count None is a new draw."""
+    from glnn_amd import autograd
+    torch.manual_seed(11)
+    c0 = autograd._drop_counter[0]
+    assert autograd.gcnii_stack_seeds(5, 4) == [528114116, 2191935343, 3855756570, 1224610501]
+    assert autograd.gat_conv_seeds(5) == (527984600, 527984595)
+    assert autograd.gatv2_conv_seeds(5) == (529352152, 529352147)
+    assert autograd.appnp_edge_seed(5) == 428303330
+    assert autograd._drop_counter[0] == c0
+    assert autograd.appnp_edge_seed(None) == autograd.appnp_edge_seed(c0 + 1) and autograd._drop_counter[0] == c0 + 1
+
+
 # ---------------------------------------------------------------------------------------------------------------- CLI, yaml
 def test_cli_flags():
     from glnn_amd.cli import get_teacher_args

@@ -406,15 +406,17 @@ def test_eval_forward_and_inference_match_the_oracle(small_graph):
 def test_autograd_path_matches_the_engine_gradients(small_graph):
     """Model.forward in training mode differentiates through GcniiStackFn: its gradients equal step_gcnii's (dropout-free), and with
     dropout it runs and gives every parameter a finite gradient."""
-    from glnn_amd import teacher
+    from glnn_amd import autograd, teacher
     from glnn_amd.train_and_eval import train
     ip, ix, g = small_graph
     m = _model(seed=2)
     x, labels, idx = _data(N_MODEL, DIMS, 5)
     tx, tl, ti = _t(x), torch.from_numpy(labels).to(DEV), torch.from_numpy(idx).to(DEV)
     m.train()
+    c0 = autograd._drop_counter[0]
     h_list, logits = m.forward_fitnet(g, tx)
     assert logits.requires_grad and len(h_list) == L_MODEL and not h_list[0].requires_grad
+    assert autograd._drop_counter[0] == c0 + 1                              # dropout-free: H_0's ReLU tail alone
     torch.nn.NLLLoss()(logits.log_softmax(dim=1)[ti], tl[ti]).backward()
     auto = {name: p.grad.detach().clone() for name, p in m.named_parameters()}
     assert all(v is not None for v in auto.values())
@@ -424,7 +426,9 @@ def test_autograd_path_matches_the_engine_gradients(small_graph):
     for name, p in m.named_parameters():
         np.testing.assert_allclose(eng.grad(p).cpu().numpy(), auto[name].cpu().numpy(), rtol=TOL, atol=TOL, err_msg=name)
     md = _model(dropout=0.5, seed=2).train()
+    c0 = autograd._drop_counter[0]
     out = md(g, tx)
+    assert autograd._drop_counter[0] == c0 + 4                              # the input's, H_0's tail, the stack's one draw, fc_out's
     torch.nn.NLLLoss()(out.log_softmax(dim=1)[ti], tl[ti]).backward()
     assert all(p.grad is not None and torch.isfinite(p.grad).all() and bool((p.grad != 0).any()) for p in md.parameters())
 

@@ -237,7 +237,7 @@ def test_fold_combines_more_than_one_partial():
         assert np.array_equal(got, ops.gpr_fold(_t(rd).reshape(-1), rows, m).cpu().numpy())
 
 
-# The numbers glnn_gpr_prop_f32 and gpr_prop_kernel derive the grid from, mirrored by name (csrc/gpr.hip; appnp.hip has the same values):
+# The numbers glnn_gpr_prop_f32 and gpr_prop_kernel derive the grid from, mirrored by name (csrc/row_gather_dev.h, which appnp.hip reads too):
 K_BLOCK = 512                 # kBlock: the rows one trip of the long-row scan looks at (n_chunks = ceil(n / kBlock))
 K_WAVES = K_BLOCK // 64       # kWaves
 K_ROWS_PER_WAVE = 8           # kRowsPerWave
