@@ -101,6 +101,9 @@ SIGNATURES = {
     "glnn_deepwalk_score_f32": [c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "glnn_deepwalk_apply_f32": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f64,
                                 c_f64, c_f64, c_f64, c_i64, c_vp, c_vp, c_vp],
+    "glnn_node2vec_walk": [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_int, c_f64, c_f64, c_u32, c_vp, c_vp],
+    "glnn_deepwalk_pairs_from_walks": [c_vp, c_i64, c_int, c_int, c_int, c_i64, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "glnn_deepwalk_score_ctx_f32": [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "glnn_gpr_prop_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp,
                           c_i64, c_vp, c_vp],
     "glnn_gpr_fold_f32": [c_vp, c_int, c_i64, c_vp, c_vp, c_i64, c_vp],

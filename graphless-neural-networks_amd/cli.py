@@ -127,7 +127,18 @@ def get_student_args(argv=None):
     p.add_argument("--position_epochs", type=int, default=5, help="Passes over the nodes (each a walk root once) of the position embedding")
     p.add_argument("--position_batch_size", type=int, default=4096, help="Walk roots per step of the position embedding")
     p.add_argument("--position_lr", type=float, default=0.01, help="Learning rate of the position embedding's lazy Adam")
+    # the rest of the node2vec family, each off at its default (the defaults are DeepWalk with uniform negatives and one table)
+    p.add_argument("--position_p", type=float, default=1.0, help="node2vec return parameter p of the position walks, in [0.25, 4] (1: unbiased)")
+    p.add_argument("--position_q", type=float, default=1.0, help="node2vec in-out parameter q of the position walks, in [0.25, 4] (1: unbiased)")
+    p.add_argument("--position_negative_power", type=float, default=0.0,
+                   help="Negatives drawn in proportion to degree ** this (0: uniform; 0.75 is the usual value)")
+    p.add_argument("--position_context_table", action="store_true",
+                   help="Score the entries of a pair against a separate context table (the embedding table stays the output)")
     args = p.parse_args(argv)
+    if not (0.25 <= args.position_p <= 4.0 and 0.25 <= args.position_q <= 4.0):
+        p.error(f"--position_p and --position_q must be in [0.25, 4] (got {args.position_p}, {args.position_q})")
+    if not args.position_negative_power >= 0.0:
+        p.error(f"--position_negative_power must be >= 0 (got {args.position_negative_power})")
     if args.position_dim < 0 or args.position_dim % 4 or args.position_dim > 256:
         p.error(f"--position_dim must be 0 (off) or a multiple of 4 up to 256 (got {args.position_dim})")
     if args.position_dim > 0:
@@ -198,7 +209,8 @@ def _with_position(args, feats, g, idx_obs, device, logger):
     gd = g.to(device)
     sub = gd if idx_obs is None else g.subgraph(idx_obs).to(device)
     dw = DeepWalk(sub, args.position_dim, args.position_walk_length, args.position_context, args.position_negatives,
-                  lr=args.position_lr, seed=args.seed)
+                  lr=args.position_lr, seed=args.seed, p=args.position_p, q=args.position_q, negative_power=args.position_negative_power,
+                  context_table=args.position_context_table)
     losses = dw.fit(args.position_epochs, args.position_batch_size)
     logger.info(f"position embedding: {sub.num_nodes()} nodes x {args.position_dim}, loss per epoch " + " ".join(f"{x:.4f}" for x in losses))
     z = dw.embedding

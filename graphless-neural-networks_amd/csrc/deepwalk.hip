@@ -13,6 +13,11 @@
 //              sum over its entries of g[eid] Zs[eid / R] (the transposed pair list, ascending edge ids), in that order; then the lazy-Adam
 //              update of row n of Z, M, V in place.  It reads Gs, Zs and g only, never Z of another row.  Nodes with neither list are not
 //              written.  One more workgroup of the same launch folds the loss partials in fp64, fixed order, into a device scalar.
+//
+// The rest of the node2vec family, each behind an entry of its own and the same kernels: glnn_deepwalk_pairs_from_walks takes the walks
+// as an input (glnn_node2vec_walk's, csrc/node2vec.hip) and may draw the negatives through a 32-bit CDF; glnn_deepwalk_score_ctx_f32 reads
+// the entries from a second table C (C == Z: the one-table bits), after which dZ comes from the start list alone and dC from the pair list
+// alone -- two dw_apply launches, each with the other list empty.
 #include "row_gather_dev.h"
 
 namespace {
@@ -22,6 +27,7 @@ constexpr int kDwMaxD = 256;
 // ------------------------------------------------------------------------------------------------ pairs
 struct PairArgs {
   const int64_t* walks; int64_t n_roots; int length, context, negatives; int64_t n_nodes; uint32_t neg_seed;
+  const uint32_t* neg_cdf;      // NULL: uniform negatives; else [n_nodes], the draw is the number of n < N - 1 with neg_cdf[n] <= r
   int32_t* start; int32_t* rest; int64_t* pair_indptr; int64_t* win_indptr;
 };
 
@@ -41,7 +47,16 @@ __global__ __launch_bounds__(256) void dw_pairs_kernel(const PairArgs a) {
     a.rest[id] = (int32_t)w[1 + t];
   } else {
     const uint32_t r = glnn::drop_hash(a.neg_seed, (uint32_t)q, (uint32_t)(t - n_pos));
-    a.rest[id] = (int32_t)(((uint64_t)r * (uint64_t)a.n_nodes) >> 32);
+    if (a.neg_cdf == nullptr) {
+      a.rest[id] = (int32_t)(((uint64_t)r * (uint64_t)a.n_nodes) >> 32);
+    } else {                                                               // upper bound over the first N - 1 entries: in [0, N - 1] whatever they hold
+      int64_t lo = 0, hi = a.n_nodes - 1;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a.neg_cdf[mid] <= r) lo = mid + 1; else hi = mid;
+      }
+      a.rest[id] = (int32_t)lo;
+    }
   }
   if (t == 0) {
     a.start[q] = (int32_t)w[0];
@@ -64,7 +79,7 @@ __device__ __forceinline__ float dw_sigmoid(float x) {
 }
 
 struct ScoreArgs {
-  const float* z; int64_t n_nodes; int d;
+  const float* z; const float* c; int64_t n_nodes; int d;      // the start row comes from z, the entries from c (c == z: one table)
   const int32_t* start; const int32_t* rest; int64_t n_win; int n_pos; int R;
   float inv_pos, inv_neg;
   float* g; float* gs; float* zs; float* loss_parts;
@@ -94,7 +109,7 @@ __global__ __launch_bounds__(256) void dw_score_kernel(const ScoreArgs a) {
       const int t = t0 + u * G + grp;
       const int x = t < a.R ? row[t] : -1;
       ok[u] = s_ok && (unsigned)x < (unsigned)a.n_nodes;
-      zx[u] = (ok[u] && col_ok) ? ld4(a.z + (int64_t)x * a.d + col4) : zero4();
+      zx[u] = (ok[u] && col_ok) ? ld4(a.c + (int64_t)x * a.d + col4) : zero4();
     }
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
@@ -220,6 +235,38 @@ int dw_width(const char* what, int d) {
   return GLNN_OK;
 }
 
+// the pair launch behind both pair entries: windows and pair rows from walks that are already on the device
+int dw_pairs_launch(const char* what, const int64_t* walks, int64_t n_roots, int length, int context, int negatives, int64_t n_nodes,
+                    uint32_t neg_seed, const uint32_t* neg_cdf, int R, int32_t* start, int32_t* rest, int64_t* pair_indptr, int64_t* win_indptr,
+                    hipStream_t st) {
+  const int64_t Q = n_roots * (int64_t)(length + 2 - context);
+  PairArgs a;
+  a.walks = walks; a.n_roots = n_roots; a.length = length; a.context = context; a.negatives = negatives; a.n_nodes = n_nodes;
+  a.neg_seed = neg_seed; a.neg_cdf = neg_cdf; a.start = start; a.rest = rest; a.pair_indptr = pair_indptr; a.win_indptr = win_indptr;
+  hipLaunchKernelGGL(dw_pairs_kernel, dim3((unsigned)((Q * R + 255) / 256)), dim3(256), 0, st, a);
+  return glnn::check_launch(what);
+}
+
+// the score launch behind both score entries
+int dw_score_launch(const char* what, const float* z, const float* c, int64_t n_nodes, int d, const int32_t* start, const int32_t* rest,
+                    int64_t n_windows, int context, int negatives, float* g, float* gs, float* zs, float* loss_parts, void* stream) {
+  int R;
+  int rc = dw_sizes(what, n_nodes, n_windows, context, negatives, &R);
+  if (rc == GLNN_OK) rc = dw_width(what, d);
+  if (rc != GLNN_OK || n_windows == 0) return rc;
+  GLNN_REQUIRE(z && c && start && rest && g && gs && zs && loss_parts, "%s: null pointer", what);
+  GLNN_REQUIRE(glnn::aligned16(z) && glnn::aligned16(c) && glnn::aligned16(gs) && glnn::aligned16(zs), "%s: z, gs and zs must be 16-byte aligned", what);
+  ScoreArgs a;
+  a.z = z; a.c = c; a.n_nodes = n_nodes; a.d = d; a.start = start; a.rest = rest; a.n_win = n_windows; a.n_pos = context - 1; a.R = R;
+  a.inv_pos = (float)(1.0 / ((double)n_windows * (context - 1)));
+  a.inv_neg = (float)(1.0 / ((double)n_windows * (context - 1) * negatives));
+  a.g = g; a.gs = gs; a.zs = zs; a.loss_parts = loss_parts;
+  const dim3 grid((unsigned)((n_windows + 3) / 4));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  with_lpr<1>(lpr_for(d / 4, 1), [&](auto L) { hipLaunchKernelGGL((dw_score_kernel<decltype(L)::value>), grid, dim3(256), 0, st, a); });
+  return glnn::check_launch(what);
+}
+
 }  // namespace
 
 extern "C" int glnn_deepwalk_pairs(const int64_t* indptr, const int32_t* indices, int64_t n_nodes, const int64_t* roots,
@@ -249,31 +296,45 @@ extern "C" int glnn_deepwalk_pairs(const int64_t* indptr, const int32_t* indices
                    (long long)roots_host[i], (long long)i, (long long)n_nodes);
   rc = glnn_random_walk(indptr, indices, roots, n_roots, length, walk_seed, walks, stream);
   if (rc != GLNN_OK) return rc;
-  PairArgs a;
-  a.walks = walks; a.n_roots = n_roots; a.length = length; a.context = context; a.negatives = negatives; a.n_nodes = n_nodes;
-  a.neg_seed = neg_seed; a.start = start; a.rest = rest; a.pair_indptr = pair_indptr; a.win_indptr = win_indptr;
-  hipLaunchKernelGGL(dw_pairs_kernel, dim3((unsigned)((Q * R + 255) / 256)), dim3(256), 0, st, a);
-  return glnn::check_launch(what);
+  return dw_pairs_launch(what, walks, n_roots, length, context, negatives, n_nodes, neg_seed, nullptr, R, start, rest, pair_indptr, win_indptr, st);
+}
+
+// glnn_deepwalk_pairs without its walk: `walks` is an input (glnn_random_walk's or glnn_node2vec_walk's), and the negatives may come from a
+// distribution given as a 32-bit CDF.  neg_cdf == NULL and glnn_random_walk's walks: glnn_deepwalk_pairs' outputs bit for bit.
+extern "C" int glnn_deepwalk_pairs_from_walks(const int64_t* walks, int64_t n_roots, int length, int context, int negatives, int64_t n_nodes,
+                                              uint32_t neg_seed, const uint32_t* neg_cdf, int32_t* start, int32_t* rest,
+                                              int64_t* pair_indptr, int64_t* win_indptr, void* stream) {
+  const char* what = "glnn_deepwalk_pairs_from_walks";
+  GLNN_REQUIRE(length >= 1 && length <= 64, "%s: walk length must be in [1, 64] (got %d)", what, length);
+  GLNN_REQUIRE(context >= 2 && context <= length + 1, "%s: context size must be in [2, walk length + 1] (got %d for walk length %d)", what,
+               context, length);
+  GLNN_REQUIRE(n_roots >= 0 && n_roots < ((int64_t)1 << 32), "%s: the number of roots must be in [0, 2^32)", what);
+  const int64_t Q = n_roots * (int64_t)(length + 2 - context);
+  int R;
+  int rc = dw_sizes(what, n_nodes, Q, context, negatives, &R);
+  if (rc != GLNN_OK) return rc;
+  GLNN_REQUIRE(pair_indptr && win_indptr, "%s: null pointer", what);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (n_roots == 0) {
+    if (hipMemsetAsync(pair_indptr, 0, sizeof(int64_t), st) != hipSuccess || hipMemsetAsync(win_indptr, 0, sizeof(int64_t), st) != hipSuccess)
+      return glnn::fail(GLNN_ERR_HIP, "%s: memset failed", what);
+    return GLNN_OK;
+  }
+  GLNN_REQUIRE(walks && start && rest, "%s: null pointer", what);
+  return dw_pairs_launch(what, walks, n_roots, length, context, negatives, n_nodes, neg_seed, neg_cdf, R, start, rest, pair_indptr, win_indptr, st);
 }
 
 extern "C" int glnn_deepwalk_score_f32(const float* z, int64_t n_nodes, int d, const int32_t* start, const int32_t* rest, int64_t n_windows,
                                        int context, int negatives, float* g, float* gs, float* zs, float* loss_parts, void* stream) {
-  const char* what = "glnn_deepwalk_score_f32";
-  int R;
-  int rc = dw_sizes(what, n_nodes, n_windows, context, negatives, &R);
-  if (rc == GLNN_OK) rc = dw_width(what, d);
-  if (rc != GLNN_OK || n_windows == 0) return rc;
-  GLNN_REQUIRE(z && start && rest && g && gs && zs && loss_parts, "%s: null pointer", what);
-  GLNN_REQUIRE(glnn::aligned16(z) && glnn::aligned16(gs) && glnn::aligned16(zs), "%s: z, gs and zs must be 16-byte aligned", what);
-  ScoreArgs a;
-  a.z = z; a.n_nodes = n_nodes; a.d = d; a.start = start; a.rest = rest; a.n_win = n_windows; a.n_pos = context - 1; a.R = R;
-  a.inv_pos = (float)(1.0 / ((double)n_windows * (context - 1)));
-  a.inv_neg = (float)(1.0 / ((double)n_windows * (context - 1) * negatives));
-  a.g = g; a.gs = gs; a.zs = zs; a.loss_parts = loss_parts;
-  const dim3 grid((unsigned)((n_windows + 3) / 4));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  with_lpr<1>(lpr_for(d / 4, 1), [&](auto L) { hipLaunchKernelGGL((dw_score_kernel<decltype(L)::value>), grid, dim3(256), 0, st, a); });
-  return glnn::check_launch(what);
+  return dw_score_launch("glnn_deepwalk_score_f32", z, z, n_nodes, d, start, rest, n_windows, context, negatives, g, gs, zs, loss_parts, stream);
+}
+
+// glnn_deepwalk_score_f32 with the entries read from a second table c [n_nodes, d]; the start row and the snapshot zs still come from z.
+// c == z: glnn_deepwalk_score_f32's bits.
+extern "C" int glnn_deepwalk_score_ctx_f32(const float* z, const float* c, int64_t n_nodes, int d, const int32_t* start, const int32_t* rest,
+                                           int64_t n_windows, int context, int negatives, float* g, float* gs, float* zs, float* loss_parts,
+                                           void* stream) {
+  return dw_score_launch("glnn_deepwalk_score_ctx_f32", z, c, n_nodes, d, start, rest, n_windows, context, negatives, g, gs, zs, loss_parts, stream);
 }
 
 extern "C" int glnn_deepwalk_apply_f32(const int64_t* tw_indptr, const int32_t* tw_indices, const int64_t* tp_indptr, const int32_t* tp_eids,

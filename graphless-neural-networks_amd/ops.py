@@ -1320,6 +1320,28 @@ def random_walk(indptr, indices, roots, length, rng_seed):
     return out
 
 
+def node2vec_walk(indptr, indices, roots, length, p, q, rng_seed):
+    """glnn_node2vec_walk (docs/POSITION_SEMANTICS.md): random_walk's output with node2vec's second-order bias -- from step 2 on a candidate
+    x of the current row is a return (x == walk[s - 2], weight 1/p), near (x is an entry of that node's row, weight 1) or far (weight 1/q),
+    drawn by integer rejection sampling (at most 256 attempts).  p = q = 1 gives random_walk's bits.  p, q in [0.25, 4].  `roots`: int64
+    vector on the CPU (checked against the graph there, then copied: no device read) or on the device (one copy back for the check).
+    A refused argument raises ValueError with the C message."""
+    _need_cuda(indptr, indices)
+    _check_csr(indptr, indices, "node2vec_walk")
+    if roots.dtype != torch.int64 or roots.dim() != 1:
+        raise ValueError("node2vec_walk: roots must be an int64 vector")
+    dev = indptr.device
+    roots_host = roots.contiguous() if not roots.is_cuda else roots.cpu().contiguous()
+    roots = roots.contiguous() if roots.is_cuda else roots_host.to(dev)
+    n, b, length = indptr.numel() - 1, roots.numel(), int(length)
+    out = torch.empty((b, length + 1) if 1 <= length <= 64 else (0, 1), dtype=torch.int64, device=dev)      # (else: refused below)
+    with _Timed("node2vec_walk", n_roots=b, length=length):
+        rc = _lib.lib().glnn_node2vec_walk(_p(indptr), _p(indices), n, _p(roots), _p(roots_host), b, length, float(p), float(q),
+                                           int(rng_seed) & 0xFFFFFFFF, _p(out), _stream())
+    _dw_check(rc, "glnn_node2vec_walk")
+    return out
+
+
 SELF_LOOP_MODES = ("keep", "add")
 
 
@@ -1671,12 +1693,61 @@ def deepwalk_pairs(indptr, indices, roots, length, context, negatives, walk_seed
     return walks, start, rest.view(q, r), pair_indptr, win_indptr
 
 
-def deepwalk_score(z, start, rest, context, negatives):
+def deepwalk_pairs_from_walks(walks, n_nodes, context, negatives, neg_seed, neg_cdf=None):
+    """glnn_deepwalk_pairs_from_walks: deepwalk_pairs' pair lists from walks [B, L + 1] (int64, device) that are given -- random_walk's or
+    node2vec_walk's.  neg_cdf None: the uniform negatives of deepwalk_pairs (the same bits from the same walks).  neg_cdf [n_nodes] (int64
+    values in [0, 2^32), CPU or device; position.negative_cdf builds it): the negative of the draw r is the number of n < n_nodes - 1 with
+    neg_cdf[n] <= r.  Returns (start [Q] int32, rest [Q, R] int32, pair_indptr [Q + 1], win_indptr [Q + 1])."""
+    _need_cuda(walks)
+    if walks.dtype != torch.int64 or walks.dim() != 2 or not walks.is_contiguous():
+        raise ValueError("deepwalk_pairs_from_walks: walks must be a contiguous int64 matrix [B, L + 1]")
+    dev = walks.device
+    b, length = walks.shape[0], walks.shape[1] - 1
+    n, context, negatives = int(n_nodes), int(context), int(negatives)
+    cdf = None
+    if neg_cdf is not None:
+        cdf = deepwalk_cdf_words(neg_cdf, dev)
+        if cdf.numel() != n:
+            raise ValueError(f"deepwalk_pairs_from_walks: neg_cdf must have one entry per node ({n}), got {cdf.numel()}")
+    q, r = deepwalk_windows(b, length, context, negatives)
+    ok = 1 <= length <= 64 and 2 <= context <= length + 1 and negatives >= 1 and q * r < 2 ** 31      # (else: refused below, nothing allocated)
+    q, r = (q, r) if ok else (0, 0)
+    start, rest = _i32(q, dev), _i32(q * r, dev)
+    pair_indptr = torch.empty(q + 1, dtype=torch.int64, device=dev)
+    win_indptr = torch.empty(q + 1, dtype=torch.int64, device=dev)
+    with _Timed("deepwalk_pairs_from_walks", n_roots=b, length=length, context=context, negatives=negatives):
+        rc = _lib.lib().glnn_deepwalk_pairs_from_walks(_p(walks), b, length, context, negatives, n, int(neg_seed) & 0xFFFFFFFF, _p(cdf),
+                                                       _p(start), _p(rest), _p(pair_indptr), _p(win_indptr), _stream())
+    _dw_check(rc, "glnn_deepwalk_pairs_from_walks")
+    return start, rest.view(q, r), pair_indptr, win_indptr
+
+
+def deepwalk_cdf_words(cdf, device):
+    """The device form of a 32-bit CDF: `cdf` holds integers in [0, 2^32) (int64 tensor or numpy array); returned as an int32 tensor with
+    the same 32 bits per entry, which the kernel reads as uint32.  A tensor that is already int32 on the device is taken as that form."""
+    if torch.is_tensor(cdf) and cdf.dtype == torch.int32:
+        return cdf.to(device).contiguous()
+    cdf = torch.as_tensor(cdf).to(torch.int64).reshape(-1)
+    if cdf.numel() and (int(cdf.min()) < 0 or int(cdf.max()) >= 2 ** 32):
+        raise ValueError("deepwalk_cdf_words: entries must be in [0, 2^32)")
+    return torch.where(cdf >= 2 ** 31, cdf - 2 ** 32, cdf).to(torch.int32).to(device).contiguous()
+
+
+def deepwalk_empty_list(n_nodes, device):
+    """An empty per-node list (all-zero indptr [N + 1], no entries) for deepwalk_apply: the side a table of the two-table update does not
+    take part in."""
+    return torch.zeros(int(n_nodes) + 1, dtype=torch.int64, device=device), _i32(0, device)
+
+
+def deepwalk_score(z, start, rest, context, negatives, ctx=None):
     """glnn_deepwalk_score_f32 at frozen z [N, d]: g [Q * R] = dLoss/ds of every pair, gs [Q, d] = sum_t g z[rest] (the start-side gradient of
     window q), zs [Q, d] = z[start] (the snapshot the entry side reads), loss_parts [2, Q] = the windows' softplus sums over positives /
-    negatives.  Returns (g, gs, zs, loss_parts)."""
-    _need_cuda(z, start, rest)
+    negatives.  Returns (g, gs, zs, loss_parts).  ctx [N, d] (glnn_deepwalk_score_ctx_f32): the entries are read from this second table,
+    s = <z[start], ctx[rest]> and gs = sum_t g ctx[rest]; ctx is z itself: the one-table bits."""
+    _need_cuda(z, start, rest, ctx)
     _dw_table(z, "deepwalk_score z")
+    if ctx is not None and tuple(_dw_table(ctx, "deepwalk_score ctx").shape) != tuple(z.shape):
+        raise ValueError("deepwalk_score: ctx must have z's shape")
     if start.dtype != torch.int32 or rest.dtype != torch.int32 or rest.dim() != 2 or not rest.is_contiguous() or not start.is_contiguous() \
             or rest.shape[0] != start.numel():
         raise ValueError("deepwalk_score: start [Q] and rest [Q, R] must be contiguous int32 (ops.deepwalk_pairs)")
@@ -1689,9 +1760,13 @@ def deepwalk_score(z, start, rest, context, negatives):
     zs = torch.empty((q, d), dtype=torch.float32, device=z.device)
     loss_parts = torch.empty((2, q), dtype=torch.float32, device=z.device)
     with _Timed("deepwalk_score", d=d, n_windows=q, row=r):
-        rc = _lib.lib().glnn_deepwalk_score_f32(_p(z), n, d, _p(start), _p(rest), q, int(context), int(negatives), _p(g), _p(gs), _p(zs),
-                                                _p(loss_parts), _stream())
-    _dw_check(rc, "glnn_deepwalk_score_f32")
+        if ctx is None:
+            rc = _lib.lib().glnn_deepwalk_score_f32(_p(z), n, d, _p(start), _p(rest), q, int(context), int(negatives), _p(g), _p(gs), _p(zs),
+                                                    _p(loss_parts), _stream())
+        else:
+            rc = _lib.lib().glnn_deepwalk_score_ctx_f32(_p(z), _p(ctx), n, d, _p(start), _p(rest), q, int(context), int(negatives), _p(g),
+                                                        _p(gs), _p(zs), _p(loss_parts), _stream())
+    _dw_check(rc, "glnn_deepwalk_score_f32" if ctx is None else "glnn_deepwalk_score_ctx_f32")
     return g, gs, zs, loss_parts
 
 
@@ -1713,15 +1788,19 @@ def deepwalk_apply(z, m, v, tw, tp, g, gs, zs, loss_parts, context, negatives, l
     r = (1 + int(negatives)) * (int(context) - 1)
     (tw_indptr, tw_indices), (tp_indptr, tp_eids) = tw, tp
     if tw_indptr.dtype != torch.int64 or tp_indptr.dtype != torch.int64 or tw_indptr.numel() != n + 1 or tp_indptr.numel() != n + 1 \
-            or tw_indices.dtype != torch.int32 or tp_eids.dtype != torch.int32 or tw_indices.numel() != q or tp_eids.numel() != q * r \
-            or g.numel() != q * r:
-        raise ValueError("deepwalk_apply: tw / tp must be the transposes of the start list (Q entries) and of the pair list (Q * R entries) over N nodes")
+            or tw_indices.dtype != torch.int32 or tp_eids.dtype != torch.int32 or tw_indices.numel() not in (0, q) \
+            or tp_eids.numel() not in (0, q * r) or g.numel() != q * r:
+        raise ValueError("deepwalk_apply: tw / tp must be the transposes of the start list (Q entries) and of the pair list (Q * R entries) over N "
+                         "nodes, or ops.deepwalk_empty_list for the side a table takes no part in")
     if loss_out is None:
         loss_out = torch.empty((), dtype=torch.float32, device=z.device)
     elif loss_out.dtype != torch.float32 or loss_out.numel() != 1:
         raise ValueError("deepwalk_apply: loss_out must be a float32 tensor of one element")
+    # (an empty list has no storage of its own, and the C entry takes no NULL: its all-zero indptr stands in, every row being empty, never read)
+    tw_entries = tw_indices if tw_indices.numel() else tw_indptr
+    tp_entries = tp_eids if tp_eids.numel() else tp_indptr
     with _Timed("deepwalk_apply", d=d, n_nodes=n, n_windows=q, row=r):
-        rc = _lib.lib().glnn_deepwalk_apply_f32(_p(tw_indptr), _p(tw_indices), _p(tp_indptr), _p(tp_eids), n, d, q, int(context),
+        rc = _lib.lib().glnn_deepwalk_apply_f32(_p(tw_indptr), _p(tw_entries), _p(tp_indptr), _p(tp_entries), n, d, q, int(context),
                                                 int(negatives), _p(g), _p(gs), _p(zs), _p(z), _p(m), _p(v), float(lr), float(betas[0]),
                                                 float(betas[1]), float(eps), int(step), _p(loss_parts), _p(loss_out), _stream())
     _dw_check(rc, "glnn_deepwalk_apply_f32")

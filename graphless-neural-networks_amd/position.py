@@ -1,23 +1,44 @@
 """DeepWalk position features for the MLP student (docs/POSITION_SEMANTICS.md): the device NOSMOG (Tian et al., ICLR 2023) adds to
 GLNN -- a DeepWalk embedding of each node concatenated to its features in front of the MLP, so that inference stays one row lookup and an
-MLP.  The skip-gram trainer is csrc/deepwalk.hip: node2vec's objective with p = q = 1, one table, batch-synchronous lazy Adam, a fixed
-summation order and no float atomics (the same seed gives the same bits).  torch owns the memory and the CPU permutation; there is no CPU
-path."""
+MLP.  The skip-gram trainer is csrc/deepwalk.hip: node2vec's objective, batch-synchronous lazy Adam, a fixed summation order and no
+float atomics (the same seed gives the same bits).  By default p = q = 1, uniform negatives and one table (DeepWalk with negative
+sampling); the rest of the node2vec family is behind switches: biased walks (csrc/node2vec.hip), negatives drawn in proportion to
+degree^power, and a separate context table.  torch owns the memory and the CPU permutation; there is no CPU path."""
+import numpy as np
 import torch
 
 from . import ops
 
 
+def negative_cdf(indices, n_nodes, power):
+    """The 32-bit CDF of the negative distribution w_n = out_degree_n ** power (docs/POSITION_SEMANTICS.md), in fp64 numpy on the CPU:
+    out_degree_n = how often n occurs in `indices` (proportional to how often an in-edge walk visits n; degree 0 gives weight 0), and
+    cdf[n] = min(2^32 - 1, floor(cumsum(w)[n] / sum(w) * 2^32)).  Returns an int64 numpy array [n_nodes] of values in [0, 2^32).  A graph
+    whose weights are all zero is refused."""
+    deg = np.bincount(np.asarray(indices, np.int64), minlength=int(n_nodes)).astype(np.float64)
+    w = np.where(deg > 0, deg ** float(power), 0.0)
+    total = w.sum()
+    if not total > 0:
+        raise ValueError("negative_cdf: every node has weight 0 (a graph without edges has no degree distribution to draw from)")
+    return np.minimum(np.floor(np.cumsum(w) / total * 2.0 ** 32), 2.0 ** 32 - 1).astype(np.int64)
+
+
 class DeepWalk:
     """One embedding table over the nodes of the square graph `g` (on the GPU), trained by skip-gram with negative sampling over the
-    windows of uniform random walks along in-edges (glnn_random_walk).
+    windows of random walks along in-edges (glnn_random_walk; glnn_node2vec_walk when (p, q) != (1, 1)).
       .embedding   [N, dim] float32 on g's device; N(0, 1) drawn on the CPU from torch.Generator().manual_seed(seed), so an oracle can
                    start from the same bits
       .step(roots, walk_seed, neg_seed)   one optimiser step over the walks from `roots`; returns the loss as a device scalar
       .fit(epochs, batch_size)            every node a root once per epoch; returns the per-epoch mean loss (one host read per epoch)
-    dim % 4 == 0, dim <= 256; 1 <= walk_length <= 64; 2 <= context_size <= walk_length + 1; num_negative >= 1."""
+    dim % 4 == 0, dim <= 256; 1 <= walk_length <= 64; 2 <= context_size <= walk_length + 1; num_negative >= 1.
+    The node2vec switches; with all four at their defaults a step makes exactly the calls it made before they existed:
+      p, q              in [0.25, 4]: the return and in-out parameters of the second-order walk
+      negative_power    > 0: negatives are drawn in proportion to out_degree ** negative_power (0.75 is word2vec's); 0: uniform
+      context_table     True: the entries of a pair are scored against .context [N, dim], N(0, 1) from manual_seed(seed + 1), which has
+                        Adam moments of its own; .embedding stays the output"""
 
-    def __init__(self, g, dim, walk_length=20, context_size=10, num_negative=1, lr=0.01, betas=(0.9, 0.999), eps=1e-8, seed=0):
+    def __init__(self, g, dim, walk_length=20, context_size=10, num_negative=1, lr=0.01, betas=(0.9, 0.999), eps=1e-8, seed=0,
+                 p=1.0, q=1.0, negative_power=0.0, context_table=False):
         if not g.indptr.is_cuda:
             raise RuntimeError("DeepWalk: the trainer runs on the GPU (move the graph with g.to(device))")
         if g.n_dst != g.n_src:
@@ -33,12 +54,31 @@ class DeepWalk:
             raise ValueError(f"DeepWalk: num_negative must be >= 1 (got {num_negative})")
         self.g, self.dim = g, dim
         self.walk_length, self.context_size, self.num_negative = walk_length, context_size, num_negative
+        p, q, negative_power = float(p), float(q), float(negative_power)
+        if not (0.25 <= p <= 4.0 and 0.25 <= q <= 4.0):
+            raise ValueError(f"DeepWalk: p and q must be in [0.25, 4] (got p = {p}, q = {q})")
+        if not negative_power >= 0.0:
+            raise ValueError(f"DeepWalk: negative_power must be >= 0 (got {negative_power})")
+        self.p, self.q, self.negative_power, self.context_table = p, q, negative_power, bool(context_table)
         self.lr, self.betas, self.eps, self.seed = float(lr), (float(betas[0]), float(betas[1])), float(eps), int(seed)
         gen = torch.Generator()
         gen.manual_seed(self.seed)
         self.embedding = torch.randn((g.n_src, dim), generator=gen, dtype=torch.float32).to(g.device)
         self.exp_avg = torch.zeros_like(self.embedding)
         self.exp_avg_sq = torch.zeros_like(self.embedding)
+        self.neg_cdf = None     # int32 words of the 32-bit CDF on the device, built once
+        if negative_power > 0.0:
+            self.neg_cdf = ops.deepwalk_cdf_words(negative_cdf(g.indices.cpu().numpy(), g.n_src, negative_power), g.device)
+        self.context = self.context_exp_avg = self.context_exp_avg_sq = None
+        if self.context_table:
+            gen = torch.Generator()
+            gen.manual_seed(self.seed + 1)
+            self.context = torch.randn((g.n_src, dim), generator=gen, dtype=torch.float32).to(g.device)
+            self.context_exp_avg = torch.zeros_like(self.context)
+            self.context_exp_avg_sq = torch.zeros_like(self.context)
+            self._no_list = ops.deepwalk_empty_list(g.n_src, g.device)
+            self._loss_scratch = torch.empty((), dtype=torch.float32, device=g.device)
+        self._plain = p == 1.0 and q == 1.0 and self.neg_cdf is None and not self.context_table
         self.steps = 0          # optimiser steps taken: Adam's global step count
         self._epoch = 0
 
@@ -50,13 +90,26 @@ class DeepWalk:
         roots = torch.as_tensor(roots, dtype=torch.int64)
         if roots.numel() == 0:
             return torch.zeros((), dtype=torch.float32, device=g.device)
-        _, start, rest, pair_indptr, win_indptr = ops.deepwalk_pairs(g.indptr, g.indices, roots, self.walk_length, c, k, walk_seed, neg_seed)
-        gr, gs, zs, loss_parts = ops.deepwalk_score(self.embedding, start, rest, c, k)
+        if self._plain:
+            _, start, rest, pair_indptr, win_indptr = ops.deepwalk_pairs(g.indptr, g.indices, roots, self.walk_length, c, k, walk_seed, neg_seed)
+        else:
+            # (at p = q = 1 this is random_walk's step and bits; the entry is used all the same because it checks the roots on the host)
+            walks = ops.node2vec_walk(g.indptr, g.indices, roots, self.walk_length, self.p, self.q, walk_seed)
+            start, rest, pair_indptr, win_indptr = ops.deepwalk_pairs_from_walks(walks, g.n_src, c, k, neg_seed, self.neg_cdf)
+        gr, gs, zs, loss_parts = ops.deepwalk_score(self.embedding, start, rest, c, k, ctx=self.context)
         q, r = rest.shape
         tw = ops.csr_transpose(win_indptr, start, q, g.n_src, q)
         tp_indptr, _, tp_eids = ops.csr_transpose_eids(pair_indptr, rest.view(-1), q, g.n_src, q * r)
-        loss = ops.deepwalk_apply(self.embedding, self.exp_avg, self.exp_avg_sq, tw, (tp_indptr, tp_eids), gr, gs, zs, loss_parts, c, k,
-                                  self.lr, self.betas, self.eps, self.steps + 1)
+        if self.context is None:
+            loss = ops.deepwalk_apply(self.embedding, self.exp_avg, self.exp_avg_sq, tw, (tp_indptr, tp_eids), gr, gs, zs, loss_parts, c, k,
+                                      self.lr, self.betas, self.eps, self.steps + 1)
+        else:
+            # two tables: dZ[a] = sum g c_x comes from the windows list alone, dC[x] = sum g z_a from the positions list alone -- the apply
+            # launch sums its two lists separately, so each table is one call of it with the other list empty, at the same step count
+            loss = ops.deepwalk_apply(self.embedding, self.exp_avg, self.exp_avg_sq, tw, self._no_list, gr, gs, zs, loss_parts, c, k,
+                                      self.lr, self.betas, self.eps, self.steps + 1)
+            ops.deepwalk_apply(self.context, self.context_exp_avg, self.context_exp_avg_sq, self._no_list, (tp_indptr, tp_eids), gr, gs, zs,
+                               loss_parts, c, k, self.lr, self.betas, self.eps, self.steps + 1, loss_out=self._loss_scratch)
         self.steps += 1
         return loss
 

@@ -843,6 +843,34 @@ GLNN_API int glnn_deepwalk_apply_f32(const int64_t* tw_indptr, const int32_t* tw
                                      double beta1, double beta2, double eps, int64_t step, const float* loss_parts, float* loss_out,
                                      void* stream);
 
+/* The rest of the node2vec family (same ABI: entries added, none changed; docs/POSITION_SEMANTICS.md).
+ *
+ * glnn_node2vec_walk: glnn_random_walk's output with the second-order bias of node2vec (Grover, Leskovec, KDD 2016).  Step 1 is
+ * glnn_random_walk's.  At step s >= 2, standing on v with t = out[i, s - 2], a candidate x of row v is a RETURN (x == t, tested first,
+ * weight 1/p), NEAR (x is an entry of row t; weight 1) or FAR (weight 1/q).  With wmax = max(1/p, 1, 1/q) and
+ * T_class = min(2^32, floor(w_class / wmax * 2^32)) formed in double, attempt a = 0, 1, ... draws
+ *     x = indices[indptr[v] + (((uint64_t)drop_hash(rng_seed, i, s + 128 a) * deg) >> 32)]
+ * and accepts it iff (uint64_t)drop_hash(rng_seed ^ 0x4E32564B, i, s + 128 a) < T_class(x); after 256 rejected attempts the 256th
+ * candidate is taken (probability <= (15/16)^256 < 7e-8 per step).  p = q = 1 accepts attempt 0 everywhere: glnn_random_walk's bits.
+ * p, q in [0.25, 4]; 1 <= length <= 64.  roots_host (optional): a host copy of roots, checked against [0, n_nodes) before the launch. */
+GLNN_API int glnn_node2vec_walk(const int64_t* indptr, const int32_t* indices, int64_t n_nodes, const int64_t* roots,
+                                const int64_t* roots_host, int64_t n_roots, int length, double p, double q, uint32_t rng_seed,
+                                int64_t* out, void* stream);
+/* glnn_deepwalk_pairs_from_walks: glnn_deepwalk_pairs' four outputs from walks [n_roots, L + 1] that are an INPUT.  neg_cdf NULL: the
+ * uniform negative of glnn_deepwalk_pairs.  neg_cdf [n_nodes] (device, ascending 32-bit CDF): with r = drop_hash(neg_seed, q, t') the
+ * negative is the number of n in [0, n_nodes - 1) with neg_cdf[n] <= r (an upper-bound binary search over the first n_nodes - 1 entries:
+ * in [0, n_nodes - 1] whatever the table holds). */
+GLNN_API int glnn_deepwalk_pairs_from_walks(const int64_t* walks, int64_t n_roots, int length, int context, int negatives,
+                                            int64_t n_nodes, uint32_t neg_seed, const uint32_t* neg_cdf, int32_t* start, int32_t* rest,
+                                            int64_t* pair_indptr, int64_t* win_indptr, void* stream);
+/* glnn_deepwalk_score_ctx_f32: glnn_deepwalk_score_f32 with the entries read from a second table, s = <z[start[q]], c[rest[q R + t]]>,
+ * gs[q] = sum_t g c[rest]; zs[q] = z[start[q]] as before.  c == z: glnn_deepwalk_score_f32's bits.  The two-table update is two
+ * glnn_deepwalk_apply_f32 calls: on (z, m_z, v_z) with the windows list and an EMPTY positions CSR (all-zero tp_indptr), and on
+ * (c, m_c, v_c) with an empty windows CSR and the positions list. */
+GLNN_API int glnn_deepwalk_score_ctx_f32(const float* z, const float* c, int64_t n_nodes, int d, const int32_t* start,
+                                         const int32_t* rest, int64_t n_windows, int context, int negatives, float* g, float* gs,
+                                         float* zs, float* loss_parts, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * GPR-GNN propagation (Chien et al., ICLR 2021): result = sum_{k = 0..K} gamma[k] P^k x0 with K + 1 learned coefficients and APPNP's
  * operator P = D_in^-1/2 A D_out^-1/2.  docs/GPR_SEMANTICS.md states the arithmetic.  ONE entry serves both directions, one call per
