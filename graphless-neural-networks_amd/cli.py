@@ -202,10 +202,11 @@ def _prop(feats, g, k, device):
 def _with_position(args, feats, g, idx_obs, device, logger):
     """--position_dim D > 0: feats with a DeepWalk embedding of D columns appended (run_student widens conf["feat_dim"] by D).  idx_obs None
     (transductive): fitted on g.  Inductive: fitted on g.subgraph(idx_obs) only, the rows of the hidden test nodes filled with the mean
-    over their observed in-neighbours (position.fill_unseen) -- NOSMOG's recipe."""
+    over their observed in-neighbours (position.fill_unseen) -- NOSMOG's recipe.  Returns (feats, table): the fitted embedding as a
+    position.PositionTable, what serve_student.py serves from (None when --position_dim is 0)."""
     if args.position_dim <= 0:
-        return feats
-    from .position import DeepWalk, fill_unseen
+        return feats, None
+    from .position import DeepWalk, PositionTable, fill_unseen
     gd = g.to(device)
     sub = gd if idx_obs is None else g.subgraph(idx_obs).to(device)
     dw = DeepWalk(sub, args.position_dim, args.position_walk_length, args.position_context, args.position_negatives,
@@ -214,11 +215,12 @@ def _with_position(args, feats, g, idx_obs, device, logger):
     losses = dw.fit(args.position_epochs, args.position_batch_size)
     logger.info(f"position embedding: {sub.num_nodes()} nodes x {args.position_dim}, loss per epoch " + " ".join(f"{x:.4f}" for x in losses))
     z = dw.embedding
+    table = PositionTable.from_deepwalk(dw, idx_obs, g.num_nodes())
     if idx_obs is not None:
         full = torch.zeros((g.num_nodes(), args.position_dim), dtype=torch.float32, device=device)
         full[torch.as_tensor(idx_obs, dtype=torch.int64, device=device)] = z
         z = fill_unseen(gd, full, idx_obs)
-    return torch.cat([feats, z.to(feats.device)], dim=1)
+    return torch.cat([feats, z.to(feats.device)], dim=1), table
 
 
 def run_teacher(args):
@@ -297,7 +299,7 @@ def run_student(args):
     if args.exp_setting == "tran":
         distill_indices = (idx_train, torch.cat([idx_train, idx_val, idx_test]), idx_val, idx_test)
         feats = _prop(feats, g, args.feature_aug_k, device)
-        feats = _with_position(args, feats, g, None, device, logger)
+        feats, table = _with_position(args, feats, g, None, device, logger)
         out, score_val, score_test = distill_run_transductive(conf, model, feats, labels, out_t, distill_indices, criterion_l,
                                                               criterion_t, evaluator, optimizer, logger, loss_and_score)
         score_lst = [score_test]
@@ -309,14 +311,91 @@ def run_student(args):
             obs_feats = _prop(feats[idx_obs], g.subgraph(idx_obs), args.feature_aug_k, device)
             feats = _prop(feats, g, args.feature_aug_k, device)
             feats[idx_obs] = obs_feats
-        feats = _with_position(args, feats, g, idx_obs, device, logger)
+        feats, table = _with_position(args, feats, g, idx_obs, device, logger)
         out, score_val, score_tt, score_ti = distill_run_inductive(conf, model, feats, labels, out_t, distill_indices, criterion_l,
                                                                    criterion_t, evaluator, optimizer, logger, loss_and_score)
         score_lst = [score_tt, score_ti]
     logger.info(f"num_layers: {conf['num_layers']}. hidden_dim: {conf['hidden_dim']}. dropout_ratio: {conf['dropout_ratio']}")
     logger.info(f"# params {sum(p.numel() for p in model.parameters())}")
     _save(args, output_dir, out, loss_and_score, model, g)
+    if table is not None and args.save_results:
+        table.save(output_dir.joinpath("position.npz"))          # what serve_student.py serves from, beside model.pth
     return score_lst
+
+
+SERVE_BATCH_IDS = 4096         # serve_student.py: ids per call of the served chain (see run_serve)
+
+
+def get_serve_args(argv=None):
+    """serve_student.py: the flags that locate a finished train_student.py run (the student's own flags, with the same defaults and the
+    same YAML merge), --serve_dtype, and --nodes."""
+    p = _parser(_COMMON + _STUDENT_ONLY, "GLNN position-feature student: serve saved artefacts by node id (HIP hot path)")
+    p.add_argument("--serve_dtype", type=str, default="float32", choices=["float32", "bfloat16"],
+                   help="Storage of the served chain (bfloat16: bf16 weights, activations and assembled rows)")
+    p.add_argument("--position_dim", type=int, default=0, help="--position_dim of the run to serve (it names the run's directory)")
+    p.add_argument("--nodes", type=str, default=None, help="An .npy of int64 node ids to serve (default: every node)")
+    args = p.parse_args(argv)
+    if args.feature_aug_k > 0:
+        p.error("serve_student.py does not serve --feature_aug_k runs: the augmented features are propagated over the graph at training "
+                "time and are not a saved artefact")
+    if args.feature_noise != 0:
+        p.error("serve_student.py does not serve --feature_noise runs: the noise drawn at training time is not a saved artefact")
+    if args.position_dim < 0 or args.position_dim % 4 or args.position_dim > 256:
+        p.error(f"--position_dim must be 0 or a multiple of 4 up to 256 (got {args.position_dim})")
+    return args
+
+
+def run_serve(args):
+    """Log-probabilities of --nodes from the artefacts of a train_student.py --position_dim D --save_results run: the dataset's features,
+    model.pth and position.npz, through serve.compile_position_student; writes served_out.npz (arr_0: [len(nodes), C] float32) into the
+    run's directory."""
+    pe = f"PE{args.position_dim}" if args.position_dim > 0 else ""
+    output_dir = _setting_dir(args, args.output_path, f"{args.teacher}_{pe}{args.student}")
+    for name, why in (("position.npz", "only runs with --position_dim D > 0 and --save_results write it"),
+                      ("model.pth", "only runs with --save_results write it")):
+        if not output_dir.joinpath(name).exists():
+            raise SystemExit(f"serve_student.py: {output_dir} has no {name} ({why}); nothing to serve")
+    device = _device(args)
+    import logging
+    from .position import PositionTable
+    from .serve import compile_position_student
+    from .train_and_eval import INFERENCE_DTYPES
+    g, feats, _, _, conf = _load(args, logging.getLogger("glnn_amd.serve_student"), args.student)
+    table = PositionTable.load(output_dir.joinpath("position.npz"), device)
+    if table.dim != args.position_dim:
+        raise SystemExit(f"serve_student.py: position.npz holds rows of {table.dim} columns, --position_dim says {args.position_dim}")
+    conf["device"] = device
+    conf["feat_dim"] += table.dim
+    model = Model(conf)
+    model.load_state_dict(torch.load(output_dir.joinpath("model.pth"), map_location=device))
+    model.eval()
+    n = g.num_nodes()
+    needs_graph = table.has_unseen or n > table.num_nodes
+    served = compile_position_student(model, feats.to(device), table, g.to(device) if needs_graph else None,
+                                      dtype=INFERENCE_DTYPES[args.serve_dtype])
+    nodes = torch.arange(n, dtype=torch.int64) if args.nodes is None else torch.from_numpy(np.load(args.nodes).astype(np.int64).reshape(-1))
+    if nodes.numel() and (int(nodes.min()) < 0 or int(nodes.max()) >= n):
+        raise SystemExit(f"serve_student.py: --nodes must hold node ids in [0, {n}) (got {int(nodes.min())} .. {int(nodes.max())})")
+    # Fixed batches: the fp32 chain picks its GEMM form (latency kernels, split-K) by the row count of the call, so the bits of a row depend
+    # on how many rows it was served with.  Every call here has SERVE_BATCH_IDS rows, the last batch padded by repeating its last id: what
+    # a node is served does not depend on the request it came in.
+    nodes = nodes.to(device)
+    out = torch.empty((nodes.numel(), conf["label_dim"]), dtype=torch.float32, device=device)
+    batch = torch.empty((SERVE_BATCH_IDS, conf["label_dim"]), dtype=torch.float32, device=device)
+    for s0 in range(0, nodes.numel(), SERVE_BATCH_IDS):
+        sub = nodes[s0:s0 + SERVE_BATCH_IDS]
+        k = sub.numel()
+        if k < SERVE_BATCH_IDS:
+            sub = torch.cat([sub, sub[-1:].expand(SERVE_BATCH_IDS - k)])
+        served.log_probs(sub, out=batch, check_ids=False)
+        out[s0:s0 + k] = batch[:k]
+    np.savez(output_dir.joinpath("served_out"), out.cpu().numpy())
+    return out
+
+
+def serve_main(argv=None):
+    out = run_serve(get_serve_args(argv))
+    print(f"served {out.shape[0]} nodes")
 
 
 def _main(args, run):

@@ -2060,3 +2060,40 @@ def gemm_bf16(a, w, ep_scale=None, ep_shift=None, relu=False, out=None, out_dtyp
                                        1 if log_softmax else 0, _stream())
     _lib.check(rc, "glnn_gemm_bf16")
     return out[:m] if out.shape[0] != m else out
+
+
+# ---------------------------------------------------------------------------------------------
+# serving a position-feature student by node id (csrc/position_serve.hip)
+def position_rows(ids, x, z, slot, g=None, out=None, out_dtype=None):
+    """glnn_position_rows (docs/POSITION_SEMANTICS.md, "Serving by node id"): out[b] = [x[ids[b]] | pos(ids[b])] in one launch.
+    ids: contiguous int64 device vector of node ids (the CALLER vouches for their range); x: [N, F] fp32 or bf16 features; z: [R, D] fp32
+    position table; slot: int32 [N], node -> row of z or -1.  pos(v) = z[slot[v]] for an embedded node, else the mean of z[slot[u]] over the
+    embedded stored entries u of row v of the in-edge CSR of `g` (zeros without one).  g None: no id is unseen (a row that is gets zeros).
+    out: `out` (at least len(ids) rows of F + D columns; its dtype decides), else a fresh matrix of out_dtype (default: x's dtype); fp32
+    rows are padded to a multiple of 4 columns, bf16 rows to 8, the padding written as 0.  bf16 features with an fp32 output are refused."""
+    _need_cuda(ids, x, z, slot, out)
+    if ids.dtype != torch.int64 or ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError("position_rows: ids must be a contiguous int64 vector")
+    if x.dtype == torch.bfloat16:
+        x = as_bf16_feat(x)
+    else:
+        _mat(x, "position_rows x")
+    _dw_table(z, "position_rows z")
+    n, f = x.shape
+    d = z.shape[1]
+    if slot.dtype != torch.int32 or slot.dim() != 1 or not slot.is_contiguous() or slot.numel() != n:
+        raise ValueError(f"position_rows: slot must be a contiguous int32 vector with one entry per row of x ({n})")
+    indptr = indices = None
+    if g is not None:
+        indptr, indices = g.indptr, g.indices
+        _need_cuda(indptr, indices)
+        _check_csr(indptr, indices, "position_rows")
+        if indptr.numel() != n + 1:
+            raise ValueError(f"position_rows: the graph has {indptr.numel() - 1} rows, x {n}")
+    m = ids.numel()
+    out = _out_like(out, out_dtype, x.dtype, m, f + d, x.device, "position_rows out")
+    with _Timed("position_rows", m=m, f=f, d=d):
+        rc = _lib.lib().glnn_position_rows(_p(ids), m, _p(x), _ld(x), _dtype_code(x), f, _p(z), _ld(z), d, z.shape[0], _p(slot), n,
+                                           _p(indptr), _p(indices), _p(out), _ld(out), _dtype_code(out), _stream())
+    _lib.check(rc, "glnn_position_rows")
+    return out[:m] if out.shape[0] != m else out

@@ -137,6 +137,78 @@ class DeepWalk:
         return means
 
 
+class PositionTable:
+    """The position embedding as a servable artefact (docs/POSITION_SEMANTICS.md, "Serving by node id"): one row per EMBEDDED node.
+      .rows        [R, D] float32, the embedding rows
+      .node_ids    [R] int64, the node each row belongs to (distinct, inside [0, num_nodes))
+      .num_nodes   the N of the graph the table was fitted against
+      .slot(n)     int32 [n], node -> its row, -1 for a node without one; n > num_nodes: the nodes that joined the graph later get -1
+      .has_unseen  whether any of the num_nodes nodes lacks a row
+      .dense(g)    the [N, D] matrix training concatenates: the rows scattered, then fill_unseen over g
+      .save(path) / PositionTable.load(path, device)    an .npz of rows, node_ids and num_nodes
+    The tensors live on whatever device they were given on; dense() and serving need the GPU."""
+
+    def __init__(self, rows, node_ids, num_nodes):
+        rows, node_ids, num_nodes = torch.as_tensor(rows), torch.as_tensor(node_ids), int(num_nodes)
+        if rows.dtype != torch.float32 or rows.dim() != 2:
+            raise ValueError("PositionTable: rows must be a float32 matrix [R, D]")
+        if node_ids.dtype != torch.int64 or node_ids.dim() != 1 or node_ids.numel() != rows.shape[0]:
+            raise ValueError("PositionTable: node_ids must be an int64 vector with one entry per row")
+        if node_ids.device != rows.device:
+            raise ValueError("PositionTable: rows and node_ids must be on one device")
+        if node_ids.numel() and (int(node_ids.min()) < 0 or int(node_ids.max()) >= num_nodes):
+            raise ValueError(f"PositionTable: node_ids must lie in [0, num_nodes = {num_nodes})")
+        if torch.unique(node_ids).numel() != node_ids.numel():
+            raise ValueError("PositionTable: node_ids must be distinct")
+        self.rows, self.node_ids, self.num_nodes = rows.contiguous(), node_ids.contiguous(), num_nodes
+        self._slots = {}
+
+    @classmethod
+    def from_deepwalk(cls, dw, idx_obs=None, num_nodes=None):
+        """The table of a fitted DeepWalk.  Transductive (idx_obs None): dw was fitted on the whole graph, row n is node n.  Inductive: dw
+        was fitted on g.subgraph(idx_obs) of a graph of num_nodes nodes, row i is node idx_obs[i]."""
+        z = dw.embedding
+        if idx_obs is None:
+            return cls(z, torch.arange(z.shape[0], dtype=torch.int64, device=z.device), z.shape[0] if num_nodes is None else num_nodes)
+        if num_nodes is None:
+            raise ValueError("PositionTable.from_deepwalk: the inductive form needs num_nodes")
+        return cls(z, torch.as_tensor(idx_obs, dtype=torch.int64).to(z.device), num_nodes)
+
+    dim = property(lambda self: self.rows.shape[1])
+    device = property(lambda self: self.rows.device)
+    has_unseen = property(lambda self: self.rows.shape[0] < self.num_nodes)
+
+    def slot(self, n_nodes=None):
+        n = self.num_nodes if n_nodes is None else int(n_nodes)
+        if n < self.num_nodes:
+            raise ValueError(f"PositionTable.slot: n_nodes = {n} is below the {self.num_nodes} nodes the table was fitted against")
+        s = self._slots.get(n)
+        if s is None:
+            s = torch.full((n,), -1, dtype=torch.int32, device=self.device)
+            s[self.node_ids] = torch.arange(self.rows.shape[0], dtype=torch.int32, device=self.device)
+            self._slots = {n: s}
+        return s
+
+    def dense(self, g):
+        n = g.num_nodes()
+        if n < self.num_nodes:
+            raise ValueError(f"PositionTable.dense: the graph has {n} nodes, the table was fitted against {self.num_nodes}")
+        full = torch.zeros((n, self.dim), dtype=torch.float32, device=self.device)
+        full[self.node_ids] = self.rows
+        return fill_unseen(g, full, self.node_ids) if self.rows.shape[0] < n else full
+
+    def to(self, device):
+        return self if torch.device(device) == self.device else PositionTable(self.rows.to(device), self.node_ids.to(device), self.num_nodes)
+
+    def save(self, path):
+        np.savez(path, rows=self.rows.detach().cpu().numpy(), node_ids=self.node_ids.cpu().numpy(), num_nodes=np.int64(self.num_nodes))
+
+    @classmethod
+    def load(cls, path, device="cpu"):
+        with np.load(path) as f:
+            return cls(torch.from_numpy(f["rows"]).to(device), torch.from_numpy(f["node_ids"]).to(device), int(f["num_nodes"]))
+
+
 def fill_unseen(g, z, idx_obs):
     """Position rows for nodes that were not embedded (NOSMOG's inductive recipe): a node outside idx_obs gets the mean of z over its
     in-edges from nodes inside idx_obs (a multi-edge counts as often as it is stored), zeros if it has none; rows inside idx_obs are

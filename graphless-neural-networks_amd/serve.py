@@ -6,7 +6,12 @@ weight before rounding.  `ServedStudent.logits / log_probs` then run the whole c
 stored as bf16 in two reused buffers, every product runs on the bf16 MFMA with fp32 accumulation, the result is fp32.
 
 The default everywhere stays the fp32 path; this module is reached through `compile_student`, `evaluate_mini_batch(dtype=torch.bfloat16)`
-and `train_student.py --serve_dtype bfloat16` only."""
+and `train_student.py --serve_dtype bfloat16` only.
+
+`compile_position_student(model, feats, table, g)` serves a student with position features BY NODE ID (csrc/position_serve.hip:
+glnn_position_rows; docs/POSITION_SEMANTICS.md, "Serving by node id"): its input rows are assembled per block of ids from the features,
+the saved position table and the graph, and either chain above runs over them unchanged.  Reached through that function and
+`serve_student.py` only."""
 import ctypes
 
 import torch
@@ -26,17 +31,22 @@ def compile_student(model, dtype=torch.bfloat16):
     MLP_MAX_LAYERS layers, training mode.  Parameters on the CPU raise GlnnError like every op."""
     if dtype != torch.bfloat16:
         raise ValueError(f"compile_student: dtype {dtype} (the serving path stores torch.bfloat16; float32 is the default path itself)")
+    return ServedStudent(model, _servable_encoder(model, "compile_student"))
+
+
+def _servable_encoder(model, who):
+    """The MLP of `model`, or the NotImplementedError of compile_student's docstring in the name of `who`."""
     enc = _encoder_of(model)
     if not isinstance(enc, MLP):
-        raise NotImplementedError(f"compile_student: {type(enc).__name__} is not an MLP student (teachers have Model.inference(dtype=...))")
+        raise NotImplementedError(f"{who}: {type(enc).__name__} is not an MLP student (teachers have Model.inference(dtype=...))")
     if enc.norm_type == "layer":
-        raise NotImplementedError("compile_student: norm_type 'layer' has per-row statistics; the bf16 serving path takes 'none' and 'batch'")
+        raise NotImplementedError(f"{who}: norm_type 'layer' has per-row statistics; the bf16 serving path takes 'none' and 'batch'")
     _check_tail(enc)
     if len(enc.layers) > _lib.MLP_MAX_LAYERS:
-        raise NotImplementedError(f"compile_student: {len(enc.layers)} layers, at most {_lib.MLP_MAX_LAYERS}")
+        raise NotImplementedError(f"{who}: {len(enc.layers)} layers, at most {_lib.MLP_MAX_LAYERS}")
     if model.training or enc.training:
-        raise NotImplementedError("compile_student: the model is in training mode (call model.eval() first: BatchNorm running statistics, no dropout)")
-    return ServedStudent(model, enc)
+        raise NotImplementedError(f"{who}: the model is in training mode (call model.eval() first: BatchNorm running statistics, no dropout)")
+    return enc
 
 
 class ServedStudent:
@@ -152,6 +162,103 @@ class ServedStudent:
     def log_probs(self, feats, out=None):
         """fp32 log_softmax(logits); for C <= 64 it is the last product's epilogue and the logits never reach memory."""
         return self._run(feats, out, True)
+
+
+POSITION_BLOCK_ROWS = 65536        # ids per assembled block of a ServedPositionStudent
+
+
+def compile_position_student(model, feats, table, g=None, dtype=torch.bfloat16):
+    """A ServedPositionStudent: an eval-mode MLP student with position features (docs/POSITION_SEMANTICS.md, "Serving by node id"), served
+    by node id from the node features `feats` [N, F] (fp32, or bf16 for the bf16 chain; on the GPU), a position.PositionTable of width D
+    and, where a node may lack a table row, the graph `g` -- the [N, F + D] matrix training concatenated is never built.
+    dtype: torch.bfloat16 (the ServedStudent chain) or torch.float32 (model.inference + ops.log_softmax).
+    Refused: whatever compile_student refuses (NotImplementedError); a first layer that is not F + D wide, a table with unseen nodes (or
+    fewer nodes than feats has rows) without g, a graph that does not have feats' rows (ValueError)."""
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"compile_position_student: dtype {dtype} (torch.bfloat16 or torch.float32)")
+    enc = _servable_encoder(model, "compile_position_student")
+    return ServedPositionStudent(model, enc, feats, table, g, dtype)
+
+
+class ServedPositionStudent:
+    """logits / log_probs of a batch of node ids.  Per block of POSITION_BLOCK_ROWS ids one ops.position_rows launch assembles
+    [x[v] | pos(v)] into a reused buffer -- bf16 [blk, round8(F + D)] or fp32 [blk, round4(F + D)] -- and the existing chain runs over
+    it: a ServedStudent (bf16), or model.inference and ops.log_softmax (fp32).  A row's result does not depend on the blocking or on the
+    other ids of the call."""
+
+    def __init__(self, model, enc, feats, table, g, dtype):
+        ops._need_cuda(feats, table.rows, table.node_ids)
+        if feats.dim() != 2 or feats.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"compile_position_student: features must be a float32 or bfloat16 matrix, got {feats.dtype} {tuple(feats.shape)}")
+        if feats.dtype == torch.bfloat16 and dtype != torch.bfloat16:
+            raise ValueError("compile_position_student: bfloat16 features need dtype=torch.bfloat16 (the kernel does not widen features)")
+        n, f = feats.shape
+        if n < table.num_nodes:
+            raise ValueError(f"compile_position_student: features have {n} rows, the table was fitted against {table.num_nodes} nodes")
+        if enc.layers[0].in_features != f + table.dim:
+            raise ValueError(f"compile_position_student: the model's first layer takes {enc.layers[0].in_features} columns, features and "
+                             f"table give {f} + {table.dim}")
+        if g is None and (table.has_unseen or n > table.num_nodes):
+            raise ValueError("compile_position_student: the table has no row for some nodes; their position is the mean over their "
+                             "in-neighbours, which needs the graph g")
+        if g is not None:
+            ops._need_cuda(g.indptr, g.indices)
+            if g.n_dst != g.n_src or g.num_nodes() != n:
+                raise ValueError(f"compile_position_student: g must be the square graph over the {n} rows of the features")
+        self.model, self.enc, self.g, self.dtype = model, enc, g, dtype
+        self.x = ops.as_bf16_feat(feats) if feats.dtype == torch.bfloat16 else ops._mat(feats, "compile_position_student features")
+        self.z, self.slot = table.rows, table.slot(n)
+        self.num_nodes, self.width = n, f + table.dim
+        self.served = ServedStudent(model, enc) if dtype == torch.bfloat16 else None
+        self._block = None
+
+    def _buffer(self, rows):
+        b = self._block
+        if b is None or b.shape[0] < rows:
+            make = ops.bf16_empty if self.dtype == torch.bfloat16 else ops.feat_empty
+            self._block = b = make(rows, self.width, self.x.device)
+        return b
+
+    def _run(self, ids, out, log_softmax, check_ids):
+        ops._need_cuda(ids, out)
+        if ids.dtype != torch.int64 or ids.dim() != 1:
+            raise ValueError("ServedPositionStudent: ids must be an int64 vector")
+        ids = ids.contiguous()
+        rows, c = ids.numel(), self.enc.layers[-1].out_features
+        if check_ids and rows:
+            lo, hi = torch.stack(torch.aminmax(ids)).tolist()          # (the call's one host read)
+            if lo < 0 or hi >= self.num_nodes:
+                raise ValueError(f"ServedPositionStudent: ids must lie in [0, {self.num_nodes}) (got {lo} .. {hi})")
+        if self.served is None and (self.model.training or self.enc.training):
+            raise NotImplementedError("ServedPositionStudent: the model went back to training mode (serving is eval-mode only)")
+        if out is None:
+            out = torch.empty((rows, c), dtype=torch.float32, device=self.x.device)
+        ops._mat(out, "ServedPositionStudent out")
+        if tuple(out.shape) != (rows, c):
+            raise ValueError(f"ServedPositionStudent: out must be float32 [{rows}, {c}]")
+        blk = min(rows, POSITION_BLOCK_ROWS)
+        buf = self._buffer(blk) if rows else None
+        with torch.no_grad():
+            for s0 in range(0, rows, blk):
+                sub = ids[s0:s0 + blk]
+                block = ops.position_rows(sub, self.x, self.z, self.slot, g=self.g, out=buf)
+                os_ = out[s0:s0 + blk]
+                if self.served is not None:
+                    self.served._run(block, os_, log_softmax)
+                elif log_softmax:
+                    ops.log_softmax(self.model.inference(None, block), out=os_)
+                else:
+                    os_.copy_(self.model.inference(None, block))
+        return out
+
+    def logits(self, ids, out=None, check_ids=True):
+        """fp32 logits [len(ids), C] of the nodes `ids` (an int64 device vector; repeats allowed).  check_ids=False skips the range check
+        and its host read: the caller then vouches that every id is a node."""
+        return self._run(ids, out, False, check_ids)
+
+    def log_probs(self, ids, out=None, check_ids=True):
+        """fp32 log_softmax(logits)."""
+        return self._run(ids, out, True, check_ids)
 
 
 def served_for(model):

@@ -1098,6 +1098,28 @@ GLNN_API int glnn_mlp_forward_bf16(const glnn_mlp_serve_desc* desc, const void* 
                                    uint16_t* buf0, uint16_t* buf1, int64_t ld_buf, float* out, int64_t ldo,
                                    int log_softmax, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Serving a position-feature student by node id (csrc/position_serve.hip; docs/POSITION_SEMANTICS.md, "Serving by node id"): the
+ * student's input rows for a batch of node ids, assembled from the features, the position table and the graph in ONE launch; nothing of
+ * size n_nodes is built.  For b < m, v = ids[b]:
+ *   out[b, 0:f]     = x[v, 0:f]     x fp32 [n_nodes, ldx] (any ldx >= f) or bf16 (ldx % 8 == 0, 16-byte aligned); fp32 -> fp32, bf16 -> bf16 copy
+ *                                   the bits, fp32 -> bf16 rounds as glnn_cast_f32_bf16; bf16 -> fp32 is GLNN_ERR_UNSUPPORTED
+ *   out[b, f:f + d] = pos(v)        rounded the same way for a bf16 output.  slot [n_nodes]: node -> row of the fp32 table z [z_rows, ldz]
+ *                                   (d % 4 == 0, 4 <= d <= 256, ldz % 4 == 0, 16-byte aligned), a value outside [0, z_rows) = not embedded.
+ *                                   Embedded: pos(v) = z[slot[v]].  Otherwise the mean, sum / (float)count in fp32, of z[slot[u]] over the
+ *                                   stored entries u of row v of the in-edge CSR (indptr, indices over n_nodes rows) that are embedded -- a
+ *                                   multi-edge counts as often as it is stored, an entry outside [0, n_nodes) is skipped -- and exact
+ *                                   zeros without one.  indptr == indices == NULL: no id of the batch is unseen (a row that is gets zeros).
+ *   out[b, f + d : round(f + d)]    = 0, round = up to a multiple of 4 (fp32 out) or 8 (bf16 out); ldo a multiple of that and >= it, out
+ *                                   16-byte aligned.  Columns beyond and rows >= m are not touched.
+ * The ids must be node ids (the callers check them); one outside [0, n_nodes) is never used as an index (its row is zeros).  One wave
+ * per batch row; an unseen row of more than 128 entries is summed by a whole workgroup, the wave partials added in wave order.  No float
+ * atomics: a row's bits depend neither on its position in the batch nor on the other ids.  n_nodes, z_rows < 2^31.  m == 0 is a no-op
+ * that reads no pointer; a refused argument is GLNN_ERR_INVALID_ARG with nothing launched. */
+GLNN_API int glnn_position_rows(const int64_t* ids, int64_t m, const void* x, int64_t ldx, int x_dtype, int f, const float* z,
+                                int64_t ldz, int d, int64_t z_rows, const int32_t* slot, int64_t n_nodes, const int64_t* indptr,
+                                const int32_t* indices, void* out, int64_t ldo, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
