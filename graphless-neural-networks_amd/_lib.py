@@ -130,6 +130,8 @@ SIGNATURES = {
     "glnn_scatter_rows_f32": [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp],
     "glnn_gemm_bf16": [c_vp, c_i64, c_int, c_i64, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_int, c_vp],
     "glnn_mlp_forward_bf16": [c_vp, c_vp, c_i64, c_int, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp],
+    "glnn_mlp_fused_bf16_tile_rows": [c_vp],
+    "glnn_mlp_forward_fused_bf16": [c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp],
     "glnn_position_rows": [c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_int, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_int,
                            c_vp],
 }

@@ -117,6 +117,8 @@ def get_student_args(argv=None):
     # bfloat16 = weights and hidden activations stored as bf16, bf16 MFMA products, fp32 accumulation and saved log-probs (glnn_amd.serve)
     p.add_argument("--serve_dtype", type=str, default="float32", choices=["float32", "bfloat16"],
                    help="Storage of the MLP student's evaluation passes (bfloat16: norm_type none / batch)")
+    p.add_argument("--serve_fused", action="store_true",
+                   help="Run the bfloat16 evaluation passes as one launch per row block (needs --serve_dtype bfloat16; same results)")
     # not reference flags: DeepWalk position features concatenated to the student's input (glnn_amd.position; docs/POSITION_SEMANTICS.md).
     # --position_dim 0 (the default) is off: nothing changes.  The YAML section is still the plain student's
     p.add_argument("--position_dim", type=int, default=0,
@@ -135,6 +137,8 @@ def get_student_args(argv=None):
     p.add_argument("--position_context_table", action="store_true",
                    help="Score the entries of a pair against a separate context table (the embedding table stays the output)")
     args = p.parse_args(argv)
+    if args.serve_fused and args.serve_dtype != "bfloat16":
+        p.error("--serve_fused is a form of the bfloat16 serving path: it needs --serve_dtype bfloat16")
     if not (0.25 <= args.position_p <= 4.0 and 0.25 <= args.position_q <= 4.0):
         p.error(f"--position_p and --position_q must be in [0.25, 4] (got {args.position_p}, {args.position_q})")
     if not args.position_negative_power >= 0.0:
@@ -328,13 +332,17 @@ SERVE_BATCH_IDS = 4096         # serve_student.py: ids per call of the served ch
 
 def get_serve_args(argv=None):
     """serve_student.py: the flags that locate a finished train_student.py run (the student's own flags, with the same defaults and the
-    same YAML merge), --serve_dtype, and --nodes."""
+    same YAML merge), --serve_dtype, --serve_fused and --nodes."""
     p = _parser(_COMMON + _STUDENT_ONLY, "GLNN position-feature student: serve saved artefacts by node id (HIP hot path)")
     p.add_argument("--serve_dtype", type=str, default="float32", choices=["float32", "bfloat16"],
                    help="Storage of the served chain (bfloat16: bf16 weights, activations and assembled rows)")
+    p.add_argument("--serve_fused", action="store_true",
+                   help="Run the bfloat16 chain as one launch per assembled block (needs --serve_dtype bfloat16; same results)")
     p.add_argument("--position_dim", type=int, default=0, help="--position_dim of the run to serve (it names the run's directory)")
     p.add_argument("--nodes", type=str, default=None, help="An .npy of int64 node ids to serve (default: every node)")
     args = p.parse_args(argv)
+    if args.serve_fused and args.serve_dtype != "bfloat16":
+        p.error("--serve_fused is a form of the bfloat16 serving path: it needs --serve_dtype bfloat16")
     if args.feature_aug_k > 0:
         p.error("serve_student.py does not serve --feature_aug_k runs: the augmented features are propagated over the graph at training "
                 "time and are not a saved artefact")
@@ -372,7 +380,7 @@ def run_serve(args):
     n = g.num_nodes()
     needs_graph = table.has_unseen or n > table.num_nodes
     served = compile_position_student(model, feats.to(device), table, g.to(device) if needs_graph else None,
-                                      dtype=INFERENCE_DTYPES[args.serve_dtype])
+                                      dtype=INFERENCE_DTYPES[args.serve_dtype], fused=args.serve_fused)
     nodes = torch.arange(n, dtype=torch.int64) if args.nodes is None else torch.from_numpy(np.load(args.nodes).astype(np.int64).reshape(-1))
     if nodes.numel() and (int(nodes.min()) < 0 or int(nodes.max()) >= n):
         raise SystemExit(f"serve_student.py: --nodes must hold node ids in [0, {n}) (got {int(nodes.min())} .. {int(nodes.max())})")

@@ -2062,6 +2062,37 @@ def gemm_bf16(a, w, ep_scale=None, ep_shift=None, relu=False, out=None, out_dtyp
     return out[:m] if out.shape[0] != m else out
 
 
+def mlp_fused_bf16_tile_rows(desc):
+    """glnn_mlp_fused_bf16_tile_rows: (rows per workgroup of the one-launch form of the chain `desc`, a _lib.MlpServeDesc; "") or
+    (0, the library's reason for not taking it)."""
+    h = _lib.lib()
+    t = h.glnn_mlp_fused_bf16_tile_rows(ctypes.byref(desc))
+    return (t, "") if t > 0 else (0, h.glnn_last_error().decode(errors="replace"))
+
+
+def mlp_forward_fused_bf16(desc, x, out, rows=None, log_softmax=False):
+    """glnn_mlp_forward_fused_bf16: the chain `desc` (a _lib.MlpServeDesc) over x [n_x, dims[0]] (fp32, or a bf16 ops.bf16_empty view) as
+    ONE launch into fp32 out [m, C]: logits, or log-probabilities (log_softmax, C <= 64).  rows None: m = n_x and batch row b is x[b];
+    otherwise a contiguous int64 device vector of m row ids into x (the kernel computes an id outside [0, n_x) from an all-zero row).
+    A chain the one-launch form does not take raises GlnnError (status -2); ask mlp_fused_bf16_tile_rows first."""
+    _need_cuda(x, out, rows)
+    x = as_bf16_feat(x) if x.dtype == torch.bfloat16 else _mat(x, "mlp_forward_fused_bf16 x")
+    n_x = x.shape[0]
+    m = n_x
+    if rows is not None:
+        if rows.dtype != torch.int64 or rows.dim() != 1 or not rows.is_contiguous():
+            raise ValueError("mlp_forward_fused_bf16: rows must be a contiguous int64 vector")
+        m = rows.numel()
+    _mat(out, "mlp_forward_fused_bf16 out")
+    if out.shape[0] != m or out.shape[1] != desc.dims[desc.num_layers]:
+        raise ValueError(f"mlp_forward_fused_bf16: out must be float32 [{m}, {desc.dims[desc.num_layers]}]")
+    with _Timed("mlp_forward_fused_bf16", m=m, layers=desc.num_layers):
+        rc = _lib.lib().glnn_mlp_forward_fused_bf16(ctypes.byref(desc), _p(x), _ld(x), _dtype_code(x), _p(rows), n_x, m, _p(out), _ld(out),
+                                                    1 if log_softmax else 0, _stream())
+    _lib.check(rc, "glnn_mlp_forward_fused_bf16")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # serving a position-feature student by node id (csrc/position_serve.hip)
 def position_rows(ids, x, z, slot, g=None, out=None, out_dtype=None):

@@ -8,6 +8,11 @@ stored as bf16 in two reused buffers, every product runs on the bf16 MFMA with f
 The default everywhere stays the fp32 path; this module is reached through `compile_student`, `evaluate_mini_batch(dtype=torch.bfloat16)`
 and `train_student.py --serve_dtype bfloat16` only.
 
+`fused=True` (opt-in on top of that: `compile_student`, `compile_position_student`, `served_for`, `--serve_fused`) runs the same chain as ONE
+launch per row block (csrc/mlp_fused_bf16.hip: glnn_mlp_forward_fused_bf16): a workgroup carries its tile of rows through every layer with
+the hidden rows in LDS, no hidden buffers exist, and the results are the chain's bit for bit.  Only that form takes `rows`, a vector of row
+ids into a resident feature matrix.
+
 `compile_position_student(model, feats, table, g)` serves a student with position features BY NODE ID (csrc/position_serve.hip:
 glnn_position_rows; docs/POSITION_SEMANTICS.md, "Serving by node id"): its input rows are assembled per block of ids from the features,
 the saved position table and the graph, and either chain above runs over them unchanged.  Reached through that function and
@@ -25,13 +30,15 @@ def _encoder_of(model):
     return getattr(model, "encoder", model)
 
 
-def compile_student(model, dtype=torch.bfloat16):
+def compile_student(model, dtype=torch.bfloat16, fused=False):
     """A ServedStudent of `model` (a models.Model wrapping an MLP, or the MLP itself), which must be in eval mode.
+    fused: the one-launch form (ServedStudent.fused tells which form runs).
     NotImplementedError: not an MLP, norm_type "layer" (per-row statistics cannot ride in a per-column epilogue), more than
-    MLP_MAX_LAYERS layers, training mode.  Parameters on the CPU raise GlnnError like every op."""
+    MLP_MAX_LAYERS layers, training mode; with fused, a chain the one-launch form does not take (the library's reason: a hidden or
+    output width above its cap, a tile the device's LDS does not hold).  Parameters on the CPU raise GlnnError like every op."""
     if dtype != torch.bfloat16:
         raise ValueError(f"compile_student: dtype {dtype} (the serving path stores torch.bfloat16; float32 is the default path itself)")
-    return ServedStudent(model, _servable_encoder(model, "compile_student"))
+    return ServedStudent(model, _servable_encoder(model, "compile_student"), fused=fused)
 
 
 def _servable_encoder(model, who):
@@ -52,13 +59,21 @@ def _servable_encoder(model, who):
 class ServedStudent:
     """The bf16 snapshot of an eval-mode MLP.  The snapshot is keyed like ops.pack_weight's cache -- (identity, torch version, data pointer)
     of every parameter and BatchNorm buffer plus ops.PARAM_EPOCH (the training engines write parameters through raw pointers) -- and is
-    re-packed by the next call after a key moved; `refresh()` re-packs unconditionally."""
+    re-packed by the next call after a key moved; `refresh()` re-packs unconditionally.
+    fused: every row block is one glnn_mlp_forward_fused_bf16 launch (tile_rows rows per workgroup) and no hidden buffer is ever allocated;
+    otherwise one glnn_gemm_bf16 launch per layer through two reused hidden buffers.  Same bits either way."""
 
-    def __init__(self, model, enc):
+    def __init__(self, model, enc, fused=False):
         self.model, self.enc = model, enc
+        self.fused = bool(fused)
+        self.tile_rows = 0
         self._key = None
         self._bufs = None
         self.refresh()
+        if self.fused:
+            self.tile_rows, why = ops.mlp_fused_bf16_tile_rows(self.desc)
+            if not self.tile_rows:
+                raise NotImplementedError(f"compile_student(fused=True): {why}")
 
     # ---- snapshot ----
     def _tensors(self):
@@ -122,8 +137,8 @@ class ServedStudent:
             self._bufs = b = [torch.empty((rows, ld), dtype=torch.bfloat16, device=device) for _ in range(n)]
         return b[0], (b[1] if len(b) > 1 else None), ld
 
-    def _run(self, feats, out, log_softmax):
-        ops._need_cuda(feats, out)
+    def _run(self, feats, out, log_softmax, rows=None, check_rows=True):
+        ops._need_cuda(feats, out, rows)
         self._ensure()
         if feats.dim() != 2 or feats.shape[1] != self.dims[0]:
             raise ValueError(f"ServedStudent: features must be [rows, {self.dims[0]}], got {tuple(feats.shape)}")
@@ -133,7 +148,19 @@ class ServedStudent:
             x = ops.as_feat(feats)
         else:
             raise ValueError(f"ServedStudent: features must be float32 or bfloat16, got {feats.dtype}")
-        rows, c = x.shape[0], self.dims[-1]
+        ids = None
+        if rows is not None:
+            if not self.fused:
+                raise ValueError("ServedStudent: rows needs the one-launch form (compile_student(..., fused=True)); the per-layer chain "
+                                 "reads consecutive rows")
+            if rows.dtype != torch.int64 or rows.dim() != 1:
+                raise ValueError("ServedStudent: rows must be an int64 vector")
+            ids = rows.contiguous()
+            if check_rows and ids.numel():
+                lo, hi = torch.stack(torch.aminmax(ids)).tolist()          # (the call's one host read)
+                if lo < 0 or hi >= x.shape[0]:
+                    raise ValueError(f"ServedStudent: rows must lie in [0, {x.shape[0]}) (got {lo} .. {hi})")
+        rows, c = (x.shape[0] if ids is None else ids.numel()), self.dims[-1]
         if out is None:
             out = torch.empty((rows, c), dtype=torch.float32, device=x.device)
         ops._mat(out, "ServedStudent out")
@@ -143,6 +170,15 @@ class ServedStudent:
             return out
         fused_lsm = log_softmax and c <= 64
         blk = min(rows, EVAL_BLOCK_ROWS)
+        if self.fused:
+            for s0 in range(0, rows, blk):
+                if ids is None:
+                    ops.mlp_forward_fused_bf16(self.desc, x[s0:s0 + blk], out[s0:s0 + blk], log_softmax=fused_lsm)
+                else:
+                    ops.mlp_forward_fused_bf16(self.desc, x, out[s0:s0 + blk], rows=ids[s0:s0 + blk], log_softmax=fused_lsm)
+            if log_softmax and not fused_lsm:
+                ops.log_softmax(out, out=out)
+            return out
         b0, b1, ld_buf = self._buffers(blk, x.device)
         lib = _lib.lib()
         for s0 in range(0, rows, blk):
@@ -154,30 +190,36 @@ class ServedStudent:
             ops.log_softmax(out, out=out)
         return out
 
-    def logits(self, feats, out=None):
+    def logits(self, feats, out=None, rows=None, check_rows=True):
         """fp32 logits [rows, C] of fp32 or bf16 features [rows, dims[0]] (rows in blocks of EVAL_BLOCK_ROWS; a row's result does not
-        depend on the blocking)."""
-        return self._run(feats, out, False)
+        depend on the blocking).  rows (the one-launch form only; ValueError otherwise): an int64 device vector of row ids into `feats`
+        (repeats allowed) -- the result is [len(rows), C], row b that of feats[rows[b]], and no gathered copy is made.  check_rows=False
+        skips the range check and its host read: the caller then vouches for the ids (one outside feats is never used as an address;
+        its row is computed from an all-zero input)."""
+        return self._run(feats, out, False, rows, check_rows)
 
-    def log_probs(self, feats, out=None):
+    def log_probs(self, feats, out=None, rows=None, check_rows=True):
         """fp32 log_softmax(logits); for C <= 64 it is the last product's epilogue and the logits never reach memory."""
-        return self._run(feats, out, True)
+        return self._run(feats, out, True, rows, check_rows)
 
 
 POSITION_BLOCK_ROWS = 65536        # ids per assembled block of a ServedPositionStudent
 
 
-def compile_position_student(model, feats, table, g=None, dtype=torch.bfloat16):
+def compile_position_student(model, feats, table, g=None, dtype=torch.bfloat16, fused=False):
     """A ServedPositionStudent: an eval-mode MLP student with position features (docs/POSITION_SEMANTICS.md, "Serving by node id"), served
     by node id from the node features `feats` [N, F] (fp32, or bf16 for the bf16 chain; on the GPU), a position.PositionTable of width D
     and, where a node may lack a table row, the graph `g` -- the [N, F + D] matrix training concatenated is never built.
     dtype: torch.bfloat16 (the ServedStudent chain) or torch.float32 (model.inference + ops.log_softmax).
+    fused (bfloat16 only; ValueError otherwise): the assembled block goes through the one-launch form -- two launches per block, not 1 + L.
     Refused: whatever compile_student refuses (NotImplementedError); a first layer that is not F + D wide, a table with unseen nodes (or
     fewer nodes than feats has rows) without g, a graph that does not have feats' rows (ValueError)."""
     if dtype not in (torch.bfloat16, torch.float32):
         raise ValueError(f"compile_position_student: dtype {dtype} (torch.bfloat16 or torch.float32)")
+    if fused and dtype != torch.bfloat16:
+        raise ValueError("compile_position_student: fused=True is a form of the bfloat16 chain")
     enc = _servable_encoder(model, "compile_position_student")
-    return ServedPositionStudent(model, enc, feats, table, g, dtype)
+    return ServedPositionStudent(model, enc, feats, table, g, dtype, fused)
 
 
 class ServedPositionStudent:
@@ -186,7 +228,7 @@ class ServedPositionStudent:
     it: a ServedStudent (bf16), or model.inference and ops.log_softmax (fp32).  A row's result does not depend on the blocking or on the
     other ids of the call."""
 
-    def __init__(self, model, enc, feats, table, g, dtype):
+    def __init__(self, model, enc, feats, table, g, dtype, fused=False):
         ops._need_cuda(feats, table.rows, table.node_ids)
         if feats.dim() != 2 or feats.dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"compile_position_student: features must be a float32 or bfloat16 matrix, got {feats.dtype} {tuple(feats.shape)}")
@@ -209,7 +251,8 @@ class ServedPositionStudent:
         self.x = ops.as_bf16_feat(feats) if feats.dtype == torch.bfloat16 else ops._mat(feats, "compile_position_student features")
         self.z, self.slot = table.rows, table.slot(n)
         self.num_nodes, self.width = n, f + table.dim
-        self.served = ServedStudent(model, enc) if dtype == torch.bfloat16 else None
+        self.served = ServedStudent(model, enc, fused=fused) if dtype == torch.bfloat16 else None
+        self.fused = bool(fused)
         self._block = None
 
     def _buffer(self, rows):
@@ -261,10 +304,12 @@ class ServedPositionStudent:
         return self._run(ids, out, True, check_ids)
 
 
-def served_for(model):
-    """The ServedStudent cached on `model` (compiled on first use; it re-packs itself when a parameter moved)."""
-    s = model.__dict__.get("_served_student")
+def served_for(model, fused=False):
+    """The ServedStudent cached on `model` (compiled on first use; it re-packs itself when a parameter moved); the one-launch form has a
+    cache slot of its own."""
+    attr = "_served_student_fused" if fused else "_served_student"
+    s = model.__dict__.get(attr)
     if s is None:
-        s = compile_student(model)
-        model.__dict__["_served_student"] = s
+        s = compile_student(model, fused=fused)
+        model.__dict__[attr] = s
     return s

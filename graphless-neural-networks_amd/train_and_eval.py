@@ -226,17 +226,23 @@ def serve_dtype(conf):
     return INFERENCE_DTYPES[conf.get("serve_dtype", "float32")]
 
 
-def evaluate_mini_batch(model, feats, labels, criterion, batch_size, evaluator, idx_eval=None, dtype=torch.float32):
+def serve_fused(conf):
+    """Whether the bfloat16 evaluation passes run the one-launch form of the chain (--serve_fused, default False)."""
+    return bool(conf.get("serve_fused", False))
+
+
+def evaluate_mini_batch(model, feats, labels, criterion, batch_size, evaluator, idx_eval=None, *, fused=False, dtype=torch.float32):
     """reference train_and_eval.py:108-136.  Eval-mode rows are independent, so the matrix goes through ONE chain of GEMMs
     per big row block instead of ceil(N/B) mini-batches; the output is the same [N, C].
     dtype=torch.bfloat16: the pass goes through the model's ServedStudent (glnn_amd.serve: bf16 weights and hidden activations, bf16 MFMA,
-    fp32 accumulation and log-probabilities); the row blocking never changes a row's result there either."""
+    fp32 accumulation and log-probabilities); the row blocking never changes a row's result there either.  fused (bfloat16 only): that
+    pass as one launch per row block instead of one per layer -- the same bits.  fused and dtype are keyword-only."""
     ops._need_cuda(feats)
     model.eval()
     if dtype == torch.bfloat16:
         from .serve import served_for
         with torch.no_grad():
-            out_all = served_for(model).log_probs(feats)
+            out_all = served_for(model, fused=fused).log_probs(feats)
             if idx_eval is None:
                 loss = _apply_criterion(criterion, out_all, labels)
                 score = evaluator(out_all, labels)
@@ -246,6 +252,8 @@ def evaluate_mini_batch(model, feats, labels, criterion, batch_size, evaluator, 
         return out_all, loss.item(), score
     if dtype != torch.float32:
         raise ValueError(f"evaluate_mini_batch: dtype {dtype} (torch.float32 or torch.bfloat16)")
+    if fused:
+        raise ValueError("evaluate_mini_batch: fused=True is a form of the bfloat16 pass (dtype=torch.bfloat16)")
     with torch.no_grad():
         # row blocks bounded so that a wide student over millions of rows does not materialise tens of GB of activations
         blk = max(int(batch_size), EVAL_BLOCK_ROWS)
@@ -352,6 +360,7 @@ def distill_run_transductive(conf, model, feats, labels, out_t_all, distill_indi
     batch_size = conf["batch_size"]
     lamb = conf["lamb"]
     sdt = serve_dtype(conf)                    # --serve_dtype: the storage of the student's evaluation passes and of the saved `out`
+    sfu = serve_fused(conf)                    # --serve_fused: those passes as one launch per row block
     idx_l, idx_t, idx_val, idx_test = [i.to(device) for i in distill_indices]
     feats, labels, out_t_all = feats.to(device), labels.to(device), out_t_all.to(device)
     feats_l, labels_l = feats[idx_l], labels[idx_l]
@@ -365,13 +374,13 @@ def distill_run_transductive(conf, model, feats, labels, out_t_all, distill_indi
         return loss_l + loss_t
 
     def eval_epoch():
-        _, l_l, s_l = evaluate_mini_batch(model, feats_l, labels_l, criterion_l, batch_size, evaluator, dtype=sdt)
-        _, l_va, s_va = evaluate_mini_batch(model, feats_val, labels_val, criterion_l, batch_size, evaluator, dtype=sdt)
-        _, l_te, s_te = evaluate_mini_batch(model, feats_test, labels_test, criterion_l, batch_size, evaluator, dtype=sdt)
+        _, l_l, s_l = evaluate_mini_batch(model, feats_l, labels_l, criterion_l, batch_size, evaluator, dtype=sdt, fused=sfu)
+        _, l_va, s_va = evaluate_mini_batch(model, feats_val, labels_val, criterion_l, batch_size, evaluator, dtype=sdt, fused=sfu)
+        _, l_te, s_te = evaluate_mini_batch(model, feats_test, labels_test, criterion_l, batch_size, evaluator, dtype=sdt, fused=sfu)
         return [l_l, l_va, l_te, s_l, s_va, s_te], s_va, f"s_l: {s_l:.4f} | s_val: {s_va:.4f} | s_test: {s_te:.4f}"
 
     best_epoch = _early_stop_loop(conf, model, logger, loss_and_score, train_epoch, eval_epoch)
-    out, _, score_val = evaluate_mini_batch(model, feats, labels, criterion_l, batch_size, evaluator, idx_val, dtype=sdt)
+    out, _, score_val = evaluate_mini_batch(model, feats, labels, criterion_l, batch_size, evaluator, idx_val, dtype=sdt, fused=sfu)
     score_test = evaluator(out[idx_test], labels_test)
     logger.info(f"Best valid model at epoch: {best_epoch: 3d}, score_val: {score_val :.4f}, score_test: {score_test :.4f}")
     return out, score_val, score_test
@@ -453,6 +462,7 @@ def distill_run_inductive(conf, model, feats, labels, out_t_all, distill_indices
     batch_size = conf["batch_size"]
     lamb = conf["lamb"]
     sdt = serve_dtype(conf)                    # --serve_dtype: the storage of the student's evaluation passes and of the saved `out`
+    sfu = serve_fused(conf)                    # --serve_fused: those passes as one launch per row block
     obs_idx_l, obs_idx_t, obs_idx_val, obs_idx_test, idx_obs, idx_test_ind = [i.to(device) for i in distill_indices]
     feats, labels, out_t_all = feats.to(device), labels.to(device), out_t_all.to(device)
     obs_feats, obs_labels, obs_out_t = feats[idx_obs], labels[idx_obs], out_t_all[idx_obs]
@@ -468,16 +478,16 @@ def distill_run_inductive(conf, model, feats, labels, out_t_all, distill_indices
         return loss_l + loss_t
 
     def eval_epoch():
-        _, l_l, s_l = evaluate_mini_batch(model, feats_l, labels_l, criterion_l, batch_size, evaluator, dtype=sdt)
-        _, l_va, s_va = evaluate_mini_batch(model, feats_val, labels_val, criterion_l, batch_size, evaluator, dtype=sdt)
-        _, l_tt, s_tt = evaluate_mini_batch(model, feats_tt, labels_tt, criterion_l, batch_size, evaluator, dtype=sdt)
-        _, l_ti, s_ti = evaluate_mini_batch(model, feats_ti, labels_ti, criterion_l, batch_size, evaluator, dtype=sdt)
+        _, l_l, s_l = evaluate_mini_batch(model, feats_l, labels_l, criterion_l, batch_size, evaluator, dtype=sdt, fused=sfu)
+        _, l_va, s_va = evaluate_mini_batch(model, feats_val, labels_val, criterion_l, batch_size, evaluator, dtype=sdt, fused=sfu)
+        _, l_tt, s_tt = evaluate_mini_batch(model, feats_tt, labels_tt, criterion_l, batch_size, evaluator, dtype=sdt, fused=sfu)
+        _, l_ti, s_ti = evaluate_mini_batch(model, feats_ti, labels_ti, criterion_l, batch_size, evaluator, dtype=sdt, fused=sfu)
         return ([l_l, l_va, l_tt, l_ti, s_l, s_va, s_tt, s_ti], s_va,
                 f"s_l: {s_l:.4f} | s_val: {s_va:.4f} | s_tt: {s_tt:.4f} | s_ti: {s_ti:.4f}")
 
     best_epoch = _early_stop_loop(conf, model, logger, loss_and_score, train_epoch, eval_epoch)
-    obs_out, _, score_val = evaluate_mini_batch(model, obs_feats, obs_labels, criterion_l, batch_size, evaluator, obs_idx_val, dtype=sdt)
-    out, _, score_test_ind = evaluate_mini_batch(model, feats, labels, criterion_l, batch_size, evaluator, idx_test_ind, dtype=sdt)
+    obs_out, _, score_val = evaluate_mini_batch(model, obs_feats, obs_labels, criterion_l, batch_size, evaluator, obs_idx_val, dtype=sdt, fused=sfu)
+    out, _, score_test_ind = evaluate_mini_batch(model, feats, labels, criterion_l, batch_size, evaluator, idx_test_ind, dtype=sdt, fused=sfu)
     score_test_tran = evaluator(obs_out[obs_idx_test], labels_tt)
     out[idx_obs] = obs_out
     logger.info(f"Best valid model at epoch: {best_epoch: 3d} score_val: {score_val :.4f}, score_test_tran: {score_test_tran :.4f}, score_test_ind: {score_test_ind :.4f}")

@@ -1098,6 +1098,24 @@ GLNN_API int glnn_mlp_forward_bf16(const glnn_mlp_serve_desc* desc, const void* 
                                    uint16_t* buf0, uint16_t* buf1, int64_t ld_buf, float* out, int64_t ldo,
                                    int log_softmax, void* stream);
 
+/* The one-launch form of that chain (csrc/mlp_fused_bf16.hip): a workgroup owns a tile of consecutive batch rows and carries it through
+ * every layer, the hidden rows as bf16 images in LDS, the weights streamed from the same packed operands.  Every accumulator sees k in
+ * the chain's order and every rounding point is the chain's, so the result equals glnn_mlp_forward_bf16's BIT FOR BIT (default MFMA form).
+ * Taken: every chain whose hidden and output widths are <= 512 (tiles of 64 rows) and, where the device's LDS holds two 32 x 1024 images
+ * plus the 32 KB weight stage (160 KB: gfx950), widths <= 1024 (tiles of 32 rows); dims[0] is arbitrary. */
+
+/* rows per workgroup the fused launch would use for this chain (> 0), or 0 when it does not take it (glnn_last_error says why) */
+GLNN_API int glnn_mlp_fused_bf16_tile_rows(const glnn_mlp_serve_desc* desc);
+
+/* glnn_mlp_forward_bf16 as ONE launch, no hidden buffers.  rows == NULL: batch row b is x[b].  Otherwise rows is an int64 device
+ * vector of m indices into the n_x rows of x: batch row b is x[rows[b]]; an index outside [0, n_x) is never used as an address,
+ * that batch row is computed from an all-zero input row.  Arguments are checked as glnn_mlp_forward_bf16 checks them
+ * (GLNN_ERR_INVALID_ARG); m == 0 is a no-op that reads no pointer.  GLNN_ERR_UNSUPPORTED with nothing launched: a hidden or output
+ * width above 1024, a tile that does not fit the device's LDS, GLNN_GEMM_BF16_MFMA16=0 in force.  Never allocates or synchronises. */
+GLNN_API int glnn_mlp_forward_fused_bf16(const glnn_mlp_serve_desc* desc, const void* x, int64_t ldx, int x_dtype,
+                                         const int64_t* rows, int64_t n_x, int64_t m, float* out, int64_t ldo,
+                                         int log_softmax, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Serving a position-feature student by node id (csrc/position_serve.hip; docs/POSITION_SEMANTICS.md, "Serving by node id"): the
  * student's input rows for a batch of node ids, assembled from the features, the position table and the graph in ONE launch; nothing of
