@@ -9,33 +9,21 @@
 // the epilogue is fp32; the output is bf16 (padding columns written as 0) or fp32.
 //
 // Structure (one kernel template): 128 x BN output tile (BN = 128, or 64 for narrow outputs), BK = 64, four waves.  Both operands are
-// staged by 16-byte global_load_lds copies into ONE __shared__ array holding two buffers; the XOR swizzle (16-byte chunk ^ ((row >> 1) & 7))
-// is applied to the SOURCE address, the LDS image stays lane-linear.  The copy of k-tile t+1 is issued before the MFMAs of tile t, one
-// barrier per k-step.  The fp32 A operand is staged through registers instead (it has to be converted).  Workgroup ids are remapped so that
-// the tiles an XCD runs concurrently share rows of A.
+// staged into ONE __shared__ array holding two buffers by the staging of bf16_mfma_dev.h (16-byte global_load_lds copies, the XOR swizzle
+// on the SOURCE address; the fp32 A operand through registers: it has to be converted); rounding, fragment read, epilogue element and
+// log-softmax tail come from that header too, shared with the one-launch form (mlp_fused_bf16.hip).  The copy of k-tile t+1 is issued
+// before the MFMAs of tile t, one barrier per k-step.  Workgroup ids are remapped so that the tiles an XCD runs concurrently share rows
+// of A.  The bf16 output goes through an LDS transpose of this file's own (padded rows, 16-byte stores).
 //
 // Fixed order: a row's accumulator sees k ascending in steps of the MFMA depth, whatever else is in the call -- no split-K, no atomics.  So
 // results are bit-equal run to run, f(x)[a:b] == f(x[a:b]), and the fp32-A and bf16-A forms of one call give the same bits.
 // A's columns behind k (row padding, or whatever follows a narrower row) are zeroed in registers in the last k-tile, never trusted.
-#include "glnn_common.h"
+#include "bf16_mfma_dev.h"
 
 namespace {
 
-typedef uint16_t bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-constexpr int kThreads = 256;
-constexpr int BM = 128, BK = 64;
-constexpr int kRowBytes = BK * 2;              // one staged row: 128 B = 8 chunks of 16 B
-
-__device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if (f != f) return 0x7FC0u;
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) { return f32_to_bf16_bits(lo) | (f32_to_bf16_bits(hi) << 16); }
+constexpr int kThreads = kStageThreads;
+constexpr int BM = 128;
 
 struct GemmArgs {
   const void* a; int64_t lda; int64_t m; int k;
@@ -44,78 +32,6 @@ struct GemmArgs {
   void* out; int64_t ldo;
   int tiles_n;
 };
-
-// 16-byte LDS-DMA copies of ROWS rows x 64 bf16 of a row-major bf16 matrix (one k-tile) into a lane-linear LDS image.
-// Rows behind the matrix are clamped to its last row (their results are never stored); chunks that start behind `ld` are redirected to
-// the row's first chunk (they only meet k indices that are masked or that W zero-fills) -- no read leaves the matrix.
-// The row pointers and swizzled chunk columns do not depend on the k-tile: computed once.
-template <int ROWS>
-struct StageBf16 {
-  static constexpr int P = ROWS * 8 / kThreads;
-  const bf16_t* rowp[P];
-  int col8[P];
-  int ld, wave_base;
-  __device__ __forceinline__ void init(const bf16_t* __restrict__ src, int64_t ld_, int64_t nrows, int64_t row0, int tid) {
-    ld = (int)ld_;
-    wave_base = (tid & ~63) * 16;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      const int idx = p * kThreads + tid;
-      const int row = idx >> 3, pc = idx & 7;
-      int64_t grow = row0 + row;
-      if (grow > nrows - 1) grow = nrows - 1;
-      rowp[p] = src + grow * ld_;
-      col8[p] = (pc ^ ((row >> 1) & 7)) * 8;
-    }
-  }
-  __device__ __forceinline__ void issue(int kt, unsigned char* dst) const {
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      int col = kt * BK + col8[p];
-      if (col >= ld) col = 0;
-      const bf16_t* g = rowp[p] + col;
-      unsigned char* l = dst + p * kThreads * 16 + wave_base;      // wave-uniform: the hardware adds lane * 16
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-    }
-  }
-};
-
-// The fp32 A operand of k-tile kt: 4 chunks of 8 floats per thread, zero-filled behind k, rows clamped.
-__device__ __forceinline__ void load_a_f32(const float* __restrict__ a, int64_t lda, int64_t m, int k, bool vec_ok, int64_t row0, int kt,
-                                           int tid, float4 (&r)[8]) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int idx = p * kThreads + tid;
-    const int row = idx >> 3, pc = idx & 7;
-    const int lc = pc ^ ((row >> 1) & 7);
-    int64_t grow = row0 + row;
-    if (grow > m - 1) grow = m - 1;
-    const int col = kt * BK + lc * 8;
-    const float* s = a + grow * lda + col;
-    if (vec_ok && col + 8 <= k) {
-      r[2 * p] = *reinterpret_cast<const float4*>(s);
-      r[2 * p + 1] = *reinterpret_cast<const float4*>(s + 4);
-    } else {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (col + j < k) ? s[j] : 0.f;
-      r[2 * p] = make_float4(v[0], v[1], v[2], v[3]);
-      r[2 * p + 1] = make_float4(v[4], v[5], v[6], v[7]);
-    }
-  }
-}
-__device__ __forceinline__ void write_a_f32(const float4 (&r)[8], unsigned char* dst, int tid) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int idx = p * kThreads + tid;
-    uint4 u;
-    u.x = pack2(r[2 * p].x, r[2 * p].y);
-    u.y = pack2(r[2 * p].z, r[2 * p].w);
-    u.z = pack2(r[2 * p + 1].x, r[2 * p + 1].y);
-    u.w = pack2(r[2 * p + 1].z, r[2 * p + 1].w);
-    *reinterpret_cast<uint4*>(dst + idx * 16) = u;
-  }
-}
 
 template <int MF> struct Acc;
 template <> struct Acc<32> { typedef floatx16 type; };
@@ -157,18 +73,22 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16_kernel(const GemmArgs g) {
 #pragma unroll
       for (int e = 0; e < NACC; ++e) acc[i][j][e] = 0.f;
 
-  float4 areg[8];
-  StageBf16<BM> sa;
-  StageBf16<BN> sw;
-  sw.init(g.w, g.ldw, g.n, col0, tid);
+  // bf16 operands: row pointers and chunk columns kept (computed once); the fp32 A keeps its registers for the rows in flight instead
+  constexpr int PA = BM * 8 / kThreads, PW = BN * 8 / kThreads;
+  float4 areg[2 * PA];
+  const ClampedRows<float, int64_t> rows32{a32, g.lda, g.m, row0};
+  const LiveChunks<ClampedRows<float, int64_t>> sa32{rows32, tid};
+  KeptChunks<PA, bf16_t> sa;
+  KeptChunks<PW, bf16_t> sw;
+  sw.init(ClampedRows<bf16_t, int64_t>{g.w, g.ldw, g.n, col0}, tid);
   if constexpr (A_F32) {
-    load_a_f32(a32, g.lda, g.m, g.k, vec_ok, row0, 0, tid, areg);
-    write_a_f32(areg, smem, tid);
+    stage_load_f32<PA>(sa32, g.k, vec_ok, 0, areg);
+    stage_write_f32<PA>(areg, smem, tid);
   } else {
-    sa.init(a16, g.lda, g.m, row0, tid);
-    sa.issue(0, smem);
+    sa.init(ClampedRows<bf16_t, int64_t>{a16, g.lda, g.m, row0}, tid);
+    stage_issue<PA>(sa, (int)g.lda, 0, smem, tid);
   }
-  sw.issue(0, smem + A_BYTES);
+  stage_issue<PW>(sw, (int)g.ldw, 0, smem + A_BYTES, tid);
 
   for (int kt = 0; kt < nk; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's LDS-DMA copies of tile kt have landed
@@ -177,11 +97,10 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16_kernel(const GemmArgs g) {
     unsigned char* nxt = smem + ((kt + 1) & 1) * BUF_BYTES;
     const bool more = kt + 1 < nk;
     if (more) {
-      if constexpr (A_F32) load_a_f32(a32, g.lda, g.m, g.k, vec_ok, row0, kt + 1, tid, areg);
-      else sa.issue(kt + 1, nxt);
-      sw.issue(kt + 1, nxt + A_BYTES);
+      if constexpr (A_F32) stage_load_f32<PA>(sa32, g.k, vec_ok, kt + 1, areg);
+      else stage_issue<PA>(sa, (int)g.lda, kt + 1, nxt, tid);
+      stage_issue<PW>(sw, (int)g.ldw, kt + 1, nxt + A_BYTES, tid);
     }
-    // the bf16 A image may hold anything behind column k (row padding, the next row): zero those elements of the fragment
     const int krem = (!A_F32 && !more) ? g.k - kt * BK : BK;      // valid k of this tile (BK: no masking)
 #pragma unroll
     for (int ks = 0; ks < BK / KS; ++ks) {
@@ -189,23 +108,12 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16_kernel(const GemmArgs g) {
       bf16x8 af[MR], bfr[NR];
 #pragma unroll
       for (int i = 0; i < MR; ++i) {
-        const int row = wm0 + i * MF + lane_r;
-        uint4 u = *reinterpret_cast<const uint4*>(cur + row * kRowBytes + ((lc ^ ((row >> 1) & 7)) << 4));
-        if (krem < BK) {
-          const int v = krem - lc * 8;      // valid elements of this chunk (<= 0: none, >= 8: all)
-          u.x = v >= 2 ? u.x : (v == 1 ? (u.x & 0xFFFFu) : 0u);
-          u.y = v >= 4 ? u.y : (v == 3 ? (u.y & 0xFFFFu) : 0u);
-          u.z = v >= 6 ? u.z : (v == 5 ? (u.z & 0xFFFFu) : 0u);
-          u.w = v >= 8 ? u.w : (v == 7 ? (u.w & 0xFFFFu) : 0u);
-        }
+        uint4 u = frag_read(cur, wm0 + i * MF + lane_r, lc);
+        if (krem < BK) mask_k_tail(u, krem - lc * 8);
         af[i] = __builtin_bit_cast(bf16x8, u);
       }
 #pragma unroll
-      for (int j = 0; j < NR; ++j) {
-        const int row = wn0 + j * MF + lane_r;
-        const uint4 u = *reinterpret_cast<const uint4*>(cur + A_BYTES + row * kRowBytes + ((lc ^ ((row >> 1) & 7)) << 4));
-        bfr[j] = __builtin_bit_cast(bf16x8, u);
-      }
+      for (int j = 0; j < NR; ++j) bfr[j] = __builtin_bit_cast(bf16x8, frag_read(cur + A_BYTES, wn0 + j * MF + lane_r, lc));
 #pragma unroll
       for (int i = 0; i < MR; ++i)
 #pragma unroll
@@ -215,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16_kernel(const GemmArgs g) {
         }
     }
     if constexpr (A_F32) {
-      if (more) write_a_f32(areg, nxt, tid);
+      if (more) stage_write_f32<PA>(areg, nxt, tid);
     }
   }
 
@@ -223,15 +131,8 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16_kernel(const GemmArgs g) {
   auto row_of = [&](int i, int e) { return wm0 + i * MF + (MF == 32 ? (e & 3) + 8 * (e >> 2) + 4 * lane_q : lane_q * 4 + e); };
   float sc[NR], sh[NR];
 #pragma unroll
-  for (int j = 0; j < NR; ++j) {
-    const int gc = col0 + wn0 + j * MF + lane_r;
-    sc[j] = (g.ep_scale && gc < g.n) ? g.ep_scale[gc] : 1.f;
-    sh[j] = (g.ep_shift && gc < g.n) ? g.ep_shift[gc] : 0.f;
-  }
-  auto epi = [&](float v, int j) {
-    v = fmaf(v, sc[j], sh[j]);
-    return g.relu ? fmaxf(v, 0.f) : v;
-  };
+  for (int j = 0; j < NR; ++j) ep_consts(g.ep_scale, g.ep_shift, col0 + wn0 + j * MF + lane_r, g.n, sc[j], sh[j]);
+  auto ep = [&](float v, int j) { return epi(v, sc[j], sh[j], g.relu); };
 
   if constexpr (OUT_BF16) {
     constexpr int LDT = (BN + 8) * 2;          // bytes per row of the LDS tile (padded: the two lane groups of a store hit different banks)
@@ -244,7 +145,7 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16_kernel(const GemmArgs g) {
         const bool live = col0 + cl < g.n;
 #pragma unroll
         for (int e = 0; e < NACC; ++e) {
-          const float v = epi(acc[i][j][e], j);
+          const float v = ep(acc[i][j][e], j);
           *reinterpret_cast<bf16_t*>(smem + row_of(i, e) * LDT + cl * 2) = live ? (bf16_t)f32_to_bf16_bits(v) : (bf16_t)0;
         }
       }
@@ -260,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16_kernel(const GemmArgs g) {
         *reinterpret_cast<uint4*>(out + (row0 + row) * g.ldo + gc) = *reinterpret_cast<const uint4*>(smem + row * LDT + c8 * 16);
     }
   } else if constexpr (LSM) {
-    constexpr int LDT = BN + 1;                // floats per row; [row][BN] holds the row's log-sum-exp
+    static_assert(BN + 1 == kLsmLd, "the log-softmax tile is 64 logits + the row's log-sum-exp");
     float* t = reinterpret_cast<float*>(smem);
     __syncthreads();
 #pragma unroll
@@ -268,23 +169,9 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16_kernel(const GemmArgs g) {
 #pragma unroll
       for (int j = 0; j < NR; ++j)
 #pragma unroll
-        for (int e = 0; e < NACC; ++e) t[row_of(i, e) * LDT + wn0 + j * MF + lane_r] = epi(acc[i][j][e], j);
+        for (int e = 0; e < NACC; ++e) t[row_of(i, e) * kLsmLd + wn0 + j * MF + lane_r] = ep(acc[i][j][e], j);
     __syncthreads();
-    if (tid < BM) {
-      const float* zr = t + tid * LDT;
-      float mx = -INFINITY;
-      for (int j = 0; j < g.n; ++j) mx = fmaxf(mx, zr[j]);
-      float se = 0.f;
-      for (int j = 0; j < g.n; ++j) se += expf(zr[j] - mx);
-      t[tid * LDT + BN] = mx + logf(se);
-    }
-    __syncthreads();
-    float* out = static_cast<float*>(g.out);
-    const int rows = (int)((g.m - row0) < BM ? (g.m - row0) : BM);
-    for (int idx = tid; idx < rows * g.n; idx += kThreads) {
-      const int row = idx / g.n, c = idx - row * g.n;
-      out[(row0 + row) * g.ldo + c] = t[row * LDT + c] - t[row * LDT + BN];
-    }
+    log_softmax_rows<BM>(t, g.n, row0, g.m, static_cast<float*>(g.out), g.ldo);
   } else {
     float* out = static_cast<float*>(g.out);
 #pragma unroll
@@ -295,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void gemm_bf16_kernel(const GemmArgs g) {
 #pragma unroll
         for (int e = 0; e < NACC; ++e) {
           const int64_t gr = row0 + row_of(i, e);
-          if (gr < g.m && gc < g.n) out[gr * g.ldo + gc] = epi(acc[i][j][e], j);
+          if (gr < g.m && gc < g.n) out[gr * g.ldo + gc] = ep(acc[i][j][e], j);
         }
       }
   }
@@ -369,17 +256,13 @@ extern "C" int glnn_gemm_bf16(const void* a, int64_t lda, int a_dtype, int64_t m
 extern "C" int glnn_mlp_forward_bf16(const glnn_mlp_serve_desc* d, const void* x, int64_t ldx, int x_dtype, int64_t m, uint16_t* buf0,
                                      uint16_t* buf1, int64_t ld_buf, float* out, int64_t ldo, int log_softmax, void* stream) {
   const char* name = "glnn_mlp_forward_bf16";
-  GLNN_REQUIRE(d, "%s: null descriptor", name);
-  GLNN_REQUIRE(d->num_layers >= 1 && d->num_layers <= GLNN_MLP_MAX_LAYERS, "%s: num_layers=%d outside 1..%d", name, d->num_layers,
-               GLNN_MLP_MAX_LAYERS);
+  GLNN_TRY(check_serve_desc(name, d, log_softmax));
   GLNN_REQUIRE(x_dtype == GLNN_DTYPE_F32 || x_dtype == GLNN_DTYPE_BF16, "%s: unknown x_dtype %d", name, x_dtype);
   GLNN_REQUIRE(m >= 0, "%s: bad m", name);
   const int L = d->num_layers;
-  for (int l = 0; l <= L; ++l) GLNN_REQUIRE(d->dims[l] >= 1, "%s: dims[%d]=%d", name, l, d->dims[l]);
   for (int l = 0; l + 1 < L; ++l)
     GLNN_REQUIRE(ld_buf % 8 == 0 && ld_buf >= d->dims[l + 1], "%s: ld_buf=%lld must be a multiple of 8 and >= every hidden width", name,
                  (long long)ld_buf);
-  GLNN_REQUIRE(!log_softmax || d->dims[L] <= 64, "%s: log_softmax needs an output width <= 64", name);
   if (m == 0) return GLNN_OK;
   GLNN_REQUIRE(x && out && (L == 1 || buf0) && (L <= 2 || buf1), "%s: null pointer", name);
   for (int l = 0; l < L; ++l) GLNN_REQUIRE(d->w[l], "%s: null weight of layer %d", name, l);

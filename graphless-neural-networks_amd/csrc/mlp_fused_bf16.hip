@@ -3,9 +3,9 @@
 //   glnn_mlp_forward_fused_bf16     the whole chain as ONE launch: no hidden buffers, no allocation, no synchronisation
 //
 // An MLP is row-local: one workgroup (256 threads, 2 x 2 waves) owns T consecutive batch rows and carries them through every layer.
-//   layer 0      the A operand comes from global memory in k-tiles of 64 exactly as gemm_bf16_kernel stages it (16-byte LDS-DMA copies of
-//                bf16 rows; fp32 rows rounded through registers with the bits of glnn_cast_f32_bf16), optionally through a `rows` index
-//   hidden rows  relu(fmaf(acc, ep_scale, ep_shift)) rounded to bf16 into one of two LDS images of T x pitch elements that ping-pong;
+//   layer 0      the A operand comes from global memory in k-tiles of 64 through the staging of bf16_mfma_dev.h (16-byte LDS-DMA copies
+//                of bf16 rows; fp32 rows rounded through registers), optionally through a `rows` index
+//   hidden rows  the fp32 epilogue (epi: relu(fmaf(acc, ep_scale, ep_shift))) rounded to bf16 into one of two LDS images of T x pitch elements that ping-pong;
 //                the next layer reads its A fragments from the image
 //   weights      the chain's packed operand (bf16 [n, ldw], ldw % 64 == 0, zeros behind k), streamed as 128-row x 64-k tiles through a
 //                double-buffered LDS stage by global_load_lds; the tile of the next (k-tile, column panel) unit is issued before the MFMAs
@@ -13,8 +13,9 @@
 //   products     v_mfma_f32_16x16x32_bf16 only.  A wave holds the accumulators of its (T / 2) x 64 block of EVERY 128-column panel of the
 //                layer (T x 1024 / 256 = 128 fp32 per thread at most), so the k loop is outermost: an A fragment is read once per k-tile
 //                and an accumulator sees k ascending in steps of 32 -- the chain's order, hence the chain's bits.
-//   last layer   fp32 logits from registers to `out`, or (log_softmax, width <= 64) through an fp32 LDS tile with the chain's sequence:
-//                max ascending, expf sum ascending, mx + logf(se), subtract.
+//   last layer   fp32 logits from registers to `out`, or (log_softmax, width <= 64) through an fp32 LDS tile and log_softmax_rows.
+// Staging, fragment read, k-tail mask, epilogue element and log-softmax tail are the definitions of bf16_mfma_dev.h, shared with the chain;
+// what is this file's own is the hidden-row image and the (k-tile, panel) loop.
 //
 // Image layout: row pitch = the widest hidden layer rounded up to 128 elements (a multiple of 256 B, one LDS bank row), the 16-byte chunk
 // index XORed with (row & 15).  A ds_read_b128 is served in groups of 16 lanes that hold 16 distinct fragment rows and two adjacent chunk
@@ -25,28 +26,16 @@
 // LDS budget: two images (2 x T x pitch x 2 B; at least 128 elements of pitch, because layer 0's A stage lives in the image layer 0 does
 // not write) + the weight stage (2 x 16 KB; the log-softmax tile reuses it).  T = 64 for widths <= 512 (160 KB at 512), T = 32 up to 1024
 // (160 KB at 1024); the entry refuses what the device's LDS does not hold.
-#include "glnn_common.h"
+#include <type_traits>
+
+#include "bf16_mfma_dev.h"
 
 namespace {
 
-typedef uint16_t bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-constexpr int kThreads = 256;
-constexpr int BK = 64;                         // k per staged tile
+constexpr int kThreads = kStageThreads;
 constexpr int NP = 128;                        // columns per panel (one weight tile: NP rows x BK)
-constexpr int kRowBytes = BK * 2;              // one staged row: 128 B = 8 chunks of 16 B
 constexpr int kWTileBytes = NP * kRowBytes;    // 16 KB
 constexpr int kCap = 1024;                     // widest hidden / output layer taken
-
-// the rounding of gemm_bf16.hip (round to nearest even, NaN -> 0x7FC0: the bits of glnn_cast_f32_bf16)
-__device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if (f != f) return 0x7FC0u;
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) { return f32_to_bf16_bits(lo) | (f32_to_bf16_bits(hi) << 16); }
 
 struct FusedArgs {
   glnn_mlp_serve_desc d;
@@ -58,129 +47,48 @@ struct FusedArgs {
   int pitch;                                   // elements per image row (a multiple of 128)
 };
 
-__device__ __forceinline__ void lds_dma16(const bf16_t* g, unsigned char* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
-// One weight tile: rows [p * NP, +NP) x k [kt * BK, +BK) of W into a lane-linear LDS image, the swizzle of StageBf16 (gemm_bf16.hip) on the
-// SOURCE chunk.  Rows behind n are clamped to the last row (their columns are never stored); a chunk behind ldw (there is none: ldw is a
-// multiple of 64 and >= k) would be redirected to the row's first chunk -- no read leaves the matrix.
-__device__ __forceinline__ void issue_w(const bf16_t* __restrict__ w, int ldw, int n, int p, int kt, unsigned char* dst, int tid) {
-  const int wave_base = (tid & ~63) * 16;
-#pragma unroll
-  for (int q = 0; q < NP * 8 / kThreads; ++q) {
-    const int idx = q * kThreads + tid;
-    const int row = idx >> 3, pc = idx & 7;
-    int gr = p * NP + row;
-    if (gr > n - 1) gr = n - 1;
-    int col = kt * BK + (pc ^ ((row >> 1) & 7)) * 8;
-    if (col >= ldw) col = 0;
-    lds_dma16(w + (int64_t)gr * ldw + col, dst + q * kThreads * 16 + wave_base);      // wave-uniform: the hardware adds lane * 16
-  }
-}
-
-// Layer 0's A operand, T rows x BK per k-tile.  src[] are the rows of x behind this thread's chunks: batch rows behind m clamped to the
-// last one, a `rows` index outside [0, n_x) replaced by row 0 (the fragment of such a row is zeroed where it is read).
-template <int T>
-struct AStage {
-  static constexpr int P = T * 8 / kThreads;
-  int64_t src[P];
-  int col8[P];
-  __device__ __forceinline__ void init(const FusedArgs& g, int64_t row0, int tid) {
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      const int idx = p * kThreads + tid;
-      const int row = idx >> 3, pc = idx & 7;
-      int64_t b = row0 + row;
-      if (b > g.m - 1) b = g.m - 1;
-      int64_t s = b;
-      if (g.rows) {
-        s = g.rows[b];
-        if (s < 0 || s >= g.n_x) s = 0;
-      }
-      src[p] = s;
-      col8[p] = (pc ^ ((row >> 1) & 7)) * 8;
-    }
-  }
-  // bf16 rows: 16-byte LDS-DMA copies; a chunk that starts behind ld is redirected to the row's first chunk (it only meets masked k)
-  __device__ __forceinline__ void issue(const bf16_t* __restrict__ x, int ld, int kt, unsigned char* dst, int tid) const {
-    const int wave_base = (tid & ~63) * 16;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      int col = kt * BK + col8[p];
-      if (col >= ld) col = 0;
-      lds_dma16(x + src[p] * ld + col, dst + p * kThreads * 16 + wave_base);
-    }
-  }
-  // fp32 rows: 8 floats per chunk through registers, zero-filled behind k
-  __device__ __forceinline__ void load(const float* __restrict__ x, int64_t ld, int k, bool vec_ok, int kt, float4 (&r)[2 * P]) const {
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      const int col = kt * BK + col8[p];
-      const float* s = x + src[p] * ld + col;
-      if (vec_ok && col + 8 <= k) {
-        r[2 * p] = *reinterpret_cast<const float4*>(s);
-        r[2 * p + 1] = *reinterpret_cast<const float4*>(s + 4);
-      } else {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (col + j < k) ? s[j] : 0.f;
-        r[2 * p] = make_float4(v[0], v[1], v[2], v[3]);
-        r[2 * p + 1] = make_float4(v[4], v[5], v[6], v[7]);
-      }
-    }
-  }
-  __device__ __forceinline__ void write(const float4 (&r)[2 * P], unsigned char* dst, int tid) const {
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      uint4 u;
-      u.x = pack2(r[2 * p].x, r[2 * p].y);
-      u.y = pack2(r[2 * p].z, r[2 * p].w);
-      u.z = pack2(r[2 * p + 1].x, r[2 * p + 1].y);
-      u.w = pack2(r[2 * p + 1].z, r[2 * p + 1].w);
-      *reinterpret_cast<uint4*>(dst + (p * kThreads + tid) * 16) = u;
-    }
-  }
-};
-
 template <int T>
 struct Geo {
   static constexpr int MR = T / 32;            // 16-row fragments per wave (waves 2 x 2 of (T / 2) x 64)
   static constexpr int NR = 4;                 // 16-column fragments per wave and panel
   static constexpr int NPANEL = 256 / T;       // panels whose accumulators a thread holds: 128 fp32
   static constexpr int A_BYTES = T * kRowBytes;
+  static constexpr int PA = T * 8 / kThreads;  // 16-byte chunks of layer 0's A stage per thread
 };
+// Layer 0's A operand, T rows x BK per k-tile: the rows of x behind this thread's chunks (batch rows through the `rows` index), kept
+template <int T, bool A_F32>
+using AChunks = KeptChunks<Geo<T>::PA, std::conditional_t<A_F32, float, bf16_t>>;
 
 // The products of one layer into acc.  FIRST: A from global memory (x / rows) through the A stage; otherwise from the image `img`.
 template <int T, bool A_F32, bool FIRST>
 __device__ __forceinline__ void layer_products(const FusedArgs& g, int k, int n, const bf16_t* __restrict__ w, int ldw,
                                                const unsigned char* img, unsigned char* astage, unsigned char* wstage,
-                                               const AStage<T>& sa, bool vec_ok, const bool (&valid)[Geo<T>::MR],
+                                               const AChunks<T, A_F32>& sa, bool vec_ok, const bool (&valid)[Geo<T>::MR],
                                                floatx4 (&acc)[Geo<T>::NPANEL][Geo<T>::MR][Geo<T>::NR]) {
-  constexpr int MR = Geo<T>::MR, NR = Geo<T>::NR, NPANEL = Geo<T>::NPANEL, A_BYTES = Geo<T>::A_BYTES;
+  constexpr int MR = Geo<T>::MR, NR = Geo<T>::NR, NPANEL = Geo<T>::NPANEL, A_BYTES = Geo<T>::A_BYTES, PA = Geo<T>::PA;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm0 = (wave >> 1) * (T / 2), wn0 = (wave & 1) * 64;
   const int lane_r = lane & 15, lane_q = lane >> 4;
   const int nk = (k + BK - 1) / BK, np = (n + NP - 1) / NP;
   const int pitch_b = g.pitch * 2;
-  const bf16_t* x16 = static_cast<const bf16_t*>(g.x);
-  const float* x32 = static_cast<const float*>(g.x);
 
-  float4 areg[2 * AStage<T>::P];
+  float4 areg[2 * PA];
   if constexpr (FIRST) {
     if constexpr (A_F32) {
-      sa.load(x32, g.ldx, k, vec_ok, 0, areg);
-      sa.write(areg, astage, tid);
+      stage_load_f32<PA>(sa, k, vec_ok, 0, areg);
+      stage_write_f32<PA>(areg, astage, tid);
     } else {
-      sa.issue(x16, (int)g.ldx, 0, astage, tid);
+      stage_issue<PA>(sa, (int)g.ldx, 0, astage, tid);
     }
   }
   // unit = (k-tile, panel), panels innermost; (ktn, pn) is the next unit whose weight tile has not been issued yet.  They are run-time
-  // values on purpose: one address computation per issue, nothing per panel for the compiler to hoist out of the loop and spill
+  // values on purpose: the weight rows are LiveChunks -- one address computation per issue, nothing per panel for the compiler to hoist
+  // out of the loop and spill.  (A chunk behind ldw, which stage_issue would redirect, does not exist: ldw % 64 == 0 and ldw >= k.)
   int pn = 0, ktn = 0;
   auto issue_next = [&](unsigned char* dst) {
     if (ktn < nk) {
-      issue_w(w, ldw, n, pn, ktn, dst, tid);
+      const ClampedRows<bf16_t, int> wrows{w, ldw, n, pn * NP};
+      stage_issue<NP * 8 / kThreads>(LiveChunks<ClampedRows<bf16_t, int>>{wrows, tid}, ldw, ktn, dst, tid);
       if (++pn == np) {
         pn = 0;
         ++ktn;
@@ -204,11 +112,10 @@ __device__ __forceinline__ void layer_products(const FusedArgs& g, int k, int n,
         if (p == 0) {
           if constexpr (FIRST) {
             if (more) {
-              if constexpr (A_F32) sa.load(x32, g.ldx, k, vec_ok, kt + 1, areg);
-              else sa.issue(x16, (int)g.ldx, kt + 1, astage + ((kt + 1) & 1) * A_BYTES, tid);
+              if constexpr (A_F32) stage_load_f32<PA>(sa, k, vec_ok, kt + 1, areg);
+              else stage_issue<PA>(sa, (int)g.ldx, kt + 1, astage + ((kt + 1) & 1) * A_BYTES, tid);
             }
           }
-          // global bf16 rows may hold anything behind column k (row padding, the next row): zero those elements of the fragment
           const int krem = (FIRST && !A_F32 && !more) ? k - kt * BK : BK;
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
@@ -218,14 +125,8 @@ __device__ __forceinline__ void layer_products(const FusedArgs& g, int k, int n,
               const int row = wm0 + i * 16 + lane_r;
               uint4 v;
               if constexpr (FIRST) {
-                v = *reinterpret_cast<const uint4*>(astage + (kt & 1) * A_BYTES + row * kRowBytes + ((lc ^ ((row >> 1) & 7)) << 4));
-                if (krem < BK) {
-                  const int e = krem - lc * 8;      // valid elements of this chunk (<= 0: none, >= 8: all)
-                  v.x = e >= 2 ? v.x : (e == 1 ? (v.x & 0xFFFFu) : 0u);
-                  v.y = e >= 4 ? v.y : (e == 3 ? (v.y & 0xFFFFu) : 0u);
-                  v.z = e >= 6 ? v.z : (e == 5 ? (v.z & 0xFFFFu) : 0u);
-                  v.w = e >= 8 ? v.w : (e == 7 ? (v.w & 0xFFFFu) : 0u);
-                }
+                v = frag_read(astage + (kt & 1) * A_BYTES, row, lc);
+                if (krem < BK) mask_k_tail(v, krem - lc * 8);
                 if (!valid[i]) v = make_uint4(0u, 0u, 0u, 0u);      // a `rows` index outside x: an all-zero input row
               } else {
                 v = *reinterpret_cast<const uint4*>(img + row * pitch_b + (((kt * 8 + lc) ^ (row & 15)) << 4));
@@ -239,17 +140,14 @@ __device__ __forceinline__ void layer_products(const FusedArgs& g, int k, int n,
           const int lc = ks * 4 + lane_q;
           bf16x8 bfr[NR];
 #pragma unroll
-          for (int j = 0; j < NR; ++j) {
-            const int row = wn0 + j * 16 + lane_r;
-            bfr[j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(cur + row * kRowBytes + ((lc ^ ((row >> 1) & 7)) << 4)));
-          }
+          for (int j = 0; j < NR; ++j) bfr[j] = __builtin_bit_cast(bf16x8, frag_read(cur, wn0 + j * 16 + lane_r, lc));
 #pragma unroll
           for (int i = 0; i < MR; ++i)
 #pragma unroll
             for (int j = 0; j < NR; ++j) acc[p][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks][i], bfr[j], acc[p][i][j], 0, 0, 0);
         }
         if constexpr (FIRST && A_F32) {
-          if (p == 0 && more) sa.write(areg, astage + ((kt + 1) & 1) * A_BYTES, tid);
+          if (p == 0 && more) stage_write_f32<PA>(areg, astage + ((kt + 1) & 1) * A_BYTES, tid);
         }
         ++u;
       }
@@ -272,8 +170,9 @@ __global__ __launch_bounds__(kThreads) void mlp_fused_kernel(const FusedArgs g) 
   const int L = g.d.num_layers;
   const bool vec_ok = A_F32 && (g.ldx % 4 == 0) && glnn::aligned16(g.x);
 
-  AStage<T> sa;
-  sa.init(g, row0, tid);
+  typedef std::conditional_t<A_F32, float, bf16_t> x_t;
+  AChunks<T, A_F32> sa;
+  sa.init(IdRows<x_t>{static_cast<const x_t*>(g.x), g.ldx, g.rows, g.n_x, g.m, row0}, tid);
   bool valid[MR];
 #pragma unroll
   for (int i = 0; i < MR; ++i) {
@@ -317,8 +216,8 @@ __global__ __launch_bounds__(kThreads) void mlp_fused_kernel(const FusedArgs g) 
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
           const int col = p * NP + wn0 + j * 16 + lane_r;
-          const float sc = (ep_scale && col < n) ? ep_scale[col] : 1.f;
-          const float sh = (ep_shift && col < n) ? ep_shift[col] : 0.f;
+          float sc, sh;
+          ep_consts(ep_scale, ep_shift, col, n, sc, sh);
           if (!last) {
             // the bf16 image of the hidden row: columns [n, round64(n)) are zeros, nothing is read behind them
             if (col < ((n + 63) & ~63)) {
@@ -327,7 +226,7 @@ __global__ __launch_bounds__(kThreads) void mlp_fused_kernel(const FusedArgs g) 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                   const int row = wm0 + i * 16 + lane_q * 4 + e;
-                  const float v = fmaxf(fmaf(acc[p][i][j][e], sc, sh), 0.f);
+                  const float v = epi(acc[p][i][j][e], sc, sh, true);
                   *reinterpret_cast<bf16_t*>(dst + row * pitch_b + ((((col >> 3) ^ (row & 15)) << 4) | ((col & 7) << 1))) =
                       col < n ? (bf16_t)f32_to_bf16_bits(v) : (bf16_t)0;
                 }
@@ -338,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void mlp_fused_kernel(const FusedArgs g) 
               for (int i = 0; i < MR; ++i)
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                  reinterpret_cast<float*>(wstage)[(wm0 + i * 16 + lane_q * 4 + e) * 65 + col] = fmaf(acc[p][i][j][e], sc, sh);
+                  reinterpret_cast<float*>(wstage)[(wm0 + i * 16 + lane_q * 4 + e) * kLsmLd + col] = epi(acc[p][i][j][e], sc, sh, false);
             }
           } else if (col < n) {
 #pragma unroll
@@ -346,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void mlp_fused_kernel(const FusedArgs g) 
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 const int64_t gr = row0 + wm0 + i * 16 + lane_q * 4 + e;
-                if (gr < g.m) g.out[gr * g.ldo + col] = fmaf(acc[p][i][j][e], sc, sh);
+                if (gr < g.m) g.out[gr * g.ldo + col] = epi(acc[p][i][j][e], sc, sh, false);
               }
           }
         }
@@ -355,37 +254,15 @@ __global__ __launch_bounds__(kThreads) void mlp_fused_kernel(const FusedArgs g) 
     __syncthreads();                           // the image is complete; the weight stage and the other image are free
   }
 
-  if (g.lsm) {
-    constexpr int LDT = 65;                    // floats per row; [row][64] holds the row's log-sum-exp
-    float* t = reinterpret_cast<float*>(wstage);
-    const int n = g.d.dims[L];
-    if (tid < T) {
-      const float* zr = t + tid * LDT;
-      float mx = -INFINITY;
-      for (int j = 0; j < n; ++j) mx = fmaxf(mx, zr[j]);
-      float se = 0.f;
-      for (int j = 0; j < n; ++j) se += expf(zr[j] - mx);
-      t[tid * LDT + 64] = mx + logf(se);
-    }
-    __syncthreads();
-    const int rows = (int)((g.m - row0) < T ? (g.m - row0) : T);
-    for (int idx = tid; idx < rows * n; idx += kThreads) {
-      const int row = idx / n, c = idx - row * n;
-      g.out[(row0 + row) * g.ldo + c] = t[row * LDT + c] - t[row * LDT + 64];
-    }
-  }
+  if (g.lsm) log_softmax_rows<T>(reinterpret_cast<float*>(wstage), g.d.dims[L], row0, g.m, g.out, g.ldo);
 }
 
 struct Plan { int tile_rows; int pitch; size_t smem; };
 
-// What the launch would use for the chain `d`: GLNN_OK and *pl, or the refusal (GLNN_ERR_INVALID_ARG for a malformed descriptor,
-// GLNN_ERR_UNSUPPORTED for a chain the fused form does not take), the reason in glnn_last_error.
+// What the launch would use for the chain `d` (behind check_serve_desc): GLNN_OK and *pl, or the refusal (GLNN_ERR_UNSUPPORTED for a chain
+// the fused form does not take), the reason in glnn_last_error.
 int make_plan(const char* name, const glnn_mlp_serve_desc* d, Plan* pl) {
-  GLNN_REQUIRE(d, "%s: null descriptor", name);
-  GLNN_REQUIRE(d->num_layers >= 1 && d->num_layers <= GLNN_MLP_MAX_LAYERS, "%s: num_layers=%d outside 1..%d", name, d->num_layers,
-               GLNN_MLP_MAX_LAYERS);
   const int L = d->num_layers;
-  for (int l = 0; l <= L; ++l) GLNN_REQUIRE(d->dims[l] >= 1, "%s: dims[%d]=%d", name, l, d->dims[l]);
   if (glnn::opts().gemm_bf16_mfma16 == 0)
     return glnn::fail(GLNN_ERR_UNSUPPORTED, "%s: GLNN_GEMM_BF16_MFMA16=0 is in force; the one-launch form exists on v_mfma_f32_16x16x32_bf16 only "
                       "(its results are defined as the bits of the default chain)", name);
@@ -432,21 +309,18 @@ int launch(const FusedArgs& g, size_t smem, hipStream_t s, const char* name) {
 }  // namespace
 
 extern "C" int glnn_mlp_fused_bf16_tile_rows(const glnn_mlp_serve_desc* desc) {
+  const char* name = "glnn_mlp_fused_bf16_tile_rows";
   Plan pl;
-  return make_plan("glnn_mlp_fused_bf16_tile_rows", desc, &pl) == GLNN_OK ? pl.tile_rows : 0;
+  return check_serve_desc(name, desc, 0) == GLNN_OK && make_plan(name, desc, &pl) == GLNN_OK ? pl.tile_rows : 0;
 }
 
 extern "C" int glnn_mlp_forward_fused_bf16(const glnn_mlp_serve_desc* d, const void* x, int64_t ldx, int x_dtype, const int64_t* rows,
                                            int64_t n_x, int64_t m, float* out, int64_t ldo, int log_softmax, void* stream) {
   const char* name = "glnn_mlp_forward_fused_bf16";
-  GLNN_REQUIRE(d, "%s: null descriptor", name);
-  GLNN_REQUIRE(d->num_layers >= 1 && d->num_layers <= GLNN_MLP_MAX_LAYERS, "%s: num_layers=%d outside 1..%d", name, d->num_layers,
-               GLNN_MLP_MAX_LAYERS);
+  GLNN_TRY(check_serve_desc(name, d, log_softmax));
   GLNN_REQUIRE(x_dtype == GLNN_DTYPE_F32 || x_dtype == GLNN_DTYPE_BF16, "%s: unknown x_dtype %d", name, x_dtype);
   GLNN_REQUIRE(m >= 0 && ldx < (1ll << 31), "%s: bad m / ldx", name);
   const int L = d->num_layers;
-  for (int l = 0; l <= L; ++l) GLNN_REQUIRE(d->dims[l] >= 1, "%s: dims[%d]=%d", name, l, d->dims[l]);
-  GLNN_REQUIRE(!log_softmax || d->dims[L] <= 64, "%s: log_softmax needs an output width <= 64", name);
   if (m == 0) return GLNN_OK;
   if (x_dtype == GLNN_DTYPE_BF16)
     GLNN_REQUIRE(ldx % 8 == 0 && ldx >= d->dims[0], "%s: ldx=%lld must be a multiple of 8 and >= dims[0] for bf16 rows", name, (long long)ldx);

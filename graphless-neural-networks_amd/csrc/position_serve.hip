@@ -26,6 +26,7 @@
 // not even 4-byte aligned (bf16, odd f): the tail of the row -- the f % E last feature elements, the d position elements and the zero
 // padding up to the next multiple of E -- is STAGED in LDS in the output's element type (one slice per wave, at most 264 words) and
 // written out as aligned 16-byte pieces behind a barrier.  No store assumes more than the row's own alignment.
+#include "bf16_mfma_dev.h"      // f32_to_bf16_bits, pack2: the bits of glnn_cast_f32_bf16
 #include "row_gather_dev.h"
 
 namespace {
@@ -42,14 +43,6 @@ struct PosArgs {
   void* out; int64_t ldo;
   int n_long_blocks;
 };
-
-// round to nearest even, NaN -> 0x7FC0: the bits of glnn_cast_f32_bf16 (csrc/sage_bf16.hip)
-__device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if (f != f) return 0x7FC0u;
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) { return f32_to_bf16_bits(lo) | (f32_to_bf16_bits(hi) << 16); }
 
 // z[slot[u]] of the entries u of a CSR row; the weight of an entry is its slot, -1 for "not embedded"
 struct SlotRows : GatherPolicy {

@@ -13,7 +13,7 @@
 // flight a wave holds TWICE the edges of the fp32 kernel of the same width.  The group sums are folded with cross-lane adds in fixed order:
 // results are bit-reproducible from run to run (no float atomics).  Stores round to nearest even (torch's Tensor.to(torch.bfloat16):
 // NaN -> the canonical quiet NaN 0x7FC0), written in plain C++.
-#include "glnn_common.h"
+#include "bf16_mfma_dev.h"      // bf16_t, f32_to_bf16_bits, pack2
 
 namespace {
 
@@ -26,15 +26,6 @@ constexpr int kRowsPerWave = 16;          // (the fp32 kernel's sweep-chosen val
 constexpr int kLongRow = 128;             // degree above which a whole workgroup takes the row (spmm.hip's GLNN_LONG_ROW)
 constexpr int kLongBlockRows = 512;
 constexpr int kLongBlockCap = 512;
-
-typedef uint16_t bf16_t;
-
-__device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if (f != f) return 0x7FC0u;
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) { return f32_to_bf16_bits(lo) | (f32_to_bf16_bits(hi) << 16); }
 
 struct F8 { float v[8]; };
 __device__ __forceinline__ F8 zero8() {
