@@ -107,6 +107,10 @@ SIGNATURES = {
     "glnn_gpr_prop_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp,
                           c_i64, c_vp, c_vp],
     "glnn_gpr_fold_f32": [c_vp, c_int, c_i64, c_vp, c_vp, c_i64, c_vp],
+    "glnn_dagnn_gate_f32": [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_vp],
+    "glnn_dagnn_gate_bwd_f32": [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp],
+    "glnn_dagnn_fold_workspace_bytes": [c_i64, c_int],
+    "glnn_dagnn_fold_f32": [c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp],
     "glnn_gcnii_layer_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_vp, c_f32, c_u32,
                              c_vp, c_i64, c_vp, c_i64, c_vp, c_vp],
     "glnn_gcnii_layer_bwd_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_f32, c_u32, c_f32,
@@ -138,6 +142,7 @@ SIGNATURES = {
 
 MLP_MAX_LAYERS = 8
 GPR_FOLD_CHUNK = 4096          # GLNN_GPR_FOLD_CHUNK of include/glnn_hip.h
+DAGNN_FOLD_CHUNK = 2048        # GLNN_DAGNN_FOLD_CHUNK of include/glnn_hip.h
 MLP_COUNTERS = 1024
 _F = ctypes.c_void_p * MLP_MAX_LAYERS
 
@@ -271,6 +276,7 @@ def lib():
         h.glnn_layernorm_bwd_workspace_floats.restype = c_i64
         h.glnn_gat_attn_bwd_workspace_floats.restype = c_i64
         h.glnn_gatv2_attn_bwd_workspace_floats.restype = c_i64
+        h.glnn_dagnn_fold_workspace_bytes.restype = c_i64
         h.glnn_sage_step_ws_bn_floats.restype = c_i64
         h.glnn_sage_step_ws_ln_floats.restype = c_i64
         h.glnn_last_error.argtypes = []

@@ -345,6 +345,81 @@ def gpr_propagate(graph, h0, gamma, k, training):
         return gpr_fwd(graph, h0, gamma, int(k))
 
 
+# ------------------------------------------------------------------------------------------ DAGNN propagation (docs/DAGNN_SEMANTICS.md)
+def dagnn_fwd(g, h0, w, b, k, keep=False):
+    """out[i] = sum_{j = 0..K} s_j[i] H_j[i],  H_0 = h0, H_j = P H_{j-1}, s_j[i] = sigmoid(<H_j[i], w> + b)  (P = APPNP's operator): per hop
+    one glnn_spmm_csr_f32 (rows scaled by dst_norm, sources by src_norm) and one glnn_dagnn_gate_f32.  keep False (eval): two ping-pong
+    buffers and out.  keep True (training): every H_j is stored once, into the saved stack [(K + 1) n, d] the next hop gathers from;
+    returns (out, (stack, gates [(K + 1) n])).  w [d] / [1, d] and b [1] are read on the device."""
+    h0 = ops.as_feat(h0)
+    n, d = h0.shape
+    k = int(k)
+    out = ops.feat_empty(n, d, h0.device)
+    stack = score = None
+    if keep:
+        stack = ops.feat_empty((k + 1) * n, d, h0.device)
+        stack[:n].copy_(h0)
+        score = torch.empty((k + 1) * n, dtype=torch.float32, device=h0.device)
+    ops.dagnn_gate(h0, 0, w, b, out, score)
+    if k > 0:
+        in_norm, out_norm = g.degree_norms()
+        buf = None if keep else _pingpong(n, d, h0.device, k)
+        x = h0
+        for j in range(1, k + 1):
+            x = ops.spmm(g.indptr, g.indices, x, n, ops.AGG_SUM, row_scale=in_norm, col_scale=out_norm,
+                         out=stack[j * n:(j + 1) * n] if keep else buf(j))
+            ops.dagnn_gate(x, j, w, b, out, score)
+    return (out, (stack, score)) if keep else out
+
+
+def dagnn_bwd(g, dy, kept, w, k):
+    """(dL/dh0, dL/dw, dL/db) from dy = dL/dout and the forward's kept (stack, gates):  q_j = <dy, H_j> s_j (1 - s_j),
+    D_j = s_j dy + q_j w,  T_K = D_K, T_j = D_j + P^T T_{j+1},  dh0 = T_0 -- per hop one glnn_spmm_csr_f32 over the transposed CSR with the
+    norms swapped and one glnn_dagnn_gate_bwd_f32 in place on its output -- and dw = sum_j H_j^T q_j, db = sum q (glnn_dagnn_fold_f32:
+    fixed-order fp64 sums over the stack)."""
+    dy = ops.as_feat(dy)
+    n, d = dy.shape
+    k = int(k)
+    stack, score = kept
+    q = torch.empty((k + 1) * n, dtype=torch.float32, device=dy.device)
+    buf = _pingpong(n, d, dy.device, k + 1)
+    x = ops.dagnn_gate_bwd(dy, stack[k * n:(k + 1) * n], k, score, w, None, buf(k), q)
+    if k > 0:
+        in_norm, out_norm = g.degree_norms()
+        tg = g.transposed(False)
+        for j in range(k - 1, -1, -1):
+            t = ops.spmm(tg.indptr, tg.indices, x, n, ops.AGG_SUM, row_scale=out_norm, col_scale=in_norm, out=buf(j))
+            x = ops.dagnn_gate_bwd(dy, stack[j * n:(j + 1) * n], j, score, w, t, t, q)
+    dw, db = ops.dagnn_fold(stack, q)
+    return x, dw, db
+
+
+class DagnnPropFn(torch.autograd.Function):
+    """DAGNNConv as a differentiable op on the HIP path: gradients for the trunk's logits and for the gate's weight and bias."""
+
+    @staticmethod
+    def forward(ctx, graph, h0, w, b, k):
+        out, (stack, score) = dagnn_fwd(graph, h0.detach(), w.detach(), b.detach(), k, keep=True)
+        ctx.graph, ctx.k = graph, k
+        ctx.save_for_backward(stack, score, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        stack, score, w = ctx.saved_tensors
+        dh0, dw, db = dagnn_bwd(ctx.graph, dy.contiguous(), (stack, score), w.detach(), ctx.k)
+        need = ctx.needs_input_grad
+        return None, dh0 if need[1] else None, dw.view_as(w) if need[2] else None, db if need[3] else None, None
+
+
+def dagnn_propagate(graph, h0, w, b, k, training):
+    """DAGNNConv forward, differentiable by _differentiable's rule."""
+    if _differentiable(training, h0, w, b):
+        return DagnnPropFn.apply(graph, h0, w, b, int(k))
+    with torch.no_grad():
+        return dagnn_fwd(graph, h0, w, b, int(k))
+
+
 # ------------------------------------------------------------------------------------------ GCNII conv stack (docs/GCNII_SEMANTICS.md)
 def gcnii_betas(num_layers, lamda):
     """beta_l = log(lamda / l + 1) for l = 1..L (the paper's identity-mapping weights)."""

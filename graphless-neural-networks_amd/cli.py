@@ -10,6 +10,7 @@ from pathlib import Path
 
 import numpy as np
 import torch
+import yaml
 from torch import optim
 
 from .dataloader import load_data, load_out_t
@@ -81,7 +82,10 @@ def get_teacher_args(argv=None):
     # Model; docs/GCNII_SEMANTICS.md).  Unset = the conf's value or the paper's defaults 0.1 / 0.5
     p.add_argument("--gcnii_alpha", type=float, default=None, help="alpha of the GCNII teacher's initial residual (default 0.1)")
     p.add_argument("--gcnii_lamda", type=float, default=None, help="lamda of the GCNII teacher's beta_l = log(lamda / l + 1) (default 0.5)")
-    # not reference flags: mini-batch training of the full-graph teachers (GCN, APPNP, GAT, GATv2, GPRGNN, GCNII) on random-walk induced
+    # not a reference flag: the DAGNN teacher's number of propagation steps (conf key `dagnn_k`, read by Model; docs/DAGNN_SEMANTICS.md).
+    # Unset = the conf's value or the paper's 10
+    p.add_argument("--dagnn_k", type=int, default=None, help="Propagation steps K of the DAGNN teacher (default 10)")
+    # not reference flags: mini-batch training of the full-graph teachers (GCN, APPNP, GAT, GATv2, GPRGNN, DAGNN, GCNII) on random-walk induced
     # subgraphs (conf keys `subgraph_walk_length`, `subgraph_self_loop`, read by run_transductive / run_inductive;
     # docs/SUBGRAPH_SEMANTICS.md).  --batch_size is then the number of walk roots per batch; 0 = the full-graph step per epoch
     p.add_argument("--subgraph_walk_length", type=int, default=0,
@@ -92,13 +96,17 @@ def get_teacher_args(argv=None):
     if not 0 <= args.subgraph_walk_length <= 64:
         p.error(f"--subgraph_walk_length must be in [0, 64] (got {args.subgraph_walk_length})")
     if args.subgraph_walk_length > 0 and teacher_kind(args.teacher) in ("sage", "mlp"):
-        p.error(f"--subgraph_walk_length applies to the full-graph teachers (GCN, APPNP, GAT, GATv2, GPRGNN, GCNII) only: SAGE trains on "
+        p.error(f"--subgraph_walk_length applies to the full-graph teachers (GCN, APPNP, GAT, GATv2, GPRGNN, DAGNN, GCNII) only: SAGE trains on "
                 f"sampled blocks and MLP on feature batches (got --teacher {args.teacher})")
     if args.subgraph_self_loop != "keep" and args.subgraph_walk_length == 0:
         p.error(f"--subgraph_self_loop {args.subgraph_self_loop} needs --subgraph_walk_length > 0")
     for flag in ("gcnii_alpha", "gcnii_lamda"):
         if getattr(args, flag) is not None and "GCNII" not in args.teacher:
             p.error(f"--{flag} applies to the GCNII teacher only (got --teacher {args.teacher})")
+    if args.dagnn_k is not None and "DAGNN" not in args.teacher:
+        p.error(f"--dagnn_k applies to the DAGNN teacher only (got --teacher {args.teacher})")
+    if args.dagnn_k is not None and args.dagnn_k < 0:
+        p.error(f"--dagnn_k must be >= 0 (got {args.dagnn_k})")
     if args.sage_mean_step != "autograd" and ("SAGE" not in args.teacher or args.sage_aggregator != "mean"):
         p.error(f"--sage_mean_step {args.sage_mean_step} applies to --teacher SAGE --sage_aggregator mean only "
                 f"(got --teacher {args.teacher} --sage_aggregator {args.sage_aggregator})")
@@ -172,6 +180,18 @@ def _setting_dir(args, root, leaf):
     raise ValueError(f"Unknown experiment setting! {args.exp_setting}")
 
 
+def _training_config(path, model_name, dataset):
+    """get_training_config.  train.conf.yaml has no DAGNN sections: a DAGNN teacher whose dataset names none takes that dataset's APPNP
+    section -- the trunk's hyper-parameters, what every GPRGNN section restates -- or the global section alone (docs/DAGNN_SEMANTICS.md)."""
+    if "DAGNN" in model_name and teacher_kind(model_name) == "dagnn":
+        with open(path) as fh:
+            cfg = yaml.safe_load(fh)
+        sections = cfg.get(dataset) or {}
+        if model_name not in sections:
+            return dict(cfg["global"], **(sections.get("APPNP") or {}), model_name=model_name)
+    return get_training_config(path, model_name, dataset)
+
+
 def _load(args, logger, model_name):
     g, labels, idx_train, idx_val, idx_test = load_data(args.dataset, args.data_path, split_idx=args.split_idx, seed=args.seed,
                                                         labelrate_train=args.labelrate_train, labelrate_val=args.labelrate_val)
@@ -184,7 +204,7 @@ def _load(args, logger, model_name):
         feats = (1 - args.feature_noise) * feats + args.feature_noise * torch.randn_like(feats)
     conf = {}
     if args.model_config_path is not None:
-        conf = get_training_config(args.model_config_path, model_name, args.dataset.replace("synthetic-", "").split("@")[0])
+        conf = _training_config(args.model_config_path, model_name, args.dataset.replace("synthetic-", "").split("@")[0])
     conf = dict(args.__dict__, **conf)          # YAML wins over CLI flags, as in the reference
     return g, feats, labels, (idx_train, idx_val, idx_test), conf
 

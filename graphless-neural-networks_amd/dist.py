@@ -385,13 +385,18 @@ UNSHARDED_TEACHERS = {
     "GPRGNN": "each of its K propagation steps needs the previous step's rows of the remote sources",
     "GCNII": "each of its conv layers needs the previous layer's hidden rows of the remote sources",
 }
+# refused the same way; a table of its own because tests/test_dist_cpu.py pins the key set of the one above
+UNSHARDED_GATED = {
+    "DAGNN": "each of its K propagation steps needs the previous step's rows of the remote sources, and its gate the whole propagated row",
+}
 
 
 def _refuse_unsharded(encoder, who):
     """The encoders neither sharded teacher runs: the kinds of UNSHARDED_TEACHERS, then a SAGE with another aggregator than 'gcn'."""
     kind = type(encoder).__name__
-    if kind in UNSHARDED_TEACHERS:
-        raise NotImplementedError(f"{who}: the {kind} teacher is not sharded -- {UNSHARDED_TEACHERS[kind]}, an exchange the sharded "
+    why = UNSHARDED_TEACHERS.get(kind) or UNSHARDED_GATED.get(kind)
+    if why:
+        raise NotImplementedError(f"{who}: the {kind} teacher is not sharded -- {why}, an exchange the sharded "
                                   f"forward does not have (whole-graph {kind} only)")
     if getattr(encoder, "aggregator_type", "gcn") != "gcn":
         raise NotImplementedError(f"{who}: the sharded teacher forward implements the SAGE 'gcn' aggregator only -- a SAGE "

@@ -17,24 +17,25 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .autograd import appnp_propagate, gcnii_stack, linear_fn, norm_act_drop
-from .nn import GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, SAGEConv, _whole_graph_only
+from .nn import DAGNNConv, GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, SAGEConv, _whole_graph_only
 
 
 _KINDS = (("MLP", "mlp"), ("SAGE", "sage"), ("GCNII", "gcnii"), ("GCN", "gcn"), ("APPNP", "appnp"), ("GATv2", "gatv2"), ("GAT", "gat"),
-          ("GPRGNN", "gpr"))
+          ("GPRGNN", "gpr"), ("DAGNN", "dagnn"))
 
 
 def teacher_kind(model_name):
     """The model family a `model_name` selects: the first of _KINDS whose key the name contains (the reference's substring dispatch,
     models.py:355,409).  The order is the rule and is written down here alone: "MLP" first ("MLP3w4" is an MLP), "GCNII" before "GCN"
-    and "GATv2" before "GAT", which they contain.  Every caller switches on the kind it returns."""
+    and "GATv2" before "GAT", which they contain ("GPRGNN" and "DAGNN" contain no other key and no other key contains them).  Every
+    caller switches on the kind it returns."""
     for key, kind in _KINDS:
         if key in model_name:
             return kind
     raise ValueError(f"Unknown model_name {model_name}")
 
 
-FULL_GRAPH_KINDS = ("gcn", "gcnii", "appnp", "gat", "gatv2", "gpr")      # the teachers whose training step takes the whole graph
+FULL_GRAPH_KINDS = ("gcn", "gcnii", "appnp", "gat", "gatv2", "gpr", "dagnn")    # the teachers whose training step takes the whole graph
 
 
 def _bn_eval_fold(bn, bias):
@@ -649,6 +650,17 @@ class GPRGNN(_TrunkProp):
         self.k, self.alpha = self.propagate.k, self.propagate.alpha
 
 
+class DAGNN(_TrunkProp):
+    """DAGNN (Liu, Gao, Ji, KDD 2020; docs/DAGNN_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it): the trunk followed by
+    DAGNNConv(k, output_dim) -- K propagation steps over APPNP's operator, each node mixing its K + 1 hops through the learned gate
+    `propagate.proj`.  No edge dropout and no dropout in front of the propagation."""
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", k=10):
+        super().__init__(num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type)
+        self.propagate = DAGNNConv(k, output_dim)     # torch's default Linear initialisation, drawn here, after the trunk's layers
+        self.k = self.propagate.k
+
+
 GCNII_MAX_LAYERS = 64
 
 
@@ -793,6 +805,9 @@ class Model(nn.Module):
             if heads < 1 or conf["hidden_dim"] < heads or conf["hidden_dim"] % heads:
                 raise ValueError(f"{who}: hidden_dim ({conf['hidden_dim']}) must be a positive multiple of num_heads ({heads})")
             enc = cls(activation=F.relu, num_heads=heads, attn_drop=conf["attn_dropout_ratio"], **common)
+        elif kind == "dagnn":
+            k = conf.get("dagnn_k")                                                  # (absent or None: the paper's 10 hops)
+            enc = DAGNN(activation=F.relu, norm_type=conf["norm_type"], k=10 if k is None else k, **common)
         else:
             enc = GPRGNN(activation=F.relu, norm_type=conf["norm_type"], k=conf.get("gpr_k", 10), alpha=conf.get("gpr_alpha", 0.1),
                          init=conf.get("gpr_init", "PPR"), **common)
@@ -826,6 +841,9 @@ class Model(nn.Module):
             if kind == "gcnii":
                 raise NotImplementedError(f"GCNII.inference(dtype={dtype}): bf16 activation storage is not implemented for the GCNII teacher "
                                           "(csrc/gcnii.hip gathers and stores fp32 rows; docs/GCNII_SEMANTICS.md, Out of scope)")
+            if kind == "dagnn":
+                raise NotImplementedError(f"DAGNN.inference(dtype={dtype}): bf16 activation storage is not implemented for the DAGNN teacher "
+                                          "(csrc/dagnn.hip gathers and stores fp32 rows; docs/DAGNN_SEMANTICS.md, Out of scope)")
             if kind != "sage":
                 raise NotImplementedError(f"{self.model_name}.inference(dtype={dtype}): bf16 activation storage is implemented for the SAGE "
                                           "teacher's whole-graph forward only")

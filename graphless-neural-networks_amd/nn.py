@@ -5,6 +5,7 @@
   GATConv(in, out, heads, ...)(g, h)             <- dgl.nn.GATConv, reference models.py:228-267 (docs/GAT_SEMANTICS.md)
   GATv2Conv(in, out, heads, ...)(g, h)           <- GATv2's attention layer (dgl 0.6.1 has none; docs/GATV2_SEMANTICS.md)
   GPRConv(k, alpha, init)(g, h)                  <- GPR-GNN's learned K-step propagation (no dgl counterpart; docs/GPR_SEMANTICS.md)
+  DAGNNConv(k, in_feats)(g, h)                   <- DAGNN's node-gated K-step propagation (no dgl counterpart; docs/DAGNN_SEMANTICS.md)
   GCNIIConv(hidden, layer, alpha, lamda)(g, h, h0) <- one GCNII conv layer (dgl 0.6.1 has none; docs/GCNII_SEMANTICS.md)
 
 Parameter names follow dgl 0.6.1 so that a reference `model.pth` loads: SAGEConv.fc_neigh.{weight,bias}
@@ -17,7 +18,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import GraphConvFn, SpmmFn, _differentiable, gat_conv, gatv2_conv, gcnii_stack, gpr_propagate, graphconv_fwd, linear_fn
+from .autograd import (GraphConvFn, SpmmFn, _differentiable, dagnn_propagate, gat_conv, gatv2_conv, gcnii_stack, gpr_propagate, graphconv_fwd,
+                       linear_fn)
 
 
 FUSED_SAGE_MAX_IN = 256   # aggregate-first layers with d_in, d_out <= 256 take the single-launch K1F kernel.  Interleaved
@@ -368,6 +370,29 @@ class GPRConv(nn.Module):
     def forward(self, graph, feat):
         _whole_graph_only(graph, feat, "GPRConv", "GPR-GNN propagates over the whole graph")
         return gpr_propagate(graph, feat, self.gamma, self.k, self.training)
+
+
+class DAGNNConv(nn.Module):
+    """DAGNN propagation (Liu, Gao, Ji, KDD 2020; docs/DAGNN_SEMANTICS.md): out[i] = sum_{j = 0..K} s_j[i] (P^j h)[i] with the node-adaptive
+    gate s_j[i] = sigmoid(proj((P^j h)[i])), proj = nn.Linear(in_feats, 1) (torch's default initialisation), and P = D_in^-1/2 A D_out^-1/2
+    (APPNP's operator).  No edge dropout, no dropout of its own, no zero-in-degree error (a row without in-edges keeps s_0 h alone)."""
+
+    def __init__(self, k=10, in_feats=1):
+        super().__init__()
+        if int(k) < 0:
+            raise ValueError(f"DAGNNConv: k must be >= 0 (got {k})")
+        if int(in_feats) > ops.DAGNN_MAX_WIDTH:
+            raise NotImplementedError(f"DAGNNConv: DAGNN rows of at most {ops.DAGNN_MAX_WIDTH} columns (the gate is one row-wide dot product; "
+                                      f"got {in_feats})")
+        self.k, self.in_feats = int(k), int(in_feats)
+        self.proj = nn.Linear(self.in_feats, 1)
+
+    def reset_parameters(self):
+        self.proj.reset_parameters()
+
+    def forward(self, graph, feat):
+        _whole_graph_only(graph, feat, "DAGNNConv", "DAGNN propagates over the whole graph")
+        return dagnn_propagate(graph, feat, self.proj.weight, self.proj.bias, self.k, self.training)
 
 
 class GCNIIConv(nn.Module):

@@ -1544,8 +1544,89 @@ def gpr_fold(row_dot, rows, m, out=None):
     return out
 
 
+# --------------------------------------------------------------------------------------------- DAGNN propagation
+DAGNN_MAX_WIDTH = 256           # kMaxD of csrc/dagnn.hip: the gate is one row-wide dot product
+
+
+def _dagnn_gate(name, w, b, d):
+    """The gate parameters as the kernels read them: w a contiguous float32 [d] (or nn.Linear's [1, d]), b a float32 [1]."""
+    _need_cuda(w, b)
+    if w.dtype != torch.float32 or w.numel() != d or not w.is_contiguous() or b.dtype != torch.float32 or b.numel() != 1:
+        raise ValueError(f"{name}: w must be a contiguous float32 vector of {d} gate weights and b a float32 scalar tensor")
+
+
+def _dagnn_width(name, d):
+    if d > DAGNN_MAX_WIDTH:
+        raise NotImplementedError(f"{name}: DAGNN rows of at most {DAGNN_MAX_WIDTH} columns (the gate is one row-wide dot product; got {d})")
+
+
+def dagnn_gate(x, k, w, b, acc, score=None):
+    """Hop k of DAGNN's forward, glnn_dagnn_gate_f32 (x = H_k [n, d], d <= 256): s = sigmoid(<x, w> + b); acc = (0 at k = 0, else acc) + s * x,
+    in place; score (training, [(K + 1) * n]): score[k * n + i] = s.  w, b are read on the device.  Returns acc."""
+    _need_cuda(x, acc, score)
+    x = as_feat(x)
+    n, d = x.shape
+    k = int(k)
+    _dagnn_width("dagnn_gate", d)
+    _dagnn_gate("dagnn_gate", w, b, d)
+    _rows_like("dagnn_gate", "acc", acc, n, d)
+    if score is not None and (score.dtype != torch.float32 or not score.is_contiguous() or score.numel() < (k + 1) * n):
+        raise ValueError("dagnn_gate: score must be contiguous float32 with >= (k + 1) * n elements")
+    with _Timed("dagnn_gate", d=d, n_dst=n, k=k):
+        rc = _lib.lib().glnn_dagnn_gate_f32(_p(x), _ld(x), n, d, _p(w), _p(b), k, _p(acc), _ld(acc), _p(score), _stream())
+    _lib.check(rc, "glnn_dagnn_gate_f32")
+    return acc
+
+
+def dagnn_gate_bwd(g, h, k, score, w, t, out, q):
+    """Hop k of DAGNN's backward, glnn_dagnn_gate_bwd_f32: q[k * n + i] = <g, h> s (1 - s) with s = score[k * n + i], g = dL/dresult,
+    h = the saved H_k; out = s * g + q * w + t, t = P^T T_{k+1} (None at k = K; may be `out` itself: in place).  Returns out."""
+    _need_cuda(g, h, score, w, t, out, q)
+    g, h = as_feat(g), as_feat(h)
+    n, d = g.shape
+    k = int(k)
+    _dagnn_width("dagnn_gate_bwd", d)
+    if w.dtype != torch.float32 or w.numel() != d or not w.is_contiguous():
+        raise ValueError(f"dagnn_gate_bwd: w must be a contiguous float32 vector of {d} gate weights")
+    for what, m in (("h", h), ("t", t), ("out", out)):
+        _rows_like("dagnn_gate_bwd", what, m, n, d)
+    if out is None:
+        raise ValueError("dagnn_gate_bwd: out is required")
+    for what, v in (("score", score), ("q", q)):
+        if v is None or v.dtype != torch.float32 or not v.is_contiguous() or v.numel() < (k + 1) * n:
+            raise ValueError(f"dagnn_gate_bwd: {what} must be contiguous float32 with >= (k + 1) * n elements")
+    with _Timed("dagnn_gate_bwd", d=d, n_dst=n, k=k):
+        rc = _lib.lib().glnn_dagnn_gate_bwd_f32(_p(g), _ld(g), _p(h), _ld(h), n, d, _p(score), _p(w), k, _p(t), 0 if t is None else _ld(t),
+                                                _p(out), _ld(out), _p(q), _stream())
+    _lib.check(rc, "glnn_dagnn_gate_bwd_f32")
+    return out
+
+
+def dagnn_fold(hs, q, dw=None, db=None):
+    """(dw [d], db [1]) = (hs^T q, sum q) over the (K + 1) * n rows of the saved stack hs, glnn_dagnn_fold_f32: fixed-order fp64 sums in chunks
+    of _lib.DAGNN_FOLD_CHUNK rows, then the chunk partials."""
+    _need_cuda(hs, q, dw, db)
+    hs = _mat(hs, "dagnn_fold hs")
+    rows, d = hs.shape
+    _dagnn_width("dagnn_fold", d)
+    if _ld(hs) % 4 or hs.data_ptr() % 16:
+        raise ValueError("dagnn_fold: hs must have float4-addressable rows (ops.feat_empty)")
+    _vec(q, rows, "dagnn_fold q")
+    if dw is None:
+        dw = torch.empty(d, dtype=torch.float32, device=hs.device)
+    if db is None:
+        db = torch.empty(1, dtype=torch.float32, device=hs.device)
+    _vec(dw, d, "dagnn_fold dw")
+    _vec(db, 1, "dagnn_fold db")
+    wsb = int(_lib.lib().glnn_dagnn_fold_workspace_bytes(rows, d))
+    ws = torch.empty(max(wsb // 8, 1), dtype=torch.float64, device=hs.device)
+    rc = _lib.lib().glnn_dagnn_fold_f32(_p(hs), _ld(hs), _p(q), rows, d, _p(dw), _p(db), _p(ws), ws.numel() * 8, _stream())
+    _lib.check(rc, "glnn_dagnn_fold_f32")
+    return dw, db
+
+
 # --------------------------------------------------------------------------------------------- GCNII conv layer
-GCNII_MAX_HIDDEN = 256          # kMaxD of csrc/gcnii.hip: the kernel's tile width
+GCNII_MAX_HIDDEN = 256         # kMaxD of csrc/gcnii.hip: the kernel's tile width
 
 
 def _gcnii_check(name, indptr, indices, n, d, tile_order):

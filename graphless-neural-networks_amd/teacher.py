@@ -37,7 +37,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .models import teacher_kind
-from .autograd import (appnp_bwd, appnp_fwd, gat_layer_bwd, gat_layer_fwd, gatv2_layer_bwd, gatv2_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd,
+from .autograd import (appnp_bwd, appnp_fwd, dagnn_bwd, dagnn_fwd, gat_layer_bwd, gat_layer_fwd, gatv2_layer_bwd, gatv2_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd,
                        graphconv_fwd)
 from .student import _mix32
 
@@ -71,13 +71,14 @@ def _check_norms_and_device(who, model):
 
 _NORM_RELU = {"sage": "SAGE with norm_type none|batch|layer and ReLU (the reference's configs)",
               "appnp": "APPNP with norm_type none|batch|layer and ReLU (models.py:282-344)",
-              "gpr": "GPRGNN with norm_type none|batch|layer and ReLU (docs/GPR_SEMANTICS.md)"}
+              "gpr": "GPRGNN with norm_type none|batch|layer and ReLU (docs/GPR_SEMANTICS.md)",
+              "dagnn": "DAGNN with norm_type none|batch|layer and ReLU (docs/DAGNN_SEMANTICS.md)"}
 _ATTN_RELU = {"gatv2": "GATv2 with ReLU hidden layers and a linear last layer (docs/GATV2_SEMANTICS.md)",
               "gat": "GAT with ReLU hidden layers and a linear last layer (models.py:202-279)"}
 
 
 def check_supported(model, criterion, optimizer):
-    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GATv2, GPRGNN or GCNII teacher."""
+    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GATv2, GPRGNN, DAGNN or GCNII teacher."""
     enc = model.encoder
     name = model.model_name
     try:
@@ -85,7 +86,7 @@ def check_supported(model, criterion, optimizer):
     except ValueError:           # (a name no family claims: refused like the MLP)
         kind = "mlp"
     if kind == "mlp":
-        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GATv2, GPRGNN or GCNII teachers only (got {name})")
+        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GATv2, GPRGNN, DAGNN or GCNII teachers only (got {name})")
     _check_criterion_and_optimizer("TeacherEngine", criterion, optimizer)
     if kind == "gcnii":          # (the encoder's constructor refused everything else)
         if enc.norm_type != "none" or not _is_relu(enc.activation):
@@ -617,7 +618,7 @@ class TeacherEngine:
         return self._tail_bwd(l, dh, z, stats, seed, bias_grad)
 
     def _trunk_fwd(self, feats):
-        """The MLP trunk of APPNP / GPRGNN in training mode: (trunk logits, layer inputs, saved tails)."""
+        """The MLP trunk of APPNP / GPRGNN / DAGNN in training mode: (trunk logits, layer inputs, saved tails)."""
         enc, L = self.enc, self.L
         a = ops.as_feat(feats)
         acts, saved = [a], []
@@ -688,6 +689,28 @@ class TeacherEngine:
         return dz
 
     _step_gpr_body = functools.partialmethod(_step_prop_body, _gpr_fwd, _gpr_bwd)
+
+    # ------------------------------------------------------------------------------------------ full-graph DAGNN
+    @torch.no_grad()
+    def step_dagnn(self, g, feats, labels, idx_train, lamb=1.0):
+        """The full-graph `train` step over DAGNN (docs/DAGNN_SEMANTICS.md): the MLP trunk with its norm / ReLU / dropout tails, per hop one
+        glnn_spmm_csr_f32 and one glnn_dagnn_gate_f32 that keep every H_k and gate, NLL over idx_train, per hop one glnn_spmm_csr_f32 over
+        the transposed graph and one glnn_dagnn_gate_bwd_f32 that leaves the per-row q, glnn_dagnn_fold_f32 into grad(proj.weight) /
+        grad(proj.bias), the trunk backward, and the ONE Adam launch (the gate's weight and bias are two more tensors of its table)."""
+        self._run_full_graph(self._step_dagnn_body, g, feats, labels, idx_train, lamb)
+
+    def _dagnn_fwd(self, g, h0):
+        proj = self.enc.propagate.proj
+        return dagnn_fwd(g, h0, proj.weight, proj.bias, self.enc.k, keep=True)
+
+    def _dagnn_bwd(self, g, dlog, h0, kept):
+        proj = self.enc.propagate.proj
+        dz, dw, db = dagnn_bwd(g, dlog, kept, proj.weight, self.enc.k)
+        self.grad(proj.weight).copy_(dw.view_as(proj.weight))
+        self.grad(proj.bias).copy_(db)
+        return dz
+
+    _step_dagnn_body = functools.partialmethod(_step_prop_body, _dagnn_fwd, _dagnn_bwd)
 
     # ------------------------------------------------------------------------------------------ full-graph GCNII
     def _gcnii_seed(self, site, step=None):

@@ -900,6 +900,41 @@ GLNN_API int glnn_gpr_fold_f32(const float* row_dot, int rows, int64_t m, float*
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DAGNN's gate (Liu, Gao, Ji, "Towards Deeper Graph Neural Networks", KDD 2020): result[i] = sum_{k = 0..K} s_k[i] H_k[i] with
+ * H_0 = x0, H_k = P H_{k-1}, APPNP's operator P = D_in^-1/2 A D_out^-1/2 and the node-adaptive gate s_k[i] = sigmoid(<H_k[i], w> + b),
+ * evaluated as 1 / (1 + expf(-(dot + b))).  docs/DAGNN_SEMANTICS.md states the arithmetic.  The propagation itself is glnn_spmm_csr_f32
+ * (GLNN_AGG_SUM with row_scale / col_scale = the two degree norms); these entries are row-local.  n rows of d <= 256 columns (the gate is
+ * one row-wide dot product; GLNN_ERR_UNSUPPORTED otherwise, nothing launched); every row pointer 16-byte aligned with a leading dimension
+ * % 4 == 0 and >= round4(d); padding columns [d, round4(d)) of every written row are 0.  w [d] and b [1] are read on the device on every
+ * call.  Deterministic (no float atomics); a row's dot products are folded over its lanes in a fixed xor order.  n == 0 is a no-op.
+ *
+ * glnn_dagnn_gate_f32 -- hop k of the forward, one call per k = 0..K, x = H_k:
+ *     s = sigmoid(<x[i], w> + b);   acc[i] = (k == 0 ? 0 : acc[i]) + s x[i];   score[k n + i] = s  (score optional, [(K + 1) n]: training)
+ *   After hop K, acc is the result.  acc does not alias x.
+ *
+ * glnn_dagnn_gate_bwd_f32 -- hop k of the backward, one call per k = K..0:
+ *     q      = <g[i], h[i]> s (1 - s),  s = score[k n + i]       g = dL/dresult, h = the saved H_k
+ *     out[i] = s g[i] + q w + t[i]                               t = P^T (the previous call's out), NULL at k = K; t may be out itself
+ *     q_out[k n + i] = q                                         q_out holds (K + 1) n floats
+ *   After k = 0, out = dL/dx0.  out aliases neither g nor h.
+ *
+ * glnn_dagnn_fold_f32 -- dw[c] = sum_r q[r] hs[r, c], db[0] = sum_r q[r] over the rows = (K + 1) n rows of the saved stack hs [rows, ldh],
+ *   accumulated in fp64 in a geometry that depends on (rows, d) alone: stage 1 sums chunks of GLNN_DAGNN_FOLD_CHUNK rows (LPR = pow2 >=
+ *   ceil(d / 4) lanes a row, 256 / LPR row groups taking the chunk's rows g, g + 256 / LPR, ... ascending, the groups added in order), stage
+ *   2 the chunk partials (thread t of 256 takes chunks t, t + 256, ...; xor tree over the lanes, the four waves in order); one rounding to
+ *   fp32.  workspace: glnn_dagnn_fold_workspace_bytes(rows, d) = ceil(rows / GLNN_DAGNN_FOLD_CHUNK) * (d + 1) * 8 bytes, 8-byte aligned.
+ *   rows = 0 writes zeros. */
+GLNN_API int glnn_dagnn_gate_f32(const float* x, int64_t ldx, int64_t n, int d, const float* w, const float* b, int k, float* acc,
+                                 int64_t ldacc, float* score, void* stream);
+GLNN_API int glnn_dagnn_gate_bwd_f32(const float* g, int64_t ldg, const float* h, int64_t ldh, int64_t n, int d, const float* score,
+                                     const float* w, int k, const float* t, int64_t ldt, float* out, int64_t ldo, float* q_out,
+                                     void* stream);
+#define GLNN_DAGNN_FOLD_CHUNK 2048
+GLNN_API int64_t glnn_dagnn_fold_workspace_bytes(int64_t rows, int d);
+GLNN_API int glnn_dagnn_fold_f32(const float* hs, int64_t ldh, const float* q, int64_t rows, int d, float* dw, float* db,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * GCNII conv layer (Chen, Wei, Huang, Ding, Li, "Simple and Deep Graph Convolutional Networks", ICML 2020), one launch per layer and
  * direction over APPNP's operator P = D_in^-1/2 A D_out^-1/2.  docs/GCNII_SEMANTICS.md states the arithmetic.  Square graph of n nodes,
  * nnz = indptr[n] < 2^31 and d <= 256 (GLNN_ERR_UNSUPPORTED otherwise); every row pointer 16-byte aligned with a leading dimension
