@@ -127,6 +127,11 @@ SIGNATURES = {
     "glnn_gatv2_attn_bwd_workspace_floats": [c_i64, c_int, c_int],
     "glnn_gatv2_attn_bwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp,
                                 c_i64, c_f32, c_f32, c_u32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp],
+    "glnn_gt_attn_fwd_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_f32, c_u32, c_int,
+                             c_vp, c_i64, c_vp, c_vp],
+    "glnn_gt_attn_bwd_workspace_floats": [c_i64, c_int],
+    "glnn_gt_attn_bwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp,
+                             c_i64, c_f32, c_u32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp],
     "glnn_sage_mean_fused_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp,
                                  c_i64, c_vp, c_vp],
     "glnn_spmm_sage_mean_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64, c_vp],
@@ -276,6 +281,7 @@ def lib():
         h.glnn_layernorm_bwd_workspace_floats.restype = c_i64
         h.glnn_gat_attn_bwd_workspace_floats.restype = c_i64
         h.glnn_gatv2_attn_bwd_workspace_floats.restype = c_i64
+        h.glnn_gt_attn_bwd_workspace_floats.restype = c_i64
         h.glnn_dagnn_fold_workspace_bytes.restype = c_i64
         h.glnn_sage_step_ws_bn_floats.restype = c_i64
         h.glnn_sage_step_ws_ln_floats.restype = c_i64

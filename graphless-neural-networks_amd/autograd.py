@@ -655,3 +655,72 @@ def gatv2_conv(graph, x, w_src, b_src, w_dst, b_dst, attn, heads, out_feats, slo
     """GATv2Conv forward (_attn_conv's rule)."""
     return _attn_conv(Gatv2ConvFn, gatv2_layer_fwd, gatv2_conv_seeds, graph, x, (w_src, b_src, w_dst, b_dst, attn),
                       (heads, out_feats, slope, relu), feat_drop, attn_drop, training)
+
+
+# ------------------------------------------------------------------------------------------ graph-transformer layer (docs/GT_SEMANTICS.md)
+gt_conv_seeds = functools.partial(_attn_seeds, tag_feat=0x47545246, tag_attn=0x47545241)
+GT_PROJECTIONS = ("key", "query", "value", "skip")        # the order of TransformerConv's four nn.Linear, and of every (w, b) list below
+
+
+def gt_layer_fwd(g, x, wk, bk, wq, bq, wv, bv, ws, bs, heads, out_feats, slope, relu, feat_p=0.0, feat_seed=0, attn_p=0.0, attn_seed=0,
+                 want_lse=False):
+    """One TransformerConv forward: the dropped copy of the input (made once, as gatv2_layer_fwd does: read by the four projections and
+    by the four weight gradients), k / q / v / skip = the four Linear layers, glnn_gt_attn_fwd_f32 (+ ReLU).  `slope` is _attn_conv's
+    shape slot and is not used.  Returns (y, (xd, q, k, v, lse)); lse only when the backward will follow."""
+    xd = ops.act_fwd(x, drop_p=feat_p, drop_seed=feat_seed, relu=False) if feat_p > 0 else x
+    k = ops.gemm(xd, wk, ep_shift=bk)
+    q = ops.gemm(xd, wq, ep_shift=bq)
+    v = ops.gemm(xd, wv, ep_shift=bv)
+    s = ops.gemm(xd, ws, ep_shift=bs)
+    y, lse = ops.gt_attn_fwd(g.indptr, g.indices, g.num_edges(), q, k, v, s, heads, out_feats, attn_p, attn_seed, relu=relu,
+                             want_lse=want_lse)
+    return y, (xd, q, k, v, lse)
+
+
+def gt_layer_bwd(g, gy, saved, wk, wq, wv, ws, heads, out_feats, attn_p=0.0, attn_seed=0, need_dx=True, dw=None, db=None):
+    """Backward of gt_layer_fwd.  gy = dL/dy ALREADY behind the activation mask (zero where a ReLU layer's y is 0).  dw / db: optional
+    lists of four output tensors in GT_PROJECTIONS order.  Returns (da = dk Wk + dq Wq + dv Wv + gy Ws -- the input gradient BEFORE the
+    feature-dropout mask, or None; [dWk, dWq, dWv, dWs]; [dbk, dbq, dbv, dbs])."""
+    xd, q, k, v, lse = saved
+    gy = ops.as_feat(gy)
+    dq, dk, dv = ops.gt_attn_bwd(g, q, k, v, lse, gy, heads, out_feats, attn_p, attn_seed)
+    hf = heads * out_feats
+    dw = [None] * 4 if dw is None else list(dw)
+    db = [None] * 4 if db is None else list(db)
+    da = None
+    for i, (dz, w) in enumerate(((dk, wk), (dq, wq), (dv, wv), (gy, ws))):       # (the skip row's gradient is gy itself)
+        if db[i] is None:
+            db[i] = torch.empty(hf, dtype=torch.float32, device=gy.device)
+        dw[i] = ops.gemm_tn(dz, xd, out=dw[i], col_sum_a=db[i])
+        if need_dx:
+            t = ops.gemm(dz, w, w_is_kn=True)
+            da = t if da is None else da.add_(t)
+    return da, dw, db
+
+
+class GtConvFn(torch.autograd.Function):
+    """TransformerConv as a differentiable op on the HIP path; the backward replays the forward's dropout masks from their seeds."""
+
+    @staticmethod
+    def forward(ctx, graph, x, wk, bk, wq, bq, wv, bv, ws, bs, heads, out_feats, slope, relu, feat_p, feat_seed, attn_p, attn_seed):
+        x = ops.as_feat(x.detach())
+        y, saved = gt_layer_fwd(graph, x, wk.detach(), bk.detach(), wq.detach(), bq.detach(), wv.detach(), bv.detach(), ws.detach(),
+                                bs.detach(), heads, out_feats, slope, relu, feat_p, feat_seed, attn_p, attn_seed, want_lse=True)
+        ctx.graph, ctx.cfg = graph, (heads, out_feats, relu, feat_p, feat_seed, attn_p, attn_seed)
+        ctx.save_for_backward(wk, wq, wv, ws, y, *saved)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        wk, wq, wv, ws, y, xd, q, k, v, lse = ctx.saved_tensors
+        heads, out_feats, relu, feat_p, feat_seed, attn_p, attn_seed = ctx.cfg
+        da, dw, db = _attn_backward(dy, y, relu, feat_p, feat_seed, lambda gy: gt_layer_bwd(
+            ctx.graph, gy, (xd, q, k, v, lse), wk.detach(), wq.detach(), wv.detach(), ws.detach(), heads, out_feats, attn_p, attn_seed,
+            need_dx=ctx.needs_input_grad[1]))
+        return (None, da, dw[0], db[0], dw[1], db[1], dw[2], db[2], dw[3], db[3]) + (None,) * 8
+
+
+def gt_conv(graph, x, wk, bk, wq, bq, wv, bv, ws, bs, heads, out_feats, relu, feat_drop, attn_drop, training):
+    """TransformerConv forward (_attn_conv's rule; the shape's slope slot is unused)."""
+    return _attn_conv(GtConvFn, gt_layer_fwd, gt_conv_seeds, graph, x, (wk, bk, wq, bq, wv, bv, ws, bs), (heads, out_feats, 0.0, relu),
+                      feat_drop, attn_drop, training)

@@ -85,7 +85,7 @@ def get_teacher_args(argv=None):
     # not a reference flag: the DAGNN teacher's number of propagation steps (conf key `dagnn_k`, read by Model; docs/DAGNN_SEMANTICS.md).
     # Unset = the conf's value or the paper's 10
     p.add_argument("--dagnn_k", type=int, default=None, help="Propagation steps K of the DAGNN teacher (default 10)")
-    # not reference flags: mini-batch training of the full-graph teachers (GCN, APPNP, GAT, GATv2, GPRGNN, DAGNN, GCNII) on random-walk induced
+    # not reference flags: mini-batch training of the full-graph teachers (GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII) on random-walk induced
     # subgraphs (conf keys `subgraph_walk_length`, `subgraph_self_loop`, read by run_transductive / run_inductive;
     # docs/SUBGRAPH_SEMANTICS.md).  --batch_size is then the number of walk roots per batch; 0 = the full-graph step per epoch
     p.add_argument("--subgraph_walk_length", type=int, default=0,
@@ -96,7 +96,7 @@ def get_teacher_args(argv=None):
     if not 0 <= args.subgraph_walk_length <= 64:
         p.error(f"--subgraph_walk_length must be in [0, 64] (got {args.subgraph_walk_length})")
     if args.subgraph_walk_length > 0 and teacher_kind(args.teacher) in ("sage", "mlp"):
-        p.error(f"--subgraph_walk_length applies to the full-graph teachers (GCN, APPNP, GAT, GATv2, GPRGNN, DAGNN, GCNII) only: SAGE trains on "
+        p.error(f"--subgraph_walk_length applies to the full-graph teachers (GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII) only: SAGE trains on "
                 f"sampled blocks and MLP on feature batches (got --teacher {args.teacher})")
     if args.subgraph_self_loop != "keep" and args.subgraph_walk_length == 0:
         p.error(f"--subgraph_self_loop {args.subgraph_self_loop} needs --subgraph_walk_length > 0")
@@ -180,15 +180,30 @@ def _setting_dir(args, root, leaf):
     raise ValueError(f"Unknown experiment setting! {args.exp_setting}")
 
 
+_SECTION_STAND_INS = {"dagnn": ("APPNP",), "gt": ("GATv2", "GAT")}      # teacher kind -> the sections that stand in for a missing one
+
+
 def _training_config(path, model_name, dataset):
-    """get_training_config.  train.conf.yaml has no DAGNN sections: a DAGNN teacher whose dataset names none takes that dataset's APPNP
-    section -- the trunk's hyper-parameters, what every GPRGNN section restates -- or the global section alone (docs/DAGNN_SEMANTICS.md)."""
-    if "DAGNN" in model_name and teacher_kind(model_name) == "dagnn":
+    """get_training_config.  train.conf.yaml has no DAGNN and no GraphTransformer sections.  A DAGNN teacher whose dataset names none takes
+    that dataset's APPNP section -- the trunk's hyper-parameters, what every GPRGNN section restates -- or the global section alone
+    (docs/DAGNN_SEMANTICS.md).  A GraphTransformer teacher takes the dataset's own section if a user added one, else its GATv2 section, else
+    its GAT section -- the conf contract is GAT's (docs/GT_SEMANTICS.md) -- and without any of them raises, naming the two keys a conf
+    must carry."""
+    kind = teacher_kind(model_name)
+    stand_ins = _SECTION_STAND_INS.get(kind)
+    if stand_ins:
         with open(path) as fh:
             cfg = yaml.safe_load(fh)
         sections = cfg.get(dataset) or {}
         if model_name not in sections:
-            return dict(cfg["global"], **(sections.get("APPNP") or {}), model_name=model_name)
+            for name in stand_ins:
+                if sections.get(name):
+                    return dict(cfg["global"], **sections[name], model_name=model_name)
+            if kind == "dagnn":
+                return dict(cfg["global"], model_name=model_name)
+            raise ValueError(f"{model_name}: {path} has no {model_name}, GATv2 or GAT section for dataset {dataset!r}, so nothing names "
+                             "num_heads and attn_dropout_ratio, the two conf keys a GraphTransformer teacher is built from; add a "
+                             f"{model_name} section that carries both")
     return get_training_config(path, model_name, dataset)
 
 

@@ -389,12 +389,15 @@ UNSHARDED_TEACHERS = {
 UNSHARDED_GATED = {
     "DAGNN": "each of its K propagation steps needs the previous step's rows of the remote sources, and its gate the whole propagated row",
 }
+UNSHARDED_DOT_PRODUCT = {
+    "GraphTransformer": "its edge softmax needs every in-edge of a row and the key and value rows of the remote sources",
+}
 
 
 def _refuse_unsharded(encoder, who):
-    """The encoders neither sharded teacher runs: the kinds of UNSHARDED_TEACHERS, then a SAGE with another aggregator than 'gcn'."""
+    """The encoders neither sharded teacher runs: the kinds of UNSHARDED_TEACHERS, UNSHARDED_GATED and UNSHARDED_DOT_PRODUCT, then a SAGE with another aggregator than 'gcn'."""
     kind = type(encoder).__name__
-    why = UNSHARDED_TEACHERS.get(kind) or UNSHARDED_GATED.get(kind)
+    why = UNSHARDED_TEACHERS.get(kind) or UNSHARDED_GATED.get(kind) or UNSHARDED_DOT_PRODUCT.get(kind)
     if why:
         raise NotImplementedError(f"{who}: the {kind} teacher is not sharded -- {why}, an exchange the sharded "
                                   f"forward does not have (whole-graph {kind} only)")

@@ -17,17 +17,17 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .autograd import appnp_propagate, gcnii_stack, linear_fn, norm_act_drop
-from .nn import DAGNNConv, GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, SAGEConv, _whole_graph_only
+from .nn import DAGNNConv, GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, SAGEConv, TransformerConv, _whole_graph_only
 
 
 _KINDS = (("MLP", "mlp"), ("SAGE", "sage"), ("GCNII", "gcnii"), ("GCN", "gcn"), ("APPNP", "appnp"), ("GATv2", "gatv2"), ("GAT", "gat"),
-          ("GPRGNN", "gpr"), ("DAGNN", "dagnn"))
+          ("GPRGNN", "gpr"), ("DAGNN", "dagnn"), ("GraphTransformer", "gt"))
 
 
 def teacher_kind(model_name):
     """The model family a `model_name` selects: the first of _KINDS whose key the name contains (the reference's substring dispatch,
     models.py:355,409).  The order is the rule and is written down here alone: "MLP" first ("MLP3w4" is an MLP), "GCNII" before "GCN"
-    and "GATv2" before "GAT", which they contain ("GPRGNN" and "DAGNN" contain no other key and no other key contains them).  Every
+    and "GATv2" before "GAT", which they contain ("GPRGNN", "DAGNN" and "GraphTransformer" contain no other key and no other key contains them).  Every
     caller switches on the kind it returns."""
     for key, kind in _KINDS:
         if key in model_name:
@@ -35,7 +35,7 @@ def teacher_kind(model_name):
     raise ValueError(f"Unknown model_name {model_name}")
 
 
-FULL_GRAPH_KINDS = ("gcn", "gcnii", "appnp", "gat", "gatv2", "gpr", "dagnn")    # the teachers whose training step takes the whole graph
+FULL_GRAPH_KINDS = ("gcn", "gcnii", "appnp", "gat", "gatv2", "gpr", "dagnn", "gt")    # the teachers whose training step takes the whole graph
 
 
 def _bn_eval_fold(bn, bias):
@@ -707,7 +707,7 @@ class GCNII(nn.Module):
 
 
 class _AttnStack(nn.Module):
-    """The layer stack GAT and GATv2 share (reference models.py:202-279): num_layers convs of class CONV, `num_heads` heads of
+    """The layer stack GAT, GATv2 and GraphTransformer share (reference models.py:202-279): num_layers convs of class CONV, `num_heads` heads of
     hidden_dim // num_heads features on every hidden layer (ReLU inside the conv, outputs flattened to [N, hidden_dim] and kept in
     h_list), one head of output_dim features on the last.  No norm layers and no dropout outside the convs (feat_drop = dropout_ratio,
     attn_drop).  A subclass names its conv, the tails of its messages and where its conf contract is written (Model.__init__)."""
@@ -768,6 +768,17 @@ class GATv2(_AttnStack):
     CONF_DOC = "docs/GATV2_SEMANTICS.md"
 
 
+class GraphTransformer(_AttnStack):
+    """The graph transformer of UniMP (Shi et al., IJCAI 2021; docs/GT_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it)
+    without its label embedding, in models.GAT's shape, over TransformerConv."""
+    CONV = TransformerConv
+    NUM_LAYERS = "models.GAT's shape: hidden multi-head layers and a one-head last layer"
+    CONF_DOC = "docs/GT_SEMANTICS.md"
+
+
+_ATTN_STACKS = {"gat": GAT, "gatv2": GATv2, "gt": GraphTransformer}
+
+
 class Model(nn.Module):
     """Wrapper of different models (reference models.py:347-429).
 
@@ -794,8 +805,8 @@ class Model(nn.Module):
             enc = GCN(activation=F.relu, norm_type=conf["norm_type"], **common)
         elif kind == "appnp":
             enc = APPNP(activation=F.relu, norm_type=conf["norm_type"], **common)
-        elif kind in ("gatv2", "gat"):               # (the conf contract of GATv2 is GAT's)
-            cls = GATv2 if kind == "gatv2" else GAT
+        elif kind in _ATTN_STACKS:                   # (the conf contract of GATv2 and GraphTransformer is GAT's)
+            cls = _ATTN_STACKS[kind]
             who = cls.__name__
             missing = [k for k in ("num_heads", "attn_dropout_ratio") if k not in conf]
             if missing:
@@ -838,6 +849,10 @@ class Model(nn.Module):
             if kind == "gatv2":
                 raise NotImplementedError(f"GATv2.inference(dtype={dtype}): bf16 activation storage is not implemented for the GATv2 teacher "
                                           "(csrc/gatv2.hip gathers and stores fp32 rows; docs/GATV2_SEMANTICS.md, What is refused)")
+            if kind == "gt":
+                raise NotImplementedError(f"GraphTransformer.inference(dtype={dtype}): bf16 activation storage is not implemented for the "
+                                          "GraphTransformer teacher (csrc/gt.hip gathers and stores fp32 rows; docs/GT_SEMANTICS.md, What "
+                                          "is refused)")
             if kind == "gcnii":
                 raise NotImplementedError(f"GCNII.inference(dtype={dtype}): bf16 activation storage is not implemented for the GCNII teacher "
                                           "(csrc/gcnii.hip gathers and stores fp32 rows; docs/GCNII_SEMANTICS.md, Out of scope)")

@@ -4,6 +4,7 @@
   GraphConv(in, out, activation=)(g, h)          <- dgl.nn.GraphConv, reference models.py:170-187,193
   GATConv(in, out, heads, ...)(g, h)             <- dgl.nn.GATConv, reference models.py:228-267 (docs/GAT_SEMANTICS.md)
   GATv2Conv(in, out, heads, ...)(g, h)           <- GATv2's attention layer (dgl 0.6.1 has none; docs/GATV2_SEMANTICS.md)
+  TransformerConv(in, out, heads, ...)(g, h)     <- UniMP's dot-product attention layer with a skip row (docs/GT_SEMANTICS.md)
   GPRConv(k, alpha, init)(g, h)                  <- GPR-GNN's learned K-step propagation (no dgl counterpart; docs/GPR_SEMANTICS.md)
   DAGNNConv(k, in_feats)(g, h)                   <- DAGNN's node-gated K-step propagation (no dgl counterpart; docs/DAGNN_SEMANTICS.md)
   GCNIIConv(hidden, layer, alpha, lamda)(g, h, h0) <- one GCNII conv layer (dgl 0.6.1 has none; docs/GCNII_SEMANTICS.md)
@@ -18,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .autograd import (GraphConvFn, SpmmFn, _differentiable, dagnn_propagate, gat_conv, gatv2_conv, gcnii_stack, gpr_propagate, graphconv_fwd,
+from .autograd import (GraphConvFn, SpmmFn, _differentiable, dagnn_propagate, gat_conv, gatv2_conv, gcnii_stack, gt_conv, gpr_propagate, graphconv_fwd,
                        linear_fn)
 
 
@@ -224,7 +225,7 @@ class GraphConv(nn.Module):
 
 
 class _AttnConv(nn.Module):
-    """What GATConv and GATv2Conv share: the constructor's refusals, relu(), forward's guards and the [N, heads, out] view.  A subclass
+    """What GATConv, GATv2Conv and TransformerConv share: the constructor's refusals, relu(), forward's guards and the [N, heads, out] view.  A subclass
     registers its parameters in make_parameters() and draws them in reset_parameters() (its own RNG stream) and ends the messages."""
     WHOLE_GRAPH = RESIDUAL = ACTIVATION = ZERO_IN_DEGREE = None
 
@@ -324,6 +325,31 @@ class GATv2Conv(_AttnConv):
         return self.by_head(gatv2_conv(graph, feat, self.fc_src.weight, self.fc_src.bias, self.fc_dst.weight, self.fc_dst.bias, self.attn,
                                        self._num_heads, self._out_feats, self.negative_slope, self.relu(), self.feat_drop.p,
                                        self.attn_drop.p, self.training))
+
+
+class TransformerConv(_AttnConv):
+    """Graph-transformer attention layer on a homogeneous graph (the TransformerConv of UniMP: Shi et al., IJCAI 2021;
+    docs/GT_SEMANTICS.md): lin_key / lin_query / lin_value / lin_skip [heads * out, in] WITH bias, torch's default Linear initialisation,
+    constructed in that order; scaled dot-product edge softmax, the skip row added to the aggregate.  No beta gate, no edge features, no
+    concat=False mean; negative_slope is accepted (the stack passes it) and unused.  forward returns [N, heads, out]."""
+    WHOLE_GRAPH = "the GraphTransformer teacher runs on the whole graph"
+    RESIDUAL = "docs/GT_SEMANTICS.md, What is refused: lin_skip is the layer's skip connection"
+    ACTIVATION = "implemented (the attention kernel's epilogue)"
+    ZERO_IN_DEGREE = "TransformerConv follows dgl GATConv"
+
+    def make_parameters(self, in_feats, out_feats, num_heads):
+        for name in ("lin_key", "lin_query", "lin_value", "lin_skip"):
+            setattr(self, name, nn.Linear(in_feats, out_feats * num_heads, bias=True))
+        self.relu()                                # an activation the kernel's epilogue lacks is refused by the constructor
+
+    def reset_parameters(self):
+        """Nothing to redraw: the four nn.Linear keep the default initialisation their constructors drew."""
+
+    def forward(self, graph, feat):
+        self.check_inputs(graph, feat)
+        lins = (self.lin_key, self.lin_query, self.lin_value, self.lin_skip)
+        return self.by_head(gt_conv(graph, feat, *(t for lin in lins for t in (lin.weight, lin.bias)), self._num_heads, self._out_feats,
+                                    self.relu(), self.feat_drop.p, self.attn_drop.p, self.training))
 
 
 def _whole_graph_only(graph, feat, who, why):

@@ -2084,6 +2084,52 @@ def gatv2_attn_bwd(graph, zl, zr, lse, attn, g, heads, out_feats, negative_slope
     return dzl, dzr, dattn
 
 
+# --------------------------------------------------------------------------------------------- graph-transformer attention (csrc/gt.hip)
+def _gt_check(name, n, hf, **rows):
+    """q / k / v / skip / g of a graph-transformer call: [n, heads * out_feats] fp32 rows on the GPU (column slabs of one stacked
+    projection are fine: each carries its own leading dimension)."""
+    _need_cuda(*rows.values())
+    for key, t in rows.items():
+        _mat(t, f"{name} {key}")
+        if t.shape != (n, hf):
+            raise ValueError(f"{name}: {key} must be [n, heads * out_feats] = [{n}, {hf}] (got {tuple(t.shape)})")
+
+
+def gt_attn_fwd(indptr, indices, nnz, q, k, v, skip, heads, out_feats, attn_drop=0.0, seed=0, relu=False, want_lse=False, out=None,
+                lse=None):
+    """glnn_gt_attn_fwd_f32: (out [n, heads * out_feats], lse [n, heads] or None) -- the scaled dot-product edge softmax, the weighted
+    aggregation of v and the skip row (docs/GT_SEMANTICS.md).  lse: a buffer to take the row log-sum-exps (implies want_lse)."""
+    q, k, v, skip = as_feat(q), as_feat(k), as_feat(v), as_feat(skip)
+    n = q.shape[0]
+    _csr_check("gt_attn_fwd", indptr, indices, n, q)
+    _gt_check("gt_attn_fwd", n, heads * out_feats, q=q, k=k, v=v, skip=skip)
+    _need_cuda(out)
+    out, lse = _attn_out("gt_attn_fwd", n, heads, out_feats, q.device, out, lse, want_lse)
+    _attn_call("gt_attn_fwd", heads, out_feats, n, nnz, attn_drop, _p(indptr), _p(indices), n, int(nnz), _p(q), _ld(q), _p(k), _ld(k),
+               _p(v), _ld(v), _p(skip), _ld(skip), heads, out_feats, float(attn_drop), int(seed) & 0xFFFFFFFF, 1 if relu else 0, _p(out),
+               _ld(out), _p(lse))
+    return out, lse
+
+
+def gt_attn_bwd(graph, q, k, v, lse, g, heads, out_feats, attn_drop=0.0, seed=0, dq=None, dk=None, dv=None):
+    """glnn_gt_attn_bwd_f32 over `graph` (CSRGraph: its in-CSR and its cached transpose with edge ids): (dq, dk, dv); the gradient of the
+    skip row is g itself.  g = dL/d out behind the activation mask.  The two [E, heads] scratches (t and a w) live for the call."""
+    q, k, v, g = as_feat(q), as_feat(k), as_feat(v), as_feat(g)
+    n = q.shape[0]
+    _csr_check("gt_attn_bwd", graph.indptr, graph.indices, n, q)
+    _gt_check("gt_attn_bwd", n, heads * out_feats, q=q, k=k, v=v, g=g)
+    _need_cuda(lse)
+    if lse.shape != (n, heads) or not lse.is_contiguous() or lse.dtype != torch.float32:
+        raise ValueError("gt_attn_bwd: lse must be contiguous fp32 [n, heads]")
+    dev = q.device
+    csr, nnz, ts, (dq, dk, dv), _ = _attn_bwd_bufs("gt_attn_bwd", graph, n, heads, out_feats, dev, {"dq": dq, "dk": dk, "dv": dv}, ())
+    ws = torch.empty(max(int(_lib.lib().glnn_gt_attn_bwd_workspace_floats(int(nnz), heads)), 1), dtype=torch.float32, device=dev)
+    _attn_call("gt_attn_bwd", heads, out_feats, n, nnz, attn_drop, *csr, _p(q), _ld(q), _p(k), _ld(k), _p(v), _ld(v), heads, out_feats,
+               _p(lse), _p(g), _ld(g), float(attn_drop), int(seed) & 0xFFFFFFFF, _p(ts), _p(dq), _ld(dq), _p(dk), _ld(dk), _p(dv), _ld(dv),
+               _p(ws), ws.numel())
+    return dq, dk, dv
+
+
 _NONNEG = []          # [(weakref to the tensor, key, answer)]: one entry
 
 

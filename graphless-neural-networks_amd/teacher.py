@@ -37,7 +37,7 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .models import teacher_kind
-from .autograd import (appnp_bwd, appnp_fwd, dagnn_bwd, dagnn_fwd, gat_layer_bwd, gat_layer_fwd, gatv2_layer_bwd, gatv2_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd,
+from .autograd import (appnp_bwd, appnp_fwd, dagnn_bwd, dagnn_fwd, gat_layer_bwd, gat_layer_fwd, gatv2_layer_bwd, gatv2_layer_fwd, gt_layer_bwd, gt_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd,
                        graphconv_fwd)
 from .student import _mix32
 
@@ -74,11 +74,12 @@ _NORM_RELU = {"sage": "SAGE with norm_type none|batch|layer and ReLU (the refere
               "gpr": "GPRGNN with norm_type none|batch|layer and ReLU (docs/GPR_SEMANTICS.md)",
               "dagnn": "DAGNN with norm_type none|batch|layer and ReLU (docs/DAGNN_SEMANTICS.md)"}
 _ATTN_RELU = {"gatv2": "GATv2 with ReLU hidden layers and a linear last layer (docs/GATV2_SEMANTICS.md)",
+              "gt": "GraphTransformer with ReLU hidden layers and a linear last layer (docs/GT_SEMANTICS.md)",
               "gat": "GAT with ReLU hidden layers and a linear last layer (models.py:202-279)"}
 
 
 def check_supported(model, criterion, optimizer):
-    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GATv2, GPRGNN, DAGNN or GCNII teacher."""
+    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN or GCNII teacher."""
     enc = model.encoder
     name = model.model_name
     try:
@@ -86,7 +87,7 @@ def check_supported(model, criterion, optimizer):
     except ValueError:           # (a name no family claims: refused like the MLP)
         kind = "mlp"
     if kind == "mlp":
-        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GATv2, GPRGNN, DAGNN or GCNII teachers only (got {name})")
+        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN or GCNII teachers only (got {name})")
     _check_criterion_and_optimizer("TeacherEngine", criterion, optimizer)
     if kind == "gcnii":          # (the encoder's constructor refused everything else)
         if enc.norm_type != "none" or not _is_relu(enc.activation):
@@ -255,7 +256,7 @@ class TeacherEngine:
         self.L = self.enc.num_layers
         self.bn = getattr(self.enc, "norm_type", "none") == "batch"
         self.ln = getattr(self.enc, "norm_type", "none") == "layer"
-        self.p = float(self.enc.layers[0].feat_drop.p if self.kind in ("gat", "gatv2") else self.enc.dropout.p)
+        self.p = float(self.enc.layers[0].feat_drop.p if self.kind in _ATTN_RELU else self.enc.dropout.p)
         params = list(model.parameters())
         self.params = params
         dev = params[0].device
@@ -768,6 +769,13 @@ class TeacherEngine:
         gradients with their bias column sums and the input gradient; the ONE Adam launch."""
         self._step_attn(self._step_gatv2_body, "GATv2Conv follows dgl GATConv", g, feats, labels, idx_train, lamb)
 
+    @torch.no_grad()
+    def step_gt(self, g, feats, labels, idx_train, lamb=1.0):
+        """The full-graph `train` step over GraphTransformer (docs/GT_SEMANTICS.md): per layer the dropped copy of the input, the four
+        projections and glnn_gt_attn_fwd_f32; NLL over idx_train; per layer glnn_gt_attn_bwd_f32 over the graph and its transpose, the
+        four weight gradients with their bias column sums and the input gradient; the ONE Adam launch."""
+        self._step_attn(self._step_gt_body, "TransformerConv follows dgl GATConv", g, feats, labels, idx_train, lamb)
+
     def _step_attn(self, body, semantics, g, feats, labels, idx_train, lamb):
         if g.has_zero_in_degree():
             raise RuntimeError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid "
@@ -812,7 +820,21 @@ class TeacherEngine:
                                lay.attn_drop.p, as_, need_dx=need_dx, dw_src=self.grad(lay.fc_src.weight), db_src=self.grad(lay.fc_src.bias),
                                dw_dst=self.grad(lay.fc_dst.weight), db_dst=self.grad(lay.fc_dst.bias), dattn=self.grad(lay.attn).view(-1))[0]
 
+    @staticmethod
+    def _gt_lins(lay):
+        return lay.lin_key, lay.lin_query, lay.lin_value, lay.lin_skip
+
+    def _gt_fwd(self, g, lay, x, relu, fs, as_, signed):
+        return gt_layer_fwd(g, x, *(t for lin in self._gt_lins(lay) for t in (lin.weight, lin.bias)), lay._num_heads, lay._out_feats,
+                            lay.negative_slope, relu, lay.feat_drop.p, fs, lay.attn_drop.p, as_, want_lse=True)
+
+    def _gt_bwd(self, g, lay, gy, x, y, sv, fs, as_, signed, need_dx):         # (the dropped input copy is among what the forward saved)
+        lins = self._gt_lins(lay)
+        return gt_layer_bwd(g, gy, sv, *(lin.weight for lin in lins), lay._num_heads, lay._out_feats, lay.attn_drop.p, as_, need_dx=need_dx,
+                            dw=[self.grad(lin.weight) for lin in lins], db=[self.grad(lin.bias) for lin in lins])[0]
+
     _step_gat_body = functools.partialmethod(_step_attn_body, _gat_fwd, _gat_bwd, True)
+    _step_gt_body = functools.partialmethod(_step_attn_body, _gt_fwd, _gt_bwd, False)
     _step_gatv2_body = functools.partialmethod(_step_attn_body, _gatv2_fwd, _gatv2_bwd, False)
 
 

@@ -1030,6 +1030,37 @@ GLNN_API int glnn_gatv2_attn_bwd_f32(const int64_t* indptr, const int32_t* indic
                                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Graph-transformer attention (the TransformerConv of UniMP, Shi et al., IJCAI 2021, without label embedding, beta gate and edge
+ * features; csrc/gt.hip; docs/GT_SEMANTICS.md states the arithmetic): per-destination scaled dot-product edge softmax with a skip row.
+ * Square graph of n nodes, indptr / indices the in-CSR (rows = destinations, edge id = CSR position); q / k / v / skip
+ * [n, heads * out_feats] the four projections, head-major columns, each a pointer and a leading dimension of its own (separate matrices
+ * or column slabs of one stacked projection).  heads <= 64, heads * out_feats <= 256, nnz < 2^31 (GLNN_ERR_UNSUPPORTED otherwise,
+ * nothing launched); every row pointer 16-byte aligned with a leading dimension % 4 == 0 and >= round4(heads * out_feats).  Attention
+ * dropout: the mask of glnn_gat_attn_mask_u8, weight 1 / (1 - attn_drop), applied AFTER the normalisation (the denominator sums every
+ * edge).  No float atomics, no grid barrier: bit-identical run to run.  n == 0 is a no-op.
+ *
+ * out[i] = act( sum_{e = (j -> i)} a_ij w_ij v[j] + skip[i] ),  a_ij = softmax over ALL in-edges of i of
+ *   e_ij[h] = <q[i, h, :], k[j, h, :]> / sqrt(out_feats); k[j] and v[j] are gathered once per edge, online softmax in a fixed edge order.
+ *   relu != 0: ReLU epilogue.  lse (optional, [n, heads]): max + log(denominator), what the backward recomputes a_ij from (0 for a row
+ *   without in-edges).  Padding columns of out are written as zeros; a row without in-edges gives its skip row. */
+GLNN_API int glnn_gt_attn_fwd_f32(const int64_t* indptr, const int32_t* indices, int64_t n, int64_t nnz, const float* q, int64_t ldq,
+                                  const float* k, int64_t ldk, const float* v, int64_t ldv, const float* skip, int64_t ldskip, int heads,
+                                  int out_feats, float attn_drop, uint32_t seed, int relu, float* out, int64_t ldo, float* lse,
+                                  void* stream);
+/* Backward of glnn_gt_attn_fwd_f32 with respect to q, k and v (the gradient of skip is g itself).  g = dL/d out behind the activation
+ * mask.  Pass 1 (in-CSR, two sweeps, each gathering k[j] and v[j]): D_i = sum_k a_ik c_ik / sum_k a_ik in fp64 from the row's own
+ * c_ik = w_ik <g_i, v_k>, then t [nnz, heads] scratch (t_ij = a_ij (c_ij - D_i)), a_ij w_ij [nnz, heads] in `workspace`
+ * (>= glnn_gt_attn_bwd_workspace_floats floats) and dq_i = sum_j t_ij k_j / sqrt(out_feats); pass 2 (transposed CSR with original edge
+ * ids, glnn_csr_transpose_eids): dk_j = sum_i t_ij q_i / sqrt(out_feats) and dv_j = sum_i a_ij w_ij g_i from the two scratches, with no
+ * score recomputed.  A row without in-edges gets dq = 0.  dq, dk, dv: [n, heads * out_feats], padding columns written as zeros. */
+GLNN_API int64_t glnn_gt_attn_bwd_workspace_floats(int64_t nnz, int heads);
+GLNN_API int glnn_gt_attn_bwd_f32(const int64_t* indptr, const int32_t* indices, const int64_t* t_indptr, const int32_t* t_indices,
+                                  const int32_t* t_eids, int64_t n, int64_t nnz, const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                  const float* v, int64_t ldv, int heads, int out_feats, const float* lse, const float* g, int64_t ldg,
+                                  float attn_drop, uint32_t seed, float* t, float* dq, int64_t lddq, float* dk, int64_t lddk, float* dv,
+                                  int64_t lddv, float* workspace, int64_t workspace_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * GraphSAGE "mean" aggregator (csrc/sage_mean.hip; docs/SAGE_MEAN_SEMANTICS.md states the arithmetic):
  *   h_neigh[v] = (1 / max(deg(v), 1)) * sum_{u->v} x[u]        out[v] = fc_neigh(h_neigh[v]) + fc_self(x_self[v])
  * Both entries: CSR over destination rows as glnn_spmm_csr_f32, n_src < 2^31, float4-addressable rows (leading dimensions multiples of 4
