@@ -132,6 +132,12 @@ SIGNATURES = {
     "glnn_gt_attn_bwd_workspace_floats": [c_i64, c_int],
     "glnn_gt_attn_bwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp,
                              c_i64, c_f32, c_u32, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp],
+    "glnn_pna_agg_fwd_f32": [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp],
+    "glnn_pna_agg_bwd_f32": [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp,
+                             c_i64, c_vp, c_i64, c_vp],
+    "glnn_pna_scale_fwd_f32": [c_vp, c_i64, c_int, c_f32, c_vp, c_i64, c_vp, c_i64, c_int, c_vp],
+    "glnn_pna_scale_bwd_f32": [c_vp, c_i64, c_int, c_f32, c_vp, c_i64, c_vp, c_i64, c_vp],
+    "glnn_pna_da_f32": [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp],
     "glnn_sage_mean_fused_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp,
                                  c_i64, c_vp, c_vp],
     "glnn_spmm_sage_mean_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64, c_vp],

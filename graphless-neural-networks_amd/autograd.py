@@ -724,3 +724,102 @@ def gt_conv(graph, x, wk, bk, wq, bq, wv, bv, ws, bs, heads, out_feats, relu, fe
     """TransformerConv forward (_attn_conv's rule; the shape's slope slot is unused)."""
     return _attn_conv(GtConvFn, gt_layer_fwd, gt_conv_seeds, graph, x, (wk, bk, wq, bq, wv, bv, ws, bs), (heads, out_feats, 0.0, relu),
                       feat_drop, attn_drop, training)
+
+
+# ------------------------------------------------------------------------------------------ PNA layer (docs/PNA_SEMANTICS.md)
+def pna_conv_seed(count=None):
+    """The feature-dropout seed of the count-th dropout draw of this process (tests replay it; None: a new draw)."""
+    return (_draw_base(count) + 0x504E4146) & 0xFFFFFFFF
+
+
+def pna_weights(w_pre, w_post, f):
+    """The operands the launches read, cut from PNAConv's two Linear weights (w_pre [F, 2F] = [W_dst | W_src], w_post [Fo, 13F] =
+    [W_x | W_0 | W_1 | W_2], one 4F block per scaler): (W_dst, W_src, W_x, W_stack) with W_stack [3 round4(Fo), 4 round4(F)] the three
+    scaler blocks one under the other in S's part layout (zeros in the padding), so that ONE product of S gives all three."""
+    fo = w_post.shape[0]
+    fp, fop = ops.round4(f), ops.round4(fo)
+    w_stack = w_post.new_zeros((3, fop, 4, fp))
+    w_stack[:, :fo, :, :f] = w_post[:, f:].reshape(fo, 3, 4, f).permute(1, 0, 2, 3)
+    return w_pre[:, :f].contiguous(), w_pre[:, f:].contiguous(), w_post[:, :f].contiguous(), w_stack.view(3 * fop, 4 * fp)
+
+
+def pna_layer_fwd(g, x, w_pre, b_pre, w_post, b_post, delta, relu, feat_p=0.0, feat_seed=0, keep=False):
+    """One PNAConv forward: the dropped copy x' of the input (made once), a = x' W_dst^T + b_pre and b = x' W_src^T,
+    glnn_pna_agg_fwd_f32 (S = [a + mean | a + min | a + max | std] of b over the in-edges), out = x' W_x^T + b_post, Z = S W_stack^T (one
+    product for the three scaler blocks: the 12F matrix is never formed) and glnn_pna_scale_fwd_f32 (out += Z_0 + s_amp Z_1 + s_att Z_2,
+    + ReLU).  Returns (out, (x', b, S, mu, arg)); mu and arg only with keep (the backward will follow)."""
+    n, f = x.shape
+    xd = ops.act_fwd(x, drop_p=feat_p, drop_seed=feat_seed, relu=False) if feat_p > 0 else x
+    w_dst, w_src, w_x, w_stack = pna_weights(w_pre, w_post, f)
+    a = ops.gemm(xd, w_dst, ep_shift=b_pre)
+    b = ops.gemm(xd, w_src)
+    s, mu, arg = ops.pna_agg_fwd(g.indptr, g.indices, g.num_edges(), b, g.num_dst_nodes(), a=a, want_arg=keep)
+    out = ops.gemm(xd, w_x, ep_shift=b_post)
+    z = ops.gemm(s, w_stack)
+    ops.pna_scale_fwd(g.indptr, z, out, delta, relu=relu)
+    return out, (xd, b, s, mu, arg)
+
+
+def pna_layer_bwd(g, gy, saved, w_pre, w_post, delta, need_dx=True, dw_pre=None, db_pre=None, dw_post=None, db_post=None):
+    """Backward of pna_layer_fwd.  gy = dL/d out ALREADY behind the activation mask.  dZ = [gy | s_amp gy | s_att gy]
+    (glnn_pna_scale_bwd_f32), dS = dZ W_stack -- the scalers are folded in BEFORE the gather, which reads 4F gradient floats per edge --
+    da (glnn_pna_da_f32), db (glnn_pna_agg_bwd_f32 over the transposed graph), the four weight gradients with their bias column sums.
+    Returns (dx' = gy W_x + da W_dst + db W_src -- the input gradient BEFORE the feature-dropout mask, or None; dW_pre; db_pre; dW_post;
+    db_post)."""
+    xd, b, s, mu, arg = saved
+    gy = ops.as_feat(gy)
+    n, f = xd.shape
+    fo = w_post.shape[0]
+    fp, fop = ops.round4(f), ops.round4(fo)
+    w_dst, w_src, w_x, w_stack = pna_weights(w_pre, w_post, f)
+    dev = gy.device
+    dw_pre = torch.empty_like(w_pre) if dw_pre is None else dw_pre
+    dw_post = torch.empty_like(w_post) if dw_post is None else dw_post
+    db_pre = torch.empty(f, dtype=torch.float32, device=dev) if db_pre is None else db_pre
+    db_post = torch.empty(fo, dtype=torch.float32, device=dev) if db_post is None else db_post
+    dz = ops.pna_scale_bwd(g.indptr, gy, delta)
+    dw_post[:, :f] = ops.gemm_tn(gy, xd, col_sum_a=db_post)
+    dw_stack = ops.gemm_tn(dz, s)
+    dw_post[:, f:] = dw_stack.view(3, fop, 4, fp)[:, :fo, :, :f].permute(1, 0, 2, 3).reshape(fo, 12 * f)
+    ds = ops.gemm(dz, w_stack, w_is_kn=True, out=torch.empty((n, 4 * fp), dtype=torch.float32, device=dev))
+    da = ops.pna_da(g.indptr, ds, f)
+    db = ops.pna_agg_bwd(g, ds, b, mu, s, arg)
+    dw_pre[:, :f] = ops.gemm_tn(da, xd, col_sum_a=db_pre)
+    dw_pre[:, f:] = ops.gemm_tn(db, xd)
+    dx = None
+    if need_dx:
+        dx = ops.gemm(gy, w_x, w_is_kn=True)
+        dx.add_(ops.gemm(da, w_dst, w_is_kn=True))
+        dx.add_(ops.gemm(db, w_src, w_is_kn=True))
+    return dx, dw_pre, db_pre, dw_post, db_post
+
+
+class PnaConvFn(torch.autograd.Function):
+    """PNAConv as a differentiable op on the HIP path; the backward replays the forward's dropout mask from its seed."""
+
+    @staticmethod
+    def forward(ctx, graph, x, w_pre, b_pre, w_post, b_post, delta, relu, feat_p, feat_seed):
+        x = ops.as_feat(x.detach())
+        y, saved = pna_layer_fwd(graph, x, w_pre.detach(), b_pre.detach(), w_post.detach(), b_post.detach(), delta, relu, feat_p, feat_seed,
+                                 keep=True)
+        ctx.graph, ctx.cfg = graph, (delta, relu, feat_p, feat_seed)
+        ctx.save_for_backward(w_pre, w_post, y, *saved)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        w_pre, w_post, y, xd, b, s, mu, arg = ctx.saved_tensors
+        delta, relu, feat_p, feat_seed = ctx.cfg
+        da, dwp, dbp, dwo, dbo = _attn_backward(dy, y, relu, feat_p, feat_seed, lambda gy: pna_layer_bwd(
+            ctx.graph, gy, (xd, b, s, mu, arg), w_pre.detach(), w_post.detach(), delta, need_dx=ctx.needs_input_grad[1]))
+        return (None, da, dwp, dbp, dwo, dbo) + (None,) * 4
+
+
+def pna_conv(graph, x, w_pre, b_pre, w_post, b_post, delta, relu, feat_drop, training):
+    """PNAConv forward: the dropout only in training (one _draw_base draw), through PnaConvFn by _differentiable's rule."""
+    fp = float(feat_drop) if training else 0.0
+    fs = pna_conv_seed(None) if fp > 0 else 0
+    if _differentiable(training, x, w_pre, b_pre, w_post, b_post):
+        return PnaConvFn.apply(graph, x, w_pre, b_pre, w_post, b_post, float(delta), relu, fp, fs)
+    with torch.no_grad():
+        return pna_layer_fwd(graph, ops.as_feat(x), w_pre, b_pre, w_post, b_post, float(delta), relu, fp, fs)[0]

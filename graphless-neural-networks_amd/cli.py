@@ -85,7 +85,11 @@ def get_teacher_args(argv=None):
     # not a reference flag: the DAGNN teacher's number of propagation steps (conf key `dagnn_k`, read by Model; docs/DAGNN_SEMANTICS.md).
     # Unset = the conf's value or the paper's 10
     p.add_argument("--dagnn_k", type=int, default=None, help="Propagation steps K of the DAGNN teacher (default 10)")
-    # not reference flags: mini-batch training of the full-graph teachers (GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII) on random-walk induced
+    # not a reference flag: the PNA teacher's degree-scaler constant (conf key `pna_delta`, read by Model; docs/PNA_SEMANTICS.md).  Unset =
+    # the conf's value, else the mean of log(deg + 1) over the training graph (run_teacher computes and logs it)
+    p.add_argument("--pna_delta", type=float, default=None,
+                   help="delta of the PNA teacher's degree scalers (default: mean of log(in-degree + 1) over the training graph)")
+    # not reference flags: mini-batch training of the full-graph teachers (GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII, PNA) on random-walk induced
     # subgraphs (conf keys `subgraph_walk_length`, `subgraph_self_loop`, read by run_transductive / run_inductive;
     # docs/SUBGRAPH_SEMANTICS.md).  --batch_size is then the number of walk roots per batch; 0 = the full-graph step per epoch
     p.add_argument("--subgraph_walk_length", type=int, default=0,
@@ -96,7 +100,7 @@ def get_teacher_args(argv=None):
     if not 0 <= args.subgraph_walk_length <= 64:
         p.error(f"--subgraph_walk_length must be in [0, 64] (got {args.subgraph_walk_length})")
     if args.subgraph_walk_length > 0 and teacher_kind(args.teacher) in ("sage", "mlp"):
-        p.error(f"--subgraph_walk_length applies to the full-graph teachers (GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII) only: SAGE trains on "
+        p.error(f"--subgraph_walk_length applies to the full-graph teachers (GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII, PNA) only: SAGE trains on "
                 f"sampled blocks and MLP on feature batches (got --teacher {args.teacher})")
     if args.subgraph_self_loop != "keep" and args.subgraph_walk_length == 0:
         p.error(f"--subgraph_self_loop {args.subgraph_self_loop} needs --subgraph_walk_length > 0")
@@ -107,6 +111,10 @@ def get_teacher_args(argv=None):
         p.error(f"--dagnn_k applies to the DAGNN teacher only (got --teacher {args.teacher})")
     if args.dagnn_k is not None and args.dagnn_k < 0:
         p.error(f"--dagnn_k must be >= 0 (got {args.dagnn_k})")
+    if args.pna_delta is not None and teacher_kind(args.teacher) != "pna":
+        p.error(f"--pna_delta applies to the PNA teacher only (got --teacher {args.teacher})")
+    if args.pna_delta is not None and not args.pna_delta > 0:
+        p.error(f"--pna_delta must be positive (got {args.pna_delta})")
     if args.sage_mean_step != "autograd" and ("SAGE" not in args.teacher or args.sage_aggregator != "mean"):
         p.error(f"--sage_mean_step {args.sage_mean_step} applies to --teacher SAGE --sage_aggregator mean only "
                 f"(got --teacher {args.teacher} --sage_aggregator {args.sage_aggregator})")
@@ -180,13 +188,20 @@ def _setting_dir(args, root, leaf):
     raise ValueError(f"Unknown experiment setting! {args.exp_setting}")
 
 
-_SECTION_STAND_INS = {"dagnn": ("APPNP",), "gt": ("GATv2", "GAT")}      # teacher kind -> the sections that stand in for a missing one
+_SECTION_STAND_INS = {"dagnn": ("APPNP",), "gt": ("GATv2", "GAT"), "pna": ("GCN",)}      # teacher kind -> the sections that stand in for a missing one
+
+
+def pna_delta(g):
+    """PNA's delta of a training graph: the mean over its rows of log(in-degree + 1), in fp64 (Corso et al., eq. 5; docs/PNA_SEMANTICS.md)."""
+    deg = g.in_degrees().cpu().numpy().astype(np.float64)
+    return float(np.mean(np.log(deg + 1.0))) if deg.size else 0.0
 
 
 def _training_config(path, model_name, dataset):
-    """get_training_config.  train.conf.yaml has no DAGNN and no GraphTransformer sections.  A DAGNN teacher whose dataset names none takes
-    that dataset's APPNP section -- the trunk's hyper-parameters, what every GPRGNN section restates -- or the global section alone
-    (docs/DAGNN_SEMANTICS.md).  A GraphTransformer teacher takes the dataset's own section if a user added one, else its GATv2 section, else
+    """get_training_config.  train.conf.yaml has no DAGNN, no GraphTransformer and no PNA sections.  A DAGNN teacher whose dataset names none
+    takes that dataset's APPNP section -- the trunk's hyper-parameters, what every GPRGNN section restates -- or the global section alone
+    (docs/DAGNN_SEMANTICS.md); a PNA teacher likewise takes the dataset's GCN section (layers, width, dropout of a conv stack) or the
+    global section alone (docs/PNA_SEMANTICS.md).  A GraphTransformer teacher takes the dataset's own section if a user added one, else its GATv2 section, else
     its GAT section -- the conf contract is GAT's (docs/GT_SEMANTICS.md) -- and without any of them raises, naming the two keys a conf
     must carry."""
     kind = teacher_kind(model_name)
@@ -199,7 +214,7 @@ def _training_config(path, model_name, dataset):
             for name in stand_ins:
                 if sections.get(name):
                     return dict(cfg["global"], **sections[name], model_name=model_name)
-            if kind == "dagnn":
+            if kind in ("dagnn", "pna"):
                 return dict(cfg["global"], model_name=model_name)
             raise ValueError(f"{model_name}: {path} has no {model_name}, GATv2 or GAT section for dataset {dataset!r}, so nothing names "
                              "num_heads and attn_dropout_ratio, the two conf keys a GraphTransformer teacher is built from; add a "
@@ -277,6 +292,11 @@ def run_teacher(args):
     logger.info(f"output_dir: {output_dir}")
     g, feats, labels, (idx_train, idx_val, idx_test), conf = _load(args, logger, args.teacher)
     conf["device"] = device
+    if teacher_kind(args.teacher) == "pna" and conf.get("pna_delta") is None:
+        # a constant of the model, fixed ONCE from the graph the teacher trains on (inductive: the observed graph) and saved with it
+        g_train = g if args.exp_setting == "tran" else g.subgraph(graph_split(idx_train, idx_val, idx_test, args.split_rate, args.seed)[3])
+        conf["pna_delta"] = pna_delta(g_train)
+        logger.info(f"pna_delta: {conf['pna_delta']!r} (mean of log(in-degree + 1) over the {g_train.num_nodes()} nodes of the training graph)")
     logger.info(f"conf: {conf}")
     model = Model(conf)
     optimizer = optim.Adam(model.parameters(), lr=conf["learning_rate"], weight_decay=conf["weight_decay"])

@@ -392,12 +392,17 @@ UNSHARDED_GATED = {
 UNSHARDED_DOT_PRODUCT = {
     "GraphTransformer": "its edge softmax needs every in-edge of a row and the key and value rows of the remote sources",
 }
+UNSHARDED_ORDER_STATISTICS = {
+    "PNA": "the min, max and std of a row need every in-edge of it and each conv layer the previous layer's hidden rows of the remote sources",
+}
 
 
 def _refuse_unsharded(encoder, who):
-    """The encoders neither sharded teacher runs: the kinds of UNSHARDED_TEACHERS, UNSHARDED_GATED and UNSHARDED_DOT_PRODUCT, then a SAGE with another aggregator than 'gcn'."""
+    """The encoders neither sharded teacher runs: the kinds of UNSHARDED_TEACHERS, UNSHARDED_GATED, UNSHARDED_DOT_PRODUCT and
+    UNSHARDED_ORDER_STATISTICS, then a SAGE with another aggregator than 'gcn'."""
     kind = type(encoder).__name__
-    why = UNSHARDED_TEACHERS.get(kind) or UNSHARDED_GATED.get(kind) or UNSHARDED_DOT_PRODUCT.get(kind)
+    why = (UNSHARDED_TEACHERS.get(kind) or UNSHARDED_GATED.get(kind) or UNSHARDED_DOT_PRODUCT.get(kind)
+           or UNSHARDED_ORDER_STATISTICS.get(kind))
     if why:
         raise NotImplementedError(f"{who}: the {kind} teacher is not sharded -- {why}, an exchange the sharded "
                                   f"forward does not have (whole-graph {kind} only)")

@@ -17,25 +17,25 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .autograd import appnp_propagate, gcnii_stack, linear_fn, norm_act_drop
-from .nn import DAGNNConv, GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, SAGEConv, TransformerConv, _whole_graph_only
+from .nn import DAGNNConv, GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, PNAConv, SAGEConv, TransformerConv, _whole_graph_only
 
 
 _KINDS = (("MLP", "mlp"), ("SAGE", "sage"), ("GCNII", "gcnii"), ("GCN", "gcn"), ("APPNP", "appnp"), ("GATv2", "gatv2"), ("GAT", "gat"),
-          ("GPRGNN", "gpr"), ("DAGNN", "dagnn"), ("GraphTransformer", "gt"))
+          ("GPRGNN", "gpr"), ("DAGNN", "dagnn"), ("GraphTransformer", "gt"), ("PNA", "pna"))
 
 
 def teacher_kind(model_name):
     """The model family a `model_name` selects: the first of _KINDS whose key the name contains (the reference's substring dispatch,
     models.py:355,409).  The order is the rule and is written down here alone: "MLP" first ("MLP3w4" is an MLP), "GCNII" before "GCN"
-    and "GATv2" before "GAT", which they contain ("GPRGNN", "DAGNN" and "GraphTransformer" contain no other key and no other key contains them).  Every
-    caller switches on the kind it returns."""
+    and "GATv2" before "GAT", which they contain ("GPRGNN", "DAGNN", "GraphTransformer" and "PNA" contain no other key and no other key
+    contains them: "APPNP" holds "PNP", not "PNA").  Every caller switches on the kind it returns."""
     for key, kind in _KINDS:
         if key in model_name:
             return kind
     raise ValueError(f"Unknown model_name {model_name}")
 
 
-FULL_GRAPH_KINDS = ("gcn", "gcnii", "appnp", "gat", "gatv2", "gpr", "dagnn", "gt")    # the teachers whose training step takes the whole graph
+FULL_GRAPH_KINDS = ("gcn", "gcnii", "appnp", "gat", "gatv2", "gpr", "dagnn", "gt", "pna")    # the teachers whose training step takes the whole graph
 
 
 def _bn_eval_fold(bn, bias):
@@ -706,6 +706,62 @@ class GCNII(nn.Module):
         return hs, linear_fn(h, self.fc_out.weight, self.fc_out.bias)
 
 
+PNA_MAX_LAYERS = 64
+
+
+class PNA(nn.Module):
+    """PNA (Corso et al., NeurIPS 2020; docs/PNA_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it) in GCNII's shape, so that
+    wide input features never reach the gather: H_0 = relu(fc_in(drop(x))), num_layers PNAConv(hidden, hidden) layers with ReLU and a
+    dropout in front of each (the conv's feat_drop), logits = fc_out(drop(H_L)).  `delta` is a persistent fp64 buffer: a constant of the
+    model, saved with it and never recomputed on a subgraph or an observed graph.  forward returns ([H_1..H_L], logits)."""
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", delta=1.0):
+        super().__init__()
+        if hidden_dim > ops.PNA_MAX_WIDTH:
+            raise NotImplementedError(f"PNA: hidden_dim of at most {ops.PNA_MAX_WIDTH} (the aggregation kernel's row width; got {hidden_dim})")
+        if norm_type != "none":
+            raise NotImplementedError(f"PNA: norm_type 'none' only (BatchNorm / LayerNorm in the PNA stack are out of scope; got {norm_type!r})")
+        if not 1 <= num_layers <= PNA_MAX_LAYERS:
+            raise NotImplementedError(f"PNA: 1 to {PNA_MAX_LAYERS} conv layers (got num_layers {num_layers})")
+        if activation is not F.relu and getattr(activation, "__name__", "") != "relu":
+            raise NotImplementedError("PNA: only the ReLU activation (the scale launch's epilogue)")
+        if not float(delta) > 0:
+            raise ValueError(f"PNA: pna_delta must be positive (got {delta})")
+        self.num_layers, self.norm_type, self.activation, self.hidden_dim = num_layers, norm_type, activation, hidden_dim
+        self.dropout = nn.Dropout(dropout_ratio)
+        self.fc_in = nn.Linear(input_dim, hidden_dim)
+        self.layers = nn.ModuleList(PNAConv(hidden_dim, hidden_dim, delta, dropout_ratio, activation) for _ in range(num_layers))
+        self.fc_out = nn.Linear(hidden_dim, output_dim)
+        self.register_buffer("delta", torch.tensor(float(delta), dtype=torch.float64))
+        self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module._sync_delta())
+
+    def _sync_delta(self):
+        """A loaded state_dict brings its own delta: the layers read it as a host float."""
+        delta = float(self.delta)
+        for layer in self.layers:
+            layer.delta = delta
+
+    def forward(self, g, feats):
+        _need_hip(feats, "PNA.forward")
+        _whole_graph_only(g, feats, "PNA", "PNA runs on the whole graph")
+        hs = []
+        if not self.training:
+            with torch.no_grad():
+                h = ops.gemm(ops.as_feat(feats), self.fc_in.weight, ep_shift=self.fc_in.bias, relu=True)
+                for layer in self.layers:
+                    h = layer(g, h)
+                    hs.append(h)
+                return hs, ops.gemm(h, self.fc_out.weight, ep_shift=self.fc_out.bias)
+        p = self.dropout.p
+        x = norm_act_drop(feats, None, p, relu=False) if p > 0 else feats
+        h = norm_act_drop(linear_fn(x, self.fc_in.weight, self.fc_in.bias), None, 0.0)
+        for layer in self.layers:
+            h = layer(g, h)
+            hs.append(h)
+        h = norm_act_drop(h, None, p, relu=False) if p > 0 else h
+        return hs, linear_fn(h, self.fc_out.weight, self.fc_out.bias)
+
+
 class _AttnStack(nn.Module):
     """The layer stack GAT, GATv2 and GraphTransformer share (reference models.py:202-279): num_layers convs of class CONV, `num_heads` heads of
     hidden_dim // num_heads features on every hidden layer (ReLU inside the conv, outputs flattened to [N, hidden_dim] and kept in
@@ -819,6 +875,12 @@ class Model(nn.Module):
         elif kind == "dagnn":
             k = conf.get("dagnn_k")                                                  # (absent or None: the paper's 10 hops)
             enc = DAGNN(activation=F.relu, norm_type=conf["norm_type"], k=10 if k is None else k, **common)
+        elif kind == "pna":
+            if conf.get("pna_delta") is None:                                        # (a property of the training graph: no default)
+                raise ValueError(f"{conf['model_name']}: the conf does not name pna_delta; a PNA teacher is built only from confs that "
+                                 "carry it -- the mean of log(deg + 1) over the training graph, which train_teacher.py computes "
+                                 "(docs/PNA_SEMANTICS.md)")
+            enc = PNA(activation=F.relu, norm_type=conf["norm_type"], delta=conf["pna_delta"], **common)
         else:
             enc = GPRGNN(activation=F.relu, norm_type=conf["norm_type"], k=conf.get("gpr_k", 10), alpha=conf.get("gpr_alpha", 0.1),
                          init=conf.get("gpr_init", "PPR"), **common)
@@ -859,6 +921,9 @@ class Model(nn.Module):
             if kind == "dagnn":
                 raise NotImplementedError(f"DAGNN.inference(dtype={dtype}): bf16 activation storage is not implemented for the DAGNN teacher "
                                           "(csrc/dagnn.hip gathers and stores fp32 rows; docs/DAGNN_SEMANTICS.md, Out of scope)")
+            if kind == "pna":
+                raise NotImplementedError(f"PNA.inference(dtype={dtype}): bf16 activation storage is not implemented for the PNA teacher "
+                                          "(csrc/pna.hip gathers and stores fp32 rows; docs/PNA_SEMANTICS.md, What is refused)")
             if kind != "sage":
                 raise NotImplementedError(f"{self.model_name}.inference(dtype={dtype}): bf16 activation storage is implemented for the SAGE "
                                           "teacher's whole-graph forward only")

@@ -8,6 +8,7 @@
   GPRConv(k, alpha, init)(g, h)                  <- GPR-GNN's learned K-step propagation (no dgl counterpart; docs/GPR_SEMANTICS.md)
   DAGNNConv(k, in_feats)(g, h)                   <- DAGNN's node-gated K-step propagation (no dgl counterpart; docs/DAGNN_SEMANTICS.md)
   GCNIIConv(hidden, layer, alpha, lamda)(g, h, h0) <- one GCNII conv layer (dgl 0.6.1 has none; docs/GCNII_SEMANTICS.md)
+  PNAConv(in, out, delta, ...)(g, h)             <- PyG's PNAConv, one tower, mean/min/max/std x three scalers (docs/PNA_SEMANTICS.md)
 
 Parameter names follow dgl 0.6.1 so that a reference `model.pth` loads: SAGEConv.fc_neigh.{weight,bias}
 (weight [out,in], xavier_uniform gain=relu; no fc_self for "gcn"), GraphConv.{weight [in,out] xavier_uniform,
@@ -20,7 +21,7 @@ import torch.nn as nn
 
 from . import ops
 from .autograd import (GraphConvFn, SpmmFn, _differentiable, dagnn_propagate, gat_conv, gatv2_conv, gcnii_stack, gt_conv, gpr_propagate, graphconv_fwd,
-                       linear_fn)
+                       linear_fn, pna_conv)
 
 
 FUSED_SAGE_MAX_IN = 256   # aggregate-first layers with d_in, d_out <= 256 take the single-launch K1F kernel.  Interleaved
@@ -457,3 +458,38 @@ class GCNIIConv(nn.Module):
         in_norm, out_norm = graph.degree_norms()
         return ops.gcnii_layer(graph.indptr, graph.indices, graph.num_edges(), feat, h0, self.weight, self.alpha, self.beta, in_norm,
                                x_norm=out_norm)
+
+
+class PNAConv(nn.Module):
+    """Principal Neighbourhood Aggregation (Corso et al., NeurIPS 2020; docs/PNA_SEMANTICS.md): PyG's PNAConv with towers=1,
+    pre_layers=1, post_layers=1, divide_input=False, no edge features, aggregators [mean, min, max, std], scalers [identity,
+    amplification, attenuation] and without its trailing `lin` (two consecutive Linear maps are one).  Parameters, in registration order,
+    torch's default Linear initialisation: pre = Linear(2 in, in) over [x_i || x_j] (destination first), post = Linear(13 in, out) over
+    [x || T].  delta > 0 is a constant of the model (the mean of log(deg + 1) over the training graph), not a parameter.  feat_drop: the
+    dropout of the layer's input, which both uses of it see; activation: None or ReLU (the scale launch's epilogue).  A row without
+    in-edges is legal: its aggregate is [0 | 0 | 0 | sqrt(1e-5)]."""
+
+    def __init__(self, in_feats, out_feats, delta, feat_drop=0.0, activation=None):
+        super().__init__()
+        if int(in_feats) > ops.PNA_MAX_WIDTH:
+            raise NotImplementedError(f"PNAConv: PNA rows of at most {ops.PNA_MAX_WIDTH} columns (one float4 lane row; got in_feats {in_feats})")
+        if int(in_feats) < 1 or int(out_feats) < 1:
+            raise ValueError(f"PNAConv: in_feats and out_feats must be >= 1 (got {in_feats}, {out_feats})")
+        if not float(delta) > 0:
+            raise ValueError(f"PNAConv: PNA's delta must be positive (got {delta})")
+        if activation is not None and activation is not torch.nn.functional.relu and getattr(activation, "__name__", "") != "relu":
+            raise NotImplementedError("PNAConv: the activation must be None or ReLU (the scale launch's epilogue)")
+        self.in_feats, self.out_feats, self.delta = int(in_feats), int(out_feats), float(delta)
+        self.activation = activation
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.pre = nn.Linear(2 * self.in_feats, self.in_feats)
+        self.post = nn.Linear(13 * self.in_feats, self.out_feats)
+
+    def reset_parameters(self):
+        self.pre.reset_parameters()
+        self.post.reset_parameters()
+
+    def forward(self, graph, feat):
+        _whole_graph_only(graph, feat, "PNAConv", "the PNA teacher runs on the whole graph")
+        return pna_conv(graph, feat, self.pre.weight, self.pre.bias, self.post.weight, self.post.bias, self.delta,
+                        self.activation is not None, self.feat_drop.p, self.training)

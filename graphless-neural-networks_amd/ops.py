@@ -1625,6 +1625,131 @@ def dagnn_fold(hs, q, dw=None, db=None):
     return dw, db
 
 
+# --------------------------------------------------------------------------------------------- PNA aggregation (docs/PNA_SEMANTICS.md)
+PNA_MAX_WIDTH = 256             # GLNN_PNA_MAX_WIDTH of include/glnn_hip.h: one float4 lane row
+PNA_AGGREGATORS = ("mean", "min", "max", "std")                     # the order of the four parts of S
+PNA_SCALERS = ("identity", "amplification", "attenuation")          # the order of the three blocks of T
+PNA_STD_EPS = 1e-5
+
+
+def _pna_width(name, d):
+    if d > PNA_MAX_WIDTH:
+        raise NotImplementedError(f"{name}: PNA rows of at most {PNA_MAX_WIDTH} columns (one float4 lane row; got {d})")
+
+
+def _pna_parts(name, what, t, n, parts, d, dtype=torch.float32):
+    """t is a contiguous [n, parts * round4(d)] buffer of `dtype` with 16-byte aligned rows: the part layout of S, dS and arg."""
+    if t.dtype != dtype or t.dim() != 2 or tuple(t.shape) != (n, parts * round4(d)) or not t.is_contiguous() or t.data_ptr() % 16:
+        raise ValueError(f"{name}: {what} must be a contiguous {dtype} [n, {parts} * round4(d)] = [{n}, {parts * round4(d)}] buffer")
+    return t
+
+
+def pna_agg_fwd(indptr, indices, nnz, b, n_dst, a=None, want_arg=False, out=None):
+    """glnn_pna_agg_fwd_f32: (S, mu, arg).  S [n_dst, 4 * round4(d)] = [a + mean | a + min | a + max | std] of the rows b[u] over the
+    in-edges u -> v, every neighbour row gathered once; a (optional, [n_dst, d]) the destination's own term; a row without in-edges gets
+    [0 | 0 | 0 | sqrt(1e-5)].  want_arg (training): mu [n_dst, d] the plain mean and arg int32 [n_dst, 2 * round4(d)] = [argmin | argmax],
+    the CSR position of the first edge that attains the value (-1: no in-edges / padding); else (S, None, None)."""
+    _need_cuda(indptr, indices, b, a, out)
+    b = as_feat(b)
+    n_src, d = b.shape
+    _pna_width("pna_agg_fwd", d)
+    _csr_check("pna_agg_fwd", indptr, indices, 0)
+    if indptr.numel() < n_dst + 1:
+        raise ValueError(f"pna_agg_fwd: indptr must hold n_dst + 1 = {n_dst + 1} entries")
+    if a is not None:
+        a = as_feat(a)
+        if tuple(a.shape) != (n_dst, d):
+            raise ValueError(f"pna_agg_fwd: a must be [n_dst, d] = [{n_dst}, {d}] (got {tuple(a.shape)})")
+    dp = round4(d)
+    s = torch.empty((n_dst, 4 * dp), dtype=torch.float32, device=b.device) if out is None else _pna_parts("pna_agg_fwd", "out", out, n_dst, 4, d)
+    mu = arg = None
+    if want_arg:
+        mu = feat_empty(n_dst, d, b.device)
+        arg = torch.empty((n_dst, 2 * dp), dtype=torch.int32, device=b.device)
+    with _Timed("pna_agg_fwd", d=d, n_dst=n_dst):
+        rc = _lib.lib().glnn_pna_agg_fwd_f32(_p(indptr), _p(indices), n_dst, n_src, int(nnz), _p(b), _ld(b), d, _p(a), 0 if a is None else _ld(a),
+                                             _p(s), 4 * dp, _p(mu), 0 if mu is None else _ld(mu), _p(arg), 2 * dp, _stream())
+    _lib.check(rc, "glnn_pna_agg_fwd_f32")
+    return s, mu, arg
+
+
+def pna_agg_bwd(graph, ds, b, mu, sigma, arg, out=None):
+    """glnn_pna_agg_bwd_f32 over `graph` (CSRGraph: its row pointers for the degrees, its cached transpose with edge ids for the pass):
+    db [n_src, d] from ds [n_dst, 4 * round4(d)] = [g_mean | g_min | g_max | g_std], the forward's b, mu, arg and sigma -- a [n_dst, d]
+    matrix or the forward's whole S, whose last part it is.  Every row of db is written; a source no edge references gets zeros."""
+    _need_cuda(ds, b, mu, sigma, arg, out)
+    b = as_feat(b)
+    n_src, d = b.shape
+    n_dst = graph.num_dst_nodes()
+    _pna_width("pna_agg_bwd", d)
+    dp = round4(d)
+    if n_src != graph.num_src_nodes():
+        raise ValueError(f"pna_agg_bwd: b must hold the graph's {graph.num_src_nodes()} source rows")
+    _pna_parts("pna_agg_bwd", "ds", ds, n_dst, 4, d)
+    _pna_parts("pna_agg_bwd", "arg", arg, n_dst, 2, d, torch.int32)
+    if tuple(sigma.shape) == (n_dst, 4 * dp):
+        sigma = _pna_parts("pna_agg_bwd", "sigma", sigma, n_dst, 4, d)[:, 3 * dp:3 * dp + d]
+    mu, sigma = as_feat(mu), as_feat(sigma)
+    for what, t in (("mu", mu), ("sigma", sigma)):
+        if tuple(t.shape) != (n_dst, d):
+            raise ValueError(f"pna_agg_bwd: {what} must be [n_dst, d] = [{n_dst}, {d}] (got {tuple(t.shape)})")
+    if out is None:
+        out = feat_empty(n_src, d, b.device)
+    _rows_like("pna_agg_bwd", "out", out, n_src, d)
+    if _ld(out) % 4 or out.data_ptr() % 16:
+        raise ValueError("pna_agg_bwd: out must have float4-addressable rows (ops.feat_empty)")
+    t, t_eids = graph.transposed_eids()
+    with _Timed("pna_agg_bwd", d=d, n_dst=n_src):
+        rc = _lib.lib().glnn_pna_agg_bwd_f32(_p(graph.indptr), n_dst, _p(t.indptr), _p(t.indices), _p(t_eids), n_src, graph.num_edges(),
+                                             _p(ds), 4 * dp, _p(b), _ld(b), d, _p(mu), _ld(mu), _p(sigma), _ld(sigma), _p(arg), 2 * dp,
+                                             _p(out), _ld(out), _stream())
+    _lib.check(rc, "glnn_pna_agg_bwd_f32")
+    return out
+
+
+def _pna_delta(name, delta):
+    delta = float(delta)
+    if not delta > 0:
+        raise ValueError(f"{name}: PNA's delta must be positive (got {delta})")
+    return delta
+
+
+def pna_scale_fwd(indptr, z, out, delta, relu=False):
+    """glnn_pna_scale_fwd_f32, in place on out [n, fo]: out = act(out + z_0 + s_amp z_1 + s_att z_2) with z [n, 3 * round4(fo)] the three
+    scaler blocks of the stacked product and s_amp = log(max(deg, 1) + 1) / delta = 1 / s_att per row."""
+    _need_cuda(indptr, z, out)
+    _mat(out, "pna_scale_fwd out")
+    n, fo = out.shape
+    if z.dtype != torch.float32 or tuple(z.shape) != (n, 3 * round4(fo)) or z.stride(1) != 1 or _ld(out) < round4(fo):
+        raise ValueError(f"pna_scale_fwd: z must be float32 [n, 3 * round4(fo)] = [{n}, {3 * round4(fo)}] and out an ops.feat_empty buffer")
+    rc = _lib.lib().glnn_pna_scale_fwd_f32(_p(indptr), n, fo, _pna_delta("pna_scale_fwd", delta), _p(z), _ld(z), _p(out), _ld(out),
+                                           1 if relu else 0, _stream())
+    _lib.check(rc, "glnn_pna_scale_fwd_f32")
+    return out
+
+
+def pna_scale_bwd(indptr, g, delta):
+    """glnn_pna_scale_bwd_f32: dz [n, 3 * round4(fo)] = [g | s_amp g | s_att g] from g [n, fo] = dL/d out behind the activation mask."""
+    _need_cuda(indptr, g)
+    g = _mat(g, "pna_scale_bwd g")
+    n, fo = g.shape
+    dz = torch.empty((n, 3 * round4(fo)), dtype=torch.float32, device=g.device)
+    rc = _lib.lib().glnn_pna_scale_bwd_f32(_p(indptr), n, fo, _pna_delta("pna_scale_bwd", delta), _p(g), _ld(g), _p(dz), 3 * round4(fo), _stream())
+    _lib.check(rc, "glnn_pna_scale_bwd_f32")
+    return dz
+
+
+def pna_da(indptr, ds, d):
+    """glnn_pna_da_f32: da [n, d] = g_mean + g_min + g_max of ds [n, 4 * round4(d)] for the rows with in-edges, zeros for the others."""
+    _need_cuda(indptr, ds)
+    n = ds.shape[0]
+    _pna_parts("pna_da", "ds", ds, n, 4, d)
+    da = feat_empty(n, d, ds.device)
+    rc = _lib.lib().glnn_pna_da_f32(_p(indptr), n, d, _p(ds), 4 * round4(d), _p(da), _ld(da), _stream())
+    _lib.check(rc, "glnn_pna_da_f32")
+    return da
+
+
 # --------------------------------------------------------------------------------------------- GCNII conv layer
 GCNII_MAX_HIDDEN = 256         # kMaxD of csrc/gcnii.hip: the kernel's tile width
 

@@ -38,7 +38,7 @@ import torch.nn.functional as F
 from . import _lib, ops
 from .models import teacher_kind
 from .autograd import (appnp_bwd, appnp_fwd, dagnn_bwd, dagnn_fwd, gat_layer_bwd, gat_layer_fwd, gatv2_layer_bwd, gatv2_layer_fwd, gt_layer_bwd, gt_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd,
-                       graphconv_fwd)
+                       graphconv_fwd, pna_layer_bwd, pna_layer_fwd)
 from .student import _mix32
 
 
@@ -79,7 +79,7 @@ _ATTN_RELU = {"gatv2": "GATv2 with ReLU hidden layers and a linear last layer (d
 
 
 def check_supported(model, criterion, optimizer):
-    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN or GCNII teacher."""
+    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII or PNA teacher."""
     enc = model.encoder
     name = model.model_name
     try:
@@ -87,11 +87,14 @@ def check_supported(model, criterion, optimizer):
     except ValueError:           # (a name no family claims: refused like the MLP)
         kind = "mlp"
     if kind == "mlp":
-        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN or GCNII teachers only (got {name})")
+        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII or PNA teachers only (got {name})")
     _check_criterion_and_optimizer("TeacherEngine", criterion, optimizer)
     if kind == "gcnii":          # (the encoder's constructor refused everything else)
         if enc.norm_type != "none" or not _is_relu(enc.activation):
             raise NotImplementedError("TeacherEngine: GCNII with norm_type none and ReLU (docs/GCNII_SEMANTICS.md)")
+    elif kind == "pna":          # (likewise)
+        if enc.norm_type != "none" or not _is_relu(enc.activation) or any(not _is_relu(lay.activation) for lay in enc.layers):
+            raise NotImplementedError("TeacherEngine: PNA with norm_type none and ReLU (docs/PNA_SEMANTICS.md)")
     elif kind in _NORM_RELU:
         if kind == "sage" and getattr(enc, "aggregator_type", "gcn") != "gcn":
             raise NotImplementedError(f"TeacherEngine: the one-call SAGE step implements the 'gcn' aggregator only; a SAGE "
@@ -747,6 +750,50 @@ class TeacherEngine:
         da = ops.gemm(dlog, fc_out.weight, w_is_kn=True)                          # dlog W_out: d/d drop_{L+1}(H_L)
         dh0 = gcnii_bwd(g, da, hs, ss, weights, enc.alpha, betas, [self.grad(w) for w in weights], p, seeds)
         dz0, _, _ = ops.bn_relu_bwd(dh0, h0, dz=dh0, dz_col_sum=self.grad(fc_in.bias))     # h0 = relu(z0): h0 > 0 <=> z0 > 0
+        ops.gemm_tn(dz0, xd, out=self.grad(fc_in.weight))
+        ops.note_param_write()
+
+    # ------------------------------------------------------------------------------------------ full-graph PNA
+    def _pna_seed(self, site, step=None):
+        """The seed of dropout site `site` (0: the input, l = 1..L: in front of conv layer l -- its feat_drop --, L + 1: in front of fc_out)
+        in step `step` (default: the current one): a stream of its own, apart from every other teacher's.  site < 131."""
+        return _stream_seed(self, 0x504E4132, 0x67, site, self.p > 0, step)
+
+    @torch.no_grad()
+    def step_pna(self, g, feats, labels, idx_train, lamb=1.0):
+        """The full-graph `train` step over PNA (docs/PNA_SEMANTICS.md): fc_in (+ ReLU) behind the input dropout; per layer the dropped
+        copy of its input, the two halves of `pre`, glnn_pna_agg_fwd_f32 (S, and the means and arguments the backward reads), the x and
+        stacked-S products of `post` and glnn_pna_scale_fwd_f32 (+ ReLU); fc_out, NLL over idx_train, fc_out's backward; per layer
+        glnn_pna_scale_bwd_f32, the weight gradients of `post`, dS, glnn_pna_da_f32, glnn_pna_agg_bwd_f32 over the transposed graph, the
+        weight gradients of `pre` and the input gradient; H_0's ReLU backward, fc_in's backward, and the ONE Adam launch.  Rows without
+        in-edges are legal."""
+        self._run_full_graph(self._step_pna_body, g, feats, labels, idx_train, lamb)
+
+    def _step_pna_body(self, g, feats, labels, idx_train, lamb):
+        enc, L, p = self.enc, self.L, self.p
+        fc_in, fc_out = enc.fc_in, enc.fc_out
+        seeds = [self._pna_seed(s) for s in range(L + 2)]
+        x = ops.as_feat(feats)
+        xd = ops.act_fwd(x, drop_p=p, drop_seed=seeds[0], relu=False) if p > 0 else x       # (signed features: materialised once, read twice)
+        acts, saved = [ops.gemm(xd, fc_in.weight, ep_shift=fc_in.bias, relu=True)], []
+        for l, lay in enumerate(enc.layers):
+            y, sv = pna_layer_fwd(g, acts[l], lay.pre.weight, lay.pre.bias, lay.post.weight, lay.post.bias, lay.delta, True, p, seeds[l + 1],
+                                  keep=True)
+            acts.append(y)
+            saved.append(sv)
+        a = ops.act_fwd(acts[L], drop_p=p, drop_seed=seeds[L + 1], relu=False) if p > 0 else acts[L]
+        logits = ops.gemm(a, fc_out.weight, ep_shift=fc_out.bias)
+        dlog = self._loss_grad(logits, labels, idx_train, lamb, g.num_dst_nodes())
+        ops.gemm_tn(dlog, a, out=self.grad(fc_out.weight), col_sum_a=self.grad(fc_out.bias))
+        da = ops.gemm(dlog, fc_out.weight, w_is_kn=True)                                 # dlog W_out: d/d drop_{L+1}(H_L)
+        for l in range(L - 1, -1, -1):
+            lay = enc.layers[l]
+            # the dropout mask of site l + 2 (in front of the next conv, or of fc_out) and the ReLU mask of H_{l+1} (stored post-ReLU)
+            gy = ops.bn_relu_bwd(da, acts[l + 1], dz=da, drop_p=p, drop_seed=seeds[l + 2])[0]
+            da = pna_layer_bwd(g, gy, saved[l], lay.pre.weight, lay.post.weight, lay.delta, need_dx=True, dw_pre=self.grad(lay.pre.weight),
+                               db_pre=self.grad(lay.pre.bias), dw_post=self.grad(lay.post.weight), db_post=self.grad(lay.post.bias))[0]
+        # layer 1's feat_drop mask and H_0 = relu(z_0): h0 > 0 <=> z0 > 0
+        dz0, _, _ = ops.bn_relu_bwd(da, acts[0], dz=da, drop_p=p, drop_seed=seeds[1], dz_col_sum=self.grad(fc_in.bias))
         ops.gemm_tn(dz0, xd, out=self.grad(fc_in.weight))
         ops.note_param_write()
 

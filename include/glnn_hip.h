@@ -1061,6 +1061,45 @@ GLNN_API int glnn_gt_attn_bwd_f32(const int64_t* indptr, const int32_t* indices,
                                   int64_t lddv, float* workspace, int64_t workspace_floats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * PNA, Principal Neighbourhood Aggregation (Corso, Cavalleri, Beaini, Lio, Velickovic, NeurIPS 2020; csrc/pna.hip;
+ * docs/PNA_SEMANTICS.md states the arithmetic): the mean, min, max and std of the rows b[u] over the in-edges u -> v of a CSR by
+ * destination, from ONE gather of every neighbour row.  Rows of d <= GLNN_PNA_MAX_WIDTH floats (GLNN_ERR_UNSUPPORTED otherwise, nothing
+ * launched), nnz and the node counts below 2^31; every row pointer 16-byte aligned with a leading dimension % 4 == 0.  dp = round4(d).
+ * Deterministic: no float atomics, a row's result does not depend on the other rows of the launch.
+ *
+ * glnn_pna_agg_fwd_f32 -- s[v] = [a[v] + mean | a[v] + min | a[v] + max | std] in four parts of dp floats (lds >= 4 dp), padding
+ *   columns [d, dp) of every part zero; a optional (NULL: no own term); std = sqrt(max(E b^2 - mean^2, 0) + 1e-5) from fp64 sums.  A row
+ *   without in-edges gets [0 | 0 | 0 | sqrt(1e-5)] and no a term.  mu and arg (both or neither: training) take the plain mean [n_dst, dp]
+ *   and arg[v] = [argmin | argmax] in two parts of dp int32 (ldarg >= 2 dp): the CSR position of the FIRST edge that attains the value,
+ *   -1 for a row without in-edges and in the padding.  A NaN never wins a comparison.  n_dst == 0 is a no-op.
+ *
+ * glnn_pna_agg_bwd_f32 -- the source pass over the transposed CSR with edge ids (glnn_csr_transpose_eids of the forward's CSR; indptr =
+ *   the FORWARD's row pointers, read for deg(v)).  With ds[v] = [g_mean | g_min | g_max | g_std] (ldds >= 4 dp), sigma = the std part of
+ *   the forward's s (its own leading dimension):
+ *     db[u] = sum_{e = (u -> v)} g_mean[v] / deg(v) + g_std[v] (b[u] - mu[v]) / (deg(v) sigma[v]) + [argmax[v] == e] g_max[v]
+ *                                + [argmin[v] == e] g_min[v]
+ *   in transposed-CSR order, one wave per source row.  Every row of db [n_src, dp] is written; a row no edge references gets zeros.
+ *
+ * The row-local pieces (fop = round4(fo)); s_amp(v) = log(max(deg(v), 1) + 1) / delta, s_att(v) = 1 / s_amp(v), delta > 0:
+ *   glnn_pna_scale_fwd_f32   out[v] = act(out[v] + z_0[v] + s_amp z_1[v] + s_att z_2[v]), z = [z_0 | z_1 | z_2] in parts of fop floats
+ *                            (ldz >= 3 fop), in place on out (ldo >= fop; padding columns zero); relu != 0: act = ReLU
+ *   glnn_pna_scale_bwd_f32   dz[v] = [g[v] | s_amp g[v] | s_att g[v]]  (lddz >= 3 fop, padding zero)
+ *   glnn_pna_da_f32          da[v] = g_mean[v] + g_min[v] + g_max[v] for deg(v) > 0, else 0  (ldda >= dp, padding zero) */
+#define GLNN_PNA_MAX_WIDTH 256
+GLNN_API int glnn_pna_agg_fwd_f32(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src, int64_t nnz, const float* b,
+                                  int64_t ldb, int d, const float* a, int64_t lda, float* s, int64_t lds, float* mu, int64_t ldmu,
+                                  int32_t* arg, int64_t ldarg, void* stream);
+GLNN_API int glnn_pna_agg_bwd_f32(const int64_t* indptr, int64_t n_dst, const int64_t* t_indptr, const int32_t* t_indices,
+                                  const int32_t* t_eids, int64_t n_src, int64_t nnz, const float* ds, int64_t ldds, const float* b,
+                                  int64_t ldb, int d, const float* mu, int64_t ldmu, const float* sigma, int64_t ldsig, const int32_t* arg,
+                                  int64_t ldarg, float* db, int64_t lddb, void* stream);
+GLNN_API int glnn_pna_scale_fwd_f32(const int64_t* indptr, int64_t n, int fo, float delta, const float* z, int64_t ldz, float* out,
+                                    int64_t ldo, int relu, void* stream);
+GLNN_API int glnn_pna_scale_bwd_f32(const int64_t* indptr, int64_t n, int fo, float delta, const float* g, int64_t ldg, float* dz,
+                                    int64_t lddz, void* stream);
+GLNN_API int glnn_pna_da_f32(const int64_t* indptr, int64_t n, int d, const float* ds, int64_t ldds, float* da, int64_t ldda, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * GraphSAGE "mean" aggregator (csrc/sage_mean.hip; docs/SAGE_MEAN_SEMANTICS.md states the arithmetic):
  *   h_neigh[v] = (1 / max(deg(v), 1)) * sum_{u->v} x[u]        out[v] = fc_neigh(h_neigh[v]) + fc_self(x_self[v])
  * Both entries: CSR over destination rows as glnn_spmm_csr_f32, n_src < 2^31, float4-addressable rows (leading dimensions multiples of 4
