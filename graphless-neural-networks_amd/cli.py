@@ -14,7 +14,8 @@ import yaml
 from torch import optim
 
 from .dataloader import load_data, load_out_t
-from .models import Model, teacher_kind
+from .kinds import BY_KIND, teacher_kind, teacher_names
+from .models import Model
 from .train_and_eval import distill_run_inductive, distill_run_transductive, run_inductive, run_transductive
 from .utils import (check_readable, check_writable, compute_min_cut_loss, feature_prop, get_evaluator, get_logger,
                     get_training_config, graph_split, set_seed)
@@ -89,9 +90,8 @@ def get_teacher_args(argv=None):
     # the conf's value, else the mean of log(deg + 1) over the training graph (run_teacher computes and logs it)
     p.add_argument("--pna_delta", type=float, default=None,
                    help="delta of the PNA teacher's degree scalers (default: mean of log(in-degree + 1) over the training graph)")
-    # not reference flags: mini-batch training of the full-graph teachers (GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII, PNA) on random-walk induced
-    # subgraphs (conf keys `subgraph_walk_length`, `subgraph_self_loop`, read by run_transductive / run_inductive;
-    # docs/SUBGRAPH_SEMANTICS.md).  --batch_size is then the number of walk roots per batch; 0 = the full-graph step per epoch
+    # not reference flags: mini-batch training of the full-graph teachers (kinds.FULL_GRAPH_KINDS) on random-walk induced subgraphs (conf keys
+    # `subgraph_walk_length`, `subgraph_self_loop`, read by run_transductive / run_inductive; docs/SUBGRAPH_SEMANTICS.md).  --batch_size is then the number of walk roots per batch; 0 = the full-graph step per epoch
     p.add_argument("--subgraph_walk_length", type=int, default=0,
                    help="Train a full-graph teacher on subgraphs induced by random walks of this many steps from --batch_size roots (0: off)")
     p.add_argument("--subgraph_self_loop", type=str, default="keep", choices=["keep", "add"],
@@ -100,19 +100,15 @@ def get_teacher_args(argv=None):
     if not 0 <= args.subgraph_walk_length <= 64:
         p.error(f"--subgraph_walk_length must be in [0, 64] (got {args.subgraph_walk_length})")
     if args.subgraph_walk_length > 0 and teacher_kind(args.teacher) in ("sage", "mlp"):
-        p.error(f"--subgraph_walk_length applies to the full-graph teachers (GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII, PNA) only: SAGE trains on "
+        p.error(f"--subgraph_walk_length applies to the full-graph teachers ({teacher_names(',')}) only: SAGE trains on "
                 f"sampled blocks and MLP on feature batches (got --teacher {args.teacher})")
     if args.subgraph_self_loop != "keep" and args.subgraph_walk_length == 0:
         p.error(f"--subgraph_self_loop {args.subgraph_self_loop} needs --subgraph_walk_length > 0")
-    for flag in ("gcnii_alpha", "gcnii_lamda"):
-        if getattr(args, flag) is not None and "GCNII" not in args.teacher:
-            p.error(f"--{flag} applies to the GCNII teacher only (got --teacher {args.teacher})")
-    if args.dagnn_k is not None and "DAGNN" not in args.teacher:
-        p.error(f"--dagnn_k applies to the DAGNN teacher only (got --teacher {args.teacher})")
+    for flag, kind in (("gcnii_alpha", "gcnii"), ("gcnii_lamda", "gcnii"), ("dagnn_k", "dagnn"), ("pna_delta", "pna")):
+        if getattr(args, flag) is not None and teacher_kind(args.teacher) != kind:
+            p.error(f"--{flag} applies to the {BY_KIND[kind].key} teacher only (got --teacher {args.teacher})")
     if args.dagnn_k is not None and args.dagnn_k < 0:
         p.error(f"--dagnn_k must be >= 0 (got {args.dagnn_k})")
-    if args.pna_delta is not None and teacher_kind(args.teacher) != "pna":
-        p.error(f"--pna_delta applies to the PNA teacher only (got --teacher {args.teacher})")
     if args.pna_delta is not None and not args.pna_delta > 0:
         p.error(f"--pna_delta must be positive (got {args.pna_delta})")
     if args.sage_mean_step != "autograd" and ("SAGE" not in args.teacher or args.sage_aggregator != "mean"):
@@ -188,9 +184,6 @@ def _setting_dir(args, root, leaf):
     raise ValueError(f"Unknown experiment setting! {args.exp_setting}")
 
 
-_SECTION_STAND_INS = {"dagnn": ("APPNP",), "gt": ("GATv2", "GAT"), "pna": ("GCN",)}      # teacher kind -> the sections that stand in for a missing one
-
-
 def pna_delta(g):
     """PNA's delta of a training graph: the mean over its rows of log(in-degree + 1), in fp64 (Corso et al., eq. 5; docs/PNA_SEMANTICS.md)."""
     deg = g.in_degrees().cpu().numpy().astype(np.float64)
@@ -198,26 +191,23 @@ def pna_delta(g):
 
 
 def _training_config(path, model_name, dataset):
-    """get_training_config.  train.conf.yaml has no DAGNN, no GraphTransformer and no PNA sections.  A DAGNN teacher whose dataset names none
-    takes that dataset's APPNP section -- the trunk's hyper-parameters, what every GPRGNN section restates -- or the global section alone
-    (docs/DAGNN_SEMANTICS.md); a PNA teacher likewise takes the dataset's GCN section (layers, width, dropout of a conv stack) or the
-    global section alone (docs/PNA_SEMANTICS.md).  A GraphTransformer teacher takes the dataset's own section if a user added one, else its GATv2 section, else
-    its GAT section -- the conf contract is GAT's (docs/GT_SEMANTICS.md) -- and without any of them raises, naming the two keys a conf
-    must carry."""
-    kind = teacher_kind(model_name)
-    stand_ins = _SECTION_STAND_INS.get(kind)
-    if stand_ins:
+    """get_training_config.  train.conf.yaml has no section for some families (DAGNN, GraphTransformer, PNA: the rows of kinds.KINDS with
+    `stand_ins`).  Such a teacher takes the dataset's own section if a user added one, else the first stand-in section the dataset has
+    (DAGNN: APPNP's, the trunk's hyper-parameters; PNA: GCN's, those of a conv stack; GraphTransformer: GATv2's, then GAT's, whose conf
+    contract it shares), else the global section alone where the row allows it, else raises, naming the two keys a conf must carry."""
+    row = BY_KIND[teacher_kind(model_name)]
+    if row.stand_ins:
         with open(path) as fh:
             cfg = yaml.safe_load(fh)
         sections = cfg.get(dataset) or {}
         if model_name not in sections:
-            for name in stand_ins:
+            for name in row.stand_ins:
                 if sections.get(name):
                     return dict(cfg["global"], **sections[name], model_name=model_name)
-            if kind in ("dagnn", "pna"):
+            if row.global_alone:
                 return dict(cfg["global"], model_name=model_name)
-            raise ValueError(f"{model_name}: {path} has no {model_name}, GATv2 or GAT section for dataset {dataset!r}, so nothing names "
-                             "num_heads and attn_dropout_ratio, the two conf keys a GraphTransformer teacher is built from; add a "
+            raise ValueError(f"{model_name}: {path} has no {model_name}, {' or '.join(row.stand_ins)} section for dataset {dataset!r}, so "
+                             f"nothing names num_heads and attn_dropout_ratio, the two conf keys a {row.key} teacher is built from; add a "
                              f"{model_name} section that carries both")
     return get_training_config(path, model_name, dataset)
 

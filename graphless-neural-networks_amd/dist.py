@@ -20,6 +20,8 @@ pass a CPU stand-in with the same signatures so the sharding / exchange logic is
 import torch
 import torch.distributed as dist
 
+from .kinds import BY_KEY
+
 
 class RowShards:
     """Contiguous destination-row ranges, one per rank.  `bounds` (world+1 row offsets) defaults to equal row counts;
@@ -378,31 +380,11 @@ def _fp32_only(dtype, who):
                                   "SAGE.inference(..., dtype=torch.bfloat16) on one device)")
 
 
-# teachers whose forward needs remote rows through an exchange the sharded forward does not have: class name -> what it needs
-UNSHARDED_TEACHERS = {
-    "GAT": "its edge softmax needs every in-edge of a row and the per-head scores of the remote sources",
-    "GATv2": "its edge softmax needs every in-edge of a row and the whole projected rows of the remote sources",
-    "GPRGNN": "each of its K propagation steps needs the previous step's rows of the remote sources",
-    "GCNII": "each of its conv layers needs the previous layer's hidden rows of the remote sources",
-}
-# refused the same way; a table of its own because tests/test_dist_cpu.py pins the key set of the one above
-UNSHARDED_GATED = {
-    "DAGNN": "each of its K propagation steps needs the previous step's rows of the remote sources, and its gate the whole propagated row",
-}
-UNSHARDED_DOT_PRODUCT = {
-    "GraphTransformer": "its edge softmax needs every in-edge of a row and the key and value rows of the remote sources",
-}
-UNSHARDED_ORDER_STATISTICS = {
-    "PNA": "the min, max and std of a row need every in-edge of it and each conv layer the previous layer's hidden rows of the remote sources",
-}
-
-
 def _refuse_unsharded(encoder, who):
-    """The encoders neither sharded teacher runs: the kinds of UNSHARDED_TEACHERS, UNSHARDED_GATED, UNSHARDED_DOT_PRODUCT and
-    UNSHARDED_ORDER_STATISTICS, then a SAGE with another aggregator than 'gcn'."""
+    """The encoders neither sharded teacher runs: the kinds whose row of kinds.KINDS says why (`unsharded`: the exchange of remote rows
+    that the sharded forward does not have), then a SAGE with another aggregator than 'gcn'."""
     kind = type(encoder).__name__
-    why = (UNSHARDED_TEACHERS.get(kind) or UNSHARDED_GATED.get(kind) or UNSHARDED_DOT_PRODUCT.get(kind)
-           or UNSHARDED_ORDER_STATISTICS.get(kind))
+    why = kind in BY_KEY and BY_KEY[kind].unsharded
     if why:
         raise NotImplementedError(f"{who}: the {kind} teacher is not sharded -- {why}, an exchange the sharded "
                                   f"forward does not have (whole-graph {kind} only)")

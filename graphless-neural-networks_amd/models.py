@@ -17,25 +17,8 @@ import torch.nn.functional as F
 
 from . import _lib, ops
 from .autograd import appnp_propagate, gcnii_stack, linear_fn, norm_act_drop
+from .kinds import BY_KIND, FULL_GRAPH_KINDS, teacher_kind      # noqa: F401  (the table of kinds; re-exported for the callers of old)
 from .nn import DAGNNConv, GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, PNAConv, SAGEConv, TransformerConv, _whole_graph_only
-
-
-_KINDS = (("MLP", "mlp"), ("SAGE", "sage"), ("GCNII", "gcnii"), ("GCN", "gcn"), ("APPNP", "appnp"), ("GATv2", "gatv2"), ("GAT", "gat"),
-          ("GPRGNN", "gpr"), ("DAGNN", "dagnn"), ("GraphTransformer", "gt"), ("PNA", "pna"))
-
-
-def teacher_kind(model_name):
-    """The model family a `model_name` selects: the first of _KINDS whose key the name contains (the reference's substring dispatch,
-    models.py:355,409).  The order is the rule and is written down here alone: "MLP" first ("MLP3w4" is an MLP), "GCNII" before "GCN"
-    and "GATv2" before "GAT", which they contain ("GPRGNN", "DAGNN", "GraphTransformer" and "PNA" contain no other key and no other key
-    contains them: "APPNP" holds "PNP", not "PNA").  Every caller switches on the kind it returns."""
-    for key, kind in _KINDS:
-        if key in model_name:
-            return kind
-    raise ValueError(f"Unknown model_name {model_name}")
-
-
-FULL_GRAPH_KINDS = ("gcn", "gcnii", "appnp", "gat", "gatv2", "gpr", "dagnn", "gt", "pna")    # the teachers whose training step takes the whole graph
 
 
 def _bn_eval_fold(bn, bias):
@@ -661,77 +644,82 @@ class DAGNN(_TrunkProp):
         self.k = self.propagate.k
 
 
-GCNII_MAX_LAYERS = 64
+STACK_MAX_LAYERS = 64
 
 
-class GCNII(nn.Module):
-    """GCNII (Chen, Wei, Huang, Ding, Li, ICML 2020; docs/GCNII_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it):
-    H_0 = relu(fc_in(drop(x))), num_layers GCNIIConv layers over H_0 and APPNP's operator with a dropout in front of each,
-    logits = fc_out(drop(H_L)).  forward returns ([H_1..H_L], logits)."""
+class _ConvStack(nn.Module):
+    """What GCNII and PNA share: H_0 = relu(fc_in(drop(x))), num_layers conv layers over hidden_dim columns with a dropout in front of
+    each, logits = fc_out(drop(H_L)); forward returns ([H_1..H_L], logits).  A subclass names its width limit and the reasons of its
+    refusals (MAX_HIDDEN, WHY = width / norm / ReLU), hands its layers' constructor to __init__ (conv(l), l = 1..num_layers, called
+    between fc_in and fc_out: the registration and RNG order) and runs the stack on H_0 (stack(g, h0) -> [H_1..H_L])."""
+    MAX_HIDDEN = WHY = None
 
-    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", alpha=0.1, lamda=0.5):
+    def __init__(self, conv, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type):
         super().__init__()
-        if hidden_dim > ops.GCNII_MAX_HIDDEN:
-            raise NotImplementedError(f"GCNII: hidden_dim of at most {ops.GCNII_MAX_HIDDEN} (the fused kernel's tile width; got {hidden_dim})")
+        who, (why_width, why_norm, why_relu) = type(self).__name__, self.WHY
+        if hidden_dim > self.MAX_HIDDEN:
+            raise NotImplementedError(f"{who}: hidden_dim of at most {self.MAX_HIDDEN} ({why_width}; got {hidden_dim})")
         if norm_type != "none":
-            raise NotImplementedError(f"GCNII: norm_type 'none' only (the paper's model has no norm layers; got {norm_type!r})")
-        if not 1 <= num_layers <= GCNII_MAX_LAYERS:
-            raise NotImplementedError(f"GCNII: 1 to {GCNII_MAX_LAYERS} conv layers (got num_layers {num_layers})")
+            raise NotImplementedError(f"{who}: norm_type 'none' only ({why_norm}; got {norm_type!r})")
+        if not 1 <= num_layers <= STACK_MAX_LAYERS:
+            raise NotImplementedError(f"{who}: 1 to {STACK_MAX_LAYERS} conv layers (got num_layers {num_layers})")
         if activation is not F.relu and getattr(activation, "__name__", "") != "relu":
-            raise NotImplementedError("GCNII: only the ReLU activation (the fused layer kernel's epilogue)")
-        self.num_layers, self.norm_type, self.activation = num_layers, norm_type, activation
-        self.hidden_dim, self.alpha, self.lamda = hidden_dim, float(alpha), float(lamda)
+            raise NotImplementedError(f"{who}: only the ReLU activation ({why_relu})")
+        self.num_layers, self.norm_type, self.activation, self.hidden_dim = num_layers, norm_type, activation, hidden_dim
         self.dropout = nn.Dropout(dropout_ratio)
         self.fc_in = nn.Linear(input_dim, hidden_dim)
-        self.layers = nn.ModuleList(GCNIIConv(hidden_dim, l, alpha, lamda) for l in range(1, num_layers + 1))
+        self.layers = nn.ModuleList(conv(l) for l in range(1, num_layers + 1))
         self.fc_out = nn.Linear(hidden_dim, output_dim)
 
-    def betas(self):
-        return [layer.beta for layer in self.layers]
-
     def forward(self, g, feats):
-        _need_hip(feats, "GCNII.forward")
-        _whole_graph_only(g, feats, "GCNII", "GCNII runs on the whole graph")
-        weights = [layer.weight for layer in self.layers]
+        who = type(self).__name__
+        _need_hip(feats, f"{who}.forward")
+        _whole_graph_only(g, feats, who, f"{who} runs on the whole graph")
         if not self.training:
             with torch.no_grad():
                 h0 = ops.gemm(ops.as_feat(feats), self.fc_in.weight, ep_shift=self.fc_in.bias, relu=True)
-                hs = gcnii_stack(g, h0, weights, self.alpha, self.betas(), 0.0, False)
+                hs = self.stack(g, h0)
                 return hs, ops.gemm(hs[-1], self.fc_out.weight, ep_shift=self.fc_out.bias)
         p = self.dropout.p
         x = norm_act_drop(feats, None, p, relu=False) if p > 0 else feats
         h0 = norm_act_drop(linear_fn(x, self.fc_in.weight, self.fc_in.bias), None, 0.0)
-        hs = gcnii_stack(g, h0, weights, self.alpha, self.betas(), p, True)
+        hs = self.stack(g, h0)
         h = norm_act_drop(hs[-1], None, p, relu=False) if p > 0 else hs[-1]
         return hs, linear_fn(h, self.fc_out.weight, self.fc_out.bias)
 
 
-PNA_MAX_LAYERS = 64
+class GCNII(_ConvStack):
+    """GCNII (Chen, Wei, Huang, Ding, Li, ICML 2020; docs/GCNII_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it): the stack
+    of GCNIIConv layers over H_0 and APPNP's operator."""
+    MAX_HIDDEN = ops.GCNII_MAX_HIDDEN
+    WHY = ("the fused kernel's tile width", "the paper's model has no norm layers", "the fused layer kernel's epilogue")
+
+    def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", alpha=0.1, lamda=0.5):
+        super().__init__(lambda l: GCNIIConv(hidden_dim, l, alpha, lamda), num_layers, input_dim, hidden_dim, output_dim, dropout_ratio,
+                         activation, norm_type)
+        self.alpha, self.lamda = float(alpha), float(lamda)
+
+    def betas(self):
+        return [layer.beta for layer in self.layers]
+
+    def stack(self, g, h0):
+        return gcnii_stack(g, h0, [layer.weight for layer in self.layers], self.alpha, self.betas(),
+                           self.dropout.p if self.training else 0.0, self.training)
 
 
-class PNA(nn.Module):
-    """PNA (Corso et al., NeurIPS 2020; docs/PNA_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it) in GCNII's shape, so that
-    wide input features never reach the gather: H_0 = relu(fc_in(drop(x))), num_layers PNAConv(hidden, hidden) layers with ReLU and a
-    dropout in front of each (the conv's feat_drop), logits = fc_out(drop(H_L)).  `delta` is a persistent fp64 buffer: a constant of the
-    model, saved with it and never recomputed on a subgraph or an observed graph.  forward returns ([H_1..H_L], logits)."""
+class PNA(_ConvStack):
+    """PNA (Corso et al., NeurIPS 2020; docs/PNA_SEMANTICS.md; neither the reference nor dgl 0.6.1 defines it) as a stack, so that wide
+    input features never reach the gather: PNAConv(hidden, hidden) layers with ReLU, the dropout in front of each being the conv's
+    feat_drop.  `delta` is a persistent fp64 buffer: a constant of the model, saved with it and never recomputed on a subgraph or an
+    observed graph."""
+    MAX_HIDDEN = ops.PNA_MAX_WIDTH
+    WHY = ("the aggregation kernel's row width", "BatchNorm / LayerNorm in the PNA stack are out of scope", "the scale launch's epilogue")
 
     def __init__(self, num_layers, input_dim, hidden_dim, output_dim, dropout_ratio, activation, norm_type="none", delta=1.0):
-        super().__init__()
-        if hidden_dim > ops.PNA_MAX_WIDTH:
-            raise NotImplementedError(f"PNA: hidden_dim of at most {ops.PNA_MAX_WIDTH} (the aggregation kernel's row width; got {hidden_dim})")
-        if norm_type != "none":
-            raise NotImplementedError(f"PNA: norm_type 'none' only (BatchNorm / LayerNorm in the PNA stack are out of scope; got {norm_type!r})")
-        if not 1 <= num_layers <= PNA_MAX_LAYERS:
-            raise NotImplementedError(f"PNA: 1 to {PNA_MAX_LAYERS} conv layers (got num_layers {num_layers})")
-        if activation is not F.relu and getattr(activation, "__name__", "") != "relu":
-            raise NotImplementedError("PNA: only the ReLU activation (the scale launch's epilogue)")
         if not float(delta) > 0:
             raise ValueError(f"PNA: pna_delta must be positive (got {delta})")
-        self.num_layers, self.norm_type, self.activation, self.hidden_dim = num_layers, norm_type, activation, hidden_dim
-        self.dropout = nn.Dropout(dropout_ratio)
-        self.fc_in = nn.Linear(input_dim, hidden_dim)
-        self.layers = nn.ModuleList(PNAConv(hidden_dim, hidden_dim, delta, dropout_ratio, activation) for _ in range(num_layers))
-        self.fc_out = nn.Linear(hidden_dim, output_dim)
+        super().__init__(lambda l: PNAConv(hidden_dim, hidden_dim, delta, dropout_ratio, activation), num_layers, input_dim, hidden_dim,
+                         output_dim, dropout_ratio, activation, norm_type)
         self.register_buffer("delta", torch.tensor(float(delta), dtype=torch.float64))
         self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module._sync_delta())
 
@@ -741,25 +729,11 @@ class PNA(nn.Module):
         for layer in self.layers:
             layer.delta = delta
 
-    def forward(self, g, feats):
-        _need_hip(feats, "PNA.forward")
-        _whole_graph_only(g, feats, "PNA", "PNA runs on the whole graph")
-        hs = []
-        if not self.training:
-            with torch.no_grad():
-                h = ops.gemm(ops.as_feat(feats), self.fc_in.weight, ep_shift=self.fc_in.bias, relu=True)
-                for layer in self.layers:
-                    h = layer(g, h)
-                    hs.append(h)
-                return hs, ops.gemm(h, self.fc_out.weight, ep_shift=self.fc_out.bias)
-        p = self.dropout.p
-        x = norm_act_drop(feats, None, p, relu=False) if p > 0 else feats
-        h = norm_act_drop(linear_fn(x, self.fc_in.weight, self.fc_in.bias), None, 0.0)
+    def stack(self, g, h0):
+        hs = [h0]
         for layer in self.layers:
-            h = layer(g, h)
-            hs.append(h)
-        h = norm_act_drop(h, None, p, relu=False) if p > 0 else h
-        return hs, linear_fn(h, self.fc_out.weight, self.fc_out.bias)
+            hs.append(layer(g, hs[-1]))
+        return hs[1:]
 
 
 class _AttnStack(nn.Module):
@@ -908,22 +882,10 @@ class Model(nn.Module):
         """dtype=torch.bfloat16: bf16 activation storage, the SAGE teacher's whole-graph forward only (SAGE.inference)."""
         kind = self.kind
         if dtype != torch.float32:
-            if kind == "gatv2":
-                raise NotImplementedError(f"GATv2.inference(dtype={dtype}): bf16 activation storage is not implemented for the GATv2 teacher "
-                                          "(csrc/gatv2.hip gathers and stores fp32 rows; docs/GATV2_SEMANTICS.md, What is refused)")
-            if kind == "gt":
-                raise NotImplementedError(f"GraphTransformer.inference(dtype={dtype}): bf16 activation storage is not implemented for the "
-                                          "GraphTransformer teacher (csrc/gt.hip gathers and stores fp32 rows; docs/GT_SEMANTICS.md, What "
-                                          "is refused)")
-            if kind == "gcnii":
-                raise NotImplementedError(f"GCNII.inference(dtype={dtype}): bf16 activation storage is not implemented for the GCNII teacher "
-                                          "(csrc/gcnii.hip gathers and stores fp32 rows; docs/GCNII_SEMANTICS.md, Out of scope)")
-            if kind == "dagnn":
-                raise NotImplementedError(f"DAGNN.inference(dtype={dtype}): bf16 activation storage is not implemented for the DAGNN teacher "
-                                          "(csrc/dagnn.hip gathers and stores fp32 rows; docs/DAGNN_SEMANTICS.md, Out of scope)")
-            if kind == "pna":
-                raise NotImplementedError(f"PNA.inference(dtype={dtype}): bf16 activation storage is not implemented for the PNA teacher "
-                                          "(csrc/pna.hip gathers and stores fp32 rows; docs/PNA_SEMANTICS.md, What is refused)")
+            row = BY_KIND[kind]
+            if row.bf16:
+                raise NotImplementedError(f"{row.key}.inference(dtype={dtype}): bf16 activation storage is not implemented for the {row.key} "
+                                          "teacher ({} gathers and stores fp32 rows; {}, {})".format(*row.bf16))
             if kind != "sage":
                 raise NotImplementedError(f"{self.model_name}.inference(dtype={dtype}): bf16 activation storage is implemented for the SAGE "
                                           "teacher's whole-graph forward only")

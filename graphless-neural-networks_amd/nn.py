@@ -12,7 +12,10 @@
 
 Parameter names follow dgl 0.6.1 so that a reference `model.pth` loads: SAGEConv.fc_neigh.{weight,bias}
 (weight [out,in], xavier_uniform gain=relu; no fc_self for "gcn"), GraphConv.{weight [in,out] xavier_uniform,
-bias zeros}.  Only what the reference constructs is implemented; anything else raises."""
+bias zeros}.  Only what the reference constructs is implemented; anything else raises.
+
+Adding a teacher family: its conv here, its row in kinds.KINDS (what every name list, refusal and dispatch reads), its encoder and
+Model.__init__ branch in models.py, TeacherEngine.step_<kind> in teacher.py."""
 
 import math
 

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .models import teacher_kind
+from .kinds import teacher_kind
 
 
 def _mix32(x):

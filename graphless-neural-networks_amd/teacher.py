@@ -36,9 +36,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib, ops
-from .models import teacher_kind
-from .autograd import (appnp_bwd, appnp_fwd, dagnn_bwd, dagnn_fwd, gat_layer_bwd, gat_layer_fwd, gatv2_layer_bwd, gatv2_layer_fwd, gt_layer_bwd, gt_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd,
-                       graphconv_fwd, pna_layer_bwd, pna_layer_fwd)
+from .kinds import BY_KIND, teacher_kind, teacher_names
+from .autograd import (appnp_bwd, appnp_fwd, dagnn_bwd, dagnn_fwd, gat_layer_bwd, gat_layer_fwd, gatv2_layer_bwd, gatv2_layer_fwd,
+                       gt_layer_bwd, gt_layer_fwd, gcnii_bwd, gcnii_fwd, gpr_bwd, gpr_fwd, graphconv_bwd, graphconv_fwd, pna_layer_bwd,
+                       pna_layer_fwd)
 from .student import _mix32
 
 
@@ -69,47 +70,34 @@ def _check_norms_and_device(who, model):
                            "pass --device 0)")
 
 
-_NORM_RELU = {"sage": "SAGE with norm_type none|batch|layer and ReLU (the reference's configs)",
-              "appnp": "APPNP with norm_type none|batch|layer and ReLU (models.py:282-344)",
-              "gpr": "GPRGNN with norm_type none|batch|layer and ReLU (docs/GPR_SEMANTICS.md)",
-              "dagnn": "DAGNN with norm_type none|batch|layer and ReLU (docs/DAGNN_SEMANTICS.md)"}
-_ATTN_RELU = {"gatv2": "GATv2 with ReLU hidden layers and a linear last layer (docs/GATV2_SEMANTICS.md)",
-              "gt": "GraphTransformer with ReLU hidden layers and a linear last layer (docs/GT_SEMANTICS.md)",
-              "gat": "GAT with ReLU hidden layers and a linear last layer (models.py:202-279)"}
-
-
 def check_supported(model, criterion, optimizer):
-    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a SAGE, GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII or PNA teacher."""
+    """Raise unless (model, criterion, optimizer) is what train_teacher.py:232-238 builds for a teacher of a family with a TeacherEngine
+    step: the rows of kinds.KINDS that name a rule, each with the sentence it is refused with."""
     enc = model.encoder
     name = model.model_name
     try:
-        kind = teacher_kind(name)
+        row = BY_KIND[teacher_kind(name)]
     except ValueError:           # (a name no family claims: refused like the MLP)
-        kind = "mlp"
-    if kind == "mlp":
-        raise NotImplementedError(f"TeacherEngine: SAGE, GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII or PNA teachers only (got {name})")
+        row = BY_KIND["mlp"]
+    if row.rule is None:
+        raise NotImplementedError(f"TeacherEngine: {teacher_names('or', graph_kinds=True)} teachers only (got {name})")
     _check_criterion_and_optimizer("TeacherEngine", criterion, optimizer)
-    if kind == "gcnii":          # (the encoder's constructor refused everything else)
-        if enc.norm_type != "none" or not _is_relu(enc.activation):
-            raise NotImplementedError("TeacherEngine: GCNII with norm_type none and ReLU (docs/GCNII_SEMANTICS.md)")
-    elif kind == "pna":          # (likewise)
-        if enc.norm_type != "none" or not _is_relu(enc.activation) or any(not _is_relu(lay.activation) for lay in enc.layers):
-            raise NotImplementedError("TeacherEngine: PNA with norm_type none and ReLU (docs/PNA_SEMANTICS.md)")
-    elif kind in _NORM_RELU:
-        if kind == "sage" and getattr(enc, "aggregator_type", "gcn") != "gcn":
+    norms = ("none",) if row.rule == "stack" else ("none", "batch", "layer")
+    if row.rule == "stack":      # GCNII, PNA (the encoder's constructor refused everything else)
+        ok = _is_relu(enc.activation) and (row.kind != "pna" or all(_is_relu(lay.activation) for lay in enc.layers))   # (PNAConv has its own)
+    elif row.rule == "norm_relu":
+        if row.kind == "sage" and getattr(enc, "aggregator_type", "gcn") != "gcn":
             raise NotImplementedError(f"TeacherEngine: the one-call SAGE step implements the 'gcn' aggregator only; a SAGE "
                                       f"{enc.aggregator_type!r} teacher trains through SAGE.forward's differentiable ops (train_sage)")
-        if enc.norm_type not in ("none", "batch", "layer") or not _is_relu(enc.activation):
-            raise NotImplementedError("TeacherEngine: " + _NORM_RELU[kind])
-    elif kind in _ATTN_RELU:
-        if not _is_relu(enc.activation) or any(not lay.relu() for lay in enc.layers[:-1]) or enc.layers[-1].relu():
-            raise NotImplementedError("TeacherEngine: " + _ATTN_RELU[kind])
-    else:
-        if enc.norm_type not in ("none", "batch", "layer"):      # train.conf.yaml: cora-style GCN none, pokec / penn94 GCN batch
-            raise NotImplementedError("TeacherEngine: GCN with norm_type none|batch|layer")
-        for lay in enc.layers[:-1]:
-            if not _is_relu(lay._activation):
-                raise NotImplementedError("TeacherEngine: GraphConv(activation=F.relu) on hidden layers (models.py:170-187)")
+        ok = _is_relu(enc.activation)
+    elif row.rule == "attn":
+        ok = _is_relu(enc.activation) and all(lay.relu() for lay in enc.layers[:-1]) and not enc.layers[-1].relu()
+    else:                        # "gcn": train.conf.yaml's cora-style GCN none, pokec / penn94 GCN batch
+        ok = True
+    if not ok or (row.rule != "attn" and enc.norm_type not in norms):      # (the attention stacks have no norm layers)
+        raise NotImplementedError("TeacherEngine: " + row.supported)
+    if row.rule == "gcn" and any(not _is_relu(lay._activation) for lay in enc.layers[:-1]):
+        raise NotImplementedError("TeacherEngine: GraphConv(activation=F.relu) on hidden layers (models.py:170-187)")
     _check_norms_and_device("TeacherEngine", model)
 
 
@@ -259,7 +247,7 @@ class TeacherEngine:
         self.L = self.enc.num_layers
         self.bn = getattr(self.enc, "norm_type", "none") == "batch"
         self.ln = getattr(self.enc, "norm_type", "none") == "layer"
-        self.p = float(self.enc.layers[0].feat_drop.p if self.kind in _ATTN_RELU else self.enc.dropout.p)
+        self.p = float(self.enc.layers[0].feat_drop.p if BY_KIND[self.kind].rule == "attn" else self.enc.dropout.p)
         params = list(model.parameters())
         self.params = params
         dev = params[0].device
@@ -731,27 +719,38 @@ class TeacherEngine:
         launch for dH_0, H_0's ReLU backward, fc_in's backward, and the ONE Adam launch."""
         self._run_full_graph(self._step_gcnii_body, g, feats, labels, idx_train, lamb)
 
-    def _step_gcnii_body(self, g, feats, labels, idx_train, lamb):
+    def _step_stack_body(self, seed_of, fwd, bwd, g, feats, labels, idx_train, lamb):
+        """A stack teacher (models._ConvStack) through its per-kind pair: fwd(self, g, h0, seeds) -> (H_L, kept) and
+        bwd(self, g, da, h0, kept, seeds) -> (dH_0, mask), which also leaves the conv layers' gradients.  mask: drop_p / drop_seed of a
+        dropout mask dH_0 still lacks, applied inside H_0's ReLU backward (PNA's layer-1 feat_drop); {} = that launch's plain variant."""
         enc, L, p = self.enc, self.L, self.p
-        n = g.num_dst_nodes()
         fc_in, fc_out = enc.fc_in, enc.fc_out
-        seeds = [self._gcnii_seed(s) for s in range(L + 2)]
-        weights = [lay.weight for lay in enc.layers]
-        betas = enc.betas()
+        seeds = [seed_of(self, s) for s in range(L + 2)]
         x = ops.as_feat(feats)
         # drop_0(x) is materialised once per step (signed features: the GEMM's operand-load dropout carries a ReLU) and read twice
         xd = ops.act_fwd(x, drop_p=p, drop_seed=seeds[0], relu=False) if p > 0 else x
         h0 = ops.gemm(xd, fc_in.weight, ep_shift=fc_in.bias, relu=True)
-        hs, ss = gcnii_fwd(g, h0, weights, enc.alpha, betas, p, seeds, save=True)
-        a = ops.act_fwd(hs[-1], drop_p=p, drop_seed=seeds[L + 1], relu=False) if p > 0 else hs[-1]
+        hl, kept = fwd(self, g, h0, seeds)
+        a = ops.act_fwd(hl, drop_p=p, drop_seed=seeds[L + 1], relu=False) if p > 0 else hl
         logits = ops.gemm(a, fc_out.weight, ep_shift=fc_out.bias)
-        dlog = self._loss_grad(logits, labels, idx_train, lamb, n)
+        dlog = self._loss_grad(logits, labels, idx_train, lamb, g.num_dst_nodes())
         ops.gemm_tn(dlog, a, out=self.grad(fc_out.weight), col_sum_a=self.grad(fc_out.bias))
         da = ops.gemm(dlog, fc_out.weight, w_is_kn=True)                          # dlog W_out: d/d drop_{L+1}(H_L)
-        dh0 = gcnii_bwd(g, da, hs, ss, weights, enc.alpha, betas, [self.grad(w) for w in weights], p, seeds)
-        dz0, _, _ = ops.bn_relu_bwd(dh0, h0, dz=dh0, dz_col_sum=self.grad(fc_in.bias))     # h0 = relu(z0): h0 > 0 <=> z0 > 0
+        dh0, mask = bwd(self, g, da, h0, kept, seeds)
+        dz0, _, _ = ops.bn_relu_bwd(dh0, h0, dz=dh0, dz_col_sum=self.grad(fc_in.bias), **mask)     # h0 = relu(z0): h0 > 0 <=> z0 > 0
         ops.gemm_tn(dz0, xd, out=self.grad(fc_in.weight))
         ops.note_param_write()
+
+    def _gcnii_fwd(self, g, h0, seeds):
+        enc, weights, betas = self.enc, [lay.weight for lay in self.enc.layers], self.enc.betas()      # (read once a step, as before)
+        hs, ss = gcnii_fwd(g, h0, weights, enc.alpha, betas, self.p, seeds, save=True)
+        return hs[-1], (hs, ss, weights, betas)
+
+    def _gcnii_bwd(self, g, da, h0, kept, seeds):
+        hs, ss, weights, betas = kept
+        return gcnii_bwd(g, da, hs, ss, weights, self.enc.alpha, betas, [self.grad(w) for w in weights], self.p, seeds), {}
+
+    _step_gcnii_body = functools.partialmethod(_step_stack_body, _gcnii_seed, _gcnii_fwd, _gcnii_bwd)
 
     # ------------------------------------------------------------------------------------------ full-graph PNA
     def _pna_seed(self, site, step=None):
@@ -769,33 +768,26 @@ class TeacherEngine:
         in-edges are legal."""
         self._run_full_graph(self._step_pna_body, g, feats, labels, idx_train, lamb)
 
-    def _step_pna_body(self, g, feats, labels, idx_train, lamb):
-        enc, L, p = self.enc, self.L, self.p
-        fc_in, fc_out = enc.fc_in, enc.fc_out
-        seeds = [self._pna_seed(s) for s in range(L + 2)]
-        x = ops.as_feat(feats)
-        xd = ops.act_fwd(x, drop_p=p, drop_seed=seeds[0], relu=False) if p > 0 else x       # (signed features: materialised once, read twice)
-        acts, saved = [ops.gemm(xd, fc_in.weight, ep_shift=fc_in.bias, relu=True)], []
-        for l, lay in enumerate(enc.layers):
-            y, sv = pna_layer_fwd(g, acts[l], lay.pre.weight, lay.pre.bias, lay.post.weight, lay.post.bias, lay.delta, True, p, seeds[l + 1],
-                                  keep=True)
+    def _pna_fwd(self, g, h0, seeds):
+        acts, saved = [h0], []
+        for l, lay in enumerate(self.enc.layers):
+            y, sv = pna_layer_fwd(g, acts[l], lay.pre.weight, lay.pre.bias, lay.post.weight, lay.post.bias, lay.delta, True, self.p,
+                                  seeds[l + 1], keep=True)
             acts.append(y)
             saved.append(sv)
-        a = ops.act_fwd(acts[L], drop_p=p, drop_seed=seeds[L + 1], relu=False) if p > 0 else acts[L]
-        logits = ops.gemm(a, fc_out.weight, ep_shift=fc_out.bias)
-        dlog = self._loss_grad(logits, labels, idx_train, lamb, g.num_dst_nodes())
-        ops.gemm_tn(dlog, a, out=self.grad(fc_out.weight), col_sum_a=self.grad(fc_out.bias))
-        da = ops.gemm(dlog, fc_out.weight, w_is_kn=True)                                 # dlog W_out: d/d drop_{L+1}(H_L)
-        for l in range(L - 1, -1, -1):
-            lay = enc.layers[l]
+        return acts[-1], (acts, saved)
+
+    def _pna_bwd(self, g, da, h0, kept, seeds):
+        acts, saved = kept
+        for l in range(self.L - 1, -1, -1):
+            lay = self.enc.layers[l]
             # the dropout mask of site l + 2 (in front of the next conv, or of fc_out) and the ReLU mask of H_{l+1} (stored post-ReLU)
-            gy = ops.bn_relu_bwd(da, acts[l + 1], dz=da, drop_p=p, drop_seed=seeds[l + 2])[0]
+            gy = ops.bn_relu_bwd(da, acts[l + 1], dz=da, drop_p=self.p, drop_seed=seeds[l + 2])[0]
             da = pna_layer_bwd(g, gy, saved[l], lay.pre.weight, lay.post.weight, lay.delta, need_dx=True, dw_pre=self.grad(lay.pre.weight),
                                db_pre=self.grad(lay.pre.bias), dw_post=self.grad(lay.post.weight), db_post=self.grad(lay.post.bias))[0]
-        # layer 1's feat_drop mask and H_0 = relu(z_0): h0 > 0 <=> z0 > 0
-        dz0, _, _ = ops.bn_relu_bwd(da, acts[0], dz=da, drop_p=p, drop_seed=seeds[1], dz_col_sum=self.grad(fc_in.bias))
-        ops.gemm_tn(dz0, xd, out=self.grad(fc_in.weight))
-        ops.note_param_write()
+        return da, dict(drop_p=self.p, drop_seed=seeds[1])      # (layer 1's feat_drop mask is still to come)
+
+    _step_pna_body = functools.partialmethod(_step_stack_body, _pna_seed, _pna_fwd, _pna_bwd)
 
     # ------------------------------------------------------------------------------------------ full-graph GAT
     def _attn_seed(self, layer):

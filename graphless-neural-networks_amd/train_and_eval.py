@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .models import FULL_GRAPH_KINDS, teacher_kind
+from .kinds import FULL_GRAPH_KINDS, teacher_kind, teacher_names
 from .graph import (FullNeighborLoader, MultiLayerFullNeighborSampler, MultiLayerNeighborSampler, NodeDataLoader,
                     RandomWalkSubgraphLoader)
 from . import teacher
@@ -29,12 +29,12 @@ EVAL_BLOCK_ROWS = 1 << 19
 
 
 def train(model, data, feats, labels, criterion, optimizer, idx_train, lamb=1):
-    """GNN full-batch training step (reference train_and_eval.py:12-29; `data` is the whole graph): one
-    TeacherEngine.step_gcn (GCN) / step_appnp (APPNP) / step_gat (GAT) / step_gatv2 (GATv2) / step_gt (GraphTransformer) / step_gpr (GPRGNN) / step_dagnn (DAGNN) / step_gcnii (GCNII) / step_pna (PNA) -- forward, NLL over idx_train, backward over the transposed graph, Adam -- on libglnn_hip.so.
-    Returns the unscaled loss like the reference's `loss.item()`."""
+    """GNN full-batch training step (reference train_and_eval.py:12-29; `data` is the whole graph): one TeacherEngine.step_<kind> of the
+    model's family (kinds.KINDS: the rows whose step takes the whole graph) -- forward, NLL over idx_train, backward over the transposed
+    graph, Adam -- on libglnn_hip.so.  Returns the unscaled loss like the reference's `loss.item()`."""
     teacher.check_supported(model, criterion, optimizer)
     if teacher_kind(model.model_name) not in FULL_GRAPH_KINDS:
-        raise NotImplementedError("train(): the full-graph step is implemented for the GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII and PNA teachers (SAGE trains "
+        raise NotImplementedError(f"train(): the full-graph step is implemented for the {teacher_names('and')} teachers (SAGE trains "
                                   "with train_sage)")
     model.train()
     eng = teacher.get_engine(model, optimizer)
@@ -99,9 +99,8 @@ def _full_graph_step(eng, model_name):
 
 
 def train_subgraph(model, loader, feats, labels, criterion, optimizer, lamb=1):
-    """Mini-batch training of a full-graph teacher (GCN, APPNP, GAT, GATv2, GraphTransformer, GPRGNN, DAGNN, GCNII, PNA) on random-walk induced subgraphs: per batch of
-    `loader` (glnn_amd.graph.RandomWalkSubgraphLoader: walks and subgraphs built on the device) the rows feats[nodes] / labels[nodes] are
-    gathered and the SAME TeacherEngine step train() picks for the model runs on the subgraph, its loss the plain mean over the subgraph's
+    """Mini-batch training of a full-graph teacher (kinds.FULL_GRAPH_KINDS) on random-walk induced subgraphs: per batch of `loader`
+    (glnn_amd.graph.RandomWalkSubgraphLoader: walks and subgraphs built on the device) the rows feats[nodes] / labels[nodes] are gathered and the SAME TeacherEngine step train() picks for the model runs on the subgraph, its loss the plain mean over the subgraph's
     training nodes (docs/SUBGRAPH_SEMANTICS.md: a biased, Cluster-GCN-style estimator).  The per-batch losses are summed on the device and
     read ONCE per epoch, as in train_sage; returns their mean."""
     kind = teacher_kind(model.model_name)

@@ -128,9 +128,9 @@ def _conf(**extra):
 
 
 def test_teacher_kind_and_the_order_of_the_keys():
-    from glnn_amd import models
+    from glnn_amd import kinds, models
     assert models.teacher_kind("DAGNN") == "dagnn" and "dagnn" in models.FULL_GRAPH_KINDS
-    keys = [k for k, _ in models._KINDS]
+    keys = [row.key for row in kinds.KINDS]
     assert all(k == "DAGNN" or (k not in "DAGNN" and "DAGNN" not in k) for k in keys)      # no key contains it, it contains none
     for name, kind in (("GPRGNN", "gpr"), ("GCNII", "gcnii"), ("GCN", "gcn"), ("GATv2", "gatv2"), ("GAT", "gat"), ("APPNP", "appnp"),
                        ("SAGE", "sage"), ("MLP3w4", "mlp")):

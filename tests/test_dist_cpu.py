@@ -540,16 +540,19 @@ def test_emulated_rank_halo_equals_unsharded_rows(world, dims, overlap):
 # ---------------------------------------------------------------------------------------------------------------- refusals
 _REFUSAL_PHRASES = {"GAT": "per-head scores of the remote sources", "GATv2": "whole projected rows of the remote sources",
                     "GPRGNN": "each of its K propagation steps needs the previous step's rows",
-                    "GCNII": "each of its conv layers needs the previous layer's hidden rows"}
+                    "GCNII": "each of its conv layers needs the previous layer's hidden rows",
+                    "DAGNN": "and its gate the whole propagated row", "GraphTransformer": "the key and value rows of the remote sources",
+                    "PNA": "the min, max and std of a row need every in-edge of it"}
 
 
 @pytest.mark.parametrize("teacher", ["ShardedTeacher", "HaloShardedTeacher"])
 @pytest.mark.parametrize("kind", sorted(_REFUSAL_PHRASES))
 def test_both_sharded_teachers_refuse_the_unsharded_kinds(teacher, kind):
-    """Every kind of dist.UNSHARDED_TEACHERS is refused by both constructors before they look at anything else, with its own reason; a
-    'mean' aggregator does not change that text (the kinds come first)."""
+    """Every family whose row of kinds.KINDS names a reason is refused by both constructors before they look at anything else, with its
+    own reason; a 'mean' aggregator does not change that text (the kinds come first)."""
     import glnn_amd.dist as gdist
-    assert set(gdist.UNSHARDED_TEACHERS) == set(_REFUSAL_PHRASES)
+    from glnn_amd.kinds import KINDS
+    assert {row.key for row in KINDS if row.unsharded} == set(_REFUSAL_PHRASES)
     enc = type(kind, (), {"aggregator_type": "mean"})()
     with pytest.raises(NotImplementedError) as e:
         getattr(gdist, teacher)(enc, None, None, None)

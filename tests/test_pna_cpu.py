@@ -162,9 +162,9 @@ def _conf(**kw):
 
 
 def test_teacher_kind_and_the_key_containment_rule():
-    from glnn_amd import models
+    from glnn_amd import kinds, models
     assert models.teacher_kind("PNA") == "pna" and models.teacher_kind("GA1PNA") == "pna" and "pna" in models.FULL_GRAPH_KINDS
-    keys = [k for k, _ in models._KINDS]
+    keys = [row.key for row in kinds.KINDS]
     assert all(k == "PNA" or (k not in "PNA" and "PNA" not in k) for k in keys)
     for name, kind in (("APPNP", "appnp"), ("GraphTransformer", "gt"), ("DAGNN", "dagnn"), ("GPRGNN", "gpr"), ("GCNII", "gcnii"),
                        ("GCN", "gcn"), ("GATv2", "gatv2"), ("GAT", "gat"), ("SAGE", "sage"), ("MLP3w4", "mlp")):
@@ -248,7 +248,8 @@ def test_engine_step_and_check_supported(monkeypatch):
 
 def test_cli_flag_stand_in_section_and_delta(tmp_path, capsys):
     import yaml
-    from glnn_amd.cli import _SECTION_STAND_INS, _training_config, get_student_args, get_teacher_args, pna_delta
+    from glnn_amd.cli import _training_config, get_student_args, get_teacher_args, pna_delta
+    from glnn_amd.kinds import BY_KIND
     from glnn_amd.graph import CSRGraph
     from glnn_amd.utils import get_training_config
     args = get_teacher_args(["--teacher", "PNA", "--pna_delta", "1.5"])
@@ -264,7 +265,7 @@ def test_cli_flag_stand_in_section_and_delta(tmp_path, capsys):
     with pytest.raises(SystemExit):
         get_teacher_args(["--teacher", "SAGE", "--subgraph_walk_length", "3"])
     assert "PNA" in capsys.readouterr().err                                  # the refusal lists the full-graph teachers
-    assert _SECTION_STAND_INS["pna"] == ("GCN",)
+    assert BY_KIND["pna"].stand_ins == ("GCN",) and BY_KIND["pna"].global_alone
     path = os.path.join(ROOT, "train.conf.yaml")
     conf = _training_config(path, "PNA", "cora")                             # no section of its own: GCN's stands in
     assert conf == dict(get_training_config(path, "GCN", "cora"), model_name="PNA")
