@@ -10,6 +10,8 @@ APPNP (an ablation teacher, models.py:282-344) runs its MLP trunk on the same ke
 csrc/appnp.hip (docs/APPNP_SEMANTICS.md).  GAT (models.py:202-279) runs its edge-softmax attention on csrc/gat.hip
 (docs/GAT_SEMANTICS.md): every encoder the reference can name is on the HIP path."""
 import contextlib
+import os
+import weakref
 
 import torch
 import torch.nn as nn
@@ -238,6 +240,19 @@ class SAGE(nn.Module):
         raise NotImplementedError("SAGE._tail: LayerNorm has per-row statistics and cannot be folded into a kernel epilogue "
                                   "(SAGE.inference applies it as its own pass; the sharded teachers do not support it)")
 
+    def _layer_tail(self, l):
+        """What layer l's launch gets in `inference`: (ep_scale, ep_shift, relu, post_ln).  A LayerNorm hidden layer's launch adds the conv's
+        bias only and LayerNorm -> ReLU follow as a pass of their own (post_ln: _eval_tail); every other layer gets the fused `_tail`."""
+        if self.norm_type == "layer" and l != self.num_layers - 1:
+            return None, self.layers[l].mean_bias() if self.aggregator_type == "mean" else self.layers[l].fc_neigh.bias, False, True
+        return self._tail(l) + (False,)
+
+    def _chains_next(self, l):
+        """Layer l is fused and layer l+1 projects first: W_{l+1} rides behind l's epilogue and l's rows never reach HBM (products: 2.5 GB)."""
+        nxt = self.layers[l + 1] if l + 1 < self.num_layers else None
+        return bool(nxt is not None and self.layers[l].fused_eligible() and nxt._in_feats > nxt._out_feats and nxt._out_feats <= 256
+                    and SAGE.CHAIN_NEXT_PROJECTION)
+
     # ---- placement of the matrices the whole-graph launches gather from (ops.placed_for_gather: which allocation holds a matrix
     #      decides whether the gather over it takes 18.1 or 19.4 ms).  Intermediate activations live in buffers that are placed once per
     #      (graph, layer) and reused by every later call -- they are internal: what inference RETURNS is always a fresh tensor; the input
@@ -249,7 +264,6 @@ class SAGE(nn.Module):
         k = (id(g), key, rows, d, str(device))
         ent = cache.get(k)
         if ent is None or ent[0]() is not g:
-            import weakref
             buf = ops.placed_for_gather(rows, d, device, g.indptr, g.indices, g.num_dst_nodes(), what=f"SAGE.inference {key[0]}{key[1]}", zero=True,
                                         probe=probe)
             cache[k] = ent = (weakref.ref(g), buf)
@@ -272,17 +286,13 @@ class SAGE(nn.Module):
         if self.aggregator_type != "gcn":
             raise NotImplementedError("SAGE._whole_graph_layer: the chained next-layer projection and the placed buffers belong to the 'gcn' "
                                       f"engine, not to aggregator_type {self.aggregator_type!r}")
-        post_ln = self.norm_type == "layer" and l != self.num_layers - 1
-        ep_scale, ep_shift, relu = (None, layer.fc_neigh.bias, False) if post_ln else self._tail(l)
+        ep_scale, ep_shift, relu, post_ln = self._layer_tail(l)
         n = g.num_dst_nodes()
         nxt = self.layers[l + 1] if l + 1 < self.num_layers else None
         if projected is not None:
             # the dense half of this layer already came out of the previous layer's kernel: aggregate + epilogue only
             return ops.spmm(g.indptr, g.indices, projected, n, ops.AGG_SAGE_GCN, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu), None
-        if nxt is not None and layer.fused_eligible() and nxt._in_feats > nxt._out_feats and nxt._out_feats <= 256 \
-                and SAGE.CHAIN_NEXT_PROJECTION and not post_ln:
-            # layer l aggregates first in the fused kernel and layer l+1 projects first: chain W_{l+1} behind the
-            # epilogue, so the hidden activations of layer l never reach HBM (products: 2.5 GB written + read)
+        if self._chains_next(l) and not post_ln:      # (LayerNorm sits between the two layers: nothing to chain behind)
             out_next = self._placed_buffer(g, ("proj", l), n, nxt._out_feats, x.device) if place else None
             _, proj = ops.sage_fused(g.indptr, g.indices, x, n, layer.fc_neigh.weight, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu,
                                      x_self=x[:n], w_next=nxt.fc_neigh.weight, want_out=False, tile_order=g.fused_tile_order(),
@@ -302,7 +312,6 @@ class SAGE(nn.Module):
     def _placed_input(self, g, feats, x):
         if not ops.placement_applies(x.shape[0], x.shape[1]) or x.shape[0] < g.num_dst_nodes():
             return x
-        import weakref
         ent = self.__dict__.get("_placed_x")
         sig = (id(g), feats.data_ptr(), tuple(feats.shape), feats._version)
         if ent is not None and ent[0]() is feats and ent[1] == sig:
@@ -334,7 +343,6 @@ class SAGE(nn.Module):
         if ent is not None and ent[0]() is g and ent[1]() is feats and ent[2] == sig and ent[3].device == x.device:
             return {"agg_in": ent[3]}, None
         self.__dict__.pop("_agg_x", None)                  # (the stale matrix goes before its successor is allocated)
-        import weakref
         try:
             if torch.cuda.mem_get_info(x.device)[0] < 2 * 4 * n * ops.round4(layer._in_feats):
                 return {}, None
@@ -357,8 +365,7 @@ class SAGE(nn.Module):
         if projected is not None:
             return ops.spmm(g.indptr, g.indices, projected, n, ops.AGG_SAGE_GCN, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu,
                             out_dtype=out_dtype), None
-        if nxt is not None and layer.fused_eligible() and nxt._in_feats > nxt._out_feats and nxt._out_feats <= 256 \
-                and SAGE.CHAIN_NEXT_PROJECTION:
+        if self._chains_next(l):
             _, proj = ops.sage_fused(g.indptr, g.indices, x, n, layer.fc_neigh.weight, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu,
                                      x_self=x[:n], w_next=nxt.fc_neigh.weight, want_out=False, tile_order=g.fused_tile_order(),
                                      out_next_dtype=torch.bfloat16)
@@ -397,38 +404,34 @@ class SAGE(nn.Module):
         # teacher CLI evaluates with: it carries `.graph` exactly then); the chunked sweep also needs the loader's global-id blocks
         if g is None or not (whole_graph or hasattr(dataloader, "global_blocks")):
             raise NotImplementedError("SAGE.inference(aggregator_type 'mean'): a glnn_amd.graph.FullNeighborLoader over the resident graph")
-        ln = self.norm_type == "layer"
         with torch.no_grad():
             x = ops.as_feat(feats)
             n = g.num_dst_nodes()
             for l, layer in enumerate(self.layers):
-                post_ln = ln and l != self.num_layers - 1
-                ep_scale, ep_shift, relu = (None, layer.mean_bias(), False) if post_ln else self._tail(l)
+                tail = self._layer_tail(l)
                 if whole_graph:
-                    y = layer(g, (x, x[:n]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu)
+                    y = layer(g, (x, x[:n]), ep_scale=tail[0], ep_shift=tail[1], relu=tail[2])
                 else:
                     y = ops.feat_empty(n, layer._out_feats, x.device, zero=True)
-                    form = layer.mean_form()
-                    wp = ops.pack_weight_pair(layer.fc_neigh.weight, layer.fc_self.weight) if form == "fused" else None
-                    r4 = ops.round4(layer._out_feats)
-                    # a layer that projects first projects x ONCE, not once per chunk
-                    p = ops.gemm(x, ops.stack_weight_pair(layer.fc_neigh.weight, layer.fc_self.weight)) if form == "project" else None
-                    dataloader.global_blocks = True
-                    try:
-                        for _, _, blocks in dataloader:
-                            block = blocks[0]
-                            s_, e_ = block.dst_range
-                            if p is not None:
-                                ops.spmm_sage_mean(block.indptr, block.indices, p[:, :layer._out_feats], p[s_:e_, r4:], e_ - s_,
-                                                   ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, out=y[s_:e_])
-                            else:
-                                layer(block, (x, x[s_:e_]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, w_packed=wp, out=y[s_:e_])
-                    finally:
-                        dataloader.global_blocks = False
-                if post_ln:
-                    y = _eval_tail(self, l, y)
-                x = y
+                    self._mean_engine_layer(l, dataloader, x, y, tail)
+                x = _eval_tail(self, l, y) if tail[3] else y
             return x
+
+    def _mean_engine_layer(self, l, dataloader, x, y, tail):
+        """Layer l of the "mean" chunked sweep into y: one launch per chunk on the caller's stream, in the layer's own form."""
+        layer, form = self.layers[l], self.layers[l].mean_form()
+        ep_scale, ep_shift, relu, _ = tail
+        wn, ws, d, r4 = layer.fc_neigh.weight, layer.fc_self.weight, layer._out_feats, ops.round4(layer._out_feats)
+        if form == "project":
+            p = ops.gemm(x, ops.stack_weight_pair(wn, ws))      # a layer that projects first projects x ONCE, not once per chunk
+            chunk = lambda s, e, block: ops.spmm_sage_mean(block.indptr, block.indices, p[:, :d], p[s:e, r4:], e - s, ep_scale=ep_scale,
+                                                           ep_shift=ep_shift, relu=relu, out=y[s:e])
+        else:
+            wp = ops.pack_weight_pair(wn, ws) if form == "fused" else None
+            chunk = lambda s, e, block: layer(block, (x, x[s:e]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, w_packed=wp, out=y[s:e])
+        with _chunk_sweep(dataloader, x.device, []) as chunks:
+            for _, s, e, block in chunks:
+                chunk(s, e, block)
 
     def inference(self, dataloader, feats, whole_graph=True, dtype=torch.float32):
         """Layer-wise full-neighbour inference (reference models.py:121-148).
@@ -449,89 +452,95 @@ class SAGE(nn.Module):
             return self._inference_mean(dataloader, feats, whole_graph, dtype)
         if dtype == torch.bfloat16:
             return self._inference_bf16(dataloader, feats, whole_graph)
-        whole_graph = whole_graph and getattr(dataloader, "graph", None) is not None     # loaders that do not sweep arange(N)
+        g = getattr(dataloader, "graph", None)
         with torch.no_grad():
             x = ops.as_feat(feats)
-            agg, agg_ent = {}, None
-            if whole_graph:
-                x = self._placed_input(dataloader.graph, feats, x)
-                agg, agg_ent = self._input_aggregate(dataloader.graph, feats, x)
+            if not whole_graph or g is None:                  # (a loader without a resident graph does not sweep arange(N))
+                return self._inference_chunked(dataloader, x)
+            x = self._placed_input(g, feats, x)
+            agg, agg_ent = self._input_aggregate(g, feats, x)
             projected = None          # x @ W_l^T handed over by the previous (fused) layer when layer l projects first
-            ln = self.norm_type == "layer"
-            for l, layer in enumerate(self.layers):
-                post_ln = ln and l != self.num_layers - 1      # LayerNorm -> ReLU as a pass of its own behind the conv (+ bias)
-                ep_scale, ep_shift, relu = (None, layer.fc_neigh.bias, False) if post_ln else self._tail(l)
-                if whole_graph:
-                    y, projected = self._whole_graph_layer(l, dataloader.graph, x, projected, agg=agg if l == 0 else None)
-                    if l == 0 and agg_ent is not None:
-                        self.__dict__["_agg_x"] = agg_ent
-                else:
-                    d_out = self.hidden_dim if l != self.num_layers - 1 else self.output_dim
-                    y = ops.feat_empty(x.shape[0], d_out, x.device, zero=True)           # models.py:129-132
-                    wp = ops.pack_weight(layer.fc_neigh.weight) if layer.fused_eligible() else None     # once per layer, not per chunk
-                    # Loaders that can hand out GLOBAL-id blocks (FullNeighborLoader.global_blocks, round 6) are asked to for this sweep: the
-                    # chunk loop of models.py:133-145 stays -- one block, one conv, one slice of y per chunk -- but feats[input_nodes] and
-                    # y[output_nodes] = h are not copies any more: the conv gathers its source rows from x itself and writes its rows of y
-                    # (products: 711 -> ~60 ms per forward; a layer that projects first projects x once, not once per chunk)
-                    engine = hasattr(dataloader, "global_blocks") and not post_ln
-                    xp = ops.gemm(x, layer.fc_neigh.weight) if engine and layer._in_feats > layer._out_feats else None
-                    if engine:
-                        dataloader.global_blocks = True
-                    # The chunks of a layer are independent (disjoint rows of y, x read-only) and SHORT -- 4096 rows are 128 tiles on 256 CUs,
-                    # ~90 us of a mostly idle part per launch -- so the engine-mode sweep issues them round-robin on SWEEP_STREAMS streams
-                    # (products: 182 -> ~60 ms per forward; the loop, the blocks and the results are what they were).
-                    cur = torch.cuda.current_stream(x.device)
-                    pool = _sweep_streams(x.device) if engine else []
-                    for st in pool:
-                        st.wait_stream(cur)
-                    # ... and launched through ONE prepared call per layer (ops.RowRangeLaunch: the per-chunk ops call's checks and argument
-                    # list done once; a chunk offsets three pointers) where the layer is a single launch
-                    launch = None
-                    if engine and getattr(dataloader, "graph", None) is not None and (xp is not None or layer.fused_eligible()):
-                        tailed = ep_scale is not None or ep_shift is not None or relu
-                        g_ = dataloader.graph
-                        launch = (ops.RowRangeLaunch(g_.indptr, g_.indices, xp, y, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu) if xp is not None else
-                                  ops.RowRangeLaunch(g_.indptr, g_.indices, x, y, w=layer.fc_neigh.weight, ep_scale=ep_scale,
-                                                     ep_shift=ep_shift if tailed else layer.fc_neigh.bias, relu=relu, w_packed=wp))
-                    try:
-                        it = iter(dataloader)
-                        k = 0
-                        for input_nodes, output_nodes, blocks in it:
-                            if input_nodes is not None:
-                                break
-                            block = blocks[0]
-                            s_, e_ = block.dst_range
-                            with torch.cuda.stream(pool[k % len(pool)]) if pool else contextlib.nullcontext():
-                                if launch is not None:
-                                    launch(s_, e_)
-                                elif xp is not None:
-                                    ops.spmm(block.indptr, block.indices, xp, e_ - s_, ops.AGG_SAGE_GCN, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu,
-                                             out=y[s_:e_], x_self=xp[s_:e_])
-                                else:
-                                    layer(block, (x, x[s_:e_]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, w_packed=wp, out=y[s_:e_])
-                            k += 1
-                        else:
-                            for st in pool:
-                                cur.wait_stream(st)
-                            x = y
-                            continue
-                    finally:
-                        if engine:
-                            dataloader.global_blocks = False
-                    for st in pool:
-                        cur.wait_stream(st)
-                    for input_nodes, output_nodes, blocks in dataloader:
-                        block = blocks[0].int().to(x.device)
-                        h = ops.gather_rows(x, input_nodes)                              # feats[input_nodes]
-                        h = layer(block, (h, h[: block.num_dst_nodes()]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, w_packed=wp)
-                        if post_ln:
-                            h = _eval_tail(self, l, h)
-                        ops.scatter_rows(h, output_nodes, y)                             # y[output_nodes] = h
-                x = y
+            for l in range(self.num_layers):
+                x, projected = self._whole_graph_layer(l, g, x, projected, agg=agg if l == 0 else None)
+                if l == 0 and agg_ent is not None:            # (remembered only once the launch that fills it has been issued)
+                    self.__dict__["_agg_x"] = agg_ent
             return x
 
+    def _inference_chunked(self, dataloader, x):
+        """The reference's sweep (models.py:129-145): global-id blocks where the loader has them and no LayerNorm follows, else its literal loop."""
+        for l, layer in enumerate(self.layers):
+            tail = self._layer_tail(l)
+            y = ops.feat_empty(x.shape[0], self.hidden_dim if l != self.num_layers - 1 else self.output_dim, x.device, zero=True)
+            wp = ops.pack_weight(layer.fc_neigh.weight) if layer.fused_eligible() else None     # once per layer, not per chunk
+            engine = hasattr(dataloader, "global_blocks") and not tail[3]
+            (self._engine_layer if engine else self._literal_layer)(l, dataloader, x, y, tail, wp)
+            x = y
+        return x
 
-SWEEP_STREAMS = int(__import__("os").environ.get("GLNN_SWEEP_STREAMS", "8"))      # streams of the engine-mode chunked sweep (<= 1: the caller's stream only)
+    def _engine_layer(self, l, dataloader, x, y, tail, wp):
+        """Layer l over global-id row-range blocks: the conv gathers its source rows from x itself and writes its rows of y (no feats[input_nodes],
+        no y[output_nodes] = h), and a layer that projects first projects x once, not per chunk.  Chunks are independent and SHORT (4096 rows:
+        128 tiles on 256 CUs), so they go round-robin on SWEEP_STREAMS streams, through ONE prepared call where the layer is a single launch."""
+        layer, g = self.layers[l], getattr(dataloader, "graph", None)
+        ep_scale, ep_shift, relu, _ = tail
+        xp = ops.gemm(x, layer.fc_neigh.weight) if layer._in_feats > layer._out_feats else None
+        if g is not None and (xp is not None or layer.fused_eligible()):
+            tailed = ep_scale is not None or ep_shift is not None or relu
+            launch = (ops.RowRangeLaunch(g.indptr, g.indices, xp, y, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu) if xp is not None else
+                      ops.RowRangeLaunch(g.indptr, g.indices, x, y, w=layer.fc_neigh.weight, ep_scale=ep_scale,
+                                         ep_shift=ep_shift if tailed else layer.fc_neigh.bias, relu=relu, w_packed=wp))
+            chunk = lambda s, e, block: launch(s, e)
+        elif xp is not None:
+            chunk = lambda s, e, block: ops.spmm(block.indptr, block.indices, xp, e - s, ops.AGG_SAGE_GCN, ep_scale=ep_scale, ep_shift=ep_shift,
+                                                 relu=relu, out=y[s:e], x_self=xp[s:e])
+        else:
+            chunk = lambda s, e, block: layer(block, (x, x[s:e]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, w_packed=wp, out=y[s:e])
+        with _chunk_sweep(dataloader, x.device, _sweep_streams(x.device)) as chunks:
+            for _, s, e, block in chunks:
+                chunk(s, e, block)
+
+    def _literal_layer(self, l, dataloader, x, y, tail, wp):
+        """Layer l as the reference's loop writes it (models.py:133-145): block build, feats[input_nodes], conv, y[output_nodes] = h."""
+        layer, (ep_scale, ep_shift, relu, post_ln) = self.layers[l], tail
+        for input_nodes, output_nodes, blocks in dataloader:
+            block = blocks[0].int().to(x.device)
+            h = ops.gather_rows(x, input_nodes)                              # feats[input_nodes]
+            h = layer(block, (h, h[: block.num_dst_nodes()]), ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, w_packed=wp)
+            if post_ln:
+                h = _eval_tail(self, l, h)
+            ops.scatter_rows(h, output_nodes, y)                             # y[output_nodes] = h
+
+
+@contextlib.contextmanager
+def _chunk_sweep(dataloader, device, pool):
+    """`with _chunk_sweep(...) as chunks: for k, s, e, block in chunks: <launch rows [s, e)>`: the loader hands out global-id row-range blocks
+    for the length of the `with` (switched back also when a chunk raises); chunk k runs with pool[k % len(pool)] as the current stream (an
+    empty pool: the caller's); the pool waits for the caller's stream before the first chunk, the caller's for the pool after the last."""
+    def chunks():
+        for k, (input_nodes, _, blocks) in enumerate(dataloader):
+            if input_nodes is not None:
+                raise RuntimeError(f"SAGE.inference: {type(dataloader).__name__} has a global_blocks attribute and ignores it: its chunks carry input_nodes")
+            s, e = blocks[0].dst_range
+            if pool:
+                with torch.cuda.stream(pool[k % len(pool)]):
+                    yield k, s, e, blocks[0]
+            else:
+                yield k, s, e, blocks[0]
+    cur = torch.cuda.current_stream(device)
+    for st in pool:
+        st.wait_stream(cur)
+    dataloader.global_blocks = True
+    it = chunks()
+    try:
+        yield it
+    finally:
+        it.close()                # (a chunk that raised left the generator inside its stream context: leave it now, not at collection)
+        dataloader.global_blocks = False
+    for st in pool:
+        cur.wait_stream(st)
+
+
+SWEEP_STREAMS = int(os.environ.get("GLNN_SWEEP_STREAMS", "8"))      # streams of the engine-mode chunked sweep (<= 1: the caller's stream only)
 _SWEEP_POOLS = {}
 
 
