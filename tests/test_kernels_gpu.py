@@ -22,7 +22,7 @@ def g2d(indptr, indices):
 
 
 # ------------------------------------------------------------------------------------------- K1/K2
-@pytest.mark.parametrize("d", [1, 7, 16, 40, 47, 64, 100, 128, 256, 300])
+@pytest.mark.parametrize("d", [1, 7, 16, 20, 32, 40, 47, 64, 100, 128, 256, 300])      # 20, 32: both ends of LPR 8
 def test_spmm_sage_gcn_vs_oracle(d):
     from glnn_amd import ops
     n = 3000
@@ -58,6 +58,7 @@ def test_spmm_block_ndst_lt_nsrc():
 
 
 @pytest.mark.parametrize("d,use_rs,use_cs", [(64, True, True), (7, True, False), (128, False, True), (33, False, False),
+                                              (24, True, True), (24, False, False), (9, False, True), (100, True, False), (200, True, True), (200, False, False),      # every LPR with and without column scales
                                               (700, True, True), (3703, False, False)])      # > 256 columns: one launch, blockIdx.y = column tile
 def test_spmm_sum_scaled_vs_oracle(d, use_rs, use_cs):
     from glnn_amd import ops
