@@ -82,6 +82,9 @@ SIGNATURES = {
                                c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "glnn_dropout_mask_u8": [c_i64, c_int, c_f32, c_u32, c_vp, c_vp],
     "glnn_sample_neighbors": [c_vp, c_vp, c_vp, c_i64, c_int, c_u32, c_vp, c_vp, c_vp],
+    "glnn_sample_csr_workspace_bytes": [c_i64],
+    "glnn_sample_csr_indptr": [c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp],
+    "glnn_sample_csr_fill": [c_vp, c_vp, c_i64, c_i64, c_vp, c_int, c_u32, c_vp, c_vp],
     "glnn_block_workspace_bytes": [c_i64, c_i64],
     "glnn_block_build": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "glnn_block_build_ids": [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp],
@@ -282,6 +285,7 @@ def lib():
         h.glnn_packed_weight_floats.restype = c_i64
         h.glnn_struct_bytes.restype = c_i64
         h.glnn_block_workspace_bytes.restype = c_i64
+        h.glnn_sample_csr_workspace_bytes.restype = c_i64
         h.glnn_csr_transpose_workspace_bytes.restype = c_i64
         h.glnn_induced_subgraph_workspace_bytes.restype = c_i64
         h.glnn_layernorm_bwd_workspace_floats.restype = c_i64

@@ -71,6 +71,12 @@ def get_teacher_args(argv=None):
     # bfloat16 = the gathered matrices stored as bf16, arithmetic and the saved log-probs fp32
     p.add_argument("--inference_dtype", type=str, default="float32", choices=["float32", "bfloat16"],
                    help="Activation storage of the SAGE teacher's evaluation forward (bfloat16: SAGE only)")
+    # not a reference flag: neighbour-sampled evaluation of the SAGE teacher (conf key `inference_fan_out`, read by run_transductive /
+    # run_inductive; docs/SAMPLED_INFERENCE_SEMANTICS.md): every evaluation forward aggregates at most this many uniformly drawn in-edges
+    # per row and layer, drawn under --seed.  Empty (the default) = off: the full-neighbour forward
+    p.add_argument("--inference_fan_out", type=str, default="",
+                   help="Per-layer fan-out of the SAGE teacher's evaluation forwards, e.g. 15,15 (length = --num_layers, values in [1, 64]; "
+                        "empty: full-neighbour)")
     # not a reference flag: the SAGE teacher's aggregator (conf key `sage_aggregator`, read by Model): "gcn" is what the reference builds,
     # "mean" dgl's default form with a separate fc_self (docs/SAGE_MEAN_SEMANTICS.md; trained through the differentiable ops, fp32 inference)
     p.add_argument("--sage_aggregator", type=str, default="gcn", choices=["gcn", "mean"],
@@ -114,6 +120,17 @@ def get_teacher_args(argv=None):
     if args.sage_mean_step != "autograd" and ("SAGE" not in args.teacher or args.sage_aggregator != "mean"):
         p.error(f"--sage_mean_step {args.sage_mean_step} applies to --teacher SAGE --sage_aggregator mean only "
                 f"(got --teacher {args.teacher} --sage_aggregator {args.sage_aggregator})")
+    if args.inference_fan_out.strip():
+        if teacher_kind(args.teacher) != "sage":
+            p.error(f"--inference_fan_out applies to the SAGE teacher only (got --teacher {args.teacher})")
+        try:
+            fan_out = [int(f) for f in args.inference_fan_out.split(",")]
+        except ValueError:
+            p.error(f"--inference_fan_out must be a comma-separated list of integers (got {args.inference_fan_out!r})")
+        if len(fan_out) != args.num_layers:
+            p.error(f"--inference_fan_out names {len(fan_out)} layers, --num_layers is {args.num_layers} (got {args.inference_fan_out!r})")
+        if not all(1 <= f <= 64 for f in fan_out):
+            p.error(f"--inference_fan_out values must be in [1, 64] (got {args.inference_fan_out!r})")
     if args.inference_dtype != "float32" and "SAGE" not in args.teacher:
         p.error(f"--inference_dtype {args.inference_dtype} is implemented for the SAGE teacher only (got --teacher {args.teacher})")
     if args.sage_aggregator != "gcn" and "SAGE" not in args.teacher:

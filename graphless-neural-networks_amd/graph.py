@@ -161,6 +161,28 @@ class CSRGraph:
             self._cache["rev"] = CSRGraph(indptr, dst_all[order].to(torch.int32), self.n_src, self.n_dst)
         return self._cache["rev"]
 
+    def sampled(self, fanout, seed):
+        """A new CSRGraph of the same n_dst and n_src that keeps at most `fanout` in-edges per row, drawn uniformly without replacement
+        (docs/SAMPLED_INFERENCE_SEMANTICS.md): row v is what glnn_sample_neighbors gives position v of seeds = arange(n_dst) under
+        `seed`, rows of at most `fanout` entries in row order.  The sampled indptr and its edge count depend on (graph, fanout) only and
+        are cached here per fan-out -- the one host read of nnz happens once per (graph, fanout); a call runs the fill launch alone.
+        The result has caches and ndata of its own (the cached indptr tensor is shared read-only, as row_range shares indices); the tile
+        order of its whole-graph launches is switched off, since no row of it is longer than `fanout`."""
+        from . import ops
+        ops._check_fanout("CSRGraph.sampled", fanout)
+        if not self.indptr.is_cuda:
+            raise RuntimeError("CSRGraph.sampled: the sampled graph is built on the GPU (move the graph with g.to(device))")
+        key = ("sampled_indptr", fanout)
+        if key not in self._cache:
+            s_indptr = ops.sample_csr_indptr(self.indptr, self.n_dst, fanout)
+            self._cache[key] = (s_indptr, int(s_indptr[-1].item()))
+        s_indptr, nnz = self._cache[key]
+        s_indices = ops.sample_csr_fill(self.indptr, self.indices, self.n_dst, self.n_src, s_indptr, nnz, fanout, int(seed) & 0xFFFFFFFF)
+        g = CSRGraph(s_indptr, s_indices, self.n_dst, self.n_src)
+        g._nnz = nnz
+        g._cache["tile_order"] = None
+        return g
+
     def row_range(self, start, stop):
         """Destination rows [start, stop) with ALL source columns kept (node-range shard / eval chunk)."""
         lo, hi = int(self.indptr[start].item()), int(self.indptr[stop].item())

@@ -63,6 +63,26 @@ def _norm_of(module, l):
     return module.norms[l] if module.norm_type != "none" else None
 
 
+def drop_hash(seed, row, col):
+    """csrc/glnn_common.h's drop_hash on host integers: lowbias32 of seed ^ row * 0x9E3779B1 ^ (col * 0x85EBCA77 + 0x632BE5AB), mod 2^32."""
+    m = 0xFFFFFFFF
+    h = ((int(seed) & m) ^ (int(row) * 0x9E3779B1 & m) ^ ((int(col) * 0x85EBCA77 + 0x632BE5AB) & m)) & m
+    h ^= h >> 16
+    h = h * 0x7FEB352D & m
+    h ^= h >> 15
+    h = h * 0x846CA68B & m
+    return h ^ (h >> 16)
+
+
+SAMPLE_SEED_SALT = 0xFA17
+
+
+def sample_layer_seed(sample_seed, l):
+    """The seed layer l's sampled graph is drawn under in SAGE.inference(fan_out=..., sample_seed=...): drop_hash(sample_seed, l, 0xFA17).
+    Each layer draws independently, as dgl's multi-layer sampler does (docs/SAMPLED_INFERENCE_SEMANTICS.md)."""
+    return drop_hash(sample_seed, l, SAMPLE_SEED_SALT)
+
+
 def _eval_tail(module, l, z, relu=True):
     """Eval-mode `norms[l] -> relu -> dropout` of a hidden layer on a materialised z (relu=False: GCN's `norms[l] -> dropout`):
     one glnn_act_fwd_f32 / glnn_norm_drop_fwd_f32 / glnn_layernorm_fwd_f32."""
@@ -433,7 +453,72 @@ class SAGE(nn.Module):
             for _, s, e, block in chunks:
                 chunk(s, e, block)
 
-    def inference(self, dataloader, feats, whole_graph=True, dtype=torch.float32):
+    def _check_fan_out(self, fan_out, dataloader, whole_graph):
+        """The refusals of `inference(fan_out=...)`, each naming fan_out; returns the fan-outs as a list of ints."""
+        if isinstance(fan_out, (str, bytes)) or not hasattr(fan_out, "__len__"):
+            raise ValueError(f"SAGE.inference: fan_out must be a list of {self.num_layers} integers, one per layer (got {fan_out!r})")
+        fan_out = list(fan_out)
+        if len(fan_out) != self.num_layers:
+            raise ValueError(f"SAGE.inference: fan_out names {len(fan_out)} layers, the encoder has {self.num_layers} (got {fan_out!r})")
+        for f in fan_out:
+            if isinstance(f, bool) or not isinstance(f, int):
+                raise ValueError(f"SAGE.inference: fan_out must hold integers (got {f!r} in {fan_out!r})")
+            if not 1 <= f <= 64:
+                raise ValueError(f"SAGE.inference: every fan_out value must be in [1, 64] (got {f} in {fan_out!r})")
+        if not whole_graph:
+            raise NotImplementedError("SAGE.inference(fan_out=...): the whole-graph sweep only (whole_graph=True); the chunked and literal "
+                                      "sweeps are full-neighbour")
+        if getattr(dataloader, "graph", None) is None:
+            raise NotImplementedError("SAGE.inference(fan_out=...): a loader over a resident graph (one that sweeps every node in id order "
+                                      "and carries `.graph`); this one has none")
+        return fan_out
+
+    def inference_over(self, graphs, feats, dtype=torch.float32):
+        """The whole-graph forward with layer l aggregating over graphs[l] (CSRGraphs of the same rows: what `inference(fan_out=...)` runs
+        over the sampled graphs).  The kernels and forms of the full-neighbour sweep, and none of its state: plain allocations, no placed
+        buffers, no placement by trial, no kept layer-1 aggregate -- nothing is read from or written to the encoder's caches."""
+        _need_hip(feats, "SAGE.inference_over")
+        if len(graphs) != self.num_layers:
+            raise ValueError(f"SAGE.inference_over: {len(graphs)} graphs for {self.num_layers} layers")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"SAGE.inference_over: dtype must be torch.float32 or torch.bfloat16, not {dtype}")
+        mean = self.aggregator_type != "gcn"
+        if mean:
+            _check_tail(self)
+            if dtype != torch.float32:
+                raise NotImplementedError("SAGE.inference(dtype=torch.bfloat16): bf16 activation storage is implemented for the 'gcn' aggregator "
+                                          "only, not for aggregator_type 'mean'")
+        elif dtype == torch.bfloat16 and self.norm_type == "layer":
+            raise NotImplementedError("SAGE.inference(dtype=torch.bfloat16): LayerNorm teachers are fp32 only (the per-row statistics pass "
+                                      "is not part of the bf16 storage path)")
+        with torch.no_grad():
+            if mean:
+                x = ops.as_feat(feats)
+                for l, (layer, g) in enumerate(zip(self.layers, graphs)):
+                    tail = self._layer_tail(l)
+                    y = layer(g, (x, x[:g.num_dst_nodes()]), ep_scale=tail[0], ep_shift=tail[1], relu=tail[2])
+                    x = _eval_tail(self, l, y) if tail[3] else y
+                return x
+            projected = None
+            if dtype == torch.bfloat16:
+                first = self.layers[0]             # (as _inference_bf16: gathered features are bf16, projected-first ones stay fp32)
+                if first._in_feats <= first._out_feats:
+                    x = ops.as_bf16_feat(feats) if feats.dtype == torch.bfloat16 else ops.to_bf16(feats)
+                else:
+                    x = feats.float() if feats.dtype == torch.bfloat16 else feats
+                for l, g in enumerate(graphs):
+                    x, projected = self._whole_graph_layer_bf16(l, g, x, projected)
+                return x
+            x = ops.as_feat(feats)
+            for l, g in enumerate(graphs):
+                x, projected = self._whole_graph_layer(l, g, x, projected, place=False)
+            return x
+
+    def sampled_graphs(self, g, fan_out, sample_seed=0):
+        """[g.sampled(fan_out[l], seed_l)] with seed_l = sample_layer_seed(sample_seed, l): one independent draw per layer."""
+        return [g.sampled(f, sample_layer_seed(sample_seed, l)) for l, f in enumerate(fan_out)]
+
+    def inference(self, dataloader, feats, whole_graph=True, dtype=torch.float32, fan_out=None, sample_seed=0):
         """Layer-wise full-neighbour inference (reference models.py:121-148).
 
         `dataloader` is a glnn_amd.graph.FullNeighborLoader.  whole_graph=True aggregates every destination row
@@ -443,7 +528,16 @@ class SAGE(nn.Module):
 
         dtype=torch.bfloat16: the whole-graph sweep with bf16 activation STORAGE (_whole_graph_layer_bf16) -- the gathered matrices move
         half the bytes; arithmetic stays fp32 and the returned logits are fp32.  `feats` may be fp32 (cast once per call) or bf16.  Its
-        buffers are plain allocations (no ops.placed_for_gather placement).  Not for whole_graph=False or LayerNorm teachers."""
+        buffers are plain allocations (no ops.placed_for_gather placement).  Not for whole_graph=False or LayerNorm teachers.
+
+        fan_out=[f_0, .., f_{L-1}] (docs/SAMPLED_INFERENCE_SEMANTICS.md): neighbour-sampled inference -- layer l aggregates over
+        g.sampled(f_l, sample_layer_seed(sample_seed, l)), at most f_l uniformly drawn in-edges per row, through `inference_over`: both
+        aggregators, bf16 storage where the full form has it, and none of the full form's caches.  fan_out=None: the full-neighbour code
+        path, call for call."""
+        if fan_out is not None:
+            fan_out = self._check_fan_out(fan_out, dataloader, whole_graph)
+            _need_hip(feats, "SAGE.inference")
+            return self.inference_over(self.sampled_graphs(dataloader.graph, fan_out, sample_seed), feats, dtype)
         _need_hip(feats, "SAGE.inference")
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"SAGE.inference: dtype must be torch.float32 or torch.bfloat16, not {dtype}")
@@ -887,9 +981,15 @@ class Model(nn.Module):
             return self.encoder(feats)
         return self.encoder(data, feats)
 
-    def inference(self, data, feats, dtype=torch.float32):
-        """dtype=torch.bfloat16: bf16 activation storage, the SAGE teacher's whole-graph forward only (SAGE.inference)."""
+    def inference(self, data, feats, dtype=torch.float32, fan_out=None, sample_seed=0):
+        """dtype=torch.bfloat16: bf16 activation storage, the SAGE teacher's whole-graph forward only (SAGE.inference).
+        fan_out / sample_seed: neighbour-sampled inference, the SAGE teacher only (SAGE.inference; docs/SAMPLED_INFERENCE_SEMANTICS.md)."""
         kind = self.kind
+        if fan_out is not None:
+            if kind != "sage":
+                raise NotImplementedError(f"{self.model_name}.inference(fan_out={fan_out!r}): neighbour-sampled inference is implemented "
+                                          "for the SAGE teacher only (the other teachers run on the whole graph)")
+            return self.encoder.inference(data, feats, dtype=dtype, fan_out=fan_out, sample_seed=sample_seed)
         if dtype != torch.float32:
             row = BY_KIND[kind]
             if row.bf16:

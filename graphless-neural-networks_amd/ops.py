@@ -1233,6 +1233,49 @@ def _i32(n, device):
     return torch.empty(max(int(n), 1), dtype=torch.int32, device=device)[:int(n)]
 
 
+def _check_fanout(name, fanout):
+    if isinstance(fanout, bool) or not isinstance(fanout, int) or not 1 <= fanout <= 64:
+        raise ValueError(f"{name}: fanout must be an integer in [1, 64] (got {fanout!r})")
+
+
+def sample_csr_indptr(indptr, n_dst, fanout):
+    """glnn_sample_csr_indptr: the indptr [n_dst + 1] of the graph's sampled neighbourhood, the exclusive prefix sum of min(deg, fanout).
+    It depends on the graph and the fan-out only (no seed); no host read."""
+    _need_cuda(indptr)
+    _check_fanout("sample_csr_indptr", fanout)
+    n_dst = int(n_dst)
+    if indptr.dtype != torch.int64 or indptr.dim() != 1 or not indptr.is_contiguous() or indptr.numel() < n_dst + 1:
+        raise ValueError("sample_csr_indptr: indptr must be a contiguous int64 vector of at least n_dst + 1 entries")
+    out = torch.empty(n_dst + 1, dtype=torch.int64, device=indptr.device)
+    wsb = int(_lib.lib().glnn_sample_csr_workspace_bytes(n_dst))
+    ws = torch.empty(max((wsb + 7) // 8, 1), dtype=torch.int64, device=indptr.device)
+    with _Timed("sample_csr_indptr", n_dst=n_dst, fanout=fanout):
+        rc = _lib.lib().glnn_sample_csr_indptr(_p(indptr), n_dst, fanout, _p(out), _p(ws), ws.numel() * 8, _stream())
+    _lib.check(rc, "glnn_sample_csr_indptr")
+    return out
+
+
+def sample_csr_fill(indptr, indices, n_dst, n_src, out_indptr, nnz, fanout, rng_seed):
+    """glnn_sample_csr_fill: the indices [nnz] (int32) of the sampled neighbourhood whose indptr is out_indptr = sample_csr_indptr(indptr,
+    n_dst, fanout) and whose edge count is nnz = out_indptr[n_dst] (the caller's host value).  Row v = what sample_neighbors gives position
+    v of seeds = arange(n_dst) under rng_seed, compacted."""
+    _need_cuda(indptr, indices, out_indptr)
+    _check_fanout("sample_csr_fill", fanout)
+    _check_csr(indptr, indices, "sample_csr_fill")
+    n_dst, nnz = int(n_dst), int(nnz)
+    if out_indptr.dtype != torch.int64 or out_indptr.dim() != 1 or not out_indptr.is_contiguous() or out_indptr.numel() != n_dst + 1 \
+            or indptr.numel() < n_dst + 1:
+        raise ValueError("sample_csr_fill: indptr / out_indptr must be contiguous int64 vectors of n_dst + 1 entries")
+    out = _i32(nnz, indptr.device)
+    if nnz == 0:              # (no row has an in-edge: nothing to fill)
+        return out
+    with _Timed("sample_csr_fill", n_dst=n_dst, fanout=fanout, nnz=nnz):
+        rc = _lib.lib().glnn_sample_csr_fill(_p(indptr), _p(indices), n_dst, int(n_src), _p(out_indptr), fanout, int(rng_seed) & 0xFFFFFFFF,
+                                             _p(out), _stream())
+    _lib.check(rc, "glnn_sample_csr_fill")
+    return out
+
+
 def block_build(seeds, graph_indptr=None, graph_indices=None, smp_src=None, smp_cnt=None, nnz_cap=None, want_global=False, n_nodes=0,
                 global_only=False):
     """glnn_block_build_ids: one 1-hop block over the destination nodes `seeds` (int64 device vector).  n_nodes: the size of the id

@@ -193,11 +193,29 @@ def inference_dtype(conf):
     return INFERENCE_DTYPES[conf.get("inference_dtype", "float32")]
 
 
-def evaluate(model, data, feats, labels, criterion, evaluator, idx_eval=None, dtype=torch.float32):
-    """reference train_and_eval.py:89-105.  dtype: Model.inference's activation storage (torch.bfloat16: SAGE teachers only)."""
+def inference_fan_out(conf):
+    """The per-layer fan-out of a SAGE teacher's evaluation forwards (--inference_fan_out / conf key `inference_fan_out`: "15,15", a list
+    of integers, or absent / empty = full-neighbour): a list of ints or None.  Its values are checked by SAGE.inference."""
+    v = conf.get("inference_fan_out")
+    if v is None or (isinstance(v, str) and not v.strip()):
+        return None
+    if isinstance(v, str):
+        try:
+            return [int(f) for f in v.split(",")]
+        except ValueError:
+            raise ValueError(f"inference_fan_out: a comma-separated list of integers, one per layer (got {v!r})") from None
+    return list(v) if hasattr(v, "__len__") else [v]
+
+
+def evaluate(model, data, feats, labels, criterion, evaluator, idx_eval=None, dtype=torch.float32, fan_out=None, sample_seed=0):
+    """reference train_and_eval.py:89-105.  dtype: Model.inference's activation storage (torch.bfloat16: SAGE teachers only).
+    fan_out / sample_seed: Model.inference's neighbour-sampled form (SAGE teachers only); None = the full-neighbour forward."""
     model.eval()
     with torch.no_grad():
-        logits = model.inference(data, feats, dtype=dtype) if dtype != torch.float32 else model.inference(data, feats)
+        kw = {} if dtype == torch.float32 else {"dtype": dtype}
+        if fan_out is not None:
+            kw.update(fan_out=fan_out, sample_seed=sample_seed)
+        logits = model.inference(data, feats, **kw)
         out = ops.log_softmax(logits)
         if idx_eval is None:
             loss = _apply_criterion(criterion, out, labels)
@@ -228,6 +246,13 @@ def serve_dtype(conf):
 def serve_fused(conf):
     """Whether the bfloat16 evaluation passes run the one-launch form of the chain (--serve_fused, default False)."""
     return bool(conf.get("serve_fused", False))
+
+
+def _log_fan_out(logger, g, fan_out):
+    """Once per run: the evaluation fan-out and the edges each layer's sampled graph keeps (sum of min(in-degree, fan-out)) of the run's graph."""
+    deg = g.in_degrees()
+    kept = [int(torch.clamp(deg, max=int(f)).sum().item()) for f in fan_out]
+    logger.info(f"inference_fan_out: {fan_out} -- sampled edges per layer {kept} of {g.number_of_edges()}")
 
 
 def evaluate_mini_batch(model, feats, labels, criterion, batch_size, evaluator, idx_eval=None, *, fused=False, dtype=torch.float32):
@@ -300,6 +325,11 @@ def run_transductive(conf, model, g, feats, labels, indices, criterion, evaluato
     device = conf["device"]
     batch_size = conf["batch_size"]
     inf_dtype = inference_dtype(conf)          # --inference_dtype: the activation storage of the SAGE teacher's evaluation forward
+    # --inference_fan_out: every evaluation forward of a SAGE teacher over sampled neighbourhoods, drawn under the run's seed (reproducible)
+    inf_kw = dict(dtype=inf_dtype)
+    if model.kind == "sage" and inference_fan_out(conf) is not None:
+        inf_kw.update(fan_out=inference_fan_out(conf), sample_seed=conf["seed"])
+        _log_fan_out(logger, g, inf_kw["fan_out"])
     idx_train, idx_val, idx_test = indices
     feats, labels = feats.to(device), labels.to(device)
     idx_train, idx_val, idx_test = idx_train.to(device), idx_val.to(device), idx_test.to(device)
@@ -335,7 +365,7 @@ def run_transductive(conf, model, g, feats, labels, indices, criterion, evaluato
             _, l_va, s_va = evaluate_mini_batch(model, feats_val, labels_val, criterion, batch_size, evaluator)
             _, l_te, s_te = evaluate_mini_batch(model, feats_test, labels_test, criterion, batch_size, evaluator)
         else:
-            out, l_tr, s_tr = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_train, dtype=inf_dtype)
+            out, l_tr, s_tr = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_train, **inf_kw)
             l_va, s_va = criterion(out[idx_val], labels[idx_val]).item(), evaluator(out[idx_val], labels[idx_val])
             l_te, s_te = criterion(out[idx_test], labels[idx_test]).item(), evaluator(out[idx_test], labels[idx_test])
         return [l_tr, l_va, l_te, s_tr, s_va, s_te], s_va, f"s_train: {s_tr:.4f} | s_val: {s_va:.4f} | s_test: {s_te:.4f}"
@@ -344,7 +374,7 @@ def run_transductive(conf, model, g, feats, labels, indices, criterion, evaluato
     if is_mlp:
         out, _, score_val = evaluate_mini_batch(model, feats, labels, criterion, batch_size, evaluator, idx_val)
     else:
-        out, _, score_val = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_val, dtype=inf_dtype)
+        out, _, score_val = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_val, **inf_kw)
     score_test = evaluator(out[idx_test], labels[idx_test])
     logger.info(f"Best valid model at epoch: {best_epoch: 3d}, score_val: {score_val :.4f}, score_test: {score_test :.4f}")
     return out, score_val, score_test
@@ -393,6 +423,11 @@ def run_inductive(conf, model, g, feats, labels, indices, criterion, evaluator, 
     device = conf["device"]
     batch_size = conf["batch_size"]
     inf_dtype = inference_dtype(conf)          # --inference_dtype: the activation storage of the SAGE teacher's evaluation forward
+    # --inference_fan_out: every evaluation forward of a SAGE teacher over sampled neighbourhoods, drawn under the run's seed (reproducible)
+    inf_kw = dict(dtype=inf_dtype)
+    if model.kind == "sage" and inference_fan_out(conf) is not None:
+        inf_kw.update(fan_out=inference_fan_out(conf), sample_seed=conf["seed"])
+        _log_fan_out(logger, g, inf_kw["fan_out"])
     obs_idx_train, obs_idx_val, obs_idx_test, idx_obs, idx_test_ind = [i.to(device) for i in indices]
     feats, labels = feats.to(device), labels.to(device)
     obs_feats, obs_labels = feats[idx_obs], labels[idx_obs]
@@ -432,10 +467,10 @@ def run_inductive(conf, model, g, feats, labels, indices, criterion, evaluator, 
             _, l_tt, s_tt = evaluate_mini_batch(model, feats_tt, labels_tt, criterion, batch_size, evaluator)
             _, l_ti, s_ti = evaluate_mini_batch(model, feats_ti, labels_ti, criterion, batch_size, evaluator)
         else:
-            obs_out, l_tr, s_tr = evaluate(model, obs_data_eval, obs_feats, obs_labels, criterion, evaluator, obs_idx_train, dtype=inf_dtype)
+            obs_out, l_tr, s_tr = evaluate(model, obs_data_eval, obs_feats, obs_labels, criterion, evaluator, obs_idx_train, **inf_kw)
             l_va, s_va = criterion(obs_out[obs_idx_val], obs_labels[obs_idx_val]).item(), evaluator(obs_out[obs_idx_val], obs_labels[obs_idx_val])
             l_tt, s_tt = criterion(obs_out[obs_idx_test], obs_labels[obs_idx_test]).item(), evaluator(obs_out[obs_idx_test], obs_labels[obs_idx_test])
-            _, l_ti, s_ti = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_test_ind, dtype=inf_dtype)
+            _, l_ti, s_ti = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_test_ind, **inf_kw)
         return ([l_tr, l_va, l_tt, l_ti, s_tr, s_va, s_tt, s_ti], s_va,
                 f"s_train: {s_tr:.4f} | s_val: {s_va:.4f} | s_tt: {s_tt:.4f} | s_ti: {s_ti:.4f}")
 
@@ -444,8 +479,8 @@ def run_inductive(conf, model, g, feats, labels, indices, criterion, evaluator, 
         obs_out, _, score_val = evaluate_mini_batch(model, obs_feats, obs_labels, criterion, batch_size, evaluator, obs_idx_val)
         out, _, score_test_ind = evaluate_mini_batch(model, feats, labels, criterion, batch_size, evaluator, idx_test_ind)
     else:
-        obs_out, _, score_val = evaluate(model, obs_data_eval, obs_feats, obs_labels, criterion, evaluator, obs_idx_val, dtype=inf_dtype)
-        out, _, score_test_ind = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_test_ind, dtype=inf_dtype)
+        obs_out, _, score_val = evaluate(model, obs_data_eval, obs_feats, obs_labels, criterion, evaluator, obs_idx_val, **inf_kw)
+        out, _, score_test_ind = evaluate(model, data_eval, feats, labels, criterion, evaluator, idx_test_ind, **inf_kw)
     score_test_tran = evaluator(obs_out[obs_idx_test], obs_labels[obs_idx_test])
     out[idx_obs] = obs_out
     logger.info(f"Best valid model at epoch: {best_epoch :3d}, score_val: {score_val :.4f}, score_test_tran: {score_test_tran :.4f}, score_test_ind: {score_test_ind :.4f}")

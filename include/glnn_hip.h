@@ -680,6 +680,25 @@ GLNN_API int glnn_sample_neighbors(const int64_t* indptr, const int32_t* indices
                                    int64_t n_seeds, int fanout, uint32_t rng_seed, int32_t* out_src,
                                    int32_t* out_cnt, void* stream);
 
+/* The sampled neighbourhood of ALL n_dst rows of a resident CSR as a CSR of its own (csrc/sample_csr.hip;
+ * docs/SAMPLED_INFERENCE_SEMANTICS.md): what SAGE.inference(fan_out=...) aggregates over.  Entries added, none changed.
+ *
+ * glnn_sample_csr_indptr: out_indptr [n_dst + 1] = exclusive prefix sum of min(deg(v), fanout) -- it depends on the graph and the
+ *   fan-out only, never on a seed; integer work, the same bits on every run.  One call, no host synchronisation.
+ *   workspace: glnn_sample_csr_workspace_bytes(n_dst) bytes, 8-byte aligned (not read when n_dst == 0).
+ * glnn_sample_csr_fill: out_indices [out_indptr[n_dst]] int32, with out_indptr from the call above under the SAME fanout.  Row v holds
+ *   exactly what glnn_sample_neighbors gives seed-list position i = v of seeds = arange(n_dst): a row of at most `fanout` entries
+ *   is copied in row order; a longer one gets indices[indptr[v] + picked[s]] in slot s, with Floyd's picks: for s = 0 .. fanout-1,
+ *   j = deg - fanout + s, t = ((uint64_t)drop_hash(rng_seed, v, s) * (j + 1)) >> 32, picked[s] = j if t was picked before, else t.
+ *   The draw is keyed by the global row id v: a row's picks do not depend on which other rows are in the launch.
+ * Both: fanout in [1, 64], n_dst and n_src below 2^31, no null pointer -- else GLNN_ERR_INVALID_ARG with nothing launched and a
+ * glnn_last_error text that names the entry; n_dst == 0 is GLNN_OK. */
+GLNN_API int64_t glnn_sample_csr_workspace_bytes(int64_t n_dst);
+GLNN_API int glnn_sample_csr_indptr(const int64_t* indptr, int64_t n_dst, int fanout, int64_t* out_indptr, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
+GLNN_API int glnn_sample_csr_fill(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src,
+                                  const int64_t* out_indptr, int fanout, uint32_t rng_seed, int32_t* out_indices, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Block construction for mini-batch teacher training / chunked inference: what dgl.dataloading.NodeDataLoader does on
  * the CPU per batch in the reference (train_and_eval.py:176-205; blocks consumed at :41 and models.py:109,134-137),
