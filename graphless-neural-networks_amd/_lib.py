@@ -28,6 +28,10 @@ SIGNATURES = {
                            c_int, c_vp, c_i64, c_int, c_vp],
     "glnn_sage_fused_bf16": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_int, c_vp,
                              c_i64, c_int, c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp],
+    "glnn_quant_rows_i8": [c_vp, c_i64, c_i64, c_int, c_vp, c_i64, c_vp],
+    "glnn_spmm_sage_gcn_i8": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_vp],
+    "glnn_sage_fused_i8": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_int, c_vp,
+                           c_i64, c_vp, c_int, c_vp, c_i64, c_vp, c_vp],
     "glnn_hub_row_threshold": [],
     "glnn_hub_segment_edges": [],
     "glnn_spmm_csr_plan_f32": [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,

@@ -68,9 +68,10 @@ def _parser(rows, description):
 def get_teacher_args(argv=None):
     p = _parser(_COMMON, "GLNN teacher (HIP hot path)")
     # not a reference flag: the activation storage of the SAGE teacher's whole-graph evaluation forward (Model.inference(dtype=...)),
-    # bfloat16 = the gathered matrices stored as bf16, arithmetic and the saved log-probs fp32
-    p.add_argument("--inference_dtype", type=str, default="float32", choices=["float32", "bfloat16"],
-                   help="Activation storage of the SAGE teacher's evaluation forward (bfloat16: SAGE only)")
+    # bfloat16 = the gathered matrices stored as bf16, int8 = as int8 rows with one fp32 scale per row (docs/INT8_INFERENCE_SEMANTICS.md);
+    # arithmetic and the saved log-probs fp32
+    p.add_argument("--inference_dtype", type=str, default="float32", choices=["float32", "bfloat16", "int8"],
+                   help="Activation storage of the SAGE teacher's evaluation forward (bfloat16, int8: SAGE only)")
     # not a reference flag: neighbour-sampled evaluation of the SAGE teacher (conf key `inference_fan_out`, read by run_transductive /
     # run_inductive; docs/SAMPLED_INFERENCE_SEMANTICS.md): every evaluation forward aggregates at most this many uniformly drawn in-edges
     # per row and layer, drawn under --seed.  Empty (the default) = off: the full-neighbour forward

@@ -376,8 +376,8 @@ def probe_link(world, rank, floats_per_rank, device, group=None, reps=3):
 
 def _fp32_only(dtype, who):
     if dtype != torch.float32:
-        raise NotImplementedError(f"{who}: the sharded teacher forward stores its activations in fp32 only (bf16 storage: "
-                                  "SAGE.inference(..., dtype=torch.bfloat16) on one device)")
+        raise NotImplementedError(f"{who}: the sharded teacher forward stores its activations in fp32 only, not as {dtype} (bf16 / int8 "
+                                  "storage: SAGE.inference(..., dtype=torch.bfloat16 / torch.int8) on one device)")
 
 
 def _refuse_unsharded(encoder, who):

@@ -23,6 +23,10 @@ from .kinds import BY_KIND, FULL_GRAPH_KINDS, teacher_kind      # noqa: F401  (t
 from .nn import DAGNNConv, GATConv, GATv2Conv, GCNIIConv, GPRConv, GraphConv, PNAConv, SAGEConv, TransformerConv, _whole_graph_only
 
 
+# the activation storages of SAGE.inference(dtype=...) and what the messages call them
+_STORAGE = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.int8: "int8"}
+
+
 def _bn_eval_fold(bn, bias):
     """Per-column (scale, shift) of  BN_eval(x + bias):  y = x*s + ((bias - rm)*s + beta), s = gamma/sqrt(rv+eps)."""
     s = bn.weight.detach() * torch.rsqrt(bn.running_var + bn.eps)
@@ -411,14 +415,76 @@ class SAGE(nn.Module):
                 x, projected = self._whole_graph_layer_bf16(l, g, x, projected)
             return x
 
+    def _check_i8(self):
+        """The refusals of int8 activation storage that depend on the encoder alone, before anything is launched."""
+        if self.aggregator_type != "gcn":
+            raise NotImplementedError("SAGE.inference(dtype=torch.int8): int8 activation storage is implemented for the 'gcn' aggregator "
+                                      f"only, not for aggregator_type {self.aggregator_type!r}")
+        if self.norm_type == "layer":
+            raise NotImplementedError("SAGE.inference(dtype=torch.int8): LayerNorm teachers are fp32 only (the per-row statistics pass "
+                                      "is not part of the int8 storage path)")
+        for l, layer in enumerate(self.layers):
+            gathered = min(layer._in_feats, layer._out_feats)
+            if gathered > ops.I8_MAX_WIDTH:
+                form = "aggregates first" if layer._in_feats <= layer._out_feats else "projects first"
+                raise NotImplementedError(f"SAGE.inference(dtype=torch.int8): layer {l} {form} and gathers rows of {gathered} columns; int8 "
+                                          f"rows hold at most {ops.I8_MAX_WIDTH} (dtype=torch.bfloat16 takes any width)")
+
+    def _input_i8(self, feats):
+        """What layer 0 reads in the int8 sweep: int8 rows when it aggregates first (fp32 / bf16 features quantised once per call, rows
+        made by ops.to_int8_rows taken as they are), the fp32 features when it projects first (only its GEMM reads them)."""
+        first = self.layers[0]
+        if feats.dtype == torch.int8:
+            if first._in_feats > first._out_feats:
+                raise ValueError("SAGE.inference(dtype=torch.int8): layer 0 projects first and its fp32 GEMM reads the features; pass them "
+                                 "as float32 or bfloat16, not as int8 rows")
+            if feats.dim() != 2 or feats.shape[1] != ops.int8_rows_ld(first._in_feats):
+                raise ValueError(f"SAGE.inference(dtype=torch.int8): int8 features must be the rows of ops.to_int8_rows for {first._in_feats} "
+                                 f"columns, {ops.int8_rows_ld(first._in_feats)} bytes each (round16(d + 4))")
+            return feats
+        x = feats.float() if feats.dtype == torch.bfloat16 else feats
+        return ops.to_int8_rows(x) if first._in_feats <= first._out_feats else x
+
+    def _whole_graph_layer_i8(self, l, g, x, projected):
+        """Layer l of the whole-graph sweep with int8 activation storage: (y, projected for layer l+1 or None).  A matrix is int8 rows
+        exactly where the bf16 sweep stores bf16 -- the chained projection, a project-first layer's x @ W^T, and a hidden layer's output
+        when the next layer aggregates first; all sums, MFMA and epilogues are fp32 and the logits come out fp32.  The fused launch writes
+        fp32, so its chained projection (or its output, when the next layer gathers it) is quantised by a launch of its own."""
+        layer = self.layers[l]
+        ep_scale, ep_shift, relu = self._tail(l)
+        n = g.num_dst_nodes()
+        nxt = self.layers[l + 1] if l + 1 < self.num_layers else None
+        out_dtype = torch.int8 if nxt is not None and nxt._in_feats <= nxt._out_feats else torch.float32
+        if projected is not None:
+            return ops.spmm_sage_gcn_i8(g.indptr, g.indices, projected, layer._out_feats, n, ep_scale=ep_scale, ep_shift=ep_shift, relu=relu,
+                                        out_dtype=out_dtype), None
+        if self._chains_next(l):
+            _, proj = ops.sage_fused_i8(g.indptr, g.indices, x, layer._in_feats, n, layer.fc_neigh.weight, ep_scale=ep_scale,
+                                        ep_shift=ep_shift, relu=relu, x_self=x[:n], w_next=nxt.fc_neigh.weight, want_out=False,
+                                        tile_order=g.fused_tile_order())
+            return None, ops.to_int8_rows(proj)
+        return layer.forward_i8(g, x, x[:n], ep_scale=ep_scale, ep_shift=ep_shift, relu=relu, out_dtype=out_dtype), None
+
+    def _inference_i8(self, dataloader, feats, whole_graph):
+        g = getattr(dataloader, "graph", None)
+        if not whole_graph or g is None:
+            raise NotImplementedError("SAGE.inference(dtype=torch.int8): the whole-graph sweep only (whole_graph=True over a loader with a "
+                                      "resident graph); the chunked and literal sweeps are fp32")
+        self._check_i8()
+        with torch.no_grad():
+            x, projected = self._input_i8(feats), None
+            for l in range(self.num_layers):
+                x, projected = self._whole_graph_layer_i8(l, g, x, projected)
+            return x
+
     def _inference_mean(self, dataloader, feats, whole_graph, dtype):
         """`inference` of a "mean" encoder, fp32: per layer ONE launch over all rows of the resident CSR (whole_graph) or one per chunk of
         the loader's sweep over global-id row ranges (the same kernels on the same rows: bit-identical), the tail as in `_tail` with the
         summed bias, LayerNorm as its own pass behind the conv.  The "gcn" engine's extras -- the chained next-layer projection, the kept
         layer-1 aggregate, bf16 storage -- are not implemented for this aggregator and raise when asked for."""
         if dtype != torch.float32:
-            raise NotImplementedError("SAGE.inference(dtype=torch.bfloat16): bf16 activation storage is implemented for the 'gcn' aggregator "
-                                      "only, not for aggregator_type 'mean'")
+            raise NotImplementedError(f"SAGE.inference(dtype={dtype}): {_STORAGE[dtype]} activation storage is implemented for the 'gcn' "
+                                      "aggregator only, not for aggregator_type 'mean'")
         g = getattr(dataloader, "graph", None)
         # whole graph: any loader that sweeps every node of a resident graph in id order (FullNeighborLoader, or the NodeDataLoader the
         # teacher CLI evaluates with: it carries `.graph` exactly then); the chunked sweep also needs the loader's global-id blocks
@@ -480,17 +546,19 @@ class SAGE(nn.Module):
         _need_hip(feats, "SAGE.inference_over")
         if len(graphs) != self.num_layers:
             raise ValueError(f"SAGE.inference_over: {len(graphs)} graphs for {self.num_layers} layers")
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError(f"SAGE.inference_over: dtype must be torch.float32 or torch.bfloat16, not {dtype}")
+        if dtype not in _STORAGE:
+            raise ValueError(f"SAGE.inference_over: dtype must be torch.float32, torch.bfloat16 or torch.int8, not {dtype}")
         mean = self.aggregator_type != "gcn"
         if mean:
             _check_tail(self)
             if dtype != torch.float32:
-                raise NotImplementedError("SAGE.inference(dtype=torch.bfloat16): bf16 activation storage is implemented for the 'gcn' aggregator "
-                                          "only, not for aggregator_type 'mean'")
+                raise NotImplementedError(f"SAGE.inference(dtype={dtype}): {_STORAGE[dtype]} activation storage is implemented for the 'gcn' "
+                                          "aggregator only, not for aggregator_type 'mean'")
         elif dtype == torch.bfloat16 and self.norm_type == "layer":
             raise NotImplementedError("SAGE.inference(dtype=torch.bfloat16): LayerNorm teachers are fp32 only (the per-row statistics pass "
                                       "is not part of the bf16 storage path)")
+        elif dtype == torch.int8:
+            self._check_i8()
         with torch.no_grad():
             if mean:
                 x = ops.as_feat(feats)
@@ -508,6 +576,11 @@ class SAGE(nn.Module):
                     x = feats.float() if feats.dtype == torch.bfloat16 else feats
                 for l, g in enumerate(graphs):
                     x, projected = self._whole_graph_layer_bf16(l, g, x, projected)
+                return x
+            if dtype == torch.int8:
+                x = self._input_i8(feats)
+                for l, g in enumerate(graphs):
+                    x, projected = self._whole_graph_layer_i8(l, g, x, projected)
                 return x
             x = ops.as_feat(feats)
             for l, g in enumerate(graphs):
@@ -530,6 +603,10 @@ class SAGE(nn.Module):
         half the bytes; arithmetic stays fp32 and the returned logits are fp32.  `feats` may be fp32 (cast once per call) or bf16.  Its
         buffers are plain allocations (no ops.placed_for_gather placement).  Not for whole_graph=False or LayerNorm teachers.
 
+        dtype=torch.int8 (docs/INT8_INFERENCE_SEMANTICS.md): the same sweep with the gathered matrices stored as int8 rows with one fp32
+        scale per row (_whole_graph_layer_i8); weights, arithmetic and the returned logits are fp32.  `feats` may be fp32 or bf16 (quantised
+        once per call) or rows already made by ops.to_int8_rows.  The bf16 form's refusals, and gathered rows of at most 256 columns.
+
         fan_out=[f_0, .., f_{L-1}] (docs/SAMPLED_INFERENCE_SEMANTICS.md): neighbour-sampled inference -- layer l aggregates over
         g.sampled(f_l, sample_layer_seed(sample_seed, l)), at most f_l uniformly drawn in-edges per row, through `inference_over`: both
         aggregators, bf16 storage where the full form has it, and none of the full form's caches.  fan_out=None: the full-neighbour code
@@ -539,13 +616,15 @@ class SAGE(nn.Module):
             _need_hip(feats, "SAGE.inference")
             return self.inference_over(self.sampled_graphs(dataloader.graph, fan_out, sample_seed), feats, dtype)
         _need_hip(feats, "SAGE.inference")
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError(f"SAGE.inference: dtype must be torch.float32 or torch.bfloat16, not {dtype}")
+        if dtype not in _STORAGE:
+            raise ValueError(f"SAGE.inference: dtype must be torch.float32, torch.bfloat16 or torch.int8, not {dtype}")
         if self.aggregator_type != "gcn":
             _check_tail(self)
             return self._inference_mean(dataloader, feats, whole_graph, dtype)
         if dtype == torch.bfloat16:
             return self._inference_bf16(dataloader, feats, whole_graph)
+        if dtype == torch.int8:
+            return self._inference_i8(dataloader, feats, whole_graph)
         g = getattr(dataloader, "graph", None)
         with torch.no_grad():
             x = ops.as_feat(feats)
@@ -982,7 +1061,7 @@ class Model(nn.Module):
         return self.encoder(data, feats)
 
     def inference(self, data, feats, dtype=torch.float32, fan_out=None, sample_seed=0):
-        """dtype=torch.bfloat16: bf16 activation storage, the SAGE teacher's whole-graph forward only (SAGE.inference).
+        """dtype=torch.bfloat16 / torch.int8: bf16 / int8 activation storage, the SAGE teacher's whole-graph forward only (SAGE.inference).
         fan_out / sample_seed: neighbour-sampled inference, the SAGE teacher only (SAGE.inference; docs/SAMPLED_INFERENCE_SEMANTICS.md)."""
         kind = self.kind
         if fan_out is not None:
@@ -992,11 +1071,12 @@ class Model(nn.Module):
             return self.encoder.inference(data, feats, dtype=dtype, fan_out=fan_out, sample_seed=sample_seed)
         if dtype != torch.float32:
             row = BY_KIND[kind]
+            what = _STORAGE.get(dtype, "bf16")
             if row.bf16:
-                raise NotImplementedError(f"{row.key}.inference(dtype={dtype}): bf16 activation storage is not implemented for the {row.key} "
+                raise NotImplementedError(f"{row.key}.inference(dtype={dtype}): {what} activation storage is not implemented for the {row.key} "
                                           "teacher ({} gathers and stores fp32 rows; {}, {})".format(*row.bf16))
             if kind != "sage":
-                raise NotImplementedError(f"{self.model_name}.inference(dtype={dtype}): bf16 activation storage is implemented for the SAGE "
+                raise NotImplementedError(f"{self.model_name}.inference(dtype={dtype}): {what} activation storage is implemented for the SAGE "
                                           "teacher's whole-graph forward only")
             return self.encoder.inference(data, feats, dtype=dtype)
         if kind == "sage":

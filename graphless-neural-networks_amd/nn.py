@@ -196,6 +196,36 @@ class SAGEConv(nn.Module):
         y = ops.gemm(agg, w, ep_scale=ep_scale, ep_shift=shift, relu=relu)
         return ops.to_bf16(y) if out_dtype == torch.bfloat16 else y
 
+    def forward_i8(self, graph, h_src, h_dst, ep_scale=None, ep_shift=None, relu=False, out_dtype=torch.float32):
+        """Eval-mode layer with int8 activation STORAGE (SAGE.inference(..., dtype=torch.int8); docs/INT8_INFERENCE_SEMANTICS.md): the forms
+        `forward_bf16` picks, where every matrix an aggregation gathers is int8 rows (ops.to_int8_rows) and all arithmetic is fp32.
+        h_src / h_dst: int8 rows of in_feats columns when the layer aggregates first, fp32 when it projects first (a GEMM is then their only
+        reader).  out_dtype: torch.int8 when the next layer gathers the result (int8 rows of out_feats columns come back)."""
+        if self._aggre_type == "mean":
+            raise NotImplementedError("SAGEConv 'mean': int8 activation storage is implemented for the 'gcn' aggregator only")
+        n_dst = graph.num_dst_nodes()
+        w, b = self.fc_neigh.weight, self.fc_neigh.bias
+        fused_tail = ep_scale is not None or ep_shift is not None or relu
+        shift = ep_shift if fused_tail else b
+        gathered = min(self._in_feats, self._out_feats)      # the width this layer's aggregation gathers
+        if gathered > ops.I8_MAX_WIDTH:
+            raise NotImplementedError(f"SAGEConv: int8 rows are at most {ops.I8_MAX_WIDTH} columns wide and this layer aggregates "
+                                      f"{gathered} columns (torch.bfloat16 storage takes any width)")
+        if self._in_feats > self._out_feats:
+            # project first in fp32, store the projection as int8 rows, aggregate them
+            hw = ops.to_int8_rows(ops.gemm(ops.as_feat(h_src), w))
+            return ops.spmm_sage_gcn_i8(graph.indptr, graph.indices, hw, self._out_feats, n_dst, ep_scale=ep_scale, ep_shift=shift, relu=relu,
+                                        out_dtype=out_dtype)
+        if self._out_feats <= 256:
+            order = graph.fused_tile_order() if n_dst == graph.n_dst else None
+            y = ops.sage_fused_i8(graph.indptr, graph.indices, h_src, self._in_feats, n_dst, w, ep_scale=ep_scale, ep_shift=shift, relu=relu,
+                                  x_self=h_dst, tile_order=order)
+        else:
+            # aggregate the int8 rows into an fp32 matrix, then the fp32 GEMM
+            agg = ops.spmm_sage_gcn_i8(graph.indptr, graph.indices, h_src, self._in_feats, n_dst, x_self=h_dst, out_dtype=torch.float32)
+            y = ops.gemm(agg, w, ep_scale=ep_scale, ep_shift=shift, relu=relu)
+        return ops.to_int8_rows(y) if out_dtype == torch.int8 else y
+
 
 class GraphConv(nn.Module):
     def __init__(self, in_feats, out_feats, norm="both", weight=True, bias=True, activation=None,

@@ -162,6 +162,152 @@ def _dtype_code(t):
     return DTYPE_BF16 if t.dtype == torch.bfloat16 else DTYPE_F32
 
 
+# ---- int8 activation storage of the SAGE teacher forward (csrc/sage_i8.hip, docs/INT8_INFERENCE_SEMANTICS.md) ----------------------
+DTYPE_I8 = 2                            # GLNN_DTYPE_I8
+I8_MAX_WIDTH = 256
+
+
+def round16(d):
+    return (d + 15) // 16 * 16
+
+
+def int8_rows_ld(d):
+    """Bytes of one int8 row of d columns: the values, zero padding, and the row's fp32 scale in the last four."""
+    return round16(d + 4)
+
+
+def int8_rows_empty(n, d, device, zero=False):
+    """An [n, round16(d + 4)] torch.int8 matrix for n int8 rows of d columns (include/glnn_hip.h: bytes [0, d) the values, [d, ld - 4) zero,
+    the last four the row's fp32 scale); a plain allocation with a 16-byte aligned base."""
+    if not 1 <= d <= I8_MAX_WIDTH:
+        raise ValueError(f"int8_rows_empty: int8 rows hold 1..{I8_MAX_WIDTH} columns (got {d})")
+    return (torch.zeros if zero else torch.empty)((n, int8_rows_ld(d)), dtype=torch.int8, device=device)
+
+
+def _i8_rows(q, d, name):
+    """q as the int8 rows of a d-column matrix, or ValueError."""
+    if q.dtype != torch.int8 or q.dim() != 2 or q.shape[1] != int8_rows_ld(d) or (q.shape[0] > 1 and q.stride(0) != q.shape[1]) \
+            or (q.shape[1] > 1 and q.stride(1) != 1) or q.data_ptr() % 16:
+        raise ValueError(f"{name}: expected int8 rows of {d} columns: a 16-byte aligned torch.int8 [n, {int8_rows_ld(d)}] matrix "
+                         "(ops.to_int8_rows)")
+    return q
+
+
+def to_int8_rows(x, out=None):
+    """glnn_quant_rows_i8: x [n, d] fp32 -> int8 rows (per row s = max|x| / 127, q = clamp(rint(x * (127 / max|x|)), -127, 127); a zero row
+    has s = 0, a row with a NaN or an Inf s = NaN and q = 0).  Returns an int8_rows_empty matrix (or fills `out`, one of those)."""
+    _need_cuda(x, out)
+    _mat(x, "to_int8_rows x")
+    n, d = x.shape
+    if out is None:
+        out = int8_rows_empty(n, d, x.device)
+    elif out.shape[0] != n:
+        raise ValueError("to_int8_rows: out must hold the rows of x")
+    _i8_rows(out, d, "to_int8_rows out")
+    if n == 0:
+        return out
+    with _Timed("quant_rows_i8", n=n, d=d):
+        rc = _lib.lib().glnn_quant_rows_i8(_p(x), _ld(x), n, d, _p(out), out.shape[1], _stream())
+    _lib.check(rc, "glnn_quant_rows_i8")
+    return out
+
+
+def int8_rows_scale(q):
+    """The per-row scales of int8 rows: the fp32 [n] view of each row's last four bytes."""
+    _need_cuda(q)
+    if q.dtype != torch.int8 or q.dim() != 2 or q.shape[1] % 16 or not q.is_contiguous():
+        raise ValueError("int8_rows_scale: expected contiguous int8 rows (ops.to_int8_rows)")
+    return q.view(torch.float32)[:, -1]
+
+
+def from_int8_rows(q, d):
+    """int8 rows -> fp32 [n, d], q * s in plain torch (tests and users; no kernel reads the result)."""
+    _need_cuda(q)
+    _i8_rows(q, d, "from_int8_rows")
+    return q[:, :d].to(torch.float32) * int8_rows_scale(q)[:, None]
+
+
+def _i8_out(out, out_dtype, n, d, device, name):
+    if out_dtype is not None and out_dtype not in (torch.float32, torch.int8):
+        raise ValueError(f"{name}: out_dtype must be torch.float32 or torch.int8")
+    if out is None:
+        return int8_rows_empty(n, d, device) if out_dtype == torch.int8 else feat_empty(n, d, device)
+    if out_dtype is not None and out.dtype != out_dtype:
+        raise ValueError(f"{name}: out is {out.dtype}, out_dtype {out_dtype}")
+    if out.dtype == torch.int8:
+        if _i8_rows(out, d, name).shape[0] != n:
+            raise ValueError(f"{name}: out must hold {n} int8 rows")
+        return out
+    _mat(out, name)
+    if out.shape[0] < n or out.shape[1] != d:
+        raise ValueError(f"{name}: out must hold {n} rows of {d} columns")
+    return out
+
+
+def _i8_graph(indptr, indices, x, d, n_dst, x_self, name):
+    _need_cuda(indptr, indices, x, x_self)
+    _i8_rows(x, d, f"{name} x")
+    if x_self is None:
+        x_self = x
+    else:
+        _i8_rows(x_self, d, f"{name} x_self")
+    if x_self.shape[0] < n_dst:
+        raise ValueError(f"{name}: x_self must hold the n_dst destination rows")
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32:
+        raise ValueError(f"{name}: indptr must be int64 and indices int32")
+    return x_self
+
+
+def spmm_sage_gcn_i8(indptr, indices, x, d, n_dst, ep_scale=None, ep_shift=None, relu=False, out=None, x_self=None, out_dtype=None):
+    """glnn_spmm_sage_gcn_i8: epi((A x + x_self) / (deg + 1)) over int8 rows x (d columns, d <= 256; x_self defaults to x's first n_dst
+    rows), fp32 sums.  The output is `out` (its dtype decides), else fresh: fp32 [n_dst, d] (default) or int8 rows (out_dtype=torch.int8:
+    each finished row quantised in the launch)."""
+    x_self = _i8_graph(indptr, indices, x, d, n_dst, x_self, "spmm_sage_gcn_i8")
+    _need_cuda(out)
+    out = _i8_out(out, out_dtype, n_dst, d, x.device, "spmm_sage_gcn_i8 out")
+    i8 = out.dtype == torch.int8
+    with _Timed("spmm_i8", d=d, n_dst=n_dst):
+        rc = _lib.lib().glnn_spmm_sage_gcn_i8(
+            _p(indptr), _p(indices), n_dst, x.shape[0], _p(x), x.shape[1], d, _p(x_self), x_self.shape[1],
+            _p(_vec(ep_scale, d, "ep_scale")), _p(_vec(ep_shift, d, "ep_shift")), 1 if relu else 0,
+            _p(out), out.shape[1] if i8 else _ld(out), DTYPE_I8 if i8 else DTYPE_F32, _stream())
+    _lib.check(rc, "glnn_spmm_sage_gcn_i8")
+    return out
+
+
+def sage_fused_i8(indptr, indices, x, d_in, n_dst, w, ep_scale=None, ep_shift=None, relu=False, out=None, x_self=None, w_packed=None,
+                  w_next=None, out_next=None, want_out=True, tile_order=None):
+    """glnn_sage_fused_i8: sage_fused over int8 rows x (d_in columns): the fp32 aggregate tile feeds the same fp32 MFMA passes.  Returns
+    out [n_dst, d_out] fp32, or (out or None, out_next [n_dst, d_out2] fp32) with the chained projection w_next.  Both outputs are fp32: a
+    projection the next layer gathers goes through to_int8_rows."""
+    x_self = _i8_graph(indptr, indices, x, d_in, n_dst, x_self, "sage_fused_i8")
+    _need_cuda(w, out, w_next, out_next, tile_order)
+    _mat(w, "sage_fused_i8 w")
+    d_out = w.shape[0]
+    if w.shape[1] != d_in:
+        raise ValueError("sage_fused_i8: weight must be [d_out, d_in]")
+    if tile_order is not None and (tile_order.dtype != torch.int32 or not tile_order.is_contiguous() or tile_order.numel() != (n_dst + 31) // 32):
+        raise ValueError("sage_fused_i8: tile_order must be a contiguous int32 permutation of the ceil(n_dst / 32) tile ids")
+    if w_packed is None:
+        w_packed = pack_weight(w)
+    if out is not None or want_out or w_next is None:
+        out = _i8_out(out, torch.float32, n_dst, d_out, x.device, "sage_fused_i8 out")
+    w2p, d_out2 = None, 0
+    if w_next is not None:
+        if w_next.shape[1] != d_out:
+            raise ValueError("sage_fused_i8: w_next must be [d_out2, d_out]")
+        w2p, d_out2 = pack_weight(w_next), w_next.shape[0]
+        out_next = _i8_out(out_next, torch.float32, n_dst, d_out2, x.device, "sage_fused_i8 out_next")
+    with _Timed("sage_fused_i8", d=d_in, n_dst=n_dst, d_out=d_out, d_chain=d_out2, d_written=(d_out if out is not None else 0) + d_out2):
+        rc = _lib.lib().glnn_sage_fused_i8(
+            _p(indptr), _p(indices), n_dst, x.shape[0], _p(x), x.shape[1], d_in, _p(x_self), x_self.shape[1],
+            _p(w_packed), d_out, _p(_vec(ep_scale, d_out, "ep_scale")), _p(_vec(ep_shift, d_out, "ep_shift")), 1 if relu else 0,
+            _p(out), _ld(out) if out is not None else 0, _p(w2p), d_out2, _p(out_next), _ld(out_next) if out_next is not None else 0,
+            _p(tile_order), _stream())
+    _lib.check(rc, "glnn_sage_fused_i8")
+    return out if w_next is None else (out, out_next)
+
+
 _RANDPERM_LOCK = __import__("threading").Lock()
 
 

@@ -185,7 +185,7 @@ def train_mini_batch(model, feats, labels, batch_size, criterion, optimizer, lam
     return eng.loss_accum.item() / num_batches      # the only host sync of the pass
 
 
-INFERENCE_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16}
+INFERENCE_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16, "int8": torch.int8}
 
 
 def inference_dtype(conf):
@@ -208,7 +208,7 @@ def inference_fan_out(conf):
 
 
 def evaluate(model, data, feats, labels, criterion, evaluator, idx_eval=None, dtype=torch.float32, fan_out=None, sample_seed=0):
-    """reference train_and_eval.py:89-105.  dtype: Model.inference's activation storage (torch.bfloat16: SAGE teachers only).
+    """reference train_and_eval.py:89-105.  dtype: Model.inference's activation storage (torch.bfloat16, torch.int8: SAGE teachers only).
     fan_out / sample_seed: Model.inference's neighbour-sampled form (SAGE teachers only); None = the full-neighbour forward."""
     model.eval()
     with torch.no_grad():

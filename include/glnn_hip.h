@@ -1188,6 +1188,46 @@ GLNN_API int glnn_sage_fused_bf16(const int64_t* indptr, const int32_t* indices,
                                   void* out2, int64_t ldo2, int out2_dtype, const int32_t* tile_order, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * int8 activation storage for the whole-graph SAGE teacher forward (csrc/sage_i8.hip, docs/INT8_INFERENCE_SEMANTICS.md).  A matrix that an
+ * aggregation gathers may be STORED as int8 rows with one fp32 scale per row; every sum, MFMA and epilogue stays fp32, weights stay fp32.
+ *
+ * Row format.  A matrix of n rows by d columns (1 <= d <= 256) is an int8 array [n, ld] with ld = round16(d + 4) bytes EXACTLY and a
+ * 16-byte aligned base:
+ *   bytes [0, d)         the quantised values q in [-127, 127] (signed)
+ *   bytes [d, ld - 4)    zero
+ *   bytes [ld - 4, ld)   the row's fp32 scale s, little endian
+ * and the value of an element is q * s (the scale sits in the row: one contiguous fetch brings everything an edge needs).
+ * Quantisation of a row x, all in fp32: amax = max |x|; s = amax / 127.0f and inv = 127.0f / amax, both correctly rounded divisions;
+ * q = min(max(rintf(x * inv), -127), 127), ties to even.  amax == 0: s = 0 and q = 0.  A row holding a NaN or an Inf: s = NaN (0x7FC00000)
+ * and q = 0, so the whole row dequantises to NaN.
+ * Every entry: n == 0 / n_dst == 0 is a no-op; d > 256 or a leading dimension of int8 rows other than round16(d + 4) is
+ * GLNN_ERR_UNSUPPORTED, any other bad argument GLNN_ERR_INVALID_ARG, both with nothing launched and a glnn_last_error text that names the
+ * entry.  Results are deterministic (fixed-order folds, no float atomics).
+ * ------------------------------------------------------------------------------------------ */
+#define GLNN_DTYPE_I8 2
+
+/* x fp32 [n, d] (ldx >= d, any) -> int8 rows `out` (ldo = round16(d + 4)), padding written as 0. */
+GLNN_API int glnn_quant_rows_i8(const float* x, int64_t ldx, int64_t n, int d, int8_t* out, int64_t ldo, void* stream);
+
+/* out[v] = epi((sum_{u->v} x[u] + x_self[v]) / (deg(v) + 1)) over int8 rows x [n_src] / x_self [n_dst] (ldx = ld_self = round16(d + 4)),
+ * the corrected division and the epilogue epi(z) = relu?(z * ep_scale + ep_shift) of glnn_spmm_csr_f32.  `out` holds fp32 (out_dtype
+ * GLNN_DTYPE_F32, ldo a multiple of 4) or int8 rows (GLNN_DTYPE_I8, ldo = round16(d + 4): the lanes that hold a finished row reduce its
+ * amax among themselves and quantise before storing).  No row_scale / col_scale / self_rows / hub / chunk variant. */
+GLNN_API int glnn_spmm_sage_gcn_i8(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src,
+                                   const int8_t* x, int64_t ldx, int d, const int8_t* x_self, int64_t ld_self,
+                                   const float* ep_scale, const float* ep_shift, int relu, void* out, int64_t ldo,
+                                   int out_dtype, void* stream);
+
+/* glnn_sage_fused_bf16 with phase A reading int8 rows x / x_self (d_in <= 256): the fp32 aggregate of the 32-row tile in LDS feeds the
+ * same fp32 MFMA passes; tile_order and the chained w2_packed / out2 as there.  Both outputs are fp32 (a chained projection that the next
+ * layer gathers is quantised by glnn_quant_rows_i8). */
+GLNN_API int glnn_sage_fused_i8(const int64_t* indptr, const int32_t* indices, int64_t n_dst, int64_t n_src,
+                                const int8_t* x, int64_t ldx, int d_in, const int8_t* x_self, int64_t ld_self,
+                                const float* w_packed, int d_out, const float* ep_scale, const float* ep_shift, int relu,
+                                float* out, int64_t ldo, const float* w2_packed, int d_out2, float* out2, int64_t ldo2,
+                                const int32_t* tile_order, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * bf16 serving of the MLP student (csrc/gemm_bf16.hip): opt-in inference with weights and hidden activations STORED as bf16, every
  * product on the bf16 MFMA (v_mfma_f32_16x16x32_bf16) with fp32 accumulation in a fixed order, an fp32 epilogue, fp32 logits.
  *   out[m, n] = epi( A[m, k] . W[n, k]^T ),  epi(v) = relu?( v * ep_scale[n] + ep_shift[n] ),  then optionally log_softmax of each row.
